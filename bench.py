@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Headline benchmark (BASELINE.json): queries/sec + recall@10 on a 10M x 128 PQ(m=16,k=256)
+"""Headline benchmark (BASELINE.json): queries/sec (+ recall@10 with --full) on a 10M x 128 PQ(m=16,k=256)
 index, batch = 1024, K = 10, row-sharded over N GPUs (one process per GPU).
 
   python bench.py --gpus 1 --steps 20 --warmup 3
@@ -11,6 +11,11 @@ distance-table build -> ADC scan of this rank's row shard + wavefront top-k -> (
 all-gather of the per-shard partial top-(K+1) lists) -> merge.  Index build (synthetic data,
 PQ training, encoding) happens once, untimed, through the same library.
 Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: build, warm up, time --steps steps, print the line.
+--full adds everything else the line can carry: the main-stage kernel's hipEvent timing during the timed
+steps (roofline), recall@K, the sub-records of other cases (extras) and the CPU baseline with its parity check.
+--dump-outputs DIR writes what the last timed step returned (rows, distances, counts, flags) as DIR/<name>.npy.
 """
 import argparse
 import ctypes as C
@@ -36,6 +41,93 @@ def kernel_source_sha16(kernel_name):
     for f in files:
         h.update(open(os.path.join(ROOT, "gulon_amd", "csrc", f), "rb").read())
     return h.hexdigest()[:16]
+
+
+def roofline(N, L, engines, nloc, m, B, steps):
+    """The roofline record (--full): the main-stage kernel's hipEvent-timed duration over the timed steps, its
+    algorithmic bytes against the HBM peak, and the physical bounds from the committed counter passes."""
+    ms_total, launches, rows_cov = C.c_double(0), C.c_int32(0), C.c_int64(0)
+    for e in engines:
+        a, b_, c_ = C.c_double(0), C.c_int32(0), C.c_int64(0)
+        N.check(L.gulon_index_profile_read_ex(e.index._h, C.byref(a), C.byref(b_), C.byref(c_)))
+        N.check(L.gulon_index_profile(e.index._h, 0))
+        ms_total.value += a.value; launches.value += b_.value; rows_cov.value += c_.value
+    # dominant kernel: the main-stage launch of the quantized filter when it is active (one launch per
+    # batch over ~95 % of the rows), else the exact scan; averages are per launch, like rocprofv3 --stats
+    scan_ms = ms_total.value / max(launches.value, 1)
+    rows_per_launch = rows_cov.value / max(launches.value, 1)
+    filtered = rows_per_launch < 0.999 * nloc
+    kernel_name = "filter_kernel" if filtered else "scan_kernel"
+
+    alg_bytes = float(B) * rows_per_launch * m            # SURVEY 8(d): m code bytes per (query, row) pair
+    achieved = alg_bytes / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0
+    # physical side of the same kernel: HBM bytes and LDS / VALU counters per launch come from the committed
+    # rocprofv3 --pmc passes of this very command (profiles/scan_traffic.json names the csv they were read from);
+    # the duration they are divided by is the one measured live above
+    traffic, physical, physical_note = None, None, None
+    tf = os.path.join(ROOT, "profiles", "scan_traffic.json")
+    if os.path.exists(tf):
+        try:
+            rec = json.load(open(tf)).get(f"{kernel_name}_n{nloc}_m{m}_B{B}")
+            if rec is None:
+                physical_note = f"no counter pass committed for {kernel_name} at n={nloc}, m={m}, B={B}"
+            elif rec.get("source_sha16") != kernel_source_sha16(kernel_name):
+                # counters of another version of the kernel say nothing about this one
+                physical_note = (f"stale: the committed counters ({rec.get('source')}) were taken from kernel sources "
+                                 f"{rec.get('source_sha16')}, this build is {kernel_source_sha16(kernel_name)}")
+                rec = None
+            traffic = rec["hbm_bytes_per_launch"] if rec else None
+            if rec and scan_ms > 0:
+                hbm_gbs = traffic / (scan_ms * 1e-3) / 1e9
+                physical = {"hbm": {"bytes_per_launch": traffic, "GB_per_s": hbm_gbs, "peak_GB_per_s": HBM_PEAK_GBS,
+                                    "frac": hbm_gbs / HBM_PEAK_GBS,
+                                    "traffic_over_algorithmic": traffic / alg_bytes if alg_bytes else None},
+                            "source": rec.get("source")}
+                if "lds_idx_active" in rec:
+                    cyc = rec["grbm_gui_active"] / 8.0                       # kernel cycles (sum over 8 XCDs / 8)
+                    free = (rec["lds_idx_active"] - rec["lds_bank_conflict"]) / rec.get("cus", 256)
+                    physical["lds"] = {
+                        "bound": "LDS gather (ds_read_b128 of 16 one-byte bounds per look-up)",
+                        "conflict_free_cycles_per_cu": free, "kernel_cycles": cyc, "frac": free / cyc,
+                        "pipe_busy": rec["lds_idx_active"] / rec.get("cus", 256) / cyc,
+                        "bank_conflict_share": rec["lds_bank_conflict"] / rec["lds_idx_active"]}
+                if "valu_busy" in rec:
+                    physical["valu_busy"] = rec["valu_busy"]
+        except Exception:
+            traffic, physical = None, None
+
+    # contract fields: ALGORITHMIC bytes (SURVEY 8d: m code bytes per (query, row) pair) over the kernel's
+    # duration against the HBM peak.  The kernel reads every code word once per 16-query tile out of
+    # L2 / Infinity Cache and decides > 99.9 % of the pairs on 8-bit bounds, so this "fraction" exceeds 1 and
+    # bounds nothing; `physical` holds the bounds that bind (HBM actually moved; the LDS gather pipe)
+    return {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "kernel": kernel_name,
+            "kernel_ms": scan_ms, "launches_per_step": launches.value / max(steps, 1),
+            "algorithmic_bytes_per_launch": alg_bytes, "basis": "algorithmic bytes, not DRAM traffic",
+            "physical": physical, "physical_note": physical_note}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, outs):
+    """What one step hands its caller, as DIR/<name>.npy: rows [B][K] and counts / flags [B] as float64 (exact for
+    every row number), distances [B][K] as float32 (as computed).  Beyond 64 MB in all, a fixed sample of the
+    queries (seed 0, ascending, its indices in sampled_queries.npy) is written instead."""
+    arrays = {}
+    for name, t in zip(("rows", "distances", "counts", "flags"), outs):
+        a = t.cpu().numpy()
+        arrays[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    b = arrays["counts"].shape[0]
+    per_query = sum(a.nbytes for a in arrays.values()) // max(b, 1) + 8
+    budget = DUMP_LIMIT_BYTES - 4096                  # room for the .npy headers
+    if b * per_query > budget:
+        sel = np.sort(np.random.default_rng(0).choice(b, budget // per_query, replace=False))
+        arrays = {name: a[sel] for name, a in arrays.items()}
+        arrays["sampled_queries"] = sel.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def run_steps(torch, shardeds, streams, Q, B, K, steps):
@@ -183,7 +275,14 @@ def main():
     ap.add_argument("--extra-steps", type=int, default=5, help="timed steps of every sub-record")
     ap.add_argument("--inflight", type=int, default=int(os.environ.get("GULON_BENCH_INFLIGHT", "0")),
                     help="query batches in flight (each on its own stream with its own scratch)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the kernel timing (roofline), recall, extras and CPU baseline; the --no-* and "
+                         "--cpu-seconds / --extra-steps options only apply here")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # stdout carries exactly ONE line, the JSON result: libraries that print to fd 1 on their own (RCCL's
     # version banner at communicator creation does) are sent to stderr instead
@@ -338,14 +437,15 @@ def main():
     drain()
     barrier()
     extra_rounds[0] = 0
-    for e in engines:
-        N.check(L.gulon_index_profile(e.index._h, 1))
+    if args.full:       # hipEvents around the main-stage kernel: the roofline record only
+        for e in engines:
+            N.check(L.gulon_index_profile(e.index._h, 1))
     barrier()
     if os.environ.get("GULON_HOST_PROFILE"):
         ShardedIndex.host_profile = {"_last": time.perf_counter()}
     t_start = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     drain()
     enqueue_s = time.perf_counter() - t_start          # host time to enqueue K steps (diagnostic)
     if ShardedIndex.host_profile is not None and rank == 0:
@@ -359,59 +459,12 @@ def main():
         te = torch.tensor([elapsed], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed = float(te.item())
-    ms_total, launches, rows_cov = C.c_double(0), C.c_int32(0), C.c_int64(0)
-    for e in engines:
-        a, b_, c_ = C.c_double(0), C.c_int32(0), C.c_int64(0)
-        N.check(L.gulon_index_profile_read_ex(e.index._h, C.byref(a), C.byref(b_), C.byref(c_)))
-        N.check(L.gulon_index_profile(e.index._h, 0))
-        ms_total.value += a.value; launches.value += b_.value; rows_cov.value += c_.value
-    # dominant kernel: the main-stage launch of the quantized filter when it is active (one launch per
-    # batch over ~95 % of the rows), else the exact scan; averages are per launch, like rocprofv3 --stats
-    scan_ms = ms_total.value / max(launches.value, 1)
-    rows_per_launch = rows_cov.value / max(launches.value, 1)
-    filtered = rows_per_launch < 0.999 * nloc
-    kernel_name = "filter_kernel" if filtered else "scan_kernel"
-
+    rf = roofline(N, L, engines, nloc, m, B, args.steps) if args.full else None
     note("timed region done")
     ms_per_step = elapsed / args.steps * 1e3
     qps = B * args.steps / elapsed
-    alg_bytes = float(B) * rows_per_launch * m            # m code bytes per (query, row) pair
-    achieved = alg_bytes / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0
-    # physical side of the same kernel: HBM bytes and LDS / VALU counters per launch come from the committed
-    # rocprofv3 --pmc passes of this very command (profiles/scan_traffic.json names the csv they were read from);
-    # the duration they are divided by is the one measured live above
-    traffic, physical, physical_note = None, None, None
-    tf = os.path.join(ROOT, "profiles", "scan_traffic.json")
-    if os.path.exists(tf):
-        try:
-            rec = json.load(open(tf)).get(f"{kernel_name}_n{nloc}_m{m}_B{B}")
-            if rec is None:
-                physical_note = f"no counter pass committed for {kernel_name} at n={nloc}, m={m}, B={B}"
-            elif rec.get("source_sha16") != kernel_source_sha16(kernel_name):
-                # counters of another version of the kernel say nothing about this one
-                physical_note = (f"stale: the committed counters ({rec.get('source')}) were taken from kernel sources "
-                                 f"{rec.get('source_sha16')}, this build is {kernel_source_sha16(kernel_name)}")
-                rec = None
-            traffic = rec["hbm_bytes_per_launch"] if rec else None
-            if rec and scan_ms > 0:
-                hbm_gbs = traffic / (scan_ms * 1e-3) / 1e9
-                physical = {"hbm": {"bytes_per_launch": traffic, "GB_per_s": hbm_gbs, "peak_GB_per_s": HBM_PEAK_GBS,
-                                    "frac": hbm_gbs / HBM_PEAK_GBS,
-                                    "traffic_over_algorithmic": traffic / alg_bytes if alg_bytes else None},
-                            "source": rec.get("source")}
-                if "lds_idx_active" in rec:
-                    cyc = rec["grbm_gui_active"] / 8.0                       # kernel cycles (sum over 8 XCDs / 8)
-                    free = (rec["lds_idx_active"] - rec["lds_bank_conflict"]) / rec.get("cus", 256)
-                    physical["lds"] = {
-                        "bound": "LDS gather (ds_read_b128 of 16 one-byte bounds per look-up)",
-                        "conflict_free_cycles_per_cu": free, "kernel_cycles": cyc, "frac": free / cyc,
-                        "pipe_busy": rec["lds_idx_active"] / rec.get("cus", 256) / cyc,
-                        "bank_conflict_share": rec["lds_bank_conflict"] / rec["lds_idx_active"]}
-                if "valu_busy" in rec:
-                    physical["valu_busy"] = rec["valu_busy"]
-        except Exception:
-            traffic, physical = None, None
-
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)     # before --full's extras reuse the workspaces
     res_idx = out_idx.cpu().numpy()
     res_cnt = out_cnt.cpu().numpy()
     res_dist = out_dist.cpu().numpy()
@@ -428,18 +481,11 @@ def main():
                    "dist_backend": dist.get_backend() if dist is not None else None,
                    "dist_world_size": dist.get_world_size() if dist is not None else 1,
                    "tie_replay_extra_rounds": extra_rounds[0]},
-        # contract fields: ALGORITHMIC bytes (m code bytes per (query, row) pair) over the kernel's
-        # duration against the HBM peak.  The kernel reads every code word once per 16-query tile out of
-        # L2 / Infinity Cache and decides > 99.9 % of the pairs on 8-bit bounds, so this "fraction" exceeds 1 and
-        # bounds nothing; `physical` holds the bounds that bind (HBM actually moved; the LDS gather pipe)
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "kernel": kernel_name,
-                     "kernel_ms": scan_ms, "launches_per_step": launches.value / max(args.steps, 1),
-                     "algorithmic_bytes_per_launch": alg_bytes, "basis": "algorithmic bytes, not DRAM traffic",
-                     "physical": physical, "physical_note": physical_note},
-        "build_seconds": build_s,
-        "host_enqueue_ms_per_step": enqueue_s / args.steps * 1e3,
     }
+    if rf is not None:
+        result["roofline"] = rf
+    result["build_seconds"] = build_s
+    result["host_enqueue_ms_per_step"] = enqueue_s / args.steps * 1e3
     if rehearse:
         result["config"]["rehearsal"] = (
             f"rank 0 of {emu}: {nloc} of the {n} rows, {emu} lists per exchange (RCCL all-gathers over a one-rank group "
@@ -448,7 +494,7 @@ def main():
             "one rank through the multi-rank pipeline (RCCL all-gathers of one list)")
 
     if rank == 0:
-        if not args.no_recall:
+        if args.full and not args.no_recall:
             t = time.perf_counter()
             mean, sd = recall_at_k(dm, Qh, K, res_idx, res_cnt)
             result["recall_at_10" if K == 10 else f"recall_at_{K}"] = mean
@@ -456,10 +502,10 @@ def main():
             result["recall_seconds"] = time.perf_counter() - t
             result["tie_flagged_queries"] = int((res_flg != 0).sum())
             note("recall done")
-        if world == 1 and enc is not None and not args.no_extras and not rehearse:
+        if args.full and world == 1 and enc is not None and not args.no_extras and not rehearse:
             result["extras"] = extras(args, g, N, L, torch, dev, HipEngine, ShardedIndex, local_shard, recall_at_k,
                                       sample_rows, dm, pq, shard, shardeds, streams, engines, Q, note)
-        if world == 1 and enc is not None and not args.no_cpu_baseline:
+        if args.full and world == 1 and enc is not None and not args.no_cpu_baseline:
             from oracle import oracle                      # CPU baseline leg only (the checker, timed)
             codes_h = np.stack(enc.encodings) if coder.width == 8 else None
             cents = pq.flat_centroids()

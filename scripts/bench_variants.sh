@@ -4,7 +4,7 @@
 extra=""
 if [ "$1" = "--inflight" ]; then extra="--inflight $2"; shift 2; fi
 run() {
-  python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras --no-recall $extra 2>/dev/null | python -c "
+  python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extras --no-recall $extra 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', round(d['value']), 'q/s', round(d['ms_per_step'],3), 'ms/step  kernel', round(d['roofline']['kernel_ms'],3))"
 }

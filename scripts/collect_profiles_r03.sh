@@ -31,7 +31,7 @@ filter_pmc() {  # tag, kernel name, bench args...
 }
 for part in $parts; do case $part in
 bench)
-  (cd "$root" && python3 bench.py --steps 20 --warmup 3 > "$out/bench_n1_with_extras.json" 2> "$out/bench_n1_with_extras.err")
+  (cd "$root" && python3 bench.py --full --steps 20 --warmup 3 > "$out/bench_n1_with_extras.json" 2> "$out/bench_n1_with_extras.err")
   stats bench python3 $root/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-recall --no-extras
   ;;
 pmc)
@@ -42,9 +42,9 @@ exact)
   ;;
 shard)
   (cd "$root"
-   for nfl in 4 1; do GULON_BENCH_REHEARSE=8 python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-extras --inflight $nfl > "$out/sharded/rank0_of_8_inflight$nfl.json" 2>/dev/null; done
-   for nfl in 4 1; do GULON_BENCH_REHEARSE=1 python3 bench.py --rows 1250000 --steps 200 --warmup 20 --no-cpu-baseline --no-extras --inflight $nfl > "$out/sharded/rehearsal_1rank_1250000_inflight$nfl.json" 2>/dev/null; done
-   python3 bench.py --rows 1250000 --steps 200 --warmup 20 --no-cpu-baseline --no-extras > "$out/sharded/plain_1250000.json" 2>/dev/null
+   for nfl in 4 1; do GULON_BENCH_REHEARSE=8 python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-extras --inflight $nfl > "$out/sharded/rank0_of_8_inflight$nfl.json" 2>/dev/null; done
+   for nfl in 4 1; do GULON_BENCH_REHEARSE=1 python3 bench.py --full --rows 1250000 --steps 200 --warmup 20 --no-cpu-baseline --no-extras --inflight $nfl > "$out/sharded/rehearsal_1rank_1250000_inflight$nfl.json" 2>/dev/null; done
+   python3 bench.py --full --rows 1250000 --steps 200 --warmup 20 --no-cpu-baseline --no-extras > "$out/sharded/plain_1250000.json" 2>/dev/null
    GULON_HOST_PROFILE=1 GULON_BENCH_REHEARSE=8 python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-extras --no-recall --inflight 4 2>&1 >/dev/null | grep "\[host\]" > "$out/sharded/rank0_of_8_host_profile.txt")
   GULON_BENCH_REHEARSE=8 stats sharded/rank0_of_8_nfl1 python3 $root/bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-extras --no-recall --inflight 1
   (cd "$root" && python3 scripts/timeline.py "$out/sharded/rank0_of_8_nfl1" > "$out/sharded/rank0_of_8_timeline.txt")
@@ -52,10 +52,10 @@ shard)
   ;;
 forms)
   (cd "$root"
-   python3 bench.py --rows 10000000 --dim 1024 --quantizers 64 --steps 10 --warmup 2 --cpu-seconds 10 --no-extras > "$out/bench_c5_10Mx1024_m64.json" 2>/dev/null
-   python3 bench.py --rows 1000000 --dim 300 --quantizers 25 --steps 30 --warmup 5 --cpu-seconds 5 --no-extras > "$out/bench_cli_default_1Mx300_m25.json" 2>/dev/null
-   python3 bench.py --rows 1000000 --steps 50 --warmup 5 --cpu-seconds 5 --no-extras > "$out/bench_c2_1M.json" 2>/dev/null
-   python3 bench.py --rows 4000000 --dim 96 --quantizers 32 --steps 20 --warmup 5 --no-cpu-baseline --no-extras > "$out/bench_4Mx96_m32.json" 2>/dev/null)
+   python3 bench.py --full --rows 10000000 --dim 1024 --quantizers 64 --steps 10 --warmup 2 --cpu-seconds 10 --no-extras > "$out/bench_c5_10Mx1024_m64.json" 2>/dev/null
+   python3 bench.py --full --rows 1000000 --dim 300 --quantizers 25 --steps 30 --warmup 5 --cpu-seconds 5 --no-extras > "$out/bench_cli_default_1Mx300_m25.json" 2>/dev/null
+   python3 bench.py --full --rows 1000000 --steps 50 --warmup 5 --cpu-seconds 5 --no-extras > "$out/bench_c2_1M.json" 2>/dev/null
+   python3 bench.py --full --rows 4000000 --dim 96 --quantizers 32 --steps 20 --warmup 5 --no-cpu-baseline --no-extras > "$out/bench_4Mx96_m32.json" 2>/dev/null)
   filter_pmc c5 "filter_kernel<8, 1, 16, 2, 1, 0>" --rows 10000000 --dim 1024 --quantizers 64
   filter_pmc m25 "filter_kernel<16, 1, 4, 2, 1, 0>" --rows 1000000 --dim 300 --quantizers 25
   ;;

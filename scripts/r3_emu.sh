@@ -9,7 +9,7 @@ mkdir -p "$out"
 cd "$root"
 run() {  # name, inflight, env...
   local name=$1 nfl=$2; shift 2
-  env GULON_BENCH_REHEARSE=$nranks "$@" python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-extras --inflight $nfl > "$out/$name.json" 2> "$out/$name.err" || { tail -5 "$out/$name.err"; return 1; }
+  env GULON_BENCH_REHEARSE=$nranks "$@" python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-extras --inflight $nfl > "$out/$name.json" 2> "$out/$name.err" || { tail -5 "$out/$name.err"; return 1; }
   python3 -c "import json; r=json.load(open('$out/$name.json')); print('$name', 'ms/step', round(r['ms_per_step'],4), 'kernel', round(r['roofline']['kernel_ms'],4), 'recall', r.get('recall_at_10'), 'flagged', r.get('tie_flagged_queries'))"
 }
 run nfl4 4

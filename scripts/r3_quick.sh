@@ -10,7 +10,7 @@ cd "$root"
 export GULON_BENCH_REHEARSE=${GULON_BENCH_REHEARSE:-1}
 common="--rows $rows --steps 200 --warmup 20 --no-cpu-baseline --no-extras --no-recall"
 for nfl in 4 1; do
-  python3 bench.py $common --inflight $nfl "$@" > "$out/reh_nfl$nfl.json" 2> "$out/reh_nfl$nfl.err"
+  python3 bench.py --full $common --inflight $nfl "$@" > "$out/reh_nfl$nfl.json" 2> "$out/reh_nfl$nfl.err"
   echo "$tag rows=$rows inflight=$nfl: $(python3 -c "import json,sys; r=json.load(open('$out/reh_nfl$nfl.json')); print(round(r['ms_per_step'],4), round(r['roofline']['kernel_ms'],4))")"
 done
 cd /tmp && export TMPDIR=/tmp

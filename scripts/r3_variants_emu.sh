@@ -10,9 +10,9 @@ line() { python3 -c "import json; r=json.load(open('$1')); print('$2', 'ms/step'
 for v in base "$@"; do
   lib=""; [ "$v" != base ] && lib="GULON_HIP_LIB=$root/build/expt/libgulon_$v.so"
   for nfl in 4 1; do
-    env $lib GULON_BENCH_REHEARSE=8 python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-extras --inflight $nfl > "$out/emu8_${v}_nfl$nfl.json" 2> "$out/emu8_${v}_nfl$nfl.err" && line "$out/emu8_${v}_nfl$nfl.json" "emu8 $v nfl$nfl"
+    env $lib GULON_BENCH_REHEARSE=8 python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-extras --inflight $nfl > "$out/emu8_${v}_nfl$nfl.json" 2> "$out/emu8_${v}_nfl$nfl.err" && line "$out/emu8_${v}_nfl$nfl.json" "emu8 $v nfl$nfl"
   done
   for nfl in 3 1; do
-    env $lib python3 bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extras --no-recall --inflight $nfl > "$out/n1_${v}_nfl$nfl.json" 2> "$out/n1_${v}_nfl$nfl.err" && line "$out/n1_${v}_nfl$nfl.json" "10M $v nfl$nfl"
+    env $lib python3 bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-extras --no-recall --inflight $nfl > "$out/n1_${v}_nfl$nfl.json" 2> "$out/n1_${v}_nfl$nfl.err" && line "$out/n1_${v}_nfl$nfl.json" "10M $v nfl$nfl"
   done
 done
