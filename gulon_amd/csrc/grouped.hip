@@ -24,6 +24,7 @@
 #include "scan.hpp"
 
 #include "grouped_filter.hpp"
+#include "topk_heap.hpp"
 using gulon::DevBuf;
 
 struct gulon_grouped_index {
@@ -48,144 +49,6 @@ struct gulon_grouped_index {
 
 namespace gulon {
 namespace {
-
-// TopKHeap.scala with lane = slot storage (K <= 63); every index is wave-uniform.
-struct RegHeap {
-  float v = 0.f;
-  int k = 0;
-  int size = 0;
-  int cap;
-  int lane;
-  __device__ RegHeap(int cap_, int lane_) : cap(cap_), lane(lane_) {}
-  __device__ float val(int i) const { return readlane_f(v, i); }
-  __device__ int key(int i) const { return readlane_i(k, i); }
-  // The reference's chains of swaps move ONE entry down (or up) the tree; here that entry travels in registers and
-  // the entries it passes are shifted into the hole it leaves -- the same comparisons in the same order, the same final
-  // arrangement, and three lane reads per level instead of eight (a batch's group selection with LimitGroups(50) over
-  // 1001 groups is ~200 serial updates per query on one wavefront: 234 us of a 0.51 ms batch with the swaps).
-  // percolateDown from the ROOT with every lane working: lane l looks at its own two children and decides where an
-  // entry of value `cur` standing at slot l would go next (the reference's two comparisons, in its order); the path from
-  // the root is then a chase through those answers -- one lane read per level -- and every slot on the path takes its
-  // chosen child's entry at once.
-  __device__ void down_root(float cur, int curk) {
-    const int lc = 2 * lane + 1, rc = 2 * lane + 2;
-    const float a0 = __int_as_float(__builtin_amdgcn_ds_bpermute(4 * (lc & 63), __float_as_int(v)));
-    const float b0 = __int_as_float(__builtin_amdgcn_ds_bpermute(4 * (rc & 63), __float_as_int(v)));
-    const bool ha = lc < size, hb = rc < size;
-    // top = l; if (lc < size && val(top) < val(lc)) top = lc; if (rc < size && val(top) < val(rc)) top = rc;
-    int nxt = -1;
-    float nv = cur;
-    if (ha && nv < a0) { nv = a0; nxt = lc; }
-    if (hb && nv < b0) { nv = b0; nxt = rc; }
-    const int kc = __builtin_amdgcn_ds_bpermute(4 * (max(nxt, 0) & 63), k);
-    unsigned long long path = 0ull;
-    int node = 0;
-    for (;;) {
-      const int n2 = readlane_i(nxt, node);
-      if (n2 < 0) break;
-      path |= 1ull << node;
-      node = n2;
-    }
-    if ((path >> lane) & 1ull) { v = nv; k = kc; }
-    if (lane == node) { v = cur; k = curk; }
-  }
-  __device__ void down(int i, float cur, int curk) {        // percolateDown, TopKHeap.scala:30-42; (cur, curk) = entry i
-    for (;;) {
-      int top = i;
-      float best = cur;
-      const int lc = 2 * i + 1, rc = 2 * i + 2;
-      if (lc < size) { const float a = val(lc); if (best < a) { best = a; top = lc; } }
-      if (rc < size) { const float b = val(rc); if (best < b) { best = b; top = rc; } }
-      if (top == i) break;
-      const int tk = key(top);
-      if (lane == i) { v = best; k = tk; }
-      i = top;
-    }
-    if (lane == i) { v = cur; k = curk; }
-  }
-  __device__ int del() {                                    // delete, TopKHeap.scala:57-67
-    size -= 1;
-    const int removed = key(0);
-    const float lv = val(size);
-    const int lk = key(size);
-#ifdef GULON_REGHEAP_SERIAL_DOWN
-    down(0, lv, lk);
-#else
-    down_root(lv, lk);
-#endif
-    return removed;
-  }
-  __device__ bool would_insert(float x) const { return size < cap || val(0) > x; }
-  __device__ void update(int kk, float x) {                 // update, TopKHeap.scala:69-79
-    if (size == cap && val(0) > x) del();
-    if (size < cap) {
-      int i = size;
-      while (i > 0) {                                       // percolateUp, TopKHeap.scala:21-28
-        const int p = (i - 1) / 2;
-        const float pv = val(p);
-        if (x > pv) {
-          const int pk = key(p);
-          if (lane == i) { v = pv; k = pk; }
-          i = p;
-        } else break;
-      }
-      if (lane == i) { v = x; k = kk; }
-      size += 1;
-    }
-  }
-};
-
-// TopKHeap.scala for k_nn > 63: the arrays in LDS (one heap per wave).  Every lane runs the same wave-uniform code
-// and reads the same entries; lane 0 stores.  (LDS operations of a wave execute in order.)  A fallback: Tests.scala
-// asks for up to 1000 neighbours, the benchmarks for 10.
-struct LdsHeap {
-  volatile float *hv;
-  volatile int *hk;
-  int size = 0;
-  int cap;
-  int lane;
-  __device__ LdsHeap(float *v_, int *k_, int cap_, int lane_) : hv(v_), hk(k_), cap(cap_), lane(lane_) {}
-  __device__ float val(int i) const { return hv[i]; }
-  __device__ int key(int i) const { return hk[i]; }
-  __device__ void put(int i, int kk, float x) { if (lane == 0) { hv[i] = x; hk[i] = kk; } }
-  __device__ void swp(int a, int b) {
-    const float va = val(a), vb = val(b);
-    const int ka = key(a), kb = key(b);
-    put(a, kb, vb);
-    put(b, ka, va);
-  }
-  __device__ void down(int i) {                             // percolateDown, TopKHeap.scala:30-42
-    for (;;) {
-      int top = i;
-      const int lc = 2 * i + 1, rc = 2 * i + 2;
-      if (lc < size && val(top) < val(lc)) top = lc;
-      if (rc < size && val(top) < val(rc)) top = rc;
-      if (top == i) break;
-      swp(i, top);
-      i = top;
-    }
-  }
-  __device__ int del() {                                    // delete, TopKHeap.scala:57-67
-    size -= 1;
-    const int removed = key(0);
-    put(0, key(size), val(size));
-    down(0);
-    return removed;
-  }
-  __device__ bool would_insert(float x) const { return size < cap || val(0) > x; }
-  __device__ void update(int kk, float x) {                 // update, TopKHeap.scala:69-79
-    if (size == cap && val(0) > x) del();
-    if (size < cap) {
-      put(size, kk, x);
-      int i = size;
-      while (i > 0) {                                       // percolateUp, TopKHeap.scala:21-28
-        const int p = (i - 1) / 2;
-        if (val(i) > val(p)) { swp(i, p); i = p; } else break;
-      }
-      size += 1;
-    }
-  }
-};
 
 // ---- coarse search: distances of every query to every group centroid -------------------------
 // MathUtils.distanceSq(centroid, query): sum of (q_e - c_e)^2, e ascending, unfused.
@@ -234,10 +97,7 @@ __global__ __launch_bounds__(64) void gq_nearest_groups(const float *__restrict_
     }
   }
   const int live = h.size;
-  for (int i = live - 1; i >= 0; i--) {                      // deleteAll(): fill from the back
-    const int kk = h.del();
-    if (lane == 0) nn[(size_t)q * stride + i] = kk;
-  }
+  h.drain([&](int i, int kk, float) { if (lane == 0) nn[(size_t)q * stride + i] = kk; });   // deleteAll()
   if (lane == 0) nn_cnt[q] = live;
 }
 
@@ -451,8 +311,8 @@ __global__ __launch_bounds__(256) void gq_select_groups(const float *__restrict_
 // queries gq_sorted_groups / gq_select_groups flagged: a TopKHeap of capacity `cap` (LimitGroups: the limit;
 // LimitVectors: all g groups) in LDS, fed the centroid distances in index order, drained in place like heapsort
 // (deleteAll fills its result from the back: slot `size` is free the moment delete() returns).  One wavefront per
-// query; every lane runs the same scalar heap code on the same LDS words (stores of equal values, broadcast reads)
-// and only the scan for centroids the heap would take is spread over the lanes.
+// query (LdsHeap: every lane runs the same scalar heap code, lane 0 stores) and only the scan for centroids the heap
+// would take is spread over the lanes.
 __global__ __launch_bounds__(64) void gq_literal_groups(const float *__restrict__ cdist, int g, int cap,
                                                         const int *__restrict__ bounds, int by_vectors, int limit,
                                                         const int *__restrict__ lit, int level, const int *__restrict__ qlist,
@@ -466,72 +326,32 @@ __global__ __launch_bounds__(64) void gq_literal_groups(const float *__restrict_
   for (int fy = blockIdx.x; fy < nq; fy += gridDim.x) {
   const int q = qlist ? qlist[fy] : fy;
   if (lit[q] != level) continue;
-  volatile float *hv = lg_lds;                                  // [cap]
-  volatile int *hk = reinterpret_cast<volatile int *>(lg_lds + cap);   // [cap]
+  LdsHeap h(lg_lds, reinterpret_cast<int *>(lg_lds + cap), cap, lane);   // [cap] values, then [cap] keys
   const float *dq = cdist + (size_t)q * g;
   bool has_nan = false;
   for (int c = lane; c < g; c += 64) has_nan = has_nan || dq[c] != dq[c];
   has_nan = __any(has_nan);
-  int size = 0;
-  auto swp = [&](int a, int b) {
-    const float va = hv[a], vb = hv[b];
-    const int ka = hk[a], kb = hk[b];
-    hv[a] = vb; hk[a] = kb; hv[b] = va; hk[b] = ka;
-  };
-  auto down = [&](int i) {                                      // percolateDown, TopKHeap.scala:30-42
-    for (;;) {
-      int top = i;
-      const int lc = 2 * i + 1, rc = 2 * i + 2;
-      if (lc < size && hv[top] < hv[lc]) top = lc;
-      if (rc < size && hv[top] < hv[rc]) top = rc;
-      if (top == i) break;
-      swp(i, top);
-      i = top;
-    }
-  };
-  auto del = [&]() {                                            // delete, TopKHeap.scala:57-67
-    size -= 1;
-    const int removed = hk[0];
-    const float lv = hv[size];
-    const int lk = hk[size];
-    hv[0] = lv; hk[0] = lk;
-    down(0);
-    return removed;
-  };
   for (int base = 0; base < g; base += 64) {
     const bool have = base + lane < g;
     const float dv = have ? dq[base + lane] : 0.f;
     // with a NaN around the heap is not ordered and every centroid goes through update; otherwise its root only falls
-    unsigned long long mk = __ballot(have && (has_nan || size < cap || hv[0] > dv));
+    unsigned long long mk = __ballot(have && (has_nan || h.size < cap || h.val(0) > dv));
     while (mk) {
       const int l = __ffsll((long long)mk) - 1;
       mk &= mk - 1;
-      const float x = readlane_f(dv, l);
-      if (size == cap && hv[0] > x) del();                      // update, TopKHeap.scala:69-79
-      if (size < cap) {
-        hv[size] = x; hk[size] = base + l;
-        int i = size;
-        while (i > 0) {                                         // percolateUp, TopKHeap.scala:21-28
-          const int p = (i - 1) / 2;
-          if (hv[i] > hv[p]) { swp(i, p); i = p; } else break;
-        }
-        size += 1;
-      }
+      h.update(base + l, readlane_f(dv, l));
     }
   }
-  const int live = size;
-  for (int j = live - 1; j >= 0; j--) {                         // deleteAll(): result(j) = delete(), j descending
-    const int kk = del();
-    hk[j] = kk;                                                 // slot j == size: outside the heap now
-  }
+  const int live = h.size;
+  h.drain([&](int j, int kk, float x) { h.put(j, kk, x); });    // deleteAll(), in place: slot j is outside the heap now
   int cnt = live;
   if (by_vectors) {                                             // searchSpace, Index.scala:289-298
     int i = 0, count = 0;
-    while (i < live && count < limit) { const int c = hk[i]; count += bounds[c + 1] - bounds[c]; i++; }
+    while (i < live && count < limit) { const int c = h.key(i); count += bounds[c + 1] - bounds[c]; i++; }
     cnt = i;
   }
   cnt = min(cnt, stride);
-  for (int e = lane; e < cnt; e += 64) nn[(size_t)q * stride + e] = hk[e];
+  for (int e = lane; e < cnt; e += 64) nn[(size_t)q * stride + e] = h.key(e);
   if (lane == 0) nn_cnt[q] = cnt;
   }
 }
@@ -1194,11 +1014,9 @@ __global__ __launch_bounds__(64) void gq_merge(const int *__restrict__ hk, const
     }
   }
   const int live = h.size;
-  for (int i = live - 1; i >= 0; i--) {                     // Result.fromHeap: max first, fill from the back
-    const float tv = h.val(0);
-    const int tk = h.del();
+  h.drain([&](int i, int tk, float tv) {                    // Result.fromHeap
     if (lane == 0) { out_idx[(size_t)q * K + i] = tk; out_dist[(size_t)q * K + i] = tv; }
-  }
+  });
   for (int i = live + lane; i < K; i += 64) { out_idx[(size_t)q * K + i] = -1; out_dist[(size_t)q * K + i] = INFINITY; }
   if (lane == 0 && out_count) out_count[q] = live;
   }

@@ -23,55 +23,11 @@
 // case is reproduced (nan_query_fix: closed form, needs nothing but the query) -- NaN centroids on a
 // sharded index keep the (distance, row id) rule (deviations).
 #include "scan.hpp"
+#include "topk_heap.hpp"
 
 namespace gulon {
 
 namespace {
-
-// the reference's heap in registers: lane i = slot i (K <= 63); every index below is wave-uniform
-struct RegHeap {
-  float hv = 0.f;
-  int hk = 0;
-  int size = 0;
-  int lane;
-  __device__ float val(int i) const { return readlane_f(hv, i); }
-  __device__ void swp(int a, int b) {
-    const float va = readlane_f(hv, a), vb = readlane_f(hv, b);
-    const int ka = readlane_i(hk, a), kb = readlane_i(hk, b);
-    if (lane == a) { hv = vb; hk = kb; }
-    if (lane == b) { hv = va; hk = ka; }
-  }
-  __device__ void down(int i) {                       // percolateDown, TopKHeap.scala:30-42
-    for (;;) {
-      int top = i;
-      const int lc = 2 * i + 1, rc = 2 * i + 2;
-      if (lc < size && val(top) < val(lc)) top = lc;
-      if (rc < size && val(top) < val(rc)) top = rc;
-      if (top == i) break;
-      swp(i, top);
-      i = top;
-    }
-  }
-  __device__ void del() {                             // delete, TopKHeap.scala:57-67
-    size -= 1;
-    const float lv = readlane_f(hv, size);
-    const int lk = readlane_i(hk, size);
-    if (lane == 0) { hv = lv; hk = lk; }
-    down(0);
-  }
-  __device__ void update(int key, float v, int K) {   // update, TopKHeap.scala:69-79
-    if (size == K && val(0) > v) del();
-    if (size < K) {
-      if (lane == size) { hv = v; hk = key; }
-      int i = size;
-      while (i > 0) {                                 // percolateUp, TopKHeap.scala:21-28
-        const int p = (i - 1) / 2;
-        if (val(i) > val(p)) { swp(i, p); i = p; } else break;
-      }
-      size += 1;
-    }
-  }
-};
 
 template <int VEC>
 __global__ __launch_bounds__(64) void literal_nonfinite(
@@ -129,8 +85,7 @@ __global__ __launch_bounds__(64) void literal_nonfinite(
       lb = __any(any) ? lb + mn : NAN;
     }
 
-    RegHeap h;
-    h.lane = lane;
+    RegHeap h(K, lane);
     bool heap_has_nan = false;
     const Word *cw = reinterpret_cast<const Word *>(codes);
     const int rb0 = row_from / 64, rb1 = (row_until + 63) / 64;
@@ -154,7 +109,7 @@ __global__ __launch_bounds__(64) void literal_nonfinite(
         const float v = readlane_f(acc, l);
         const int before = h.size;
         const bool ins = before < K || h.val(0) > v;
-        h.update(rb * 64 + l + row_base, v, K);
+        h.update(rb * 64 + l + row_base, v);
         if (ins && !(v == v)) heap_has_nan = true;
         if (h.size == K && !heap_has_nan && before == K) {
           // full, ordered heap: drop the lanes the new (lower) root already rules out
@@ -162,14 +117,10 @@ __global__ __launch_bounds__(64) void literal_nonfinite(
         }
       }
     }
-    // Result.fromHeap (Index.scala:83-94): max first, filled from the back
     const int live = h.size;
-    for (int i = live - 1; i >= 0; i--) {
-      const float tv = h.val(0);
-      const int tk = readlane_i(h.hk, 0);
+    h.drain([&](int i, int tk, float tv) {                  // Result.fromHeap
       if (lane == 0) { out_idx[(size_t)q * K + i] = tk; out_dist[(size_t)q * K + i] = tv; }
-      h.del();
-    }
+    });
     if (lane >= live && lane < K) { out_idx[(size_t)q * K + lane] = -1; out_dist[(size_t)q * K + lane] = INFINITY; }
     if (lane == 0) {
       if (out_count) out_count[q] = live;

@@ -24,6 +24,7 @@
 //            drained like Result.fromHeap.
 // Distances are the same bit-exact j-ordered sums as in the main scan.
 #include "scan.hpp"
+#include "topk_heap.hpp"
 
 namespace gulon {
 
@@ -441,73 +442,19 @@ __global__ __launch_bounds__(256) void rp_heap(const int *__restrict__ packs, in
     if (kept > RP_KEEP) continue;
     if (dbg && tid == 0 && f == 0) dbg[3] = wall_clock64();
     if (tid < 64) {
-      // the heap lives in registers: lane i = slot i (K <= 63); every index below is wave-uniform
       const int lane = tid;
-      float hv = 0.f;
-      int hk = 0;
-      int size = 0;
-      // percolateDown from the root with every lane working (grouped.hip's RegHeap::down_root): lane l decides from its
-      // own two children where an entry of value `cur` standing at slot l would go next -- the reference's two
-      // comparisons in its order --, the path from the root is a chase through those answers and the slots on it take
-      // their chosen child's entry at once
-      auto down_root = [&](float cur, int curk) {
-        const int lc = 2 * lane + 1, rc = 2 * lane + 2;
-        const float a0 = __int_as_float(__builtin_amdgcn_ds_bpermute(4 * (lc & 63), __float_as_int(hv)));
-        const float b0 = __int_as_float(__builtin_amdgcn_ds_bpermute(4 * (rc & 63), __float_as_int(hv)));
-        int nxt = -1;
-        float nv = cur;
-        if (lc < size && nv < a0) { nv = a0; nxt = lc; }
-        if (rc < size && nv < b0) { nv = b0; nxt = rc; }
-        const int kc = __builtin_amdgcn_ds_bpermute(4 * (max(nxt, 0) & 63), hk);
-        unsigned long long path = 0ull;
-        int node = 0;
-        for (;;) {
-          const int n2 = readlane_i(nxt, node);
-          if (n2 < 0) break;
-          path |= 1ull << node;
-          node = n2;
-        }
-        if ((path >> lane) & 1ull) { hv = nv; hk = kc; }
-        if (lane == node) { hv = cur; hk = curk; }
-      };
-      auto del = [&]() {                                        // delete, TopKHeap.scala:57-67
-        size -= 1;
-        const float lv = readlane_f(hv, size);
-        const int lk = readlane_i(hk, size);
-        down_root(lv, lk);
-      };
+      RegHeap h(K, lane);
       for (int base = 0; base < kept; base += 64) {
         const float ev = base + lane < kept ? sv[base + lane] : 0.f;
         const int ek = base + lane < kept ? si[base + lane] : 0;
         const int ne = min(64, kept - base);
-        for (int e = 0; e < ne; e++) {
-          const float v = readlane_f(ev, e);
-          const int kk = readlane_i(ek, e);
-          if (size == K && readlane_f(hv, 0) > v) del();        // update, TopKHeap.scala:69-79
-          if (size < K) {
-            int i = size;
-            while (i > 0) {                                     // percolateUp, TopKHeap.scala:21-28
-              const int p = (i - 1) / 2;
-              const float pv = readlane_f(hv, p);
-              if (v > pv) {
-                const int pk = readlane_i(hk, p);
-                if (lane == i) { hv = pv; hk = pk; }
-                i = p;
-              } else break;
-            }
-            if (lane == i) { hv = v; hk = kk; }
-            size += 1;
-          }
-        }
+        for (int e = 0; e < ne; e++) h.update(readlane_i(ek, e), readlane_f(ev, e));
       }
       const int q = p0.list()[f];
-      const int live = size;
-      for (int i = live - 1; i >= 0; i--) {                     // Result.fromHeap: max first, fill from the back
-        const float tv = readlane_f(hv, 0);
-        const int tk = readlane_i(hk, 0);
+      const int live = h.size;
+      h.drain([&](int i, int tk, float tv) {                    // Result.fromHeap
         if (lane == 0) { out_idx[(size_t)q * K + i] = tk; out_dist[(size_t)q * K + i] = tv; }
-        del();
-      }
+      });
       if (lane >= live && lane < K) { out_idx[(size_t)q * K + lane] = -1; out_dist[(size_t)q * K + lane] = INFINITY; }
       if (lane == 0) {
         if (out_count) out_count[q] = live;
