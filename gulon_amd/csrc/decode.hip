@@ -1,0 +1,256 @@
+// Decoding rows of a device-resident PQIndex back into vectors, on the device:
+//   ProductQuantizer.decode(EncodedVector) (ProductQuantizer.scala:37-50)  -- decode_rows_kernel
+//   GroupedIndex.lookup (Index.scala:247-253)                               -- the same kernel with a group base
+//   MathUtils.normalize (MathUtils.scala:100-120), fused behind a flag        -- for cosine query-by-row
+//   ProductQuantizer.decode(EncodedMatrix) (ProductQuantizer.scala:58-78)  -- decode_range_kernel (bandwidth-bound)
+// A decoded coordinate is a copy of a codebook entry (plus one fp32 add for the grouped lookup), so results are
+// bit-exact by construction.  Codes are read in the layout the handle already keeps (scan.hip / wide.hip):
+//   byte codes (widths 0/2/4/8): codes[(((i >> 6) * ng + j / vec) * 64 + (i & 63)) * vec + j % vec]
+//   wide codes (10/12/16):       wcodes[((i >> 6) * m + j) * 64 + (i & 63)]
+#include "scan.hpp"
+
+namespace gulon {
+namespace {
+
+// Vectors.subvectors (Vectors.scala:84-104) inverted: the quantizer that coordinate e belongs to.  The first `full`
+// quantizers are `ideal` wide, the rest ideal - 1 (common.hpp subvectors, from which ix->from / ix->sdim are made).
+struct SubvectorMap {
+  int ideal, full;
+  __host__ __device__ SubvectorMap(int d, int m) : ideal((d + m - 1) / m), full(m - ((d + m - 1) / m * m - d)) {}
+  __device__ int quantizer(int e) const {
+    const int split = full * ideal;
+    return e < split ? e / ideal : full + (e - split) / (ideal - 1);
+  }
+  __device__ int from(int j) const { return j < full ? j * ideal : full * ideal + (j - full) * (ideal - 1); }
+  __device__ int sdim(int j) const { return j < full ? ideal : ideal - 1; }
+};
+
+struct CodeSrc {
+  const uint8_t *codes;     // byte layout (nullptr when wide)
+  const uint16_t *wcodes;   // wide layout
+  int ng, vec, m;
+  __device__ int code(long long i, int j) const {
+    if (wcodes) return wcodes[((size_t)(i >> 6) * m + j) * 64 + (i & 63)];
+    return codes[(((size_t)(i >> 6) * ng + j / vec) * 64 + (i & 63)) * vec + j % vec];
+  }
+};
+
+// java.util.Arrays.binarySearch(int[] a, int key), restated literally (an empty group repeats an offset: the
+// search may land on any of the equal entries, which is what the reference's lookup then uses).
+__device__ int java_binary_search(const int *__restrict__ a, int len, int key) {
+  int low = 0, high = len - 1;
+  while (low <= high) {
+    const int mid = (int)((unsigned)(low + high) >> 1);
+    const int v = a[mid];
+    if (v < key) low = mid + 1;
+    else if (v > key) high = mid - 1;
+    else return mid;
+  }
+  return -(low + 1);
+}
+
+// One workgroup (one wavefront) per requested row.  gcent != nullptr: GroupedIndex.lookup, base = the centroid of
+// the partition the reference's binarySearch over the raw offsets names, out = base + decode(row) (MathUtils.add,
+// MathUtils.scala:63-71).  normalize: MathUtils.normalize of the result.  A row outside [0, n) gives an all-NaN
+// vector and sets *err (nothing is read for it).
+__global__ __launch_bounds__(64) void decode_rows_kernel(CodeSrc src, const float *__restrict__ cents, int n, int d, int k,
+                                                         const int *__restrict__ rows, const float *__restrict__ gcent,
+                                                         const int *__restrict__ offsets, int n_offsets, int normalize,
+                                                         float *__restrict__ out, int *__restrict__ err) {
+  extern __shared__ float xs[];   // [d]
+  const int r = blockIdx.x, lane = threadIdx.x;
+  const int row = rows[r];
+  float *o = out + (size_t)r * d;
+  if (row < 0 || row >= n) {
+    for (int e = lane; e < d; e += 64) o[e] = __int_as_float(0x7FC00000);
+    if (lane == 0 && err) *err = 1;
+    return;
+  }
+  const SubvectorMap sv(d, src.m);
+  const float *base = nullptr;
+  if (gcent) {
+    const int i = java_binary_search(offsets, n_offsets, row);
+    base = gcent + (size_t)(i < 0 ? -i - 1 : i + 1) * d;
+  }
+  for (int e = lane; e < d; e += 64) {
+    const int j = sv.quantizer(e), fr = sv.from(j), sj = sv.sdim(j);
+    const float c = cents[(size_t)k * fr + (size_t)src.code(row, j) * sj + (e - fr)];
+    xs[e] = base ? base[e] + c : c;
+  }
+  if (!normalize) {
+    for (int e = lane; e < d; e += 64) o[e] = xs[e];
+    return;
+  }
+  __syncthreads();
+  // MathUtils.distance(xs): sequential fp32 sum of x * x in coordinate order (every lane computes it; the LDS reads
+  // are broadcasts), math.sqrt in double, .toFloat
+  float sum = 0.f;
+  for (int e = 0; e < d; e++) { const float x = xs[e]; sum += x * x; }
+  const float dist = (float)__dsqrt_rn((double)sum);
+  for (int e = lane; e < d; e += 64) o[e] = __fdiv_rn(xs[e], dist);
+}
+
+// Rows [from, until) into out[(i - from) * d + e].  One workgroup per 64-row block: the block's codes are staged in LDS
+// once (16-byte loads), then the block's slice of the output -- contiguous in row-major order -- is written with
+// 16-byte stores, consecutive lanes on consecutive addresses (VEC4: d % 4 == 0, so a float4 never spans two rows and
+// every row starts 16-byte aligned).  Centroids are read through the caches (k * d * 4 bytes).
+constexpr int DR_THREADS = 256;
+template <bool WIDE, bool VEC4>
+__global__ __launch_bounds__(DR_THREADS) void decode_range_kernel(CodeSrc src, const float *__restrict__ cents, int d,
+                                                                  int k, int from, int until, int rb0,
+                                                                  float *__restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lcode[];
+  const int rb = rb0 + blockIdx.x;
+  const int tid = threadIdx.x;
+  const int m = src.m;
+  // stage: byte layout [ng][64][vec] bytes, wide [m][64] uint16 -- both contiguous per block, multiples of 16 bytes
+  const int chunk = WIDE ? m * 128 : src.ng * 64 * src.vec;
+  const uint4 *gsrc = WIDE ? (const uint4 *)(src.wcodes + (size_t)rb * m * 64)
+                           : (const uint4 *)(src.codes + (size_t)rb * chunk);
+  for (int t = tid; t < chunk / 16; t += DR_THREADS) ((uint4 *)lcode)[t] = gsrc[t];
+  __syncthreads();
+  const int r_lo = max(rb * 64, from), r_hi = min(rb * 64 + 64, until);
+  const SubvectorMap sv(d, m);
+  auto code_of = [&](int l, int j) -> int {
+    if (WIDE) return ((const uint16_t *)lcode)[j * 64 + l];
+    return lcode[(j / src.vec) * 64 * src.vec + l * src.vec + j % src.vec];
+  };
+  auto value = [&](int l, int e) -> float {
+    const int j = sv.quantizer(e), fr = sv.from(j), sj = sv.sdim(j);
+    return cents[(size_t)k * fr + (size_t)code_of(l, j) * sj + (e - fr)];
+  };
+  float *o = out + (size_t)(r_lo - from) * d;
+  const int total = (r_hi - r_lo) * d;          // floats of this block's output
+  const int l0 = r_lo - rb * 64;
+  if (VEC4) {
+    for (int f = tid * 4; f < total; f += DR_THREADS * 4) {
+      const int l = l0 + f / d, e = f % d;
+      f32x4 v;
+      v.x = value(l, e); v.y = value(l, e + 1); v.z = value(l, e + 2); v.w = value(l, e + 3);
+      *(gptr<f32x4>)as_global(o + f) = v;
+    }
+  } else {
+    for (int f = tid; f < total; f += DR_THREADS) o[f] = value(l0 + f / d, f % d);
+  }
+}
+
+CodeSrc code_src(const gulon_index *ix) {
+  CodeSrc s;
+  s.codes = ix->wide ? nullptr : ix->codes.p;
+  s.wcodes = ix->wide ? ix->wcodes.p : nullptr;
+  s.ng = ix->ng; s.vec = ix->vec; s.m = ix->m;
+  return s;
+}
+
+void check_rows_host(const gulon_index *ix, const int32_t *rows, int b) {
+  for (int r = 0; r < b; r++)
+    GULON_REQUIRE(rows[r] >= 0 && rows[r] < ix->n, "row %d = %d outside [0, %d)", r, rows[r], ix->n);
+}
+
+}  // namespace
+
+void ensure_row_err(gulon_index *ix) {
+  if (ix->row_err.n) return;
+  ix->row_err.alloc(1);
+  HIP_CHECK(hipMemset(ix->row_err.p, 0, sizeof(int)));
+}
+
+int take_row_err(gulon_index *ix) {
+  int v = 0;
+  if (ix->row_err.n == 0) return 0;
+  HIP_CHECK(hipDeviceSynchronize());
+  HIP_CHECK(hipMemcpy(&v, ix->row_err.p, sizeof(int), hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemset(ix->row_err.p, 0, sizeof(int)));
+  return v;
+}
+
+void launch_decode_rows(const gulon_index *ix, const int *d_rows, int b, const float *gcent, const int *offsets,
+                        int n_offsets, bool normalize, float *d_out, int *d_err, hipStream_t st) {
+  GULON_REQUIRE(b >= 0, "batch size must be non-negative");
+  GULON_UNSUPPORTED((size_t)ix->d * sizeof(float) > 64 * 1024, "d = %d: a decoded row does not fit in LDS", ix->d);
+  if (b == 0) return;
+  GULON_REQUIRE(d_rows != nullptr && d_out != nullptr, "null argument");
+  hipLaunchKernelGGL(decode_rows_kernel, dim3(b), dim3(64), (size_t)ix->d * sizeof(float), st, code_src(ix), ix->cents.p,
+                     ix->n, ix->d, ix->k, d_rows, gcent, offsets, n_offsets, normalize ? 1 : 0, d_out, d_err);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_decode_range(const gulon_index *ix, int from, int until, float *d_out, hipStream_t st) {
+  GULON_REQUIRE(0 <= from && from <= until && until <= ix->n, "expected: 0 <= from <= until <= length");
+  if (from == until) return;
+  const int rb0 = from / 64, nrb = ceil_div(until, 64) - rb0;
+  const size_t lds = ix->wide ? (size_t)ix->m * 128 : (size_t)ix->ng * 64 * ix->vec;
+  GULON_UNSUPPORTED(lds > 64 * 1024, "m = %d: one row block's codes do not fit in LDS", ix->m);
+  const bool v4 = ix->d % 4 == 0;
+#define DR(W, V) hipLaunchKernelGGL((decode_range_kernel<W, V>), dim3(nrb), dim3(DR_THREADS), lds, st, code_src(ix), \
+                                    ix->cents.p, ix->d, ix->k, from, until, rb0, d_out)
+  if (ix->wide) { if (v4) DR(true, true); else DR(true, false); }
+  else { if (v4) DR(false, true); else DR(false, false); }
+#undef DR
+  HIP_CHECK(hipGetLastError());
+}
+
+void decode_rows_host(const gulon_index *ix, DevBuf<int> &rows_buf, DevBuf<float> &out_buf, const int32_t *rows, int b,
+                      const float *gcent, const int *offsets, int n_offsets, bool normalize, float *out,
+                      hipStream_t st) {
+  GULON_REQUIRE(b >= 0, "batch size must be non-negative");
+  GULON_REQUIRE(b == 0 || (rows != nullptr && out != nullptr), "null argument");
+  check_rows_host(ix, rows, b);
+  if (b == 0) return;
+  rows_buf.upload(rows, (size_t)b, st);
+  out_buf.ensure((size_t)b * ix->d);
+  launch_decode_rows(ix, rows_buf.p, b, gcent, offsets, n_offsets, normalize, out_buf.p, nullptr, st);
+  out_buf.download(out, (size_t)b * ix->d, st);
+  HIP_CHECK(hipStreamSynchronize(st));
+}
+
+}  // namespace gulon
+
+using namespace gulon;
+
+GULON_API int32_t gulon_index_decode_rows(gulon_index *idx, const int32_t *rows, int32_t b, int32_t normalize,
+                                          float *out) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr, "index is null");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    idx->pend_b = -1;
+    StreamOrder so(idx, nullptr);
+    decode_rows_host(idx, idx->stage_rows, idx->stage_q, rows, b, nullptr, nullptr, 0, normalize != 0, out, nullptr);
+    so.done();
+  });
+}
+
+GULON_API int32_t gulon_index_decode_rows_dev(gulon_index *idx, const int32_t *d_rows, int32_t b, int32_t normalize,
+                                              float *d_out, void *stream) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr, "index is null");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    ensure_row_err(idx);
+    launch_decode_rows(idx, d_rows, b, nullptr, nullptr, 0, normalize != 0, d_out, idx->row_err.p, (hipStream_t)stream);
+  });
+}
+
+GULON_API int32_t gulon_index_decode_dataset(gulon_index *idx, int32_t from, int32_t until, gulon_dataset **out) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr && out != nullptr, "null argument");
+    *out = nullptr;
+    GULON_REQUIRE(0 <= from && from <= until && until <= idx->n, "expected: 0 <= from <= until <= length");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    std::unique_ptr<gulon_dataset> ds(new gulon_dataset());
+    ds->n = until - from; ds->d = idx->d;
+    ds->x.alloc(std::max<size_t>((size_t)ds->n * ds->d, 1));
+    StreamOrder so(idx, nullptr);
+    launch_decode_range(idx, from, until, ds->x.p, nullptr);
+    so.done();
+    HIP_CHECK(hipStreamSynchronize(nullptr));
+    *out = ds.release();
+  });
+}
+
+GULON_API int32_t gulon_index_row_error(gulon_index *idx, int32_t *out) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr && out != nullptr, "null argument");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    *out = take_row_err(idx);
+  });
+}

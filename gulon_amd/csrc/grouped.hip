@@ -36,6 +36,8 @@ struct gulon_grouped_index {
   // scratch (grown on demand under mu)
   DevBuf<float> q_dev, cdist, hv, od;
   DevBuf<int> nn, nn_cnt, hk, hs, oi, oc, qlist, qcount, sel_ok, nn_sized, lit_flag;
+  DevBuf<int> rows_dev;            // row ids of the host-pointer lookup / query-by-row calls
+  DevBuf<float> lq;                // decoded queries of gulon_grouped_index_query_rows_dev
   DevBuf<float> wide_tables;       // k > 256: residual tables, one slot per workgroup of gq_group_scan_wide
   // approximate pre-selection (gq_approx_scan): |g + decode(codes_i)|^2 per row, its maximum, per-query tables, lists
   DevBuf<float> xnorm, ptab, apv, amv;
@@ -1493,5 +1495,84 @@ GULON_API int32_t gulon_grouped_index_batch_query(gulon_grouped_index *idx, cons
     if (bk) { idx->oi.download(out_idx, bk, st); idx->od.download(out_dist, bk, st); }
     if (b > 0 && out_count) idx->oc.download(out_count, b, st);
     HIP_CHECK(hipStreamSynchronize(st));
+  });
+}
+
+// ---- GroupedIndex.lookup (Index.scala:247-253) on row ids: centroids(partition) + decode(row), the partition found as
+// the reference finds it -- Arrays.binarySearch(offsets, row), then i < 0 ? -i - 1 : i + 1 -- on the RAW offsets
+// (bounds[1..g-1]).  Where offsets repeat (empty groups) that can be another group than the row's own (clusterOf's
+// searchsorted(side = right)); the reference adds that group's centroid, and so does this (decode.hip).
+GULON_API int32_t gulon_grouped_index_lookup_rows(gulon_grouped_index *idx, const int32_t *rows, int32_t b,
+                                                  int32_t normalize, float *out) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr, "index is null");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    decode_rows_host(idx->pq, idx->rows_dev, idx->q_dev, rows, b, idx->gcent.p, idx->bounds.p + 1, idx->g - 1,
+                     normalize != 0, out, nullptr);
+  });
+}
+
+GULON_API int32_t gulon_grouped_index_lookup_rows_dev(gulon_grouped_index *idx, const int32_t *d_rows, int32_t b,
+                                                      int32_t normalize, float *d_out, void *stream) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr, "index is null");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    ensure_row_err(idx->pq);
+    launch_decode_rows(idx->pq, d_rows, b, idx->gcent.p, idx->bounds.p + 1, idx->g - 1, normalize != 0, d_out,
+                       idx->pq->row_err.p, (hipStream_t)stream);
+  });
+}
+
+// Index.queryByWord (Index.scala:38-45) for a GroupedIndex on row ids: the lookup above (normalize: MathUtils.normalize,
+// as GroupedIndex.query does for a normalized metric, :265-268), then gulon_grouped_index_batch_query on one stream.
+GULON_API int32_t gulon_grouped_index_query_rows_dev(gulon_grouped_index *idx, const int32_t *d_rows, int32_t b,
+                                                     int32_t k_nn, int32_t normalize, int32_t strategy, int32_t limit,
+                                                     int32_t *d_out_idx, float *d_out_dist, int32_t *d_out_count,
+                                                     void *stream) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr, "index is null");
+    GULON_REQUIRE(b >= 0 && k_nn >= 0, "k and batch size must be non-negative");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    const hipStream_t st = (hipStream_t)stream;
+    ensure_row_err(idx->pq);
+    idx->lq.ensure((size_t)b * idx->d + 1);
+    launch_decode_rows(idx->pq, d_rows, b, idx->gcent.p, idx->bounds.p + 1, idx->g - 1, normalize != 0, idx->lq.p,
+                       idx->pq->row_err.p, st);
+    run_grouped_query(idx, idx->lq.p, b, k_nn, strategy, limit, d_out_idx, d_out_dist, d_out_count, st);
+  });
+}
+
+GULON_API int32_t gulon_grouped_index_query_rows(gulon_grouped_index *idx, const int32_t *rows, int32_t b, int32_t k_nn,
+                                                 int32_t normalize, int32_t strategy, int32_t limit, int32_t *out_idx,
+                                                 float *out_dist, int32_t *out_count) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr, "index is null");
+    GULON_REQUIRE(b >= 0 && k_nn >= 0, "k and batch size must be non-negative");
+    GULON_REQUIRE(b == 0 || rows != nullptr, "rows is null");
+    for (int r = 0; r < b; r++)   // checked before anything is launched
+      GULON_REQUIRE(rows[r] >= 0 && rows[r] < idx->n, "row %d = %d outside [0, %d)", r, rows[r], idx->n);
+    std::lock_guard<std::mutex> lock(idx->mu);
+    const size_t bk = (size_t)b * (size_t)k_nn;
+    idx->q_dev.ensure((size_t)b * idx->d + 1);
+    idx->rows_dev.ensure((size_t)b + 1);
+    idx->oi.ensure(bk + 1); idx->od.ensure(bk + 1); idx->oc.ensure((size_t)b + 1);
+    hipStream_t st = nullptr;
+    if (b > 0) {
+      HIP_CHECK(hipMemcpyAsync(idx->rows_dev.p, rows, sizeof(int32_t) * (size_t)b, hipMemcpyHostToDevice, st));
+      launch_decode_rows(idx->pq, idx->rows_dev.p, b, idx->gcent.p, idx->bounds.p + 1, idx->g - 1, normalize != 0,
+                         idx->q_dev.p, nullptr, st);
+    }
+    run_grouped_query(idx, idx->q_dev.p, b, k_nn, strategy, limit, idx->oi.p, idx->od.p, idx->oc.p, st);
+    if (bk) { idx->oi.download(out_idx, bk, st); idx->od.download(out_dist, bk, st); }
+    if (b > 0 && out_count) idx->oc.download(out_count, b, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+  });
+}
+
+GULON_API int32_t gulon_grouped_index_row_error(gulon_grouped_index *idx, int32_t *out) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr && out != nullptr, "null argument");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    *out = take_row_err(idx->pq);
   });
 }

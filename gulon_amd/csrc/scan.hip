@@ -1338,3 +1338,67 @@ GULON_API int32_t gulon_prepare_query(const float *cents, int32_t d, int32_t m, 
     HIP_CHECK(hipDeviceSynchronize());
   });
 }
+
+// ---- query by stored rows (Index.queryByWord, Index.scala:38-45, with SortedIndex.lookup, Index.scala:318-319):
+// decode the rows on the device (decode.hip), optionally MathUtils.normalize them (SortedIndex.prepare for a
+// normalized metric, Index.scala:324-331), then the batch query of gulon_index_batch_query, all on one stream.  The
+// decoded queries live in the handle's (or host context's) stage_q.
+GULON_API int32_t gulon_index_query_rows_dev(gulon_index *idx, const int32_t *d_rows, int32_t b, int32_t k_nn,
+                                             int32_t normalize, int32_t from, int32_t until, int32_t *d_out_idx,
+                                             float *d_out_dist, int32_t *d_out_count, int32_t *d_out_flags,
+                                             void *stream) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr, "index is null");
+    GULON_REQUIRE(b >= 0 && k_nn >= 0, "k and batch size must be non-negative");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    idx->pend_b = -1;
+    const hipStream_t st = (hipStream_t)stream;
+    StreamOrder so(idx, st);
+    ensure_row_err(idx);
+    idx->stage_q.ensure((size_t)b * idx->d + 1);
+    launch_decode_rows(idx, d_rows, b, nullptr, nullptr, 0, normalize != 0, idx->stage_q.p, idx->row_err.p, st);
+    run_query(idx, idx->stage_q.p, b, k_nn, from, until, true, d_out_idx, d_out_dist, d_out_count, d_out_flags, nullptr,
+              nullptr, st);
+    so.done();
+  });
+}
+
+GULON_API int32_t gulon_index_query_rows(gulon_index *idx, const int32_t *rows, int32_t b, int32_t k_nn,
+                                         int32_t normalize, int32_t from, int32_t until, int32_t *out_idx,
+                                         float *out_dist, int32_t *out_count, int32_t *out_flags) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr, "index is null");
+    GULON_REQUIRE(b >= 0 && k_nn >= 0, "k and batch size must be non-negative");
+    GULON_REQUIRE(b == 0 || rows != nullptr, "rows is null");
+    for (int r = 0; r < b; r++)   // checked before anything is launched
+      GULON_REQUIRE(rows[r] >= 0 && rows[r] < idx->n, "row %d = %d outside [0, %d)", r, rows[r], idx->n);
+    gulon_index *c = acquire_host_context(idx);
+    struct Release { gulon_index *i, *c; ~Release() { release_host_context(i, c); } } rel{idx, c};
+    std::lock_guard<std::mutex> lock(c->mu);
+    c->pend_b = -1;
+    const size_t bk = (size_t)b * (size_t)k_nn;
+    c->stage_q.ensure((size_t)b * c->d + 1);
+    c->stage_rows.ensure((size_t)b + 1);
+    c->stage_oi.ensure(bk + 1);
+    c->stage_od.ensure(bk + 1);
+    c->stage_oc.ensure((size_t)b + 1);
+    c->stage_of.ensure((size_t)b + 1);
+    if (!c->host_stream) HIP_CHECK(hipStreamCreateWithFlags(&c->host_stream, hipStreamNonBlocking));
+    hipStream_t st = c->host_stream;
+    StreamOrder so(c, st);
+    if (b > 0) {
+      HIP_CHECK(hipMemcpyAsync(c->stage_rows.p, rows, sizeof(int32_t) * (size_t)b, hipMemcpyHostToDevice, st));
+      launch_decode_rows(c, c->stage_rows.p, b, nullptr, nullptr, 0, normalize != 0, c->stage_q.p, nullptr, st);
+    }
+    run_query(c, c->stage_q.p, b, k_nn, from, until, true, c->stage_oi.p, c->stage_od.p, c->stage_oc.p,
+              c->stage_of.p, nullptr, nullptr, st);
+    if (bk) {
+      c->stage_oi.download(out_idx, bk, st);
+      c->stage_od.download(out_dist, bk, st);
+    }
+    if (b > 0 && out_count) c->stage_oc.download(out_count, b, st);
+    if (b > 0 && out_flags) c->stage_of.download(out_flags, b, st);
+    so.done();
+    HIP_CHECK(hipStreamSynchronize(st));
+  });
+}

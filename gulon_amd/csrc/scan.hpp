@@ -52,6 +52,8 @@ struct gulon_index {
   DevBuf<int> stage_oi, stage_oc, stage_of;
   DevBuf<float> stage_od;
   DevBuf<int> flags_scratch;
+  DevBuf<int> stage_rows;  // row ids of the host-pointer decode / query-by-row calls (decode.hip)
+  DevBuf<int> row_err;     // set by the row decode when a *_dev call asked for a row outside [0, n)
   DevBuf<unsigned long long> dbg;   // GULON_SCAN_TIMELINE stamps
   // large-K peeling rounds
   DevBuf<float> peel_v, peel_tv, peel_lbv;
@@ -251,4 +253,16 @@ void run_tie_replay(gulon_index *ix, const float *dQ, int B, int K, int from, in
 void launch_conflict_order(const uint8_t *src, uint8_t *dst, uint8_t *perm, long long nblk, int nq, int rounds,
                            hipStream_t st);
 bool conflict_order_windowed();   // the ordering spans windows of four blocks (default) or single blocks
+// decode.hip: rows of the index back into vectors (ProductQuantizer.decode, GroupedIndex.lookup).  gcent != nullptr:
+// out = gcent[partition] + decode(row), the partition by Arrays.binarySearch over offsets[0..n_offsets); normalize:
+// MathUtils.normalize of the result.  d_rows / d_out are device pointers; rows outside [0, n) give NaN rows and set
+// *d_err (nullable).  launch_decode_range: rows [from, until) into d_out [until - from][d].
+void launch_decode_rows(const gulon_index *ix, const int *d_rows, int b, const float *gcent, const int *offsets,
+                        int n_offsets, bool normalize, float *d_out, int *d_err, hipStream_t st);
+void launch_decode_range(const gulon_index *ix, int from, int until, float *d_out, hipStream_t st);
+// host rows (checked: GULON_ERR_INVALID_ARGUMENT before any launch) -> host out, through the given scratch; synchronises
+void decode_rows_host(const gulon_index *ix, DevBuf<int> &rows_buf, DevBuf<float> &out_buf, const int32_t *rows, int b,
+                      const float *gcent, const int *offsets, int n_offsets, bool normalize, float *out, hipStream_t st);
+void ensure_row_err(gulon_index *ix);   // the handle's row_err word, allocated and zeroed on first use
+int take_row_err(gulon_index *ix);      // synchronises; returns and clears it
 }  // namespace gulon

@@ -134,6 +134,41 @@ class GroupedIndex:
     def query(self, k, query):                                   # Index.scala:265-282
         return self.batch_query(k, N.f32(query).reshape(1, -1))[0]
 
+    def lookup_rows(self, rows):
+        """GroupedIndex.lookup (Index.scala:247-253) of every row id in `rows`, on the device:
+        centroids(partition) + decode(row), the partition by the reference's Arrays.binarySearch(offsets, row) --
+        which, where offsets repeat, can differ from the row's own group (cluster_of)."""
+        r = N.i32(rows).reshape(-1)
+        out = np.zeros((r.size, self.dimension), np.float32)
+        if r.size:
+            N.check(N.lib().gulon_grouped_index_lookup_rows(self._h, r, r.size, 0, out.reshape(-1)))
+        else:
+            N.check(N.lib().gulon_grouped_index_lookup_rows(self._h, np.zeros(1, np.int32), 0, 0,
+                                                            np.zeros(1, np.float32)))
+        return out
+
+    def lookup_row(self, row):
+        return self.lookup_rows([row])[0]
+
+    def batch_query_rows_raw(self, k, rows):
+        r = N.i32(rows).reshape(-1)
+        b = r.size
+        s, limit = self._strategy()
+        oi = np.zeros((b, max(k, 1)), np.int32)
+        od = np.zeros((b, max(k, 1)), np.float32)
+        oc = np.zeros(max(b, 1), np.int32)
+        N.check(N.lib().gulon_grouped_index_query_rows(self._h, r if b else np.zeros(1, np.int32), b, k,
+                                                       int(self.metric == "cosine"), s, limit, oi.reshape(-1),
+                                                       od.reshape(-1), oc))
+        return oi[:, :k], od[:, :k], oc[:b]
+
+    def batch_query_rows(self, k, rows):
+        """Index.queryByWord (Index.scala:38-45) on row ids: query(k, lookup(row)) for every row, looked up (and for a
+        cosine index normalised) on the device."""
+        from .index import Result
+        oi, od, oc = self.batch_query_rows_raw(k, rows)
+        return [Result(oi[i, :oc[i]].copy(), od[i, :oc[i]].copy(), 0) for i in range(len(oc))]
+
     def close(self):
         if self._h is not None and self._h.value:
             N.lib().gulon_grouped_index_destroy(self._h)

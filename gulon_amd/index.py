@@ -131,6 +131,43 @@ class PQIndex:
             out[q.frm:q.frm + q.dimension] = q.clusters.centroids[idx[j]]
         return out
 
+    def decode_rows(self, rows, normalize=False):
+        """ProductQuantizer.decode (ProductQuantizer.scala:37-50) of every row id in `rows`, on the device
+        (gulon_index_decode_rows); normalize: MathUtils.normalize of each.  -> [len(rows)][d] float32."""
+        r = N.i32(rows).reshape(-1)
+        out = np.zeros((r.size, self.dimension), np.float32)
+        if r.size:
+            N.check(N.lib().gulon_index_decode_rows(self._h, r, r.size, int(bool(normalize)), out.reshape(-1)))
+        else:
+            N.check(N.lib().gulon_index_decode_rows(self._h, np.zeros(1, np.int32), 0, 0, np.zeros(1, np.float32)))
+        return out
+
+    def decode_matrix(self, frm=0, until=None):
+        """ProductQuantizer.decode(EncodedMatrix) (ProductQuantizer.scala:58-78) of rows [frm, until) into HBM."""
+        from .matrix import DeviceMatrix
+        until = self.length if until is None else until
+        h = C.c_void_p()
+        N.check(N.lib().gulon_index_decode_dataset(self._h, frm, until, C.byref(h)))
+        return DeviceMatrix(h, until - frm, self.dimension)
+
+    def batch_query_rows_raw(self, k, rows, frm=0, until=None, normalize=False):
+        r = N.i32(rows).reshape(-1)
+        until = self.length if until is None else until
+        b = r.size
+        oi = np.zeros((b, max(k, 1)), np.int32)
+        od = np.zeros((b, max(k, 1)), np.float32)
+        oc = np.zeros(max(b, 1), np.int32)
+        of = np.zeros(max(b, 1), np.int32)
+        N.check(N.lib().gulon_index_query_rows(self._h, r if b else np.zeros(1, np.int32), b, k, int(bool(normalize)),
+                                               frm, until, oi.reshape(-1), od.reshape(-1), oc, of))
+        return oi[:, :k], od[:, :k], oc[:b], of[:b]
+
+    def batch_query_rows(self, k, rows, frm=0, until=None, normalize=False):
+        """batchQuery(k, rows decoded) without leaving the device (gulon_index_query_rows): the same results as
+        batch_query(k, decode_rows(rows, normalize), frm, until)."""
+        oi, od, oc, of = self.batch_query_rows_raw(k, rows, frm, until, normalize)
+        return [Result(oi[i, :oc[i]].copy(), od[i, :oc[i]].copy(), int(of[i])) for i in range(len(oc))]
+
     def close(self):
         if self._h is not None and self._h.value:
             N.lib().gulon_index_destroy(self._h)
@@ -182,6 +219,14 @@ class SortedIndex:
 
     def lookup_row(self, row):                                        # Index.scala:318-319
         return self.vector_index.decode(row)
+
+    def lookup_rows(self, rows):                                      # Index.scala:318-319, on the device
+        return self.vector_index.decode_rows(rows)
+
+    def batch_query_rows(self, k, rows):
+        """Index.queryByWord (Index.scala:38-45) on row ids: query(k, lookup(row)) for every row, decoded (and for a
+        cosine index normalised, Index.scala:324-331) on the device."""
+        return self.vector_index.batch_query_rows(k, rows, normalize=self.metric == "cosine")
 
 
 class Index:

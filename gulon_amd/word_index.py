@@ -1,0 +1,102 @@
+"""An index with its words: Index.lookup / queryByWord / query (Index.scala:25-45) over a saved index file.
+
+`WordIndex.load` reads a protobuf.Index (index_file.load_index) -- the words stay on the host, the vector side is a
+device SortedIndex or GroupedIndex.  Word -> row goes through KeyIndex.Sorted / KeyIndex.Grouped (word_vectors.py,
+KeyIndex.scala:15-61); the row is looked up and queried on the device (decode.hip), so `query_by_word` queries with
+the index's DECODED vector, as the reference does."""
+import os
+from dataclasses import dataclass
+from typing import List, Optional
+
+import numpy as np
+
+from .word_vectors import KeyIndexGrouped, KeyIndexSorted
+
+BATCH = 1024          # rows per device batch of batch_query_by_words / batch_query
+
+
+@dataclass
+class WordResult:
+    """Index.Result (Index.scala:56-74): neighbour words and distances, nearest first; rows = their row ids."""
+    words: List[str]
+    distances: np.ndarray
+    rows: np.ndarray
+    flags: int = 0
+
+    def __len__(self):
+        return len(self.words)
+
+    def __iter__(self):
+        return iter(zip(self.words, self.distances.tolist()))
+
+
+class WordIndex:
+    def __init__(self, words, index):
+        from .grouped import GroupedIndex
+        self.words, self.index = list(words), index
+        if len(self.words) != index.size:
+            raise ValueError(f"{len(self.words)} words for an index of {index.size} rows")
+        self._grouped = isinstance(index, GroupedIndex)
+        self.key_index = KeyIndexGrouped(self.words, index.offsets) if self._grouped else KeyIndexSorted(self.words)
+
+    @classmethod
+    def load(cls, source):
+        """source: the bytes of a protobuf.Index, or a path to a file holding them (Index.read, Index.scala:147-149)."""
+        from .index_file import load_index
+        if isinstance(source, (bytes, bytearray, memoryview)):
+            buf = bytes(source)
+        else:
+            with open(os.fspath(source), "rb") as fh:
+                buf = fh.read()
+        words, index = load_index(buf)
+        return cls(words, index)
+
+    @property
+    def dimension(self):
+        return self.index.dimension
+
+    @property
+    def size(self):
+        return len(self.words)
+
+    def row_of(self, word) -> Optional[int]:
+        return self.key_index.lookup(word)
+
+    def lookup(self, word) -> Optional[np.ndarray]:
+        """Index.lookup (Index.scala:38): the index's approximation of the word's vector, None if it is absent."""
+        row = self.row_of(word)
+        return None if row is None else self.index.lookup_rows([row])[0]
+
+    def _result(self, r) -> WordResult:
+        return WordResult([self.words[i] for i in r.rows.tolist()], r.distances, r.rows, r.flags)
+
+    def batch_query_by_words(self, k, words) -> List[Optional[WordResult]]:
+        """Index.queryByWord (Index.scala:43-45) for every word, in order: None for a word the index lacks.  The words
+        present are queried on the device, up to BATCH per batch."""
+        words = list(words)
+        rows = [self.row_of(w) for w in words]
+        present = [i for i, r in enumerate(rows) if r is not None]
+        out: List[Optional[WordResult]] = [None] * len(words)
+        for s in range(0, len(present), BATCH):
+            part = present[s:s + BATCH]
+            results = self.index.batch_query_rows(k, np.asarray([rows[i] for i in part], np.int32))
+            for i, r in zip(part, results):
+                out[i] = self._result(r)
+        return out
+
+    def query_by_word(self, k, word) -> Optional[WordResult]:
+        return self.batch_query_by_words(k, [word])[0]
+
+    def batch_query(self, k, vectors) -> List[WordResult]:
+        """Index.batchQuery (Index.scala:25-32) with the results' words."""
+        q = np.ascontiguousarray(vectors, np.float32).reshape(-1, self.dimension)
+        out = []
+        for s in range(0, len(q), BATCH):
+            out.extend(self._result(r) for r in self.index.batch_query(k, q[s:s + BATCH]))
+        return out
+
+    def query(self, k, vector) -> WordResult:
+        return self.batch_query(k, np.asarray(vector, np.float32).reshape(1, -1))[0]
+
+    def close(self):
+        (self.index if self._grouped else self.index.vector_index).close()

@@ -199,5 +199,7 @@ class KeyedIndex:
         return [(self.vectors.word(int(i)), float(d)) for i, d in zip(r.rows, r.distances)]
 
     def query_word(self, k, word):
+        """Queries with the word's RAW vector from the WordVectors.  The reference's Index.queryByWord
+        (Index.scala:38-45) queries with the index's DECODED vector: that is gulon_amd.word_index.WordIndex.query_by_word."""
         i = self.vectors.key_index.lookup(word) if self.vectors.key_index is not None else None
         return None if i is None else self.query(k, self.vectors[i])

@@ -347,6 +347,49 @@ int32_t gulon_grouped_index_batch_query_dev(gulon_grouped_index *idx, const floa
                                             int32_t k_nn, int32_t strategy, int32_t limit, int32_t *d_out_idx,
                                             float *d_out_dist, int32_t *d_out_count, void *stream);
 
+/* ---- Decoding stored rows; query by stored row (decode.hip) ------------------------------------------
+ * Row ids are LOCAL rows of the index (0..n; for a GroupedIndex: grouped row positions).  The host-pointer forms
+ * check every id before launching anything (GULON_ERR_INVALID_ARGUMENT for one outside [0, n)).  The _dev forms take
+ * device pointers and a stream, do not synchronise, and cannot check ids on the host: a row outside [0, n) comes back
+ * as an all-NaN vector (its query as the query of an all-NaN vector) and sets the handle's row-error word, which
+ * gulon_index_row_error / gulon_grouped_index_row_error return and clear (synchronising the device).
+ * normalize != 0 applies MathUtils.normalize (MathUtils.scala:100-120: sequential fp32 sum of x * x, sqrt in double,
+ * one division per coordinate; a zero vector gives NaN) -- the handles carry no metric, so a cosine index passes 1.
+ *
+ * ProductQuantizer.decode(EncodedVector) (ProductQuantizer.scala:37-50), i.e. PQIndex.decode (Index.scala:390-391)
+ * and SortedIndex.lookup (Index.scala:318-319) for b rows: out [b][d]. */
+int32_t gulon_index_decode_rows(gulon_index *idx, const int32_t *rows, int32_t b, int32_t normalize, float *out);
+int32_t gulon_index_decode_rows_dev(gulon_index *idx, const int32_t *d_rows, int32_t b, int32_t normalize,
+                                    float *d_out, void *stream);
+/* ProductQuantizer.decode(EncodedMatrix) (ProductQuantizer.scala:58-78) of rows [from, until) into a new device
+ * dataset of until - from rows (destroy with gulon_dataset_destroy). */
+int32_t gulon_index_decode_dataset(gulon_index *idx, int32_t from, int32_t until, gulon_dataset **out);
+/* GroupedIndex.lookup (Index.scala:247-253) for b rows: centroids(partition) + decode(row), one fp32 add per
+ * coordinate (MathUtils.add, MathUtils.scala:63-71), partition = the reference's Arrays.binarySearch(offsets, row)
+ * rule -- which, where offsets repeat (empty groups), can name another group than the row's own. */
+int32_t gulon_grouped_index_lookup_rows(gulon_grouped_index *idx, const int32_t *rows, int32_t b, int32_t normalize,
+                                        float *out);
+int32_t gulon_grouped_index_lookup_rows_dev(gulon_grouped_index *idx, const int32_t *d_rows, int32_t b,
+                                            int32_t normalize, float *d_out, void *stream);
+/* Index.queryByWord (Index.scala:38-45) on row ids: PQIndex.batchQuery (Index.scala:417-440) of the decoded rows over
+ * [from, until), outputs as gulon_index_batch_query. */
+int32_t gulon_index_query_rows(gulon_index *idx, const int32_t *rows, int32_t b, int32_t k_nn, int32_t normalize,
+                               int32_t from, int32_t until, int32_t *out_idx, float *out_dist, int32_t *out_count,
+                               int32_t *out_flags);
+int32_t gulon_index_query_rows_dev(gulon_index *idx, const int32_t *d_rows, int32_t b, int32_t k_nn, int32_t normalize,
+                                   int32_t from, int32_t until, int32_t *d_out_idx, float *d_out_dist,
+                                   int32_t *d_out_count, int32_t *d_out_flags, void *stream);
+/* The same for a GroupedIndex: GroupedIndex.lookup, then GroupedIndex.batchQuery (Index.scala:254-299), outputs
+ * as gulon_grouped_index_batch_query. */
+int32_t gulon_grouped_index_query_rows(gulon_grouped_index *idx, const int32_t *rows, int32_t b, int32_t k_nn,
+                                       int32_t normalize, int32_t strategy, int32_t limit, int32_t *out_idx,
+                                       float *out_dist, int32_t *out_count);
+int32_t gulon_grouped_index_query_rows_dev(gulon_grouped_index *idx, const int32_t *d_rows, int32_t b, int32_t k_nn,
+                                           int32_t normalize, int32_t strategy, int32_t limit, int32_t *d_out_idx,
+                                           float *d_out_dist, int32_t *d_out_count, void *stream);
+int32_t gulon_index_row_error(gulon_index *idx, int32_t *out);
+int32_t gulon_grouped_index_row_error(gulon_grouped_index *idx, int32_t *out);
+
 /* Kernel timing for the roofline line of bench.py: when enabled, every scan-kernel
  * launch of this index is bracketed by hipEvents on the launch stream;
  * gulon_index_profile_read synchronises them and returns the summed duration. */
