@@ -11,11 +11,10 @@ HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fa
 SRCS = $(CSRC)/api_core.hip $(CSRC)/scan.hip $(CSRC)/knn.hip $(CSRC)/kmeans.hip $(CSRC)/kmeans_stream.hip $(CSRC)/kmeans_mfma.hip $(CSRC)/replay.hip $(CSRC)/filter.hip $(CSRC)/grouped.hip $(CSRC)/grouped_filter.hip $(CSRC)/wide.hip $(CSRC)/wide_filter.hip $(CSRC)/conflict_order.hip $(CSRC)/sharded.hip $(CSRC)/literal.hip $(CSRC)/decode.hip
 OBJS = $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 HDRS = $(CSRC)/common.hpp $(CSRC)/scan.hpp $(CSRC)/kmeans.hpp include/gulon_hip.h $(CSRC)/grouped_filter.hpp $(CSRC)/topk_heap.hpp
-# The product library carries no test code.  The self-tests of three kernels (gulon_selftest_*) and the measured-and-
-# dropped fused k-means update (kmeans_fused.hip) live in a second library that only tests/ loads: the same objects,
-# with the four files that have hooks compiled again under -DGULON_TEST_HOOKS.
+# The product library carries no test code.  The self-tests of the kernels (gulon_selftest_*) live in a second library
+# that only tests/ loads: the same objects, with the four files that have hooks compiled again under -DGULON_TEST_HOOKS.
 HOOKLIB = gulon_amd/lib/libgulon_hip_testhooks.so
-HOOKED = kmeans kmeans_stream kmeans_mfma conflict_order kmeans_fused
+HOOKED = kmeans kmeans_stream kmeans_mfma conflict_order
 HOOKOBJS = $(patsubst %,$(OBJDIR)/%.hooks.o,$(HOOKED)) $(filter-out $(patsubst %,$(OBJDIR)/%.o,$(HOOKED)),$(OBJS))
 
 all: $(LIB) $(HOOKLIB) oracle build/test_host_api

@@ -49,14 +49,6 @@ __device__ inline float table_at(const float *__restrict__ tables, int W, int m_
   return tables[(((size_t)(q / W) * m_pad + j) * 256 + c) * W + q % W];
 }
 
-#ifdef GULON_FILTER_STAMPS
-// experiment builds only (scripts/variant.sh ... -DGULON_FILTER_STAMPS): every wave of every main-stage workgroup records
-// when it started, had its tables staged and left its row loop (100 MHz wall clock) and where it ran
-// (HW_ID, XCC_ID) -> GULON_FILTER_STAMPS=<file> dumps [workgroup][52] uint64 after every main-stage launch
-__device__ unsigned long long *g_filter_stamps;
-__device__ unsigned long long *g_qt_stamps;   // qt_quantize: [workgroup][4] = entry, bounds ready, loop done, 0
-__device__ unsigned long long *g_bt_stamps;   // bound_tables: [workgroup][8] = entry, tables built, scan done, end, + 4 inside the table build
-#endif
 // ---- quantize the tables of four queries (one dword of an entry) against the current bounds ----
 __global__ __launch_bounds__(256) void qt_quantize(const float *__restrict__ tables, int W, int Bp, int m_pad, int k,
                                                    int B, const float *__restrict__ mins,
@@ -73,9 +65,6 @@ __global__ __launch_bounds__(256) void qt_quantize(const float *__restrict__ tab
   __shared__ int s_dead[4];
   __shared__ float s_mins[4 * 144];                // the four queries' table minima (m_pad <= 144)
   const int g4 = blockIdx.x, j = blockIdx.y, c = threadIdx.x;
-#ifdef GULON_FILTER_STAMPS
-  const unsigned long long qs0 = __builtin_amdgcn_s_memrealtime();
-#endif
   // everything the workgroup reads is requested up front -- its table entries, the 4 x m_pad minima (coalesced) and
   // each query's bound -- so that the memory round trips overlap
   float vv[4];
@@ -130,9 +119,6 @@ __global__ __launch_bounds__(256) void qt_quantize(const float *__restrict__ tab
     s_min[c] = s_mins[c * m_pad + j];
   }
   __syncthreads();
-#ifdef GULON_FILTER_STAMPS
-  const unsigned long long qs1 = __builtin_amdgcn_s_memrealtime();
-#endif
   // The level of an entry in fp32, rounded DOWN for certain: x = T - min (one rounding, <= 2^-24 relative), times the
   // reciprocal of delta, which the prologue shrank by 2^-21 (fp64 -> fp32, the shrinking, the subtraction, the product: four roundings of
   // 2^-24 each = 2^-22) -- they cannot carry the product above the real quotient x / delta, so  level * delta <= x  holds as the bound
@@ -156,12 +142,6 @@ __global__ __launch_bounds__(256) void qt_quantize(const float *__restrict__ tab
   // queries 4 g4 .. + 3 -> dword (4 g4 % QW) / 4 of entry [4 g4 / QW][j][c] (QW bytes per entry)
   const int grp = (g4 * 4) / QW, part = (g4 * 4 % QW) / 4;
   reinterpret_cast<uint32_t *>(qtab)[(((size_t)grp * m_pad + j) * 256 + c) * (QW / 4) + part] = word;
-#ifdef GULON_FILTER_STAMPS
-  if (c == 0 && g_qt_stamps) {
-    unsigned long long *o = g_qt_stamps + 4 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
-    o[0] = qs0; o[1] = qs1; o[2] = __builtin_amdgcn_s_memrealtime(); o[3] = 0;
-  }
-#endif
 }
 
 // ---- initial bounds from a strided sample of row blocks ---------------------------------------
@@ -256,9 +236,6 @@ __global__ __launch_bounds__(BOUND_THREADS) void bound_tables(
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qg = blockIdx.x;
-#ifdef GULON_FILTER_STAMPS
-  unsigned long long bt0 = __builtin_amdgcn_s_memrealtime(), bt1 = 0, bt2 = 0, bx[4] = {0, 0, 0, 0};
-#endif
   // (1) this batch's counters: pruning thresholds of the fallback scan, tile flags, survivor sub-queue fill levels
   for (int t = qg * BOUND_THREADS + tid; t < max(n_gtau, max(n_fb, n_cnt)); t += gridDim.x * BOUND_THREADS) {
     if (t < n_gtau) gtau[t] = 0x7F800000u;   // +inf
@@ -275,10 +252,6 @@ __global__ __launch_bounds__(BOUND_THREADS) void bound_tables(
   for (int j = wave; j < m_pad; j += NW) {
     int fr = 0, s = 0;
     if (j < m) { fr = from[j]; s = sdim[j]; }
-#ifdef GULON_FILTER_STAMPS
-    asm volatile("" :: "s"(fr), "s"(s));
-    if (j == wave) bx[0] = __builtin_amdgcn_s_memrealtime();     // sub-vector bounds arrived
-#endif
     const float *cc = cents + (size_t)k * fr;
     float mnu[W];
 #pragma unroll
@@ -325,11 +298,6 @@ __global__ __launch_bounds__(BOUND_THREADS) void bound_tables(
           }
         }
       }
-#ifdef GULON_FILTER_STAMPS
-      asm volatile("" :: "v"(acc[0]));
-      if (j == wave && i == 0) bx[1] = __builtin_amdgcn_s_memrealtime();   // first centroid group evaluated
-      if (j == wave && i == 3) bx[2] = __builtin_amdgcn_s_memrealtime();   // last centroid group evaluated
-#endif
       TV tv;
 #pragma unroll
       for (int u = 0; u < W; u++) {
@@ -347,13 +315,7 @@ __global__ __launch_bounds__(BOUND_THREADS) void bound_tables(
       if (lane == 0) mins[(size_t)(qg * W + u) * m_pad + j] = x;
     }
   }
-#ifdef GULON_FILTER_STAMPS
-  bx[3] = __builtin_amdgcn_s_memrealtime();                      // this wave's quantizers done (before the barrier)
-#endif
   __syncthreads();
-#ifdef GULON_FILTER_STAMPS
-  bt1 = __builtin_amdgcn_s_memrealtime();
-#endif
   // (3) the sample scan (see above): lane = row, every lane keeps the minimum exact distance it saw
   const Word *cw = reinterpret_cast<const Word *>(codes);
   int mp_p = wave / mp.width, mp_r = wave - mp_p * mp.width;
@@ -407,9 +369,6 @@ __global__ __launch_bounds__(BOUND_THREADS) void bound_tables(
     }
   }
   __syncthreads();                     // the table is dead: reuse LDS for the per-wave sorted minima
-#ifdef GULON_FILTER_STAMPS
-  bt2 = __builtin_amdgcn_s_memrealtime();
-#endif
   float *sv = reinterpret_cast<float *>(qlds);
 #pragma unroll
   for (int u = 0; u < W; u++) sv[(u * NW + wave) * 64 + lane] = mn[u];
@@ -430,13 +389,6 @@ __global__ __launch_bounds__(BOUND_THREADS) void bound_tables(
       if (bounds_out && lane < keff) bounds_out[(size_t)q * keff + lane] = best;   // for the other shards
     }
   }
-#ifdef GULON_FILTER_STAMPS
-  if (tid == 0 && g_bt_stamps) {
-    unsigned long long *o = g_bt_stamps + 8 * (size_t)qg;
-    o[0] = bt0; o[1] = bt1; o[2] = bt2; o[3] = __builtin_amdgcn_s_memrealtime();
-    o[4] = bx[0]; o[5] = bx[1]; o[6] = bx[2]; o[7] = bx[3];
-  }
-#endif
 }
 
 // ---- bounds shared across shards: tau0[q] = the keff-th smallest of the union of `lists` ascending
@@ -478,19 +430,6 @@ __global__ __launch_bounds__(256) void shared_tau(const float *__restrict__ all 
 // ---- the filter: lane = row, 16*NQG queries per workgroup, NADD entries summed per byte -------
 // MAIN only tags the instantiation used for the last (large) stage, so that profilers list it apart
 // from the short first stage.
-#ifdef GULON_FILTER_STAMPS
-__global__ void dummy_kernel(const int *p) { if (p == nullptr) __builtin_trap(); }
-// experiment (timing only, results are stale): GULON_SKIP = 1 bound_tables | 2 qt_quantize | 4 survivors | 8 fallback + merges | 16 main stage | 32 short first stage
-static std::atomic<int> skip_calls{0};   // batches seen; the mask applies from batch GULON_SKIP_AFTER on (default 16)
-static int skip_mask() {
-  static const int m = getenv("GULON_SKIP") ? atoi(getenv("GULON_SKIP")) : 0;
-  static const int after = getenv("GULON_SKIP_AFTER") ? atoi(getenv("GULON_SKIP_AFTER")) : 16;
-  return skip_calls.load() > after ? m : 0;
-}
-#define GULON_SKIPPED(bit) (skip_mask() & (bit))
-#else
-#define GULON_SKIPPED(bit) false
-#endif
 template <int QW> struct QEntry;                     // QW queries (one byte each) per table entry
 template <> struct QEntry<16> { using type = uint4; };
 template <> struct QEntry<8> { using type = uint2; };
@@ -515,7 +454,7 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_kernel(
   // of up front: 3.21, 3.23, 3.36; five 3.96, eight 5.58 -- the L1 path saturates quickly).  It pays only where
   // LDS is the one busy pipe: 16-byte entries, four entries summed per widening, two workgroups per CU (m <= 16);
   // with 4-byte code words, wider indexes (m = 32, 64, 100) or the 7-bit levels it measured 2-50 % slower.
-  constexpr int GLB = (QW == 16 && NQG == 1 && VEC == 16 && (NADD == 4 || NADD == 8) && NG1) ? GULON_FILTER_GLB : 0;
+  constexpr int GLB = (QW == 16 && NQG == 1 && VEC == 16 && NADD == 4 && NG1) ? GULON_FILTER_GLB : 0;
   using Word = typename CodeWord<VEC>::type;
   using QE = typename QEntry<QW>::type;
   extern __shared__ uint4 qlds_raw[];
@@ -527,10 +466,6 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_kernel(
   const int tile = MAIN == 2 ? blockIdx.y : blockIdx.x, chunk = MAIN == 2 ? blockIdx.x : blockIdx.y;
   const int ntile = MAIN == 2 ? gridDim.y : gridDim.x;
   const int tab = m_pad * 256;   // entries per QW-query group
-#ifdef GULON_FILTER_STAMPS
-  unsigned long long stamp0 = 0, stamp1 = 0;
-  if constexpr (MAIN == 1) stamp0 = __builtin_amdgcn_s_memrealtime();
-#endif
   {   // every query of this tile already goes to the exact scan: nothing to do here
     const int q_lo = tile * NQG * QW, q_hi = min(B, q_lo + NQG * QW);
     bool any_live = false;
@@ -555,9 +490,6 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_kernel(
     if (tid == 0) *reinterpret_cast<int *>(qlds_raw + n16) = NW;   // run counter: the first NW runs are the waves' own
   }
   __syncthreads();
-#ifdef GULON_FILTER_STAMPS
-  if constexpr (MAIN == 1) stamp1 = __builtin_amdgcn_s_memrealtime();
-#endif
 
   const int e0 = chunk * e_per_chunk;
   const int e1 = min(e_limit, e0 + e_per_chunk);
@@ -674,11 +606,7 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_kernel(
           }
 #pragma unroll
           for (int dd = 0; dd < DW; dd++) {
-#ifdef GULON_FILTER_MASKED_EVEN
-            acc[s][2 * dd] += xs[dd] & 0x00FF00FFu;
-#else
             acc[s][2 * dd] += xs[dd];                                                // (unmasked: see `acc`)
-#endif
             acc[s][2 * dd + 1] += __builtin_amdgcn_perm(0u, xs[dd], 0x0C030C01u);   // bytes 1 and 3
           }
         }
@@ -711,11 +639,7 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_kernel(
           }
 #pragma unroll
           for (int dd = 0; dd < DW; dd++) {
-#ifdef GULON_FILTER_MASKED_EVEN
-            acc[s][2 * dd] += xs[dd] & 0x00FF00FFu;
-#else
             acc[s][2 * dd] += xs[dd];                                                // (unmasked: see `acc`)
-#endif
             acc[s][2 * dd + 1] += __builtin_amdgcn_perm(0u, xs[dd], 0x0C030C01u);   // bytes 1 and 3
           }
         }
@@ -723,7 +647,6 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_kernel(
       return wn;
     };
     if constexpr (NG1) (void)word(0, std::true_type{}, w);
-#ifndef GULON_FILTER_WORDS_LOOP
 #define WC(G) w = word_c(std::integral_constant<int, G>{}, w)
     // (the two forms measured: BASELINE config 5's m = 64 -- 15.16 -> 14.5 ms per batch -- and the reference CLI's default
     // m = 25 -- 0.759 -> 0.716 ms.  Unrolled for every word count the kernels grew to the 128-register limit, and the
@@ -731,16 +654,13 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_kernel(
     else if (QW == 8 && VEC == 16 && ng == 4) { WC(0); WC(1); WC(2); WC(3); }
     else if (QW == 16 && VEC == 4 && ng == 7) { WC(0); WC(1); WC(2); WC(3); WC(4); WC(5); WC(6); }
 #undef WC
-#endif
     else
       for (int g = 0; g < ng; g++) w = word(g, std::false_type{}, w);
 
-#ifndef GULON_FILTER_MASKED_EVEN
 #pragma unroll
     for (int s = 0; s < NQG; s++)
 #pragma unroll
       for (int dd = 0; dd < DW; dd++) acc[s][2 * dd] -= acc[s][2 * dd + 1] << 8;
-#endif
     // conflict-ordered copy: which row a lane holds is only looked up (one byte) when a lane has something to report
     constexpr bool PERM = NG1 == 2;
     int row = rb * 64 + lane;
@@ -792,16 +712,6 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_kernel(
         }
     }
   }
-#ifdef GULON_FILTER_STAMPS
-  if constexpr (MAIN == 1) {   // per workgroup: [wave][start, staged, end] + [48] = (XCC_ID << 32) | HW_ID of wave 0
-    if (lane == 0 && g_filter_stamps) {
-      unsigned long long *o = g_filter_stamps + 52 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
-      o[3 * wave] = stamp0; o[3 * wave + 1] = stamp1; o[3 * wave + 2] = __builtin_amdgcn_s_memrealtime();
-      if (wave == 0)
-        o[48] = ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) | (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);
-    }
-  }
-#endif
 }
 
 // ---- exact re-evaluation of the survivors; one workgroup (4 waves) per query -------------------
@@ -933,17 +843,26 @@ template <int QW, int NQG, int VEC, int NADD>
 void launch_filter_t(gulon_index *ix, int ftiles, int nchunks, int rb_begin, int e_count, int e_per_chunk, RbMap mp,
                      int from, int until, int cap, int stage, int B, hipStream_t st, int *fb, int qt) {
   const int W_fp32 = ix->w;
-  // (GULON_FILTER_LDS_PAD: experiment knob -- bytes of LDS a main-stage workgroup claims on top of its tables, so
-  // that fewer of them fit a CU)
-  static const size_t lds_pad = getenv("GULON_FILTER_LDS_PAD") ? (size_t)atoi(getenv("GULON_FILTER_LDS_PAD")) : 0;
-  const size_t lds_bytes = (size_t)NQG * ix->m_pad * 256 * QW + 16 + (stage == 1 ? lds_pad : 0);   // tables + the run counter
+  const size_t lds_bytes = (size_t)NQG * ix->m_pad * 256 * QW + 16;   // tables + the run counter
   // (the single-word form only for the instantiation the headline index runs on: m = 16, two workgroups per CU)
-  constexpr bool one_word_form = QW == 16 && NQG == 1 && VEC == 16 && (NADD == 4 || NADD == 8);
+  constexpr bool one_word_form = QW == 16 && NQG == 1 && VEC == 16 && NADD == 4;
   // stage: 0 a short stage, 1 the main stage (a tag of its own for the profilers), 2 the tie replay's long level
   // (per-tile row limits behind the flags)
 #define GULON_FILTER_PICK(NG1_) \
   (stage == 1 ? filter_kernel<QW, NQG, VEC, NADD, 1, NG1_> : stage == 2 ? filter_kernel<QW, NQG, VEC, NADD, 2, NG1_> \
                                                                          : filter_kernel<QW, NQG, VEC, NADD, 0, NG1_>)
+  // the one-word form and the WC(...) forms address the tables from LDS offset 0: no kernel this launch can pick may
+  // have static LDS (checked once per instantiation)
+  static const bool lds_at_zero = [] {
+    for (int stage = 0; stage < 3; stage++)
+      for (auto k : {GULON_FILTER_PICK(0), GULON_FILTER_PICK(one_word_form), GULON_FILTER_PICK(2 * one_word_form)}) {
+        hipFuncAttributes fa;
+        HIP_CHECK(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k)));
+        if (fa.sharedSizeBytes != 0) return false;
+      }
+    return true;
+  }();
+  GULON_REQUIRE(lds_at_zero, "internal: the filter kernels address their tables from LDS offset 0");
   auto kern = GULON_FILTER_PICK(0);
   const uint8_t *codes = ix->codes.p, *perm = nullptr;
   if (one_word_form && ix->ng == 1) {
@@ -953,42 +872,13 @@ void launch_filter_t(gulon_index *ix, int ftiles, int nchunks, int rb_begin, int
       codes = ix->fcodes.p;
       perm = ix->fperm.p;
     }
-    hipFuncAttributes fa;
-    HIP_CHECK(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kern)));
-    GULON_REQUIRE(fa.sharedSizeBytes == 0, "internal: the single-word filter kernel addresses its tables from LDS offset 0");
   }
   HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds_bytes));
-#ifdef GULON_FILTER_STAMPS
-  static unsigned long long *stamps_d = nullptr;
-  static size_t stamps_n = 0;
-  if (stage == 1 && getenv("GULON_FILTER_STAMPS")) {
-    const size_t need = (size_t)52 * ftiles * nchunks;
-    if (need > stamps_n) {
-      if (stamps_d) (void)hipFree(stamps_d);
-      HIP_CHECK(hipMalloc((void **)&stamps_d, need * 8));
-      stamps_n = need;
-      HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_filter_stamps), &stamps_d, sizeof(stamps_d)));
-    }
-  }
-#endif
   hipLaunchKernelGGL(kern, stage == 2 ? dim3(nchunks, ftiles) : dim3(ftiles, nchunks), dim3(FILTER_THREADS), lds_bytes, st, codes, perm, ix->ng, ix->m_pad,
                      ix->qtab.p, from, until, rb_begin, e_count, e_per_chunk, mp, ix->sv_cnt.p, ix->sv_queue.p, cap,
                      fb ? fb : ix->fb_tile.p, fb ? qt : W_fp32 * ix->nsub, B, perm ? ix->fwindow - 1 : 0);
   HIP_CHECK(hipGetLastError());
-#ifdef GULON_FILTER_STAMPS
-  if (stage == 1 && stamps_d && getenv("GULON_FILTER_STAMPS")) {
-    HIP_CHECK(hipStreamSynchronize(st));
-    std::vector<unsigned long long> h((size_t)52 * ftiles * nchunks);
-    HIP_CHECK(hipMemcpy(h.data(), stamps_d, h.size() * 8, hipMemcpyDeviceToHost));
-    if (FILE *f = fopen(getenv("GULON_FILTER_STAMPS"), "wb")) {
-      const int hdr[4] = {ftiles, nchunks, e_count, e_per_chunk};
-      fwrite(hdr, sizeof(int), 4, f);
-      fwrite(h.data(), 8, h.size(), f);
-      fclose(f);
-    }
-  }
-#endif
 }
 
 // The filter kernel owns the LDS of every CU, so two of them (query batches in flight on
@@ -1040,8 +930,30 @@ int filter_qw(const gulon_index *ix) {
 // fit a CU's 160 KiB -- two resident workgroups hide each other's table staging and barriers
 // (measured at m = 16: 3.18 -> 3.01 ms for the main stage against one workgroup with two groups)
 int filter_nqg(const gulon_index *ix) {
-  if (const char *e = getenv("GULON_FILTER_NQG")) { int v = atoi(e); if (v == 1 || v == 2) return v; }   // experiment knob
   return (size_t)ix->m_pad * 256 * filter_qw(ix) * 4 <= 160 * 1024 ? 2 : 1;
+}
+
+// the launch shape run_filter_query and replay_level2_filtered share
+struct FilterShape {
+  int qw, nqg;      // queries per quantized table entry, entry groups per workgroup
+  int nadd, qmax;   // table entries summed in 8 bits before widening, the top quantisation level
+  int cap;          // entries per survivor sub-queue
+  int slots;        // filter workgroups the chip holds at once
+};
+FilterShape filter_shape(const gulon_index *ix) {
+  const ScanTuning &t = tuning_of(ix);
+  FilterShape f;
+  f.qw = filter_qw(ix);
+  f.nqg = filter_nqg(ix);
+  // 4 (6-bit levels) is cheapest, but the bound's slack grows with m / levels, so wide indexes take 2 (7-bit levels)
+  // unless told otherwise
+  f.nadd = t.filter_nadd ? t.filter_nadd : (ix->m_pad <= 16 ? 4 : 2);
+  f.qmax = 255 / f.nadd;
+  f.cap = std::max(64, t.filter_cap / NSLOT);
+  const size_t filter_lds = (size_t)f.nqg * ix->m_pad * 256 * f.qw;
+  const int resident = std::max(1, std::min(2048 / FILTER_THREADS, (int)(160 * 1024 / filter_lds)));
+  f.slots = device_cus() * resident;
+  return f;
 }
 
 void launch_filter(gulon_index *ix, int qw, int nqg, int nadd, int ftiles, int nchunks, int rb_begin, int e_count,
@@ -1049,11 +961,7 @@ void launch_filter(gulon_index *ix, int qw, int nqg, int nadd, int ftiles, int n
                    int *fb = nullptr /* tile flags other than the index's own, one per `qt` queries */, int qt = 1) {
 #define GO(W_, Q, V, A) \
   launch_filter_t<W_, Q, V, A>(ix, ftiles, nchunks, rb_begin, e_count, e_per_chunk, mp, from, until, cap, stage, B, st, fb, qt)
-#ifdef GULON_FILTER_NADD8   // experiment builds: 5-bit levels, eight entries per widening (one-word form only)
-#define GO_QV(W_, Q, V) do { if (nadd == 8 && W_ == 16 && Q == 1 && V == 16) GO(16, 1, 16, 8); else if (nadd == 4) GO(W_, Q, V, 4); else GO(W_, Q, V, 2); } while (0)
-#else
 #define GO_QV(W_, Q, V) do { if (nadd == 4) GO(W_, Q, V, 4); else GO(W_, Q, V, 2); } while (0)
-#endif
 #define GO_W(W_) do {                                                  \
     if (ix->vec == 16) { if (nqg == 2) GO_QV(W_, 2, 16); else GO_QV(W_, 1, 16); } \
     else               { if (nqg == 2) GO_QV(W_, 2, 4); else GO_QV(W_, 1, 4); }   \
@@ -1205,7 +1113,7 @@ static void filter_block_range(const gulon_index *ix, int qw, int nqg, int nadd,
                                int &rb_total) {
   rb_begin = from / 64;
   int rb_end = ceil_div(until, 64);
-  const bool ordered = ix->fcodes.p && ix->ng == 1 && ix->vec == 16 && qw == 16 && nqg == 1 && (nadd == 4 || nadd == 8) &&
+  const bool ordered = ix->fcodes.p && ix->ng == 1 && ix->vec == 16 && qw == 16 && nqg == 1 && nadd == 4 &&
                        tuning_of(ix).filter_order > 0;
   if (ordered && ix->fwindow > 1) {
     const int w = ix->fwindow;
@@ -1226,23 +1134,15 @@ void run_filter_query(gulon_index *ix, const float *dQ, int B, int K, int from, 
                       const SharedBounds *sb) {
   const ScanTuning &t = tuning_of(ix);
   const int phase = sb ? sb->phase : 0;
-#ifdef GULON_FILTER_STAMPS
-  if (phase != 2) skip_calls++;
-#endif
   const int keff = K + 1;
   const int W = ix->w;               // fp32 table interleave of the exact kernels
   const int QT = W * ix->nsub;
   const int ntiles = ceil_div(B, QT);
   const int Bp = ntiles * QT;
-  const int qw = filter_qw(ix);
-  const int nqg = filter_nqg(ix);
-  // entries summed in 8 bits before widening: 4 (6-bit levels) is cheapest, but the bound's slack
-  // grows with m / levels, so wide indexes take 2 (7-bit levels) unless told otherwise
-  const int nadd = t.filter_nadd ? t.filter_nadd : (ix->m_pad <= 16 ? 4 : 2);
-  const int qmax = 255 / nadd;
+  const FilterShape fs = filter_shape(ix);
+  const int qw = fs.qw, nqg = fs.nqg, nadd = fs.nadd, qmax = fs.qmax, cap = fs.cap, slots = fs.slots;
   const int ftiles = ceil_div(B, qw * nqg);
   const int Bq = ceil_div(ftiles * nqg * qw, 16) * 16;   // whole 16-query quantisation groups
-  const int cap = std::max(64, t.filter_cap / NSLOT);   // entries per sub-queue
   const int rb_begin = from / 64;
   const int rb_total = ceil_div(until, 64) - rb_begin;
   int frb_begin = rb_begin, frb_total = rb_total;        // what the filter launches scan (whole ordering windows)
@@ -1273,15 +1173,10 @@ void run_filter_query(gulon_index *ix, const float *dQ, int B, int K, int from, 
   // 64-128 KiB of tables once (268 MB through L2 for 4096 workgroups), so it should get >= 768 row blocks
   // (48 per wave) where the range allows; the launch is a whole number of rounds of what the chip holds
   // at once (CUs x resident workgroups) where that is possible
-  static const size_t lds_pad = getenv("GULON_FILTER_LDS_PAD") ? (size_t)atoi(getenv("GULON_FILTER_LDS_PAD")) : 0;
-  const size_t filter_lds = (size_t)nqg * ix->m_pad * 256 * qw + lds_pad;
-  const int resident = std::max(1, std::min(2048 / FILTER_THREADS, (int)(160 * 1024 / filter_lds)));
-  const int slots = device_cus() * resident;
   auto chunking = [&](int e_count, int tiles, int target, int &nchunks, int &per) {
     const int most = std::max(1, ceil_div(target, tiles));        // launch-size cap
     const int fill = std::max(1, ceil_div(slots, tiles));         // every slot of the chip taken once
-    static const int wg_blocks = getenv("GULON_FILTER_WG_BLOCKS") ? std::max(16, atoi(getenv("GULON_FILTER_WG_BLOCKS"))) : 768;   // experiment knob
-    int nc = std::max(fill, std::min(most, e_count / wg_blocks));
+    int nc = std::max(fill, std::min(most, e_count / 768));
     if (nc > fill) nc -= nc % fill;                               // whole rounds
     nc = std::min(nc, std::max(1, e_count / NW));                 // at least one block per wave
     per = ceil_div(e_count, nc);
@@ -1331,29 +1226,10 @@ void run_filter_query(gulon_index *ix, const float *dQ, int B, int K, int from, 
                          phase == 1 ? sb->bounds_out : nullptr, ix->gtau.p, Bp, ix->fb_tile.p, ntiles,              \
                          ix->sv_cnt.p, Bq * NSLOT);                                                                 \
     }
-#ifdef GULON_FILTER_STAMPS
-    static unsigned long long *bt_d = nullptr;
-    if (getenv("GULON_FILTER_STAMPS") && !bt_d) {
-      HIP_CHECK(hipMalloc((void **)&bt_d, 8 * 8 * 65536));
-      HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_bt_stamps), &bt_d, sizeof(bt_d)));
-    }
-#endif
-    if (GULON_SKIPPED(1)) {}
-    else if (ix->vec == 16) { if (W == 4) BS(16, 4) else if (W == 2) BS(16, 2) else BS(16, 1) }
+    if (ix->vec == 16) { if (W == 4) BS(16, 4) else if (W == 2) BS(16, 2) else BS(16, 1) }
     else               { if (W == 4) BS(4, 4) else if (W == 2) BS(4, 2) else BS(4, 1) }
 #undef BS
     HIP_CHECK(hipGetLastError());
-#ifdef GULON_FILTER_STAMPS
-    if (bt_d && Bp / W <= 65536) {
-      HIP_CHECK(hipStreamSynchronize(st));
-      std::vector<unsigned long long> h((size_t)8 * (Bp / W));
-      HIP_CHECK(hipMemcpy(h.data(), bt_d, h.size() * 8, hipMemcpyDeviceToHost));
-      if (FILE *f = fopen((std::string(getenv("GULON_FILTER_STAMPS")) + ".bt").c_str(), "wb")) {
-        fwrite(h.data(), 8, h.size(), f);
-        fclose(f);
-      }
-    }
-#endif
   }
   if (phase == 1) return;     // the caller exchanges the bounds and comes back with phase 2
   if (phase == 2) {
@@ -1367,30 +1243,11 @@ void run_filter_query(gulon_index *ix, const float *dQ, int B, int K, int from, 
     if (en <= 0) continue;
     int nc = 1, per = 1;
     chunking(en, ftiles, t.filter_blocks, nc, per);
-#ifdef GULON_FILTER_STAMPS
-    static unsigned long long *qt_d = nullptr;
-    if (getenv("GULON_FILTER_STAMPS") && !qt_d) {
-      HIP_CHECK(hipMalloc((void **)&qt_d, 8 * 4 * 65536));
-      HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_qt_stamps), &qt_d, sizeof(qt_d)));
-    }
-#endif
-    if (!GULON_SKIPPED(2))
     hipLaunchKernelGGL(qt_quantize, dim3(Bq / 4, ix->m_pad), dim3(256), 0, st, ix->tables.p, W, Bp, ix->m_pad, ix->k,
                        B, ix->qmins.p, ix->fin_v.p, ix->fin_i.p, ix->tau0.p, keff, qmax, qw, ix->qtab.p,
                        ix->fb_tile.p, QT);
     HIP_CHECK(hipGetLastError());
-#ifdef GULON_FILTER_STAMPS
-    if (qt_d && (Bq / 4) * ix->m_pad <= 65536) {
-      HIP_CHECK(hipStreamSynchronize(st));
-      std::vector<unsigned long long> h((size_t)4 * (Bq / 4) * ix->m_pad);
-      HIP_CHECK(hipMemcpy(h.data(), qt_d, h.size() * 8, hipMemcpyDeviceToHost));
-      if (FILE *f = fopen((std::string(getenv("GULON_FILTER_STAMPS")) + ".qt").c_str(), "wb")) {
-        fwrite(h.data(), 8, h.size(), f);
-        fclose(f);
-      }
-    }
-#endif
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, lane_pending = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     const bool main_stage = sidx == 2;
     // a first stage that keeps more than ~3 % of its (query, row) pairs means the bounds do not
     // separate anything for this query: give up on it before the main stage
@@ -1407,18 +1264,14 @@ void run_filter_query(gulon_index *ix, const float *dQ, int B, int K, int from, 
       const hipEvent_t lane_ev = filter_lane().of(dev, fresh);
       // only the main stage takes turns.  (Two host threads enqueueing at the same instant may both wait for the SAME
       // earlier launch and then share the chip once: the event orders launches for throughput, never for results.)
-      static const bool take_turns = !(getenv("GULON_FILTER_LANE") && atoi(getenv("GULON_FILTER_LANE")) == 0);   // experiment knob
       // (ranges below ~2 M rows -- a shard of an 8-GPU index -- do better without the turn-taking: 0.413 against 0.430 ms
       // per batch at 1.25 M rows, three batches in flight; 10 M rows: 2.36 against 2.38, within the noise, and the
       // kernel durations the bench reports stay those of one kernel at a time)
-      const bool turns = take_turns && (long long)rb_total * 64 >= (2ll << 20);
+      const bool turns = (long long)rb_total * 64 >= (2ll << 20);
       if (main_stage && !fresh && turns) HIP_CHECK(hipStreamWaitEvent(st, lane_ev, 0));
       if (timed) HIP_CHECK(hipEventRecord(ev0, st));         // after the wait: the kernel's own duration
-      if (!(main_stage && GULON_SKIPPED(16)) && !(!main_stage && GULON_SKIPPED(32)))
       launch_filter(ix, qw, nqg, nadd, ftiles, nc, frb_begin, en, per, mp, from, until, cap, main_stage ? 1 : 0, B, st);
-      static const int lane_after = getenv("GULON_LANE_AFTER_SURVIVORS") ? atoi(getenv("GULON_LANE_AFTER_SURVIVORS")) : 0;   // experiment knob
-      if (main_stage && !lane_after) HIP_CHECK(hipEventRecord(lane_ev, st));
-      lane_pending = main_stage && lane_after ? lane_ev : nullptr;
+      if (main_stage) HIP_CHECK(hipEventRecord(lane_ev, st));
     }
     if (stats) {   // debugging aid (GULON_FILTER_STATS=1): synchronous survivor statistics
       HIP_CHECK(hipStreamSynchronize(st));
@@ -1438,13 +1291,11 @@ void run_filter_query(gulon_index *ix, const float *dQ, int B, int K, int from, 
       const size_t sv_lds = (size_t)ix->m_pad * 256 * W * sizeof(float);
       auto kern = ix->vec == 16 ? survivors_kernel<16> : survivors_kernel<4>;
       HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sv_lds));
-      if (!GULON_SKIPPED(4))
-        hipLaunchKernelGGL(kern, dim3(Bq / W), dim3(64 * SV_WAVES * W), sv_lds, st, ix->codes.p, ix->ng, ix->m_pad, ix->tables.p,
-                           W, ix->row_base, ix->sv_cnt.p, ix->sv_queue.p, cap, B, keff, ix->fin_v.p, ix->fin_i.p,
-                           ix->fb_tile.p, QT, give_up);
+      hipLaunchKernelGGL(kern, dim3(Bq / W), dim3(64 * SV_WAVES * W), sv_lds, st, ix->codes.p, ix->ng, ix->m_pad, ix->tables.p,
+                         W, ix->row_base, ix->sv_cnt.p, ix->sv_queue.p, cap, B, keff, ix->fin_v.p, ix->fin_i.p,
+                         ix->fb_tile.p, QT, give_up);
     }
     HIP_CHECK(hipGetLastError());
-    if (lane_pending) HIP_CHECK(hipEventRecord(lane_pending, st));   // the next batch's main stage starts behind this batch's survivor pass
   }
 
   // fallback (device-side decision): flagged query tiles are rescanned exactly over all rows
@@ -1461,20 +1312,12 @@ void run_filter_query(gulon_index *ix, const float *dQ, int B, int K, int from, 
     if (*hint != 0) { *hint = 0; ix->fb_wide_left = 8; }
     const bool wide = ix->fb_wide_left > 0;
     if (wide) ix->fb_wide_left--;
-    if (!GULON_SKIPPED(8))
     launch_scan(ix, fb_tiles, cfb_n, rb_begin, rb_total, pfb, all, from, until, keff, st, nullptr, nullptr,
                 ix->fb_tile.p, true, wide ? fb_tiles : 8, ix->fb_hint_d);
   }
-  if (!GULON_SKIPPED(8))
   launch_merge_enabled(ix->part_v.p, ix->part_i.p, cfb_n, (long long)keff, (long long)cfb_n * keff, B, K, ix->fin_v.p,
                        ix->fin_i.p, ix->fb_tile.p, QT, st);
 
-#ifdef GULON_FILTER_STAMPS
-  {   // experiment: what does one more (empty) launch per batch cost while other batches are in flight?
-    static const int dummies = getenv("GULON_DUMMY_LAUNCHES") ? atoi(getenv("GULON_DUMMY_LAUNCHES")) : 0;
-    for (int i = 0; i < dummies; i++) hipLaunchKernelGGL(dummy_kernel, dim3(64), dim3(64), 0, st, ix->fb_tile.p);
-  }
-#endif
   if (stats) {
     HIP_CHECK(hipStreamSynchronize(st));
     std::vector<int> h((size_t)ntiles);
@@ -1504,13 +1347,11 @@ bool replay_level2_filtered(gulon_index *ix, int F, int K, int rb_lo, int rb_hi,
   // (the same conditions as filter_eligible; the byte-code kernels only)
   if (!t.filter || ix->wide || (size_t)ix->m_pad * 256 * 4 > FILTER_LDS_BUDGET || e_count < t.filter_min_rb || K < 1)
     return false;
-  const int qw = filter_qw(ix), nqg = filter_nqg(ix);
-  const int nadd = t.filter_nadd ? t.filter_nadd : (ix->m_pad <= 16 ? 4 : 2);
-  const int qmax = 255 / nadd;
+  const FilterShape fs = filter_shape(ix);
+  const int qw = fs.qw, nqg = fs.nqg, nadd = fs.nadd, cap = fs.cap;
   filter_block_range(ix, qw, nqg, nadd, rb_lo * 64, std::min(until, rb_hi * 64), rb_lo, e_count);   // whole ordering windows
   const int ftiles = ceil_div(F, qw * nqg);
   const int Fq = ceil_div(ftiles * nqg * qw, 16) * 16;
-  const int cap = std::max(64, t.filter_cap / NSLOT);
   // a launch is worth its fixed costs (quantisation, table staging of every workgroup) from about two query tiles on
   const int min_flagged = 2 * qw;
   GULON_REQUIRE(F <= 1024, "internal: %d flagged queries per replay round", F);
@@ -1528,13 +1369,10 @@ bool replay_level2_filtered(gulon_index *ix, int F, int K, int rb_lo, int rb_hi,
   // tables of the flagged queries are [slot][m_pad][256]: "one query per entry" (W = 1) in qt_quantize's terms, read
   // through the order; queries beyond F (the padding of the last 16-query group) read no table
   hipLaunchKernelGGL(qt_quantize, dim3(Fq / 4, ix->m_pad), dim3(256), 0, st, tables, 1, F, ix->m_pad, ix->k, F, mins,
-                     ix->rp_finv.p, ix->rp_fini.p, ix->rp_tau.p, 1, qmax, qw, ix->qtab.p, ix->rp_fb.p, 1, ix->rp_order.p);
+                     ix->rp_finv.p, ix->rp_fini.p, ix->rp_tau.p, 1, fs.qmax, qw, ix->qtab.p, ix->rp_fb.p, 1, ix->rp_order.p);
   HIP_CHECK(hipGetLastError());
-  const size_t filter_lds = (size_t)nqg * ix->m_pad * 256 * qw;
-  const int resident = std::max(1, std::min(2048 / FILTER_THREADS, (int)(160 * 1024 / filter_lds)));
-  const int slots = device_cus() * resident;
   const int NW = FILTER_THREADS / 64;
-  int nc = std::max(1, std::min(std::max(ceil_div(slots, ftiles), e_count / 768), std::max(1, e_count / NW)));
+  int nc = std::max(1, std::min(std::max(ceil_div(fs.slots, ftiles), e_count / 768), std::max(1, e_count / NW)));
   const int per = ceil_div(e_count, nc);
   nc = ceil_div(e_count, per);
   const RbMap all{1, 0, 1};

@@ -838,15 +838,14 @@ __global__ __launch_bounds__(256) void gq_ptables(const float *__restrict__ pq_c
 
 constexpr int GA_WAVES = 16;    // waves of one query's workgroup: each takes every 16th searched group
 constexpr int GA_C = 64;        // candidates kept per query
+static_assert(GF_WAVES == GA_WAVES && GF_LIST == GA_C, "gf_survivors writes gq_approx_scan's lists");
 template <int VEC>
 __global__ __launch_bounds__(64 * GA_WAVES) void gq_approx_scan(const uint8_t *__restrict__ codes, int ng, int m_pad, int d,
                                                                 const float *__restrict__ P, const float *__restrict__ xnorm,
                                                                 const float *__restrict__ gcent,
                                                                 const int *__restrict__ bounds, const float *__restrict__ Q,
                                                                 const int *__restrict__ nn, int nn_stride,
-                                                                const int *__restrict__ nn_cnt, int gmax /* searched groups taken at most */,
-                                                                int split /* waves that share a group's row blocks (1, 2, 4 ..) */,
-                                                                float *__restrict__ lv,
+                                                                const int *__restrict__ nn_cnt, float *__restrict__ lv,
                                                                 int *__restrict__ li, int *__restrict__ nanflag) {
   using Word = typename CodeWord<VEC>::type;
   extern __shared__ float ga_lds[];           // m_pad * 256 table entries, then d query coordinates
@@ -862,9 +861,9 @@ __global__ __launch_bounds__(64 * GA_WAVES) void gq_approx_scan(const uint8_t *_
   WaveList wl;
   wl.init();
   int cnt = 0, saw_nan = 0;
-  const int ngroups = min(nn_cnt[q], gmax);
+  const int ngroups = nn_cnt[q];
   const Word *cw = reinterpret_cast<const Word *>(codes);
-  for (int t = wave / split; t < ngroups; t += GA_WAVES / split) {
+  for (int t = wave; t < ngroups; t += GA_WAVES) {
     const int c = nn[(size_t)q * nn_stride + t];
     const int row_from = bounds[c], row_until = bounds[c + 1];
     float qg = 0.f;
@@ -872,12 +871,12 @@ __global__ __launch_bounds__(64 * GA_WAVES) void gq_approx_scan(const uint8_t *_
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) qg += __shfl_xor(qg, o);
     const float base = qq - 2.0f * qg;
-    const int rb_first = (row_from >> 6) + wave % split, rb_end = (row_until + 63) >> 6;
+    const int rb_first = row_from >> 6, rb_end = (row_until + 63) >> 6;
     Word wnext{};
     if (rb_first < rb_end) wnext = cw[((size_t)rb_first * ng) * 64 + lane];
-    for (int rb = rb_first; rb < rb_end; rb += split) {
+    for (int rb = rb_first; rb < rb_end; rb++) {
       const Word w0 = wnext;
-      if (rb + split < rb_end) wnext = cw[((size_t)(rb + split) * ng) * 64 + lane];
+      if (rb + 1 < rb_end) wnext = cw[((size_t)(rb + 1) * ng) * 64 + lane];
       const int row = rb * 64 + lane;
       const bool valid = row >= row_from && row < row_until;
       float acc = base + (valid ? xnorm[row] : 0.f);
@@ -1282,8 +1281,8 @@ void run_grouped_query(gulon_grouped_index *gx, const float *dQ, int B, int K, i
                          gx->anan.p, st);
       else {
         hipLaunchKernelGGL(kern, dim3(B), dim3(64 * GA_WAVES), lds_ga, st, ix->codes.p, ix->ng, ix->m_pad, ix->d, gx->ptab.p,
-                           gx->xnorm.p, gx->gcent.p, gx->bounds.p, dQ, gx->nn.p, nn_stride, gx->nn_cnt.p, INT_MAX, 1, gx->apv.p,
-                           gx->api.p, gx->anan.p);
+                           gx->xnorm.p, gx->gcent.p, gx->bounds.p, dQ, gx->nn.p, nn_stride, gx->nn_cnt.p, gx->apv.p, gx->api.p,
+                           gx->anan.p);
         launch_merge(false, gx->apv.p, gx->api.p, GA_WAVES, (long long)GA_C, (long long)GA_WAVES * GA_C, B, GA_C - 1, nullptr,
                      nullptr, nullptr, nullptr, gx->amv.p, gx->ami.p, st);
       }

@@ -720,15 +720,13 @@ __global__ void mean_division_selftest(int n_max, int per, unsigned long long se
 // The cluster's slices are contiguous in xb (sort_place).  A three-deep software pipeline of 32-step batches
 // keeps 64 steps of loads in flight per lane (no load depends on the chain).  The kernel is one wave per 64
 // chains and there are barely more waves than SIMDs (1280 at BASELINE config 3, two on some SIMDs), so it is
-// as fast as its instruction stream is short: SP (the bucket row stride) is a template parameter so that every
-// load of a batch is one instruction with an immediate offset from a pointer that advances once per batch, the
-// main loop runs clear of the cluster's end (no index clamps), and the range test of the fast quotient is one
-// min and one max per step, looked at once per batch.
-template <int SP /* bucket row stride in floats; 0: read it from the descriptor */>
+// as fast as its instruction stream is short: the main loop runs clear of the cluster's end (no index clamps), and the
+// range test of the fast quotient is one min and one max per step, looked at once per batch.  This is the form for
+// problems of different bucket row strides; one shared stride up to 16 takes update_chains_pk.
 __global__ __launch_bounds__(64) void update_chains(const UpdDesc *__restrict__ descs, int k,
                                                     const float *__restrict__ rcp /* scalar loads: see update_chains_pk */) {
   const UpdDescG D = load_desc(descs, blockIdx.x);           // x = problem, y = block of 64 chains: blocks are dispatched x-fastest,
-  const int s = D.s, sp = SP ? SP : ((s + 1) & ~1);   // so every problem's longest chains (block 0) come first
+  const int s = D.s, sp = (s + 1) & ~1;                      // so every problem's longest chains (block 0) come first
   int t = blockIdx.y * blockDim.x + threadIdx.x;
   if (t >= k * s) return;
   const int slot = t / s, j = t - slot * s;
@@ -749,13 +747,8 @@ __global__ __launch_bounds__(64) void update_chains(const UpdDesc *__restrict__ 
     auto nxt = col + (size_t)2 * U * sp;
     // batches whose look-ahead (two batches) stays inside the cluster
     for (; i + 3 * U <= len; i += U, nxt += (size_t)U * sp) {
-#ifdef GULON_CHAINS_NOLOAD   // timing experiment (wrong results): the recurrence alone, no loads in the loop --
-#pragma unroll              // 5.5 ms against 8.4 ms for the first update at BASELINE config 3 (longest chain: 118 K steps)
-      for (int u = 0; u < U; u++) xc[u] = xa[u] * 1.0001f;
-#else
 #pragma unroll
       for (int u = 0; u < U; u++) xc[u] = nxt[(size_t)u * sp];
-#endif
       const float p0 = p;
       float lo = INFINITY, hi = 0.f;
       float nf = (float)(int)(i + 1);
@@ -844,15 +837,9 @@ __global__ __launch_bounds__(64) void update_chains_pk(const UpdDesc *__restrict
     auto batch = [&](const f32x2 (&cur)[U], float ycur, f32x2 (&ld)[U], float &yld) {
       const bool live = b < nb;                    // this lane's cluster still has this batch
       const auto src = nxt + (size_t)(live ? 2 * U * HP : 0);   // (a finished lane re-reads where it stands: inside its cluster)
-#ifdef GULON_CHAINS_NOLOAD   // timing experiment (wrong results): the recurrence alone, no loads in the loop
-#pragma unroll
-      for (int u = 0; u < U; u++) ld[u] = cur[u] * 1.0001f;
-      yld = ycur;
-#else
 #pragma unroll
       for (int u = 0; u < U; u++) ld[u] = src[(size_t)u * HP];
       yld = rcp[i + 2 * U + l32];
-#endif
       const f32x2 p0 = p;
       float lo = INFINITY, hi = 0.f;
       const float nfv = (float)(int)(i + 1 + l32);
@@ -1177,8 +1164,7 @@ static void launch_counting_sort(UpdDesc *d_descs, int np, int n, int k, int sma
                                                                                                        : sort_place<16>;
   HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(place), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)shm_place));
-  static const bool xcd_env = [] { const char *e = getenv("GULON_PLACE_XCD"); return !e || atoi(e) != 0; }();
-  const int cpx = xcd_env && staged ? (int)ceil_div(nchunks, 8LL) : 0;
+  const int cpx = staged ? (int)ceil_div(nchunks, 8LL) : 0;
   if (cpx > 0)
     hipLaunchKernelGGL(place, dim3((unsigned)(8LL * cpx * np)), dim3(256), shm_place, st, d_descs, n, k, key_bits, cpx);
   else
@@ -1227,9 +1213,6 @@ void kmeans_update_batch(const std::vector<UpdDesc> &descs, UpdDesc *d_descs, in
     for (const UpdDesc &D : descs) kmeans_update_bigk(D, d_descs, n, k, st);
     return;
   }
-#ifdef GULON_TEST_HOOKS
-  if (kmeans_update_fused(descs, d_descs, n, k, st)) return;   // the measured-and-dropped fused update (kmeans_fused.hip; GULON_UPDATE_FUSED=1)
-#endif
   HIP_CHECK(hipMemcpyAsync(d_descs, descs.data(), sizeof(UpdDesc) * np, hipMemcpyHostToDevice, st));
   int smax = 1;
   for (const UpdDesc &D : descs) smax = std::max(smax, D.s);
@@ -1239,15 +1222,11 @@ void kmeans_update_batch(const std::vector<UpdDesc> &descs, UpdDesc *d_descs, in
   launch_counting_sort(d_descs, np, n, k, smax, compact, st);
   bool one_stride = true;   // every problem with the same bucket row stride: the chains take it as a constant
   for (const UpdDesc &D : descs) one_stride = one_stride && ((D.s + 1) & ~1) == sp_max;
-  auto chains = !one_stride ? update_chains<0> : sp_max == 2 ? update_chains<2> : sp_max == 4 ? update_chains<4>
-              : sp_max == 6 ? update_chains<6> : sp_max == 8 ? update_chains<8> : sp_max == 10 ? update_chains<10>
-              : sp_max == 12 ? update_chains<12> : sp_max == 14 ? update_chains<14> : sp_max == 16 ? update_chains<16>
-              : update_chains<0>;
   // one wave per workgroup; with more workgroups than SIMDs, 40 KiB of (unused) LDS each keeps four per CU -- one per
   // SIMD at full issue rate -- and the rest, the SHORTEST chains (size order), start as the first ones finish
-  // two chains per lane on the packed pipe wherever the stride is a compile-time constant (GULON_CHAINS_PK=0: one per lane)
-  static const bool pk_env = [] { const char *e = getenv("GULON_CHAINS_PK"); return !e || atoi(e) != 0; }();
-  const bool pk = pk_env && one_stride && sp_max <= 16;
+  // two chains per lane on the packed pipe wherever the stride is a compile-time constant, else one
+  const bool pk = one_stride && sp_max <= 16;
+  auto chains = update_chains;
   if (pk) {
     chains = sp_max == 2 ? update_chains_pk<2> : sp_max == 4 ? update_chains_pk<4> : sp_max == 6 ? update_chains_pk<6>
            : sp_max == 8 ? update_chains_pk<8> : sp_max == 10 ? update_chains_pk<10> : sp_max == 12 ? update_chains_pk<12>
@@ -1256,9 +1235,9 @@ void kmeans_update_batch(const std::vector<UpdDesc> &descs, UpdDesc *d_descs, in
   const int chain_blocks = pk ? ceil_div((long long)k * (sp_max / 2), 64) : ceil_div((long long)k * smax, 64);
   int cus = 256;
   { int dev = 0; HIP_CHECK(hipGetDevice(&dev)); HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)); }
-  static const int cap_env = [] { const char *e = getenv("GULON_CHAINS_PER_CU"); return e ? atoi(e) : 4; }();
+  constexpr int per_cu = 4;
   size_t chain_lds = 0;
-  if (cap_env > 0 && (long long)chain_blocks * np > (long long)cap_env * cus) chain_lds = (size_t)(160 * 1024) / cap_env;
+  if ((long long)chain_blocks * np > (long long)per_cu * cus) chain_lds = (size_t)(160 * 1024) / per_cu;
   HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(chains), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)std::max<size_t>(chain_lds, 1)));
   hipLaunchKernelGGL(chains, dim3(np, chain_blocks), dim3(64), chain_lds, st, d_descs, k, descs[0].rcp);
@@ -1477,7 +1456,7 @@ void kmeans_train_batch(const float *dX, int n, int ld, int np, const int *from,
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemsetAsync(pr.a_prev.p, 0, sizeof(int) * (size_t)n, pr.st));
     pr.use_mfma = mfma_assign_supported(s, k);
-    pr.xs.alloc((size_t)n * s + 2);   // (+2: update_fused reads rows as pairs of floats)
+    pr.xs.alloc((size_t)n * s);
     GULON_UNSUPPORTED((long long)n * s >= (1ll << 32), "slice of %lld elements: a dispatch carries fewer than 2^32 work-items",
                       (long long)n * s);
     hipLaunchKernelGGL(copy_slice, dim3(ceil_div((long long)n * s, 256)), dim3(256), 0, pr.st, dX, ld, from[p], s,
@@ -1568,8 +1547,7 @@ void kmeans_train_batch(const float *dX, int n, int ld, int np, const int *from,
         tt.mfma_flops += fm; tt.update_bytes += ub;
       }
     }
-    static const bool speculate = [] { const char *e = getenv("GULON_UPDATE_SPECULATE"); return !(e && atoi(e) == 0); }();
-    if (stream_update && speculate && i < max_iterations) {
+    if (stream_update && i < max_iterations) {
       // The next update's chunk order depends on nothing but this assignment: it runs now, on the batch stream, under
       // the convergence test's downloads and host round trip (~1 ms in which the GPU was idle).  Wasted only in the
       // iteration that finds every problem converged.

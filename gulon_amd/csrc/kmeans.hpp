@@ -136,8 +136,6 @@ void stream_pack_pairs(const float *xs, int n, int s, float *xp /* [pairs][ns] f
 void kmeans_stream_order(const std::vector<StreamDesc> &descs, StreamDesc *d_descs, int n, int k, hipStream_t st);
 void kmeans_stream_chains(const std::vector<StreamDesc> &descs, StreamDesc *d_descs, int n, int k, hipStream_t st);
 
-// kmeans_fused.hip: KMeans.fromAssignment without the regrouped copy (false: the shape keeps the bucketed path)
-bool kmeans_update_fused(const std::vector<UpdDesc> &descs, UpdDesc *d_descs, int n, int k, hipStream_t st);
 void kmeans_update_dev(KmeansWorkspace &ws, const float *dX, int n, int ld, int from, int s, int k,
                        const int *d_assign, float *dC, hipStream_t st);
 

@@ -547,9 +547,6 @@ __global__ __launch_bounds__(256) GULON_BF16_WAVES void assign_bf16(const uint4 
                                                    int *__restrict__ assign, int *__restrict__ flag_rows,
                                                    unsigned *__restrict__ flag_count, float *__restrict__ probe) {
   extern __shared__ float sm[];
-#ifdef GULON_BF16_CLOCKS   // experiment builds: shader cycles per 100 MHz tick over the life of workgroup 0
-  const unsigned long long clk_c0 = clock64(), clk_w0 = wall_clock64();
-#endif
   constexpr int NMF = COMPACT ? 2 * NA : 12;                       // matrix instructions per block and tile pair
   uint4 *sA = reinterpret_cast<uint4 *>(sm);                       // [nkb][NA][64]
   float *sOff = sm + (size_t)nkb * NA * 64 * 4;                     // 2 copies of nkb*32
@@ -793,24 +790,16 @@ __global__ __launch_bounds__(256) GULON_BF16_WAVES void assign_bf16(const uint4 
       if (flagged) flag_rows[base + __popcll(fm & ((1ull << lane) - 1ull))] = (int)row;
     }
   }
-#ifdef GULON_BF16_CLOCKS
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    const unsigned long long dc = clock64() - clk_c0, dw = wall_clock64() - clk_w0;
-    printf("[clocks] %llu shader cycles in %llu ticks of 10 ns: %.3f GHz\n", dc, dw, (double)dc / (double)dw / 10.0);
-  }
-#endif
 }
 
 // operand words per lane, tile and centroid block: 0 = three pieces (six matrix instructions), else the compact layout
 static int split_compact_words(int s) {
-  static const bool off = [] { const char *e = getenv("GULON_KMEANS_COMPACT"); return e && atoi(e) == 0; }();   // A/B knob
-  return !off && split_words(s) < 6 ? split_words(s) : 0;
+  return split_words(s) < 6 ? split_words(s) : 0;
 }
 static bool mfma_split(int s, int k) {
-  static const bool off = getenv("GULON_KMEANS_F32_MFMA") != nullptr;   // A/B knob: the fp32 matrix instruction instead
   const int nkb = (k + 31) / 32;
   const int na = split_compact_words(s) ? split_compact_words(s) : 3;
-  return !off && s >= 1 && s <= 16 && ((size_t)nkb * (na * 64 * 16 + 64 * 4)) <= 60 * 1024;
+  return s >= 1 && s <= 16 && ((size_t)nkb * (na * 64 * 16 + 64 * 4)) <= 60 * 1024;
 }
 static float split_errk(int s) {
   // band = 2.1 * E + key perturbation (see the kernel's header): E / S = [(s+1) + 6 (s+2)] 2^-24 + 2^-22.9

@@ -270,14 +270,7 @@ __global__ __launch_bounds__(T + L) void stream_chains(const StreamDesc *__restr
   };
   // chunk t: its values are in dat_s[t & 1]; register slot t % RING is free (stashed one chunk ago) and takes chunk
   // t + RING; chunk t + 1 leaves slot (t + 1) % RING for dat_s[(t + 1) & 1] after the chain steps
-#ifdef STREAM_STAMPS
-  unsigned long long st_head = 0, st_loop = 0, st_stash = 0, st_bar = 0, st_steps = 0, st_vm = 0;
-#define STAMP(v) const unsigned long long v = __builtin_readcyclecounter()
-#else
-#define STAMP(v)
-#endif
   auto chunk = [&](int t, int slot_cur, int slot_next) {
-    STAMP(t0);
     const int cs = active ? rs[slot_cur] : 0, ce = active ? re[slot_cur] : 0;
     if constexpr (L == 0) load_data(t + RING, rd[slot_cur], ro[slot_cur]);
     load_range(t + RING, rs[slot_cur], re[slot_cur]);
@@ -293,22 +286,14 @@ __global__ __launch_bounds__(T + L) void stream_chains(const StreamDesc *__restr
     f32x2 xa[4], xb[4];
 #pragma unroll
     for (int u = 0; u < 4; u++) xa[u] = dat[min(cs, CH) + u];
-    STAMP(t1);
     for (int i = cs; __ballot(i < ce) != 0ull; i += 8) {
-#ifdef STREAM_STAMPS
-      st_steps += 4;
-#endif
       group(dat, i, ce, xa, xb);
       if (__ballot(i + 4 < ce) == 0ull) break;
-#ifdef STREAM_STAMPS
-      st_steps += 4;
-#endif
       group(dat, i + 4, ce, xb, xa);
     }
     // trusted: every nonzero numerator at least 2^-100 and every divisor below 2^24 (the float count is exact; the
     // corrected product holds for EVERY such divisor with y = RN(1 / n): tests/test_markstein_exhaustive.py for the
     // divisors 2^j - 1 the proofs single out, gulon_selftest_mean_division)
-    STAMP(t2);
     const bool redo = wild || emin < -99 || cnt_end >= (1 << 24);
     if (redo) {
       p = p_start;
@@ -321,18 +306,9 @@ __global__ __launch_bounds__(T + L) void stream_chains(const StreamDesc *__restr
       }
     }
     cnt = cnt_end;
-#ifdef STREAM_STAMPS
-    const unsigned long long t2b = __builtin_readcyclecounter();
-    st_vm += t2b - t2;
-#endif
     if constexpr (L == 0)
       if (t + 1 < nchunks) stash((t + 1) & 1, rd[slot_next], ro[slot_next]);
-    STAMP(t3);
     __syncthreads();
-#ifdef STREAM_STAMPS
-    const unsigned long long t4 = __builtin_readcyclecounter();
-    st_head += t1 - t0; st_loop += t2 - t1; st_stash += t3 - t2; st_bar += t4 - t3;
-#endif
   };
   int t = 0;
   for (; t + RING <= nchunks; t += RING) {
@@ -342,11 +318,6 @@ __global__ __launch_bounds__(T + L) void stream_chains(const StreamDesc *__restr
 #pragma unroll
   for (int r = 0; r < RING; r++)
     if (t + r < nchunks) chunk(t + r, r, (r + 1) % RING);
-#ifdef STREAM_STAMPS
-  if ((c & 63) == 0 && blockIdx.x < 2 && blockIdx.y < 2)
-    printf("stream_chains wg (%d,%d) wave %d: head %llu loop %llu stash %llu (check/redo %llu) barrier %llu cycles, %llu step slots, %d chunks\n",
-           (int)blockIdx.x, (int)blockIdx.y, c >> 6, st_head, st_loop, st_stash, st_vm, st_bar, st_steps, nchunks);
-#endif
   if (active) {
     const int j = 2 * pair;
     cout[(size_t)c * s + j] = p.x;

@@ -150,10 +150,8 @@ __device__ __forceinline__ void scan_body(
     int keff, float *__restrict__ part_v, int *__restrict__ part_i, unsigned *__restrict__ gtau, int tau_off4,
     int prune_from, const float *__restrict__ lbv, const int *__restrict__ lbi,
     const uint8_t *__restrict__ perm /* non-null: `codes` is the conflict-ordered copy (conflict_order.hip), perm its row order */,
-    const int tile /* query tile of this pass */, unsigned long long *__restrict__ dbg) {
+    const int tile /* query tile of this pass */) {
   constexpr int QT = W * NSUB;
-  // optional timeline (GULON_SCAN_TIMELINE=1): 4 stamps per workgroup, 100 MHz wall clock
-  if (dbg && threadIdx.x == 0) dbg[(blockIdx.y * gridDim.x + blockIdx.x) * 4 + 0] = wall_clock64();
   constexpr int NW = THREADS / 64;
   using Word = typename CodeWord<VEC>::type;
   using TV = typename TabVec<W>::type;
@@ -182,7 +180,6 @@ __device__ __forceinline__ void scan_body(
   }
   __syncthreads();
 
-  if (dbg && threadIdx.x == 0) dbg[(blockIdx.y * gridDim.x + blockIdx.x) * 4 + 1] = wall_clock64();
   WaveList wl[QT];
   int cnt[QT];
 #pragma unroll
@@ -324,7 +321,6 @@ __device__ __forceinline__ void scan_body(
 
   // merge the NW per-wave lists of every query through LDS (tables are dead now)
   __syncthreads();
-  if (dbg && threadIdx.x == 0) dbg[(blockIdx.y * gridDim.x + blockIdx.x) * 4 + 2] = wall_clock64();
   float *sv = reinterpret_cast<float *>(lds_raw);
   int *si = reinterpret_cast<int *>(sv + QT * NW * 64);
 #pragma unroll
@@ -353,7 +349,6 @@ __device__ __forceinline__ void scan_body(
       __hip_atomic_fetch_min(&gtau[tile * QT + q], __float_as_uint(out.tau), __ATOMIC_RELAXED,
                              __HIP_MEMORY_SCOPE_AGENT);
   }
-  if (dbg && threadIdx.x == 0) dbg[(blockIdx.y * gridDim.x + blockIdx.x) * 4 + 3] = wall_clock64();
 }
 
 #define GULON_SCAN_PARAMS                                                                                          \
@@ -367,8 +362,8 @@ __device__ __forceinline__ void scan_body(
 
 // workgroup (x, y) = query tile x (fastest: the tiles of one chunk run together) x chunk y of the row blocks
 template <int W, int NSUB, int VEC, int THREADS, bool PRUNE>
-__global__ __launch_bounds__(THREADS) void scan_kernel(GULON_SCAN_PARAMS, unsigned long long *__restrict__ dbg) {
-  scan_body<W, NSUB, VEC, THREADS, PRUNE>(GULON_SCAN_ARGS, (int)blockIdx.x, dbg);
+__global__ __launch_bounds__(THREADS) void scan_kernel(GULON_SCAN_PARAMS) {
+  scan_body<W, NSUB, VEC, THREADS, PRUNE>(GULON_SCAN_ARGS, (int)blockIdx.x);
 }
 
 // The filter's fallback launch: only the query tiles flagged in tile_enable (one flag per tile_div tiles) are
@@ -386,7 +381,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(7))) vo
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     if (tile_enable[tile / tile_div] == 0) continue;
     if (hint && threadIdx.x == 0 && blockIdx.y == 0) *hint = 1;
-    scan_body<W, NSUB, VEC, THREADS, PRUNE>(GULON_SCAN_ARGS, tile, nullptr);
+    scan_body<W, NSUB, VEC, THREADS, PRUNE>(GULON_SCAN_ARGS, tile);
     __syncthreads();   // every wave is done with this tile's tables and thresholds in LDS
   }
 }
@@ -649,7 +644,7 @@ bool ScanTuning::set(const char *key, int v) {
   else if (k == "GULON_FILTER_PERIOD") { if (v >= 3) filter_period = v; }
   else if (k == "GULON_FILTER_STAGE1") { if (v >= 1) filter_stage1 = v; }
   else if (k == "GULON_FILTER_CAP") { if (v >= 64) filter_cap = v; }
-  else if (k == "GULON_FILTER_NADD") { if (v == 0 || v == 2 || v == 4 || v == 8) filter_nadd = v; }   // (8: experiment builds only)
+  else if (k == "GULON_FILTER_NADD") { if (v == 0 || v == 2 || v == 4) filter_nadd = v; }
   else if (k == "GULON_FILTER_SAMPLE") { if (v >= 1) filter_sample = v; }
   else if (k == "GULON_FILTER_STAGE0") { if (v >= 0) filter_stage0 = v; }
   else if (k == "GULON_FILTER_BLOCKS") { if (v >= 1) filter_blocks = v; }
@@ -690,11 +685,6 @@ void launch_scan_p(gulon_index *ix, int ntiles, int nchunks, int rb_begin, int e
   lds_bytes += 64;
   int prune_from = tuning_of(ix).prune_from >= 0 ? tuning_of(ix).prune_from : ix->m_pad / 2;
   if (prune_from < 4) prune_from = 4;
-  unsigned long long *dbg = nullptr;
-  if (getenv("GULON_SCAN_TIMELINE") && !tile_enable) {
-    ix->dbg.ensure((size_t)ntiles * nchunks * 4);
-    dbg = ix->dbg.p;
-  }
   if (tile_enable) {   // the filter's fallback (launch_scan with one_sub): grid_x workgroups loop over the tiles
     if constexpr (NSUB == 1) {
       auto kern = scan_kernel_lean<W, NSUB, VEC, SCAN_THREADS, PRUNE>;
@@ -721,28 +711,9 @@ void launch_scan_p(gulon_index *ix, int ntiles, int nchunks, int rb_begin, int e
                      ix->ng, ix->m_pad,
                      reinterpret_cast<const float4 *>(ix->tables.p), from, until, ix->row_base, rb_begin, e_count,
                      e_per_chunk, mp, nchunks, keff, ix->part_v.p, ix->part_i.p, ix->gtau.p, tau_off4, prune_from, lbv,
-                     lbi, ordered ? ix->fperm.p : (const uint8_t *)nullptr, dbg);
+                     lbi, ordered ? ix->fperm.p : (const uint8_t *)nullptr);
   HIP_CHECK(hipGetLastError());
-  if (dbg) {   // debugging aid: synchronous dump of the per-workgroup timeline
-    HIP_CHECK(hipStreamSynchronize(st));
-    const size_t nb = (size_t)ntiles * nchunks;
-    std::vector<unsigned long long> h(nb * 4);
-    HIP_CHECK(hipMemcpy(h.data(), dbg, sizeof(unsigned long long) * nb * 4, hipMemcpyDeviceToHost));
-    unsigned long long t0 = ~0ull, t1 = 0;
-    double stage = 0, loop = 0, merge = 0;
-    for (size_t b = 0; b < nb; b++) {
-      t0 = std::min(t0, h[b * 4]); t1 = std::max(t1, h[b * 4 + 3]);
-      stage += (double)(h[b * 4 + 1] - h[b * 4]); loop += (double)(h[b * 4 + 2] - h[b * 4 + 1]);
-      merge += (double)(h[b * 4 + 3] - h[b * 4 + 2]);
-    }
-    std::vector<double> ends;
-    for (size_t b = 0; b < nb; b++) ends.push_back((double)(h[b * 4 + 3] - t0) / 100.0);
-    std::sort(ends.begin(), ends.end());
-    fprintf(stderr, "[scan timeline] %zu workgroups, kernel span %.1f us; per workgroup: stage %.1f us, loop %.1f us, "
-            "merge %.1f us; last-finish quantiles 50%%=%.0f 90%%=%.0f 99%%=%.0f 100%%=%.0f us\n", nb,
-            (double)(t1 - t0) / 100.0, stage / nb / 100.0, loop / nb / 100.0, merge / nb / 100.0,
-            ends[nb / 2], ends[nb * 9 / 10], ends[nb * 99 / 100], ends[nb - 1]);
-  }
+
 }
 
 template <int W, int NSUB, int VEC>

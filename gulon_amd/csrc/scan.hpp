@@ -54,7 +54,7 @@ struct gulon_index {
   DevBuf<int> flags_scratch;
   DevBuf<int> stage_rows;  // row ids of the host-pointer decode / query-by-row calls (decode.hip)
   DevBuf<int> row_err;     // set by the row decode when a *_dev call asked for a row outside [0, n)
-  DevBuf<unsigned long long> dbg;   // GULON_SCAN_TIMELINE stamps
+  DevBuf<unsigned long long> dbg;   // GULON_REPLAY_STATS stamps (replay.hip)
   // large-K peeling rounds
   DevBuf<float> peel_v, peel_tv, peel_lbv;
   DevBuf<int> peel_i, peel_ti, peel_lbi;

@@ -136,8 +136,8 @@ SIGNATURES = {
 _lib = None
 
 
-# libgulon_hip_testhooks.so (tests only): the product library's objects plus the kernels' self-tests and the
-# measured-and-dropped fused k-means update (GULON_UPDATE_FUSED=1) -- include/gulon_hip.h under GULON_TEST_HOOKS
+# libgulon_hip_testhooks.so (tests only): the product library's objects plus the kernels' self-tests --
+# include/gulon_hip.h under GULON_TEST_HOOKS
 HOOKS_LIB_PATH = os.path.join(_HERE, "lib", "libgulon_hip_testhooks.so")
 TEST_HOOK_SIGNATURES = {
     "gulon_selftest_mean_division": (_i32, [_i32, _i32, C.c_uint64, C.POINTER(C.c_int64)]),

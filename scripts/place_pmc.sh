@@ -1,6 +1,6 @@
 #!/bin/bash
 # HBM-side counters of the k-means placement kernel (one update at BASELINE config 3):
-#   scripts/place_pmc.sh <tag>     (environment selects the variant, e.g. GULON_PLACE_STREAM=0)
+#   scripts/place_pmc.sh <tag>     (GULON_HIP_LIB=build/expt/libgulon_<tag>.so measures a scripts/variant.sh build)
 set -e
 tag=$1
 root=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}

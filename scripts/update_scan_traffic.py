@@ -1,5 +1,5 @@
 """Refresh the filter-kernel entries of profiles/scan_traffic.json from the counter summaries of a collection run:
-    python scripts/update_scan_traffic.py gpurun_out/r03      (after scripts/collect_profiles_r03.sh pmc forms)
+    python scripts/update_scan_traffic.py <dir>      (<dir>: the output directory of scripts/collect_profiles.sh <tag>)
 Every entry is stamped with the hash of the kernel sources of THIS tree (bench.py reports entries of other sources as
 stale), so run it on the tree the counters were taken from."""
 import csv

@@ -41,7 +41,7 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_product_library_carries_no_test_hooks():
-    """Self-tests and the dropped fused-update experiment are in libgulon_hip_testhooks.so only."""
+    """Self-tests are in libgulon_hip_testhooks.so only."""
     from gulon_amd import native
     hooks = _header_symbols(hooks=True)
     assert hooks == sorted(native.TEST_HOOK_SIGNATURES) and len(hooks) == 4
@@ -52,7 +52,7 @@ def test_product_library_carries_no_test_hooks():
     assert not [s for s in prod if "selftest" in s]
     assert set(hooks) <= hk and {s for s in prod if s.startswith("gulon_")} <= hk
     sym = subprocess.check_output(["nm", "-C", native.LIB_PATH], text=True)
-    assert "update_fused" not in sym                       # the experiment's kernels are not linked into the product
+    assert "update_fused" not in sym                       # the dropped fused k-means update stays out of the product
 
 
 def test_host_only_entry_points_match_oracle(oracle):
