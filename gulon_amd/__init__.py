@@ -10,12 +10,14 @@ from .matrix import DeviceMatrix, Matrix
 from .product_quantizer import EncodedMatrix, ProductQuantizer, Quantizer
 from .product_quantizer import Config as ProductQuantizerConfig
 from .vectors import Vectors, subvector_bounds, subvectors
-from .word_vectors import (GroupedWordVectors, KeyedIndex, KeyIndexGrouped, KeyIndexSorted, WordVectors,
-                           read_word2vec)
+from .word_vectors import (DeviceWordVectors, GroupedWordVectors, KeyedIndex, KeyIndexGrouped, KeyIndexSorted,
+                           WordVectors, read_word2vec, read_word2vec_device)
+from .build import build_index
 from .word_index import WordIndex, WordResult
 
 __all__ = ["native", "GroupedIndex", "GroupedVectors", "LimitGroups", "LimitVectors", "group", "Coder", "width_for_clusters", "Index", "PQIndex", "Result", "SortedIndex",
            "exact_nearest_neighbours", "prepare_query", "tune_live", "KMeans", "KMeansConfig", "DeviceMatrix", "Matrix",
            "EncodedMatrix", "ProductQuantizer", "Quantizer", "ProductQuantizerConfig", "Vectors",
            "subvector_bounds", "subvectors", "GroupedWordVectors", "KeyedIndex", "KeyIndexGrouped", "KeyIndexSorted",
-           "WordVectors", "read_word2vec", "WordIndex", "WordResult"]
+           "WordVectors", "read_word2vec", "WordIndex", "WordResult", "DeviceWordVectors", "read_word2vec_device",
+           "build_index"]

@@ -1,4 +1,9 @@
-"""`python -m gulon_amd`: the reference's query commands (command/Main.scala:8-11).
+"""`python -m gulon_amd`: the reference's build and query commands (command/Main.scala:8-11).
+
+  build-index -d l2|cosine -o INDEX [-k N] [-m N] [-n N] [-p [--partitions N] [-l N]] FILE
+                                       command/BuildIndex.scala: a word2vec text file -> an index file; the text is
+                                       parsed on the device (word_vectors.read_word2vec_device) and every later stage
+                                       runs there too (build.build_index)
 
   query-words -i INDEX [-k N] [FILE]   command/QueryWords.scala: one word per line of FILE (or stdin), printed as
                                        `word: w1,w2,...` or `word: not found`, in input order
@@ -10,6 +15,8 @@ batches; the output is the same as querying them one at a time."""
 import argparse
 import re
 import sys
+from dataclasses import dataclass
+from typing import Optional
 
 _EOL = re.compile(r"\r\n|\r|\n")
 CHUNK = 1024        # lines per batch of query-words
@@ -36,9 +43,57 @@ def _positive(s):
     return v
 
 
+@dataclass(frozen=True)
+class BuildConfig:
+    """BuildIndex.Config (BuildIndex.scala:15-22); partitioned: build.Partitioned or None."""
+    metric: str
+    num_clusters: int
+    num_quantizers: int
+    max_iterations: int
+    partitioned: Optional[object]
+    output: str
+    input: str
+
+
+def _integer(s):
+    try:
+        return int(s)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"invalid integer: {s!r}")
+
+
+def _clusters(s):                                            # BuildIndex.scala:29-34
+    v = _integer(s)
+    if v <= 0:
+        raise argparse.ArgumentTypeError("clusters must be at least 1")
+    if v > 65536:
+        raise argparse.ArgumentTypeError("too many clusters, must be at most 65536")
+    return v
+
+
+def _metric(s):                                              # BuildIndex.scala:35-41
+    if s not in ("l2", "cosine"):
+        raise argparse.ArgumentTypeError(f"unsupported metric: {s}")
+    return s
+
+
 def _parser():
-    p = argparse.ArgumentParser(prog="python -m gulon_amd", description="query a Gulon nearest neighbour index")
+    p = argparse.ArgumentParser(prog="python -m gulon_amd",
+                                description="build and query a Gulon nearest neighbour index")
     sub = p.add_subparsers(dest="command", required=True)
+    b = sub.add_parser("build-index", help="build a nearest neighbour index",
+                       description="build a nearest neighbour index")
+    b.add_argument("-d", "--metric", type=_metric, required=True, metavar="l2,cosine", help="distance metric to use")
+    b.add_argument("-k", "--clusters", type=_clusters, default=256, metavar="num_clusters",
+                   help="clusters per quantizer, between 1 and 65536")
+    b.add_argument("-m", "--quantizers", type=_integer, default=25, metavar="num", help="number of quantizers used")
+    b.add_argument("-n", "--max-iters", type=_integer, default=100, metavar="iterations",
+                   help="maximum number of iterations per quantizer")
+    b.add_argument("-p", "--partitioned", action="store_true", help="enable faster queries by partitioning vectors")
+    b.add_argument("--partitions", type=_integer, default=None, metavar="num", help="set fixed number of partitions")
+    b.add_argument("-l", "--limit", type=_integer, default=None, metavar="num", help="number of partitions to search")
+    b.add_argument("-o", "--output", required=True, metavar="file", help="index output file")
+    b.add_argument("file", metavar="file")
     for name, help_, need_file in (("query-words", "query nearest neighbour index by word", False),
                                    ("query", "query nearest neighbour index", True)):
         s = sub.add_parser(name, help=help_, description=help_)
@@ -66,10 +121,42 @@ def query(index, k, vectors, write):
         write(_line(word, result) + "\n")
 
 
-def main(argv=None, stdin=None, stdout=None, load=None):
+def build_config(parser, args):
+    """The parsed build-index arguments as BuildIndex.Config (BuildIndex.scala:52-61 for the partitioning options)."""
+    from .build import Partitioned
+    if args.partitioned:
+        partitioned = Partitioned(args.partitions, args.limit)
+    elif args.partitions is None and args.limit is None:
+        partitioned = None
+    else:
+        parser.error("--partitions and --limit are only applicable with --partitioned")
+    return BuildConfig(args.metric, args.clusters, args.quantizers, args.max_iters, partitioned, args.output, args.file)
+
+
+def run_build_index(config: BuildConfig, write):
+    """BuildIndex.run (BuildIndex.scala:110-121): read (normalised for cosine), build, write."""
+    from .build import build_index, log_task
+    from .index_file import dump_index
+    from .product_quantizer import Config
+    from .word_vectors import read_word2vec_device
+    vectors = log_task(write, "Reading word vectors",
+                       lambda: read_word2vec_device(config.input, normalize=config.metric == "cosine"),
+                       lambda v: f"Read {v.size} word vectors")             # CommandUtils.scala:112-115
+    words, index = build_index(vectors, config.metric, config.partitioned,
+                               Config(config.num_clusters, config.num_quantizers, config.max_iterations), write)
+
+    def dump():                                                              # CommandUtils.writeIndex (:117-120)
+        with open(config.output, "wb") as fh:
+            fh.write(dump_index(index, words))
+    log_task(write, f"Writing index to {config.output}", dump, f"Wrote index to {config.output}")
+
+
+def main(argv=None, stdin=None, stdout=None, load=None, build=None):
     """Returns the exit code.  stdin / stdout: binary streams (default: the process's); load: path -> index with
-    batch_query_by_words / batch_query (default WordIndex.load)."""
-    args = _parser().parse_args(argv)
+    batch_query_by_words / batch_query (default WordIndex.load); build: (BuildConfig, write) -> None, the whole of
+    build-index behind its argument handling (default run_build_index)."""
+    parser = _parser()
+    args = parser.parse_args(argv)
     stdin = stdin if stdin is not None else sys.stdin.buffer
     stdout = stdout if stdout is not None else sys.stdout.buffer
     if load is None:
@@ -79,7 +166,14 @@ def main(argv=None, stdin=None, stdout=None, load=None):
     def write(text):
         stdout.write(text.encode("utf-8"))
 
-    if args.command == "query-words":
+    if args.command == "build-index":
+        config = build_config(parser, args)
+
+        def log(text):
+            write(text)
+            stdout.flush()
+        (build if build is not None else run_build_index)(config, log)
+    elif args.command == "query-words":
         index = load(args.index)
         if args.file is None:
             data = stdin.read()

@@ -282,6 +282,27 @@ GULON_API int32_t gulon_dataset_get_rows(const gulon_dataset *ds, const int32_t 
   });
 }
 
+// WordVectors.sorted / WordVectors.grouped reorder rows (WordVectors.scala:60-71): out[i] = ds[rows[i]], on the device
+GULON_API int32_t gulon_dataset_gather(const gulon_dataset *ds, const int32_t *rows, int32_t n, gulon_dataset **out) {
+  return guarded([&] {
+    GULON_REQUIRE(ds != nullptr && out != nullptr && n >= 0 && (rows != nullptr || n == 0), "bad arguments");
+    *out = nullptr;
+    for (int i = 0; i < n; i++)
+      GULON_REQUIRE(rows[i] >= 0 && rows[i] < ds->n, "row %d out of range [0,%d)", rows[i], ds->n);
+    std::unique_ptr<gulon_dataset> g(new gulon_dataset());
+    g->n = n; g->d = ds->d;
+    const long long total = (long long)n * ds->d;
+    g->x.alloc(std::max<size_t>((size_t)total, 1));
+    if (total) {
+      DevBuf<int> dr; dr.upload(rows, (size_t)n);
+      hipLaunchKernelGGL(gather_rows, dim3(ceil_div(total, 256)), dim3(256), 0, 0, ds->x.p, ds->d, dr.p, total, g->x.p);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipDeviceSynchronize());
+    }
+    *out = g.release();
+  });
+}
+
 GULON_API int32_t gulon_distance_sq_rows(const gulon_dataset *ds, const float *queries, int32_t b,
                                          const int32_t *rows, int32_t k_nn, float *out) {
   return guarded([&] {

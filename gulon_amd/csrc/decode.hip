@@ -7,6 +7,7 @@
 // bit-exact by construction.  Codes are read in the layout the handle already keeps (scan.hip / wide.hip):
 //   byte codes (widths 0/2/4/8): codes[(((i >> 6) * ng + j / vec) * 64 + (i & 63)) * vec + j % vec]
 //   wide codes (10/12/16):       wcodes[((i >> 6) * m + j) * 64 + (i & 63)]
+#include "normalize.hpp"
 #include "scan.hpp"
 
 namespace gulon {
@@ -82,12 +83,7 @@ __global__ __launch_bounds__(64) void decode_rows_kernel(CodeSrc src, const floa
     return;
   }
   __syncthreads();
-  // MathUtils.distance(xs): sequential fp32 sum of x * x in coordinate order (every lane computes it; the LDS reads
-  // are broadcasts), math.sqrt in double, .toFloat
-  float sum = 0.f;
-  for (int e = 0; e < d; e++) { const float x = xs[e]; sum += x * x; }
-  const float dist = (float)__dsqrt_rn((double)sum);
-  for (int e = lane; e < d; e += 64) o[e] = __fdiv_rn(xs[e], dist);
+  normalize_staged_row(xs, d, lane, 64, o);
 }
 
 // Rows [from, until) into out[(i - from) * d + e].  One workgroup per 64-row block: the block's codes are staged in LDS

@@ -49,6 +49,7 @@ class KMeansTraceTotals(C.Structure):
 
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
+_i64p = np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 _vp = C.c_void_p
 _i32 = C.c_int32
@@ -76,6 +77,13 @@ SIGNATURES = {
     "gulon_dataset_shape": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "gulon_dataset_device_ptr": (_i32, [_vp, C.POINTER(_vp)]),
     "gulon_dataset_get_rows": (_i32, [_vp, _i32p, _i32, _f32p]),
+    "gulon_dataset_gather": (_i32, [_vp, _i32p, _i32, C.POINTER(_vp)]),
+    "gulon_ingest_word2vec": (_i32, [_vp, C.c_uint64, C.c_uint64, _i32, C.c_uint64, C.POINTER(_vp)]),
+    "gulon_ingest_counts": (_i32, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "gulon_ingest_words": (_i32, [_vp, _i64p, _i32p]),
+    "gulon_ingest_flagged": (_i32, [_vp, _i64p, _i32p, _i64p, _i32p]),
+    "gulon_ingest_finish": (_i32, [_vp, _i64p, _i32p, _f32p, C.c_int64, _i32, C.POINTER(_vp)]),
+    "gulon_ingest_destroy": (_i32, [_vp]),
     "gulon_kmeans_init": (_i32, [_vp, _i32, _i32, _i32, _i32, _f32p, _vp]),
     "gulon_kmeans_assign": (_i32, [_vp, _i32, _i32, _f32p, _i32, _i32, _i32p]),
     "gulon_kmeans_update": (_i32, [_vp, _i32, _i32, _i32, _i32p, _f32p]),

@@ -109,6 +109,37 @@ int32_t gulon_dataset_shape(const gulon_dataset *ds, int32_t *n, int32_t *d);
 int32_t gulon_dataset_device_ptr(const gulon_dataset *ds, const float **out);
 /* copy rows[0..nrows) (row-major) back to the host */
 int32_t gulon_dataset_get_rows(const gulon_dataset *ds, const int32_t *rows, int32_t nrows, float *out_host);
+/* WordVectors.sorted (WordVectors.scala:60-71) and every other reordering of rows: a new dataset of n rows with
+ * out[i] = ds[rows[i]], gathered on the device (rows: host ints in [0, ds rows); destroy with gulon_dataset_destroy). */
+int32_t gulon_dataset_gather(const gulon_dataset *ds, const int32_t *rows, int32_t n, gulon_dataset **out);
+
+/* ---- word2vec text ingest (WordVectors.readWord2Vec, WordVectors.scala:141-252) -----------------
+ * text[0, len): the bytes of the file (host memory; copied to the device in chunks of about chunk_bytes cut at line
+ * ends, 0 = 64 MiB), data_offset: where the first data line starts (the header line, if any, is the host's:
+ * readDimension, WordVectors.scala:143-160), d: the dimension.  Lines end at \n only; an empty line adds no row; a last line without
+ * \n counts; fields are separated by single blanks; the word is the bytes before the first blank, the vector fields
+ * 1 .. d; further fields are ignored (readFast, WordVectors.scala:162-197).  Each token becomes the correctly rounded binary32
+ * (java.lang.Float.parseFloat, :190) on the device, or is FLAGGED: outside the plain decimal grammar, or not decidable
+ * in the 64-bit significand the kernel carries (gulon_amd/csrc/ingest_parse.h).  The caller converts the flagged
+ * tokens and passes them to gulon_ingest_finish; their coordinates are 0 until then.
+ *   gulon_ingest_counts   rows read, flagged tokens, and the first row with fewer than d components (-1: none --
+ *                         the reference fails on such a line, :183-189; its coordinates are not defined)
+ *   gulon_ingest_words    per row the byte offset in text and the length of its word (:183)
+ *   gulon_ingest_flagged  per flagged token (in no particular order): row, component 0 .. d-1, byte offset, length
+ *   gulon_ingest_finish   writes patch_value[i] to (patch_row[i], patch_field[i]), then, normalize != 0,
+ *                         MathUtils.normalize of every row (MathUtils.scala:100-120, as
+ *                         readWord2Vec(..., normalize = true) does per line, :222-227), and hands the matrix over as
+ *                         a gulon_dataset; once per ingest
+ * Rows keep the order of the file. */
+typedef struct gulon_ingest gulon_ingest;
+int32_t gulon_ingest_word2vec(const uint8_t *text, uint64_t len, uint64_t data_offset, int32_t d,
+                              uint64_t chunk_bytes, gulon_ingest **out);
+int32_t gulon_ingest_counts(const gulon_ingest *in, int64_t *rows, int64_t *flagged, int64_t *first_short_row);
+int32_t gulon_ingest_words(const gulon_ingest *in, int64_t *begin, int32_t *length);
+int32_t gulon_ingest_flagged(const gulon_ingest *in, int64_t *row, int32_t *field, int64_t *begin, int32_t *length);
+int32_t gulon_ingest_finish(gulon_ingest *in, const int64_t *patch_row, const int32_t *patch_field,
+                            const float *patch_value, int64_t n_patch, int32_t normalize, gulon_dataset **out);
+int32_t gulon_ingest_destroy(gulon_ingest *in);
 
 /* ---- KMeans (KMeans.scala) ------------------------------------------------ */
 /* KMeans.init (KMeans.scala:188-196): k rows drawn with java.util.Random(seed),
