@@ -1,4 +1,4 @@
-"""`python -m gulon_amd`: the reference's build and query commands (command/Main.scala:8-11).
+"""`python -m gulon_amd`: the reference's four commands (command/Main.scala:7-11).
 
   build-index -d l2|cosine -o INDEX [-k N] [-m N] [-n N] [-p [--partitions N] [-l N]] FILE
                                        command/BuildIndex.scala: a word2vec text file -> an index file; the text is
@@ -9,6 +9,11 @@
                                        `word: w1,w2,...` or `word: not found`, in input order
   query -i INDEX [-k N] FILE           command/Query.scala: a word2vec text file of query vectors, printed as
                                        `key: w1,w2,...`
+  test -v VECTORS -i INDEX [-s SIZE] [-e ERROR]
+                                       command/Test.scala: the recall of an index file against the exact neighbours in
+                                       the word2vec text file it was built from, `R@k: mean +/- stdDev` for
+                                       k = 1 ... 1000 over SIZE sampled vectors (tests_recall.Tests; the vectors are
+                                       read, the exact neighbours found and the results evaluated on the device)
 
 Input is UTF-8; lines end as java.io.BufferedReader.readLine ends them (\\n, \\r or \\r\\n).  Words are queried in
 batches; the output is the same as querying them one at a time."""
@@ -77,6 +82,32 @@ def _metric(s):                                              # BuildIndex.scala:
     return s
 
 
+@dataclass(frozen=True)
+class RecallConfig:
+    """Test.Options (Test.scala:11-15); epsilon is a binary32."""
+    vectors: str
+    index: str
+    sample_size: int
+    epsilon: float
+
+
+def _sample_size(s):                                         # Test.scala:24-28
+    if _integer(s) <= 0:
+        raise argparse.ArgumentTypeError("must be greater than 0")
+    return _integer(s)
+
+
+def _epsilon(s):                                             # Test.scala:29-33
+    from .word_vectors import parse_float
+    try:
+        v = parse_float(s)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"invalid float: {s!r}")
+    if not v >= 0:
+        raise argparse.ArgumentTypeError("must be non-negative")
+    return v
+
+
 def _parser():
     p = argparse.ArgumentParser(prog="python -m gulon_amd",
                                 description="build and query a Gulon nearest neighbour index")
@@ -101,6 +132,13 @@ def _parser():
                        help="number of nearest neighbours to return")
         s.add_argument("-i", "--index", required=True, metavar="file", help="path to ANN index")
         s.add_argument("file", nargs=None if need_file else "?", metavar="file")
+    t = sub.add_parser("test", help="calculate recall of index", description="calculate recall of index")
+    t.add_argument("-v", "--vectors", required=True, metavar="file", help="word2vec word vectors")
+    t.add_argument("-i", "--index", required=True, metavar="file", help="path to ANN index")
+    t.add_argument("-s", "--sample", type=_sample_size, default=1000, metavar="size",
+                   help="number of queries to sample for recall calculation")
+    t.add_argument("-e", "--error", type=_epsilon, default=0.0, metavar="relative error",
+                   help="amount of relative error allowed when calculating recall")
     return p
 
 
@@ -151,10 +189,37 @@ def run_build_index(config: BuildConfig, write):
     log_task(write, f"Writing index to {config.output}", dump, f"Wrote index to {config.output}")
 
 
-def main(argv=None, stdin=None, stdout=None, load=None, build=None):
+def run_recall(config: RecallConfig, write, load):
+    """Test.run up to the result (Test.scala:47-51, CommandUtils.scala:153-164) -> {k: SummaryStats}.
+    The vectors are read with normalize=False ALWAYS, for a cosine index too, as the reference does (Test.scala:48
+    passes `false`): the index normalises the query itself, the recall distances are taken on the raw vectors.
+    An index form that cannot answer k = 1000 fails here with the library's message; k is never clamped."""
+    from .build import log_task
+    from .tests_recall import Tests
+    from .word_vectors import read_word2vec_device
+    vectors = log_task(write, "Reading word vectors", lambda: read_word2vec_device(config.vectors, normalize=False),
+                       lambda v: f"Read {v.size} word vectors")
+    index = load(config.index)
+    tests = log_task(write, "Sampling test vectors and precomputing distances",
+                     lambda: Tests.sample(vectors.sorted(), config.sample_size),
+                     f"Sampled {config.sample_size} vectors")
+    write("\u001b[36mRUNNING:\u001b[0m Calculating recall of index\n")
+    return tests.recall_of(index, config.epsilon)
+
+
+def print_results(recall, write):
+    """Test.printResults (Test.scala:39-43): ascending k; a k that no query kept is not in the map."""
+    from .tests_recall import java_float_to_string
+    for k in sorted(recall):
+        stats = recall[k]
+        write(f"R@{k}: {java_float_to_string(stats.mean)} +/- {java_float_to_string(stats.std_dev)}\n")
+
+
+def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None):
     """Returns the exit code.  stdin / stdout: binary streams (default: the process's); load: path -> index with
     batch_query_by_words / batch_query (default WordIndex.load); build: (BuildConfig, write) -> None, the whole of
-    build-index behind its argument handling (default run_build_index)."""
+    build-index behind its argument handling (default run_build_index); recall: (RecallConfig, write, load) ->
+    {k: SummaryStats}, the whole of test between its argument handling and its result lines (default run_recall)."""
     parser = _parser()
     args = parser.parse_args(argv)
     stdin = stdin if stdin is not None else sys.stdin.buffer
@@ -166,13 +231,15 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None):
     def write(text):
         stdout.write(text.encode("utf-8"))
 
-    if args.command == "build-index":
-        config = build_config(parser, args)
+    def log(text):                                  # task lines appear as the tasks run
+        write(text)
+        stdout.flush()
 
-        def log(text):
-            write(text)
-            stdout.flush()
-        (build if build is not None else run_build_index)(config, log)
+    if args.command == "build-index":
+        (build if build is not None else run_build_index)(build_config(parser, args), log)
+    elif args.command == "test":
+        config = RecallConfig(args.vectors, args.index, args.sample, args.error)
+        print_results((recall if recall is not None else run_recall)(config, log, load), write)
     elif args.command == "query-words":
         index = load(args.index)
         if args.file is None:

@@ -95,6 +95,23 @@ class WordIndex:
             out.extend(self._result(r) for r in self.index.batch_query(k, q[s:s + BATCH]))
         return out
 
+    def batch_query_raw(self, k, vectors):
+        """batch_query as arrays, for callers that take thousands of neighbours per query and no words (Tests.recallOf):
+        (rows [B][k] int32 with -1 after a query's last entry, distances [B][k], counts [B], flags [B]; a grouped
+        index sets no flags)."""
+        q = np.ascontiguousarray(vectors, np.float32).reshape(-1, self.dimension)
+        rows, dist = np.full((len(q), k), -1, np.int32), np.zeros((len(q), k), np.float32)
+        counts, flags = np.zeros(len(q), np.int32), np.zeros(len(q), np.int32)
+        for s in range(0, len(q), BATCH):
+            part = q[s:s + BATCH]
+            if self._grouped:
+                oi, od, oc = self.index.batch_query_raw(k, part)
+            else:
+                oi, od, oc, flags[s:s + BATCH] = self.index.vector_index.batch_query_raw(k, self.index._prepare(part))
+            have = np.arange(k)[None, :] < oc[:, None]
+            rows[s:s + BATCH], dist[s:s + BATCH], counts[s:s + BATCH] = np.where(have, oi, -1), np.where(have, od, 0), oc
+        return rows, dist, counts, flags
+
     def query(self, k, vector) -> WordResult:
         return self.batch_query(k, np.asarray(vector, np.float32).reshape(1, -1))[0]
 

@@ -472,6 +472,16 @@ int32_t gulon_exact_knn(const gulon_dataset *ds, int32_t from, int32_t until, co
  * recall harness (Tests.scala:18-41): out[B][K]; rows < 0 are skipped (0). */
 int32_t gulon_distance_sq_rows(const gulon_dataset *ds, const float *queries, int32_t b,
                                const int32_t *rows, int32_t k_nn, float *out);
+/* Tests.recallOf (Tests.scala:18-41) for a batch, evaluated on the device (recall.hip): rows[b][max_k] are the
+ * dataset rows an index returned for each query, in result order, negative = none (padding after a short result).
+ * For every query and every j < nks: out_tp[q][j] = #{p < ks[j] : rows[q][p] >= 0 and
+ * MathUtils.distanceSq(query_q, X[rows[q][p]]) <= cutoffs[q][j]} (a NaN distance or cutoff counts nothing).
+ * ks ascending, 1 <= ks[j] <= max_k <= GULON_MAX_K_PEELED, nks <= 16.  out_dist: NULL, or [b][max_k] for the
+ * distances themselves (0 where there is no row), the same bits as gulon_distance_sq_rows.  A row >= n is
+ * GULON_ERR_INVALID_ARGUMENT (found on the device; the outputs are then undefined). */
+int32_t gulon_recall_counts(const gulon_dataset *ds, const float *queries, int32_t b, const int32_t *rows,
+                            int32_t max_k, const int32_t *ks, int32_t nks, const float *cutoffs, int32_t *out_tp,
+                            float *out_dist);
 
 #ifdef __cplusplus
 }
