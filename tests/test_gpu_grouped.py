@@ -17,9 +17,10 @@ def g():
     return gulon_amd
 
 
-def _build(oracle, g, n, d, groups, m, k, seed, dup=0, iters=3):
+def _build(oracle, g, n, d, groups, m, k, seed, dup=0, iters=3, X=None):
     rng = np.random.default_rng(seed)
-    X = (rng.standard_normal((n, d)) + 3.0 * rng.integers(0, 4, (n, 1))).astype(np.float32)
+    if X is None:
+        X = (rng.standard_normal((n, d)) + 3.0 * rng.integers(0, 4, (n, 1))).astype(np.float32)
     if dup:
         X[-dup:] = X[:dup]                                   # exact duplicates: distance ties everywhere
     dm = g.DeviceMatrix.from_host(X)

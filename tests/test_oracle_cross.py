@@ -3,6 +3,7 @@ bit for bit on small inputs (both are written from the Scala source)."""
 import numpy as np
 import pytest
 
+import value_regimes as vr
 from conftest import bits
 from oracle import py_oracle as po
 
@@ -19,19 +20,30 @@ def _data(seed, n, d, scale=1.0, dup=False):
     (0, 200, 6, 0, 6, 5, False), (1, 300, 9, 3, 7, 8, False), (2, 120, 4, 1, 3, 16, True),
     (3, 64, 3, 0, 1, 4, True)])
 def test_kmeans_pieces(oracle, seed, n, d, fr, un, k, dup):
-    X = _data(seed, n, d, dup=dup)
+    _kmeans_pieces(oracle, _data(seed, n, d, dup=dup), seed, fr, un, k, nan=False)
+
+
+@pytest.mark.parametrize("regime", vr.BUILD_REGIMES)
+@pytest.mark.parametrize("seed,n,d,fr,un,k", [(0, 200, 6, 0, 6, 5), (1, 300, 9, 3, 7, 8), (2, 120, 4, 1, 3, 16)])
+def test_kmeans_pieces_value_regimes(oracle, regime, seed, n, d, fr, un, k):
+    """The two CPU references agree at the value-range edges too: this pins the oracle before a GPU result is compared with it."""
+    with np.errstate(all="ignore"):
+        _kmeans_pieces(oracle, vr.build_case(oracle, regime, n, d, fr, un - fr, k, seed, dup=seed == 2), seed, fr, un, k, nan=True)
+
+
+def _kmeans_pieces(oracle, X, seed, fr, un, k, nan):
     s = un - fr
     C0, rows = oracle.kmeans_init(X, fr, s, k, seed)
     P0 = po.kmeans_init(X.tolist(), fr, un, k, seed)
-    assert np.array_equal(bits(C0), bits(np.array(P0, np.float32)))
-    assert np.array_equal(bits(oracle.kmeans_offsets(C0)), bits(np.array(po.kmeans_offsets(P0), np.float32)))
+    vr.same_bits(C0, np.array(P0, np.float32), nan)
+    vr.same_bits(oracle.kmeans_offsets(C0), np.array(po.kmeans_offsets(P0), np.float32), nan)
     for rb in (0, 50):
         a = oracle.kmeans_assign(X, fr, s, C0, rb)
         b = po.kmeans_assign(X.tolist(), fr, P0, rb)
         assert a.tolist() == b
     C1 = oracle.kmeans_from_assignment(X, fr, s, k, a)
     P1 = po.kmeans_from_assignment(X.tolist(), fr, s, k, b)
-    assert np.array_equal(bits(C1), bits(np.array(P1, np.float32)))
+    vr.same_bits(C1, np.array(P1, np.float32), nan)
 
 
 def test_compute_clusters(oracle):
@@ -62,26 +74,95 @@ def test_query_path(oracle, n, d, m, k, B, K, fr, un):
     cents = rng.standard_normal(k * d).astype(np.float32)
     idx = rng.integers(0, k, (m, n)).astype(np.int32)
     Q = rng.standard_normal((B, d)).astype(np.float32)
+    _query_path(oracle, cents, idx, Q, n, d, m, k, B, K, fr, un, nan=False)
+
+
+@pytest.mark.parametrize("regime", vr.QUERY_REGIMES)
+@pytest.mark.parametrize("n,d,m,k,B,K,fr,un", [(300, 10, 4, 7, 5, 5, 0, 300), (3000, 12, 6, 16, 5, 10, 100, 2700)])
+def test_query_path_value_regimes(oracle, regime, n, d, m, k, B, K, fr, un):
+    with np.errstate(all="ignore"):
+        cents, idx, Q = vr.query_case(oracle, regime, n, d, m, k, B)
+        _query_path(oracle, cents, idx, Q, n, d, m, k, B, K, fr, un, nan=True)
+
+
+def _query_path(oracle, cents, idx, Q, n, d, m, k, B, K, fr, un, nan):
     T = oracle.prepare_query(cents, d, m, k, Q)
     sub = po.subvectors(d, m)
     quant = [(f, [[np.float32(v) for v in cents[k * f + c * (u - f): k * f + (c + 1) * (u - f)]]
                   for c in range(k)]) for f, u in sub]
     PT = po.prepare_query(quant, Q.tolist())
-    assert np.array_equal(bits(T), bits(np.array(PT, np.float32)))
+    vr.same_bits(T, np.array(PT, np.float32), nan)
     oi, od, oc = oracle.pq_batch_query(idx, d, k, cents, Q, K, fr, un)
     pres = po.pq_batch_query(quant, idx.tolist(), n, Q.tolist(), K, fr, un)
     for q in range(B):
         ks, vs = pres[q]
         assert oc[q] == len(ks) == min(K, un - fr)
         assert oi[q, :oc[q]].tolist() == ks
-        assert np.array_equal(bits(od[q, :oc[q]]), bits(np.array(vs, np.float32)))
+        vr.same_bits(od[q, :oc[q]], np.array(vs, np.float32), nan)
 
 
 def test_exact_knn(oracle):
-    X = _data(11, 500, 7)
-    Q = _data(12, 3, 7)
+    _exact_knn(oracle, _data(11, 500, 7), _data(12, 3, 7), nan=False)
+
+
+@pytest.mark.parametrize("regime", vr.BUILD_REGIMES)
+def test_exact_knn_value_regimes(oracle, regime):
+    with np.errstate(all="ignore"):
+        X = vr.build_case(oracle, regime, 503, 7, 0, 7, 4)
+        _exact_knn(oracle, X[3:], X[:3] if regime == "degenerate" else vr.build_case(oracle, regime, 3, 7, 0, 7, 4, seed=1), nan=True)
+
+
+def _exact_knn(oracle, X, Q, nan):
     oi, od, oc = oracle.exact_knn(X, Q, 10, 20, 480)
     for q in range(3):
         ks, vs = po.exact_knn(X.tolist(), Q[q].tolist(), 10, 20, 480)
         assert oi[q].tolist() == ks
-        assert np.array_equal(bits(od[q]), bits(np.array(vs, np.float32)))
+        vr.same_bits(od[q], np.array(vs, np.float32), nan)
+
+
+@pytest.mark.parametrize("regime", vr.QUERY_REGIMES)
+@pytest.mark.parametrize("form", list(vr.FORMS))
+def test_query_regimes_exhibit_their_edge(oracle, regime, form):
+    """A regime that does not show its edge at some shape of the GPU tests is a broken test: this is where that shows."""
+    n, d, m, k = vr.FORMS[form]
+    with np.errstate(all="ignore"):
+        cents, idx, Q = vr.query_case(oracle, regime, n, d, m, k, vr.QUERY_B)
+        vr.query_predicate(oracle, regime, cents, idx, Q, d, m, k, K=10)
+
+
+@pytest.mark.parametrize("name,shape,B", [(f, s, vr.PRODUCTION_B) for f, s in vr.PRODUCTION_FORMS.items()]
+                         + [("tie_" + f, s[:4], s[5]) for f, s in vr.TIE_FORMS.items()])
+def test_tight_regime_is_tight_at_the_large_shapes(oracle, name, shape, B):
+    n, d, m, k = shape
+    cents, idx, Q = vr.query_case(oracle, "tight", n, d, m, k, B, per=50 if name.startswith("tie_") else vr.PRODUCTION_PER)
+    vr.query_predicate(oracle, "tight", cents, idx, Q, d, m, k, K=vr.PRODUCTION_K)
+
+
+@pytest.mark.parametrize("regime", vr.BUILD_REGIMES)
+@pytest.mark.parametrize("form", list(vr.BUILD_FORMS))
+def test_build_regimes_exhibit_their_edge(oracle, regime, form):
+    d, frm, s, k = vr.BUILD_FORMS[form]
+    with np.errstate(all="ignore"):
+        X = vr.build_case(oracle, regime, vr.BUILD_N, d, frm, s, k)
+        vr.build_predicate(oracle, regime, X, frm, s, k)
+
+
+@pytest.mark.parametrize("regime", vr.BUILD_REGIMES)
+def test_other_build_inputs_exhibit_their_edge(oracle, regime):
+    """... and the rows of the exact-kNN case, of the product quantizer's training (every sub-vector) and of the grouped index"""
+    with np.errstate(all="ignore"):
+        n, d = vr.KNN_SHAPE
+        vr.build_predicate(oracle, regime, vr.build_case(oracle, regime, n, d, 0, d, 16), 0, d, 16)
+        n, d, m, k = vr.PQ_BUILD
+        X = vr.build_case(oracle, regime, n, d, 0, d // m, k)
+        for f, u in po.subvectors(d, m)[: 1 if regime == "degenerate" else m]:      # (its constant and zero columns: the first)
+            vr.build_predicate(oracle, regime, X, f, u - f, k)
+        if regime in vr.GROUPED_REGIMES:
+            for n, d, groups, m, k, limit, K in vr.GROUPED_PATHS.values():
+                vr.build_predicate(oracle, regime, vr.build_case(oracle, regime, n, d, 0, d, groups), 0, d, groups)
+
+
+def test_tight_rows_of_the_exact_knn_case(oracle):
+    n, d = vr.KNN_SHAPE
+    cents, idx, Q = vr.query_case(oracle, "tight", n, d, *vr.KNN_TIGHT_MK, 12)
+    vr.query_predicate(oracle, "tight", cents, idx, Q, d, *vr.KNN_TIGHT_MK, K=10)
