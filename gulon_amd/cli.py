@@ -5,15 +5,23 @@
                                        parsed on the device (word_vectors.read_word2vec_device) and every later stage
                                        runs there too (build.build_index)
 
-  query-words -i INDEX [-k N] [FILE]   command/QueryWords.scala: one word per line of FILE (or stdin), printed as
+  query-words -i INDEX [-k N] [-v VECTORS [-c N]] [FILE]
+                                       command/QueryWords.scala: one word per line of FILE (or stdin), printed as
                                        `word: w1,w2,...` or `word: not found`, in input order
-  query -i INDEX [-k N] FILE           command/Query.scala: a word2vec text file of query vectors, printed as
+  query -i INDEX [-k N] [-v VECTORS [-c N]] FILE
+                                       command/Query.scala: a word2vec text file of query vectors, printed as
                                        `key: w1,w2,...`
-  test -v VECTORS -i INDEX [-s SIZE] [-e ERROR]
+  test -v VECTORS -i INDEX [-s SIZE] [-e ERROR] [-c N]
                                        command/Test.scala: the recall of an index file against the exact neighbours in
                                        the word2vec text file it was built from, `R@k: mean +/- stdDev` for
                                        k = 1 ... 1000 over SIZE sampled vectors (tests_recall.Tests; the vectors are
                                        read, the exact neighbours found and the results evaluated on the device)
+
+-v VECTORS on the query commands (not in the reference): the index's N candidates per query (-c, default 10 * k) are
+re-ranked by their exact distance to the original vectors of that word2vec text file, and the k nearest are printed
+(refine.RefinedIndex).  test -c N reports the recall of that refined index.  The recall harness asks ONE query per
+sampled vector at the largest k it kept and scores prefixes of the answer, so every R@k line is a prefix of one refined
+result -- the max(N, largest k) candidates re-ranked, the largest k kept -- not a refined query at that k.
 
 Input is UTF-8; lines end as java.io.BufferedReader.readLine ends them (\\n, \\r or \\r\\n).  Words are queried in
 batches; the output is the same as querying them one at a time."""
@@ -89,6 +97,7 @@ class RecallConfig:
     index: str
     sample_size: int
     epsilon: float
+    candidates: Optional[int] = None      # -c: the recall of the index refined over this many candidates
 
 
 def _sample_size(s):                                         # Test.scala:24-28
@@ -131,6 +140,12 @@ def _parser():
         s.add_argument("-k", "--neighbours", type=_positive, default=1, metavar="num",
                        help="number of nearest neighbours to return")
         s.add_argument("-i", "--index", required=True, metavar="file", help="path to ANN index")
+        s.add_argument("-v", "--vectors", default=None, metavar="file",
+                       help="word2vec word vectors the index was built from: re-rank the index's candidates by their "
+                            "exact distance to these")
+        s.add_argument("-c", "--candidates", type=_positive, default=None, metavar="num",
+                       help="candidates taken from the index per query before re-ranking (needs --vectors; "
+                            "default 10 * neighbours)")
         s.add_argument("file", nargs=None if need_file else "?", metavar="file")
     t = sub.add_parser("test", help="calculate recall of index", description="calculate recall of index")
     t.add_argument("-v", "--vectors", required=True, metavar="file", help="word2vec word vectors")
@@ -139,6 +154,10 @@ def _parser():
                    help="number of queries to sample for recall calculation")
     t.add_argument("-e", "--error", type=_epsilon, default=0.0, metavar="relative error",
                    help="amount of relative error allowed when calculating recall")
+    t.add_argument("-c", "--candidates", type=_positive, default=None, metavar="num",
+                   help="report the recall of the index refined against the vectors: num candidates per query re-ranked "
+                        "by exact distance.  Each R@k is a prefix of ONE refined result per query, over "
+                        "max(num, largest k) candidates, not a refined query at that k")
     return p
 
 
@@ -193,15 +212,23 @@ def run_recall(config: RecallConfig, write, load):
     """Test.run up to the result (Test.scala:47-51, CommandUtils.scala:153-164) -> {k: SummaryStats}.
     The vectors are read with normalize=False ALWAYS, for a cosine index too, as the reference does (Test.scala:48
     passes `false`): the index normalises the query itself, the recall distances are taken on the raw vectors.
-    An index form that cannot answer k = 1000 fails here with the library's message; k is never clamped."""
+    An index form that cannot answer k = 1000 fails here with the library's message; k is never clamped.
+    config.candidates: the recall of RefinedIndex(index, vectors, candidates) instead.  Its vectors are what the index
+    prepares its queries for -- a NORMALISED reading of the same file for a cosine index -- while the queries and the
+    recall distances stay on the raw vectors."""
     from .build import log_task
     from .tests_recall import Tests
     from .word_vectors import read_word2vec_device
     vectors = log_task(write, "Reading word vectors", lambda: read_word2vec_device(config.vectors, normalize=False),
                        lambda v: f"Read {v.size} word vectors")
     index = load(config.index)
+    raw = vectors.sorted()
+    if config.candidates is not None:
+        cosine = index.metric == "cosine"
+        originals = read_word2vec_device(config.vectors, normalize=True).sorted() if cosine else raw
+        index = index.refined(originals, config.candidates)
     tests = log_task(write, "Sampling test vectors and precomputing distances",
-                     lambda: Tests.sample(vectors.sorted(), config.sample_size),
+                     lambda: Tests.sample(raw, config.sample_size),
                      f"Sampled {config.sample_size} vectors")
     write("\u001b[36mRUNNING:\u001b[0m Calculating recall of index\n")
     return tests.recall_of(index, config.epsilon)
@@ -215,13 +242,31 @@ def print_results(recall, write):
         write(f"R@{k}: {java_float_to_string(stats.mean)} +/- {java_float_to_string(stats.std_dev)}\n")
 
 
-def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None):
+def read_originals(path, normalize):
+    """The -v vectors of the query commands: on the device, in word order (their key index resolves the index's words)."""
+    from .word_vectors import read_word2vec_device
+    return read_word2vec_device(path, normalize=normalize).sorted()
+
+
+def _refined(args, index, vectors):
+    """The loaded index, or with -v its refined form; -c needs -v."""
+    if args.vectors is None:
+        return index
+    candidates = args.candidates if args.candidates is not None else 10 * args.neighbours
+    return index.refined(vectors(args.vectors, index.metric == "cosine"), candidates)
+
+
+def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None, vectors=None):
     """Returns the exit code.  stdin / stdout: binary streams (default: the process's); load: path -> index with
     batch_query_by_words / batch_query (default WordIndex.load); build: (BuildConfig, write) -> None, the whole of
     build-index behind its argument handling (default run_build_index); recall: (RecallConfig, write, load) ->
-    {k: SummaryStats}, the whole of test between its argument handling and its result lines (default run_recall)."""
+    {k: SummaryStats}, the whole of test between its argument handling and its result lines (default run_recall);
+    vectors: (path, normalize) -> the word vectors behind -v of the query commands (default read_originals)."""
     parser = _parser()
     args = parser.parse_args(argv)
+    if args.command in ("query", "query-words") and args.candidates is not None and args.vectors is None:
+        parser.error("--candidates is only applicable with --vectors")
+    vectors = vectors if vectors is not None else read_originals
     stdin = stdin if stdin is not None else sys.stdin.buffer
     stdout = stdout if stdout is not None else sys.stdout.buffer
     if load is None:
@@ -238,10 +283,10 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None)
     if args.command == "build-index":
         (build if build is not None else run_build_index)(build_config(parser, args), log)
     elif args.command == "test":
-        config = RecallConfig(args.vectors, args.index, args.sample, args.error)
+        config = RecallConfig(args.vectors, args.index, args.sample, args.error, args.candidates)
         print_results((recall if recall is not None else run_recall)(config, log, load), write)
     elif args.command == "query-words":
-        index = load(args.index)
+        index = _refined(args, load(args.index), vectors)
         if args.file is None:
             data = stdin.read()
         else:
@@ -250,8 +295,8 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None)
         query_words(index, args.neighbours, read_lines(data), write)
     else:
         from .word_vectors import read_word2vec
-        vectors = read_word2vec(args.file)
-        index = load(args.index)
-        query(index, args.neighbours, vectors, write)
+        queries = read_word2vec(args.file)
+        index = _refined(args, load(args.index), vectors)
+        query(index, args.neighbours, queries, write)
     stdout.flush()
     return 0

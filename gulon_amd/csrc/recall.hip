@@ -2,27 +2,20 @@
 // (MathUtils.scala:85-95) to each returned row of the dataset and, for every k of the caller's list, the number of
 // entries among the first k whose distance is <= that k's cutoff.  One workgroup per query; the B x max_k distances
 // stay on the device unless the caller asks for them.
-#include "common.hpp"
+#include "row_tile.hpp"
 
 namespace gulon {
 
-constexpr int RC_THREADS = 256;   // positions of one query handled per pass, lane = position
-constexpr int RC_DT = 32;         // dims staged per step
-constexpr int RC_QS = 4096;       // query components held in LDS (the whole query for d <= 4096)
 constexpr int RC_MAX_KS = 16;
 
-// VEC4: d % 4 == 0, rows are 16-byte aligned -- eight lanes read the 128 bytes of a row's RC_DT floats with one
-// 16-byte load each; otherwise 32 lanes read them with 4-byte loads.  Either way the sum of a row is taken afterwards
-// from LDS by the row's own lane, i ascending (the tile is padded to RC_DT + 1 floats: no bank conflicts there).
+// The rows are gathered and summed by tile_distance_sq (row_tile.hpp), VEC4 as there.
 template <bool VEC4>
 __global__ __launch_bounds__(RC_THREADS) void recall_counts_kernel(
     const float *__restrict__ X, int n, int d, const float *__restrict__ Q, const int *__restrict__ rows, int max_k,
     const int *__restrict__ ks, int nks, const float *__restrict__ cutoffs, int *__restrict__ out_tp,
     float *__restrict__ out_dist, int *__restrict__ bad_row) {
   constexpr int NW = RC_THREADS / 64;
-  __shared__ float xs[RC_THREADS * (RC_DT + 1)];
-  __shared__ float qs[RC_QS];
-  __shared__ int rs[RC_THREADS];
+  __shared__ RowTile tile;
   __shared__ int sc[NW * RC_MAX_KS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int q = blockIdx.x;
@@ -43,41 +36,7 @@ __global__ __launch_bounds__(RC_THREADS) void recall_counts_kernel(
     const int p = p0 + tid;
     int row = p < max_k ? qrows[p] : -1;
     if (row >= n) { *bad_row = row; row = -1; }   // any one offender is reported; the entry is not read
-    __syncthreads();                               // the previous pass has finished with rs, xs and qs
-    rs[tid] = row;
-    float acc = 0.f;
-    for (int s0 = 0; s0 < d; s0 += RC_QS) {
-      const int s1 = min(d, s0 + RC_QS);
-      if (!whole_query || p0 == 0) {
-        __syncthreads();
-        for (int i = s0 + tid; i < s1; i += RC_THREADS) qs[i - s0] = query[i];
-      }
-      for (int d0 = s0; d0 < s1; d0 += RC_DT) {
-        __syncthreads();
-        if (VEC4) {
-          for (int e = tid; e < RC_THREADS * (RC_DT / 4); e += RC_THREADS) {
-            const int r = e / (RC_DT / 4), c = (e % (RC_DT / 4)) * 4;
-            const int rr = rs[r];
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (rr >= 0 && d0 + c < s1) v = *(const f32x4 *)(X + (size_t)rr * d + d0 + c);
-            float *o = xs + r * (RC_DT + 1) + c;
-            o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-          }
-        } else {
-          for (int e = tid; e < RC_THREADS * RC_DT; e += RC_THREADS) {
-            const int r = e / RC_DT, c = e % RC_DT;
-            const int rr = rs[r];
-            xs[r * (RC_DT + 1) + c] = (rr >= 0 && d0 + c < s1) ? X[(size_t)rr * d + d0 + c] : 0.f;
-          }
-        }
-        __syncthreads();
-        const int dl = min(RC_DT, s1 - d0);
-        for (int c = 0; c < dl; c++) {
-          float dx = qs[d0 - s0 + c] - xs[tid * (RC_DT + 1) + c];   // dx = y(i) - x(i), y = query (MathUtils.scala:90)
-          acc += dx * dx;
-        }
-      }
-    }
+    const float acc = tile_distance_sq<VEC4>(tile, X, d, query, row, !whole_query || p0 == 0);
     const bool present = row >= 0;
     if (out_dist != nullptr && p < max_k) out_dist[(size_t)q * max_k + p] = present ? acc : 0.f;
 #pragma unroll

@@ -1,0 +1,174 @@
+// Exact re-ranking of an index's candidates against the original vectors (DESIGN.md "Refined queries"): for every query
+//   heap = TopKHeap(k); for p = 0 .. c-1 in order: heap.update(cand[p], MathUtils.distanceSq(query, V[map[cand[p]]]));
+//   Result.fromHeap(heap)
+// (TopKHeap.scala:69-79, MathUtils.scala:85-95, Index.scala:83-94).  One workgroup per query: all of it gathers the
+// candidates' rows and sums their distances (row_tile.hpp, the bits of gulon_recall_counts), the c distances stay in
+// LDS, and the workgroup's first wave then replays them through the reference's heap in candidate order.
+#include "row_tile.hpp"
+#include "topk_heap.hpp"
+
+namespace gulon {
+
+// The replay is not c serial updates.  update(key, x) on a FULL heap does nothing unless root > x, so a candidate can be
+// left out as soon as `root > x` is known to be false AT THE MOMENT THE REFERENCE WOULD INSPECT IT.  While the heap
+// holds no NaN it is a max-heap in the ordinary sense: its root is its largest value, and an effective update replaces
+// that by something smaller, so the root never increases -- a candidate that fails `root > x` against the root of NOW
+// fails it against every later root too.  The wave therefore ballots 64 candidates at a time against the current root
+// and runs update only for the set bits, lowest position first, asking again after every update (the root fell: more
+// bits may clear).  The updates that run are the reference's effective ones in its order, those left out are no-ops:
+// the same heap arrangement.  +-inf are ordinary values here, and a NaN candidate fails `root > NaN` like any no-op.
+// A NaN INSIDE the heap (it can only get in while the heap fills) ends the argument: comparisons with it are false, so
+// percolateUp stops below it and a value larger than the root can sit under it; delete moves the last slot to the
+// root, which can then RISE.  From the first NaN taken in, every candidate goes through update itself, one by one,
+// which makes the reference's own test at the reference's own moment.
+template <class Heap>
+__device__ void refine_replay(Heap &h, const int *__restrict__ qcand, const float *sd, int c, int lane) {
+  bool nan_inside = false;
+  for (int base = 0; base < c; base += 64) {
+    const int p = base + lane;
+    const int id = p < c ? qcand[p] : -1;
+    const float x = p < c ? sd[p] : 0.f;
+    unsigned long long pend = __ballot(id >= 0);           // a negative candidate is padding: never offered
+    while (pend) {
+      if (h.size == h.cap && !nan_inside) {
+        pend &= __ballot(h.val(0) > x);
+        if (!pend) break;
+      }
+      const int j = __builtin_amdgcn_readfirstlane(__ffsll((long long)pend) - 1);
+      pend &= pend - 1;
+      const float xj = readlane_f(x, j);
+      if (h.size < h.cap && xj != xj) nan_inside = true;
+      h.update(readlane_i(id, j), xj);
+    }
+  }
+}
+
+// dyn: the query's c distances, then (k > GULON_MAX_K) the LdsHeap's k values and k keys.
+// out_count[q] = the result's length, or -1 when a candidate of the query has no row in X (see gulon_hip.h).
+template <bool VEC4>
+__global__ __launch_bounds__(RC_THREADS) void refine_topk_kernel(
+    const float *__restrict__ X, int n, int d, const float *__restrict__ Q, const int *__restrict__ cand, int c,
+    const int *__restrict__ row_map, int map_len, int k, int *__restrict__ out_idx, float *__restrict__ out_dist,
+    int *__restrict__ out_count) {
+  __shared__ RowTile tile;
+  __shared__ int bad;
+  extern __shared__ float rf_dyn[];
+  float *sd = rf_dyn;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int q = blockIdx.x;
+  const float *query = Q + (size_t)q * d;
+  const int *qcand = cand + (size_t)q * c;
+  if (tid == 0) bad = 0;                           // (ordered before its readers by the barriers of the first pass)
+
+  const bool whole_query = d <= RC_QS;
+  for (int p0 = 0; p0 < c; p0 += RC_THREADS) {
+    const int p = p0 + tid;
+    const int id = p < c ? qcand[p] : -1;
+    int row = id;
+    bool outside = false;
+    if (id >= 0) {
+      if (row_map != nullptr) {
+        outside = id >= map_len;
+        row = outside ? -1 : row_map[id];
+      }
+      outside = outside || row < 0 || row >= n;
+      if (outside) row = -1;                       // reported below; the entry is not read
+    }
+    const float acc = tile_distance_sq<VEC4>(tile, X, d, query, row, !whole_query || p0 == 0);
+    if (outside) bad = 1;
+    if (p < c) sd[p] = acc;
+  }
+  __syncthreads();
+  if (wave != 0) return;
+
+  int *oi = out_idx + (size_t)q * k;
+  float *od = out_dist + (size_t)q * k;
+  int count;
+  auto put = [&](int i, int kk, float x) {
+    if (lane == 0) { oi[i] = kk; od[i] = x; }
+  };
+  if (k <= GULON_MAX_K) {
+    RegHeap h(k, lane);
+    refine_replay(h, qcand, sd, c, lane);
+    count = h.size;
+    h.drain(put);
+  } else {
+    LdsHeap h(rf_dyn + c, (int *)(rf_dyn + c + k), k, lane);
+    refine_replay(h, qcand, sd, c, lane);
+    count = h.size;
+    h.drain(put);
+  }
+  for (int i = count + lane; i < k; i += 64) { oi[i] = -1; od[i] = 0.f; }
+  if (lane == 0) out_count[q] = bad ? -1 : count;
+}
+
+static size_t refine_dyn_lds(int c, int k) { return sizeof(float) * ((size_t)c + (k > GULON_MAX_K ? 2 * (size_t)k : 0)); }
+
+static void check_refine_args(const gulon_dataset *ds, int32_t b, int32_t c, const int32_t *row_map, int32_t map_len,
+                              int32_t k_nn) {
+  GULON_REQUIRE(ds != nullptr, "dataset is null");
+  GULON_REQUIRE(b >= 0 && k_nn >= 1 && c >= k_nn, "bad arguments b=%d c=%d k_nn=%d (1 <= k_nn <= c)", b, c, k_nn);
+  GULON_REQUIRE(row_map == nullptr || map_len >= 0, "map_len = %d", map_len);
+  GULON_UNSUPPORTED(c > GULON_MAX_K_PEELED, "c = %d > %d", c, GULON_MAX_K_PEELED);
+  // the tile, the c distances and the heap of k > GULON_MAX_K share one workgroup's LDS (160 KiB on gfx950)
+  static_assert(sizeof(RowTile) + 64 + sizeof(float) * 3 * (size_t)GULON_MAX_K_PEELED <= 160 * 1024, "LDS");
+}
+
+}  // namespace gulon
+
+using namespace gulon;
+
+GULON_API int32_t gulon_refine_topk_dev(const gulon_dataset *ds, const float *d_queries, int32_t b,
+                                        const int32_t *d_cand_rows, int32_t c, const int32_t *d_row_map,
+                                        int32_t map_len, int32_t k_nn, int32_t *d_out_idx, float *d_out_dist,
+                                        int32_t *d_out_count, void *stream) {
+  return guarded([&] {
+    check_refine_args(ds, b, c, d_row_map, map_len, k_nn);
+    if (b == 0) return;
+    GULON_REQUIRE(d_queries && d_cand_rows && d_out_idx && d_out_dist && d_out_count, "null argument");
+    const int d = ds->d;
+    const size_t lds = refine_dyn_lds(c, k_nn);
+    const bool vec4 = d % 4 == 0 && (uintptr_t)ds->x.p % 16 == 0;
+    auto kern = vec4 ? refine_topk_kernel<true> : refine_topk_kernel<false>;
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds));
+    hipLaunchKernelGGL(kern, dim3(b), dim3(RC_THREADS), lds, (hipStream_t)stream, ds->x.p, ds->n, d, d_queries,
+                       d_cand_rows, c, d_row_map, map_len, k_nn, d_out_idx, d_out_dist, d_out_count);
+    HIP_CHECK(hipGetLastError());
+  });
+}
+
+GULON_API int32_t gulon_refine_topk(const gulon_dataset *ds, const float *queries, int32_t b, const int32_t *cand_rows,
+                                    int32_t c, const int32_t *row_map, int32_t map_len, int32_t k_nn, int32_t *out_idx,
+                                    float *out_dist, int32_t *out_count) {
+  return guarded([&] {
+    check_refine_args(ds, b, c, row_map, map_len, k_nn);
+    if (b == 0) return;
+    GULON_REQUIRE(queries && cand_rows && out_idx && out_dist && out_count, "null argument");
+    const size_t bc = (size_t)b * c, bk = (size_t)b * k_nn;
+    DevBuf<float> dq, dod(bk);
+    DevBuf<int> dc, dmap, doi(bk), doc((size_t)b);
+    dq.upload(queries, (size_t)b * ds->d);
+    dc.upload(cand_rows, bc);
+    if (row_map != nullptr) dmap.upload(row_map, (size_t)map_len);
+    // (an empty map still has to read as a map: every candidate is then outside it)
+    const int32_t *map_arg = row_map == nullptr ? nullptr : (map_len ? dmap.p : (const int32_t *)dc.p);
+    const int32_t rc = gulon_refine_topk_dev(ds, dq.p, b, dc.p, c, map_arg, map_len, k_nn, doi.p, dod.p, doc.p, nullptr);
+    if (rc != GULON_OK) throw DeviceError{rc};
+    doi.download(out_idx, bk);
+    dod.download(out_dist, bk);
+    doc.download(out_count, (size_t)b);
+    HIP_CHECK(hipDeviceSynchronize());
+    for (int q = 0; q < b; q++) {
+      if (out_count[q] >= 0) continue;
+      for (int p = 0; p < c; p++) {                // name the offender
+        const int id = cand_rows[(size_t)q * c + p];
+        if (id < 0) continue;
+        GULON_REQUIRE(row_map == nullptr || id < map_len, "candidate row %d outside the row map [0,%d)", id, map_len);
+        const int row = row_map ? row_map[id] : id;
+        GULON_REQUIRE(row >= 0 && row < ds->n, "row %d out of range [0,%d)", row, ds->n);
+      }
+      GULON_REQUIRE(false, "query %d has a candidate row outside the dataset", q);
+    }
+  });
+}

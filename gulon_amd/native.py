@@ -140,6 +140,8 @@ SIGNATURES = {
     "gulon_exact_knn": (_i32, [_vp, _i32, _i32, _f32p, _i32, _i32, _i32p, _f32p, _i32p, _i32p]),
     "gulon_distance_sq_rows": (_i32, [_vp, _f32p, _i32, _i32p, _i32, _f32p]),
     "gulon_recall_counts": (_i32, [_vp, _f32p, _i32, _i32p, _i32, _i32p, _i32, _f32p, _i32p, _vp]),
+    "gulon_refine_topk": (_i32, [_vp, _f32p, _i32, _i32p, _i32, _vp, _i32, _i32, _i32p, _f32p, _i32p]),
+    "gulon_refine_topk_dev": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -59,6 +59,16 @@ class WordIndex:
     def size(self):
         return len(self.words)
 
+    @property
+    def metric(self):
+        return self.index.metric
+
+    def refined(self, vectors, candidates):
+        """This index with its results re-ranked against the original `vectors` (refine.RefinedIndex): `candidates`
+        index results per query, the k nearest of them by exact distance."""
+        from .refine import RefinedIndex
+        return RefinedIndex(self, vectors, candidates)
+
     def row_of(self, word) -> Optional[int]:
         return self.key_index.lookup(word)
 

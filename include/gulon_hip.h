@@ -482,6 +482,25 @@ int32_t gulon_distance_sq_rows(const gulon_dataset *ds, const float *queries, in
 int32_t gulon_recall_counts(const gulon_dataset *ds, const float *queries, int32_t b, const int32_t *rows,
                             int32_t max_k, const int32_t *ks, int32_t nks, const float *cutoffs, int32_t *out_tp,
                             float *out_dist);
+/* Exact re-ranking of candidate lists (refine.hip; DESIGN.md "Refined queries"): per query
+ *   heap = TopKHeap(k_nn); for p = 0 .. c-1, in that order, with id = cand_rows[q][p] >= 0:
+ *     heap.update(id, MathUtils.distanceSq(query_q, X[row_map ? row_map[id] : id]));   Result.fromHeap(heap)
+ * (TopKHeap.scala:69-79, MathUtils.scala:85-95, Index.scala:83-94): ties and NaN as the heap decides them.
+ * cand_rows[b][c]: an index's result rows in result order, negative = none; row_map[map_len] takes such a row to the row
+ * of the dataset that holds the same vector (NULL: the identity; map_len is then ignored).  1 <= k_nn <= c <=
+ * GULON_MAX_K_PEELED.  out_idx/out_dist: [b][k_nn], the candidates' OWN ids (not the mapped ones) and their exact
+ * distances, ascending, -1 / 0 after the last entry; out_count[b] = entries.  A candidate >= map_len, or one whose
+ * (mapped) row is outside [0, n), is GULON_ERR_INVALID_ARGUMENT (found on the device; the outputs are then undefined).
+ * Device form: every pointer but ds is a device pointer, the work is enqueued on `stream` (hipStream_t) and not
+ * synchronised, nothing is allocated.  It cannot return what the device finds: a query with such a candidate gets
+ * d_out_count[q] = -1 (its other outputs are undefined) -- the caller's status word, to be tested after the stream. */
+int32_t gulon_refine_topk(const gulon_dataset *ds, const float *queries, int32_t b, const int32_t *cand_rows,
+                          int32_t c, const int32_t *row_map, int32_t map_len, int32_t k_nn, int32_t *out_idx,
+                          float *out_dist, int32_t *out_count);
+int32_t gulon_refine_topk_dev(const gulon_dataset *ds, const float *d_queries, int32_t b,
+                              const int32_t *d_cand_rows, int32_t c, const int32_t *d_row_map, int32_t map_len,
+                              int32_t k_nn, int32_t *d_out_idx, float *d_out_dist, int32_t *d_out_count,
+                              void *stream);
 
 #ifdef __cplusplus
 }
