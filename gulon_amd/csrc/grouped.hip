@@ -733,6 +733,9 @@ __global__ __launch_bounds__(64 * QM_WAVES) void gq_scan_qm(
 // global scratch (one slot per workgroup, which walks the (query, group) pairs), and the group's rows go through
 // the LITERAL TopKHeap in row order -- the same heaps, stored in array order, as gq_group_scan<.., true>, so
 // that gq_merge folds them exactly as GroupedIndex.query does (Index.scala:265-282).  Generality over speed.
+// BIG (k_nn > 63): the pair's heap is an LdsHeap behind the residual (K values, then K keys), stored in the same
+// array order at stride K and folded by gq_merge<true>.
+template <bool BIG>
 __global__ __launch_bounds__(64) void gq_group_scan_wide(const uint16_t *__restrict__ wcodes, int m, int k, int d,
                                                          const float *__restrict__ pq_cents,
                                                          const int *__restrict__ from, const int *__restrict__ sdim,
@@ -741,7 +744,7 @@ __global__ __launch_bounds__(64) void gq_group_scan_wide(const uint16_t *__restr
                                                          int nn_stride, const int *__restrict__ nn_cnt, int stride, int B,
                                                          int K, float *__restrict__ scratch /*[gridDim.x][m][k]*/,
                                                          int *__restrict__ hk, float *__restrict__ hv, int *__restrict__ hs) {
-  extern __shared__ float gw_res[];   // d
+  extern __shared__ float gw_res[];   // d (BIG: then K heap values and K heap keys)
   const int lane = threadIdx.x;
   float *T = scratch + (size_t)blockIdx.x * m * k;
   const long long pairs = (long long)B * stride;
@@ -765,7 +768,10 @@ __global__ __launch_bounds__(64) void gq_group_scan_wide(const uint16_t *__restr
     }
     __threadfence();   // the table is read back by other lanes through the vector L1
     const int row_from = bounds[c], row_until = bounds[c + 1];
-    RegHeap h(K, lane);
+    typename std::conditional<BIG, LdsHeap, RegHeap>::type h = [&] {
+      if constexpr (BIG) return LdsHeap(gw_res + d, reinterpret_cast<int *>(gw_res + d + K), K, lane);
+      else return RegHeap(K, lane);
+    }();
     for (int rb = row_from / 64; rb < (row_until + 63) / 64; rb++) {
       const uint16_t *p = wcodes + (size_t)rb * m * 64 + lane;
       float acc = 0.f;                 // PQIndex.distances: j ascending, unfused fp32
@@ -781,7 +787,11 @@ __global__ __launch_bounds__(64) void gq_group_scan_wide(const uint16_t *__restr
       }
     }
     const size_t o = ((size_t)q * stride + t) * K;
-    if (lane < h.size) { hk[o + lane] = h.k; hv[o + lane] = h.v; }
+    if constexpr (BIG) {
+      for (int i = lane; i < h.size; i += 64) { hk[o + i] = h.key(i); hv[o + i] = h.val(i); }
+    } else {
+      if (lane < h.size) { hk[o + lane] = h.k; hv[o + lane] = h.v; }
+    }
     if (lane == 0) hs[(size_t)q * stride + t] = h.size;
     __threadfence();   // the next pair overwrites the table slot
   }
@@ -1096,8 +1106,6 @@ void run_grouped_query(gulon_grouped_index *gx, const float *dQ, int B, int K, i
   if (B == 0) return;
   gulon_index *ix = gx->pq;
   const int g = gx->g;
-  GULON_UNSUPPORTED(big_k && ix->wide, "k_nn = %d > GULON_MAX_K = %d is not supported by a grouped index with 16-bit codes", K,
-                    GULON_MAX_K);
   if (big_k) {   // the per-group heaps are B x groups x k_nn entries: batches of queries that keep them under 2 GiB
     const long long per_query = (long long)std::max(1, std::min(strategy == 1 ? g : limit, g)) * K;
     const int sub = (int)std::max<long long>(1, std::min<long long>(B, (1ll << 28) / std::max<long long>(1, per_query)));
@@ -1195,11 +1203,23 @@ void run_grouped_query(gulon_grouped_index *gx, const float *dQ, int B, int K, i
                                                                       std::max<long long>(64, (1ll << 30) / (long long)slot)));
     gx->wide_tables.ensure((size_t)blocks * ix->m * ix->k);
     HIP_CHECK(hipMemsetAsync(gx->hs.p, 0, sizeof(int) * (size_t)B * stride, st));
-    hipLaunchKernelGGL(gq_group_scan_wide, dim3(blocks), dim3(64), sizeof(float) * (size_t)ix->d, st, ix->wcodes.p, ix->m,
-                       ix->k, ix->d, ix->cents.p, ix->from.p, ix->sdim.p, gx->gcent.p, gx->bounds.p, dQ, gx->nn.p, nn_stride,
-                       gx->nn_cnt.p, stride, B, K, gx->wide_tables.p, gx->hk.p, gx->hv.p, gx->hs.p);
-    hipLaunchKernelGGL(gq_merge<false>, dim3(B), dim3(64), 0, st, gx->hk.p, gx->hv.p, gx->hs.p, gx->nn_cnt.p, stride, K, d_oi,
-                       d_od, d_oc, (const int *)nullptr, (const int *)nullptr);
+    if (big_k) {   // the heaps in LDS (2 K words behind the residual), folded by the LDS merge
+      const size_t lds = sizeof(float) * ((size_t)ix->d + 2 * (size_t)K);
+      GULON_UNSUPPORTED(lds > 160 * 1024, "grouped query needs %zu B of LDS (d = %d, k_nn = %d)", lds, ix->d, K);
+      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gq_group_scan_wide<true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL(gq_group_scan_wide<true>, dim3(blocks), dim3(64), lds, st, ix->wcodes.p, ix->m, ix->k, ix->d,
+                         ix->cents.p, ix->from.p, ix->sdim.p, gx->gcent.p, gx->bounds.p, dQ, gx->nn.p, nn_stride,
+                         gx->nn_cnt.p, stride, B, K, gx->wide_tables.p, gx->hk.p, gx->hv.p, gx->hs.p);
+      hipLaunchKernelGGL(gq_merge<true>, dim3(B), dim3(64), sizeof(float) * 2 * (size_t)K, st, gx->hk.p, gx->hv.p, gx->hs.p,
+                         gx->nn_cnt.p, stride, K, d_oi, d_od, d_oc, (const int *)nullptr, (const int *)nullptr);
+    } else {
+      hipLaunchKernelGGL(gq_group_scan_wide<false>, dim3(blocks), dim3(64), sizeof(float) * (size_t)ix->d, st, ix->wcodes.p,
+                         ix->m, ix->k, ix->d, ix->cents.p, ix->from.p, ix->sdim.p, gx->gcent.p, gx->bounds.p, dQ, gx->nn.p,
+                         nn_stride, gx->nn_cnt.p, stride, B, K, gx->wide_tables.p, gx->hk.p, gx->hv.p, gx->hs.p);
+      hipLaunchKernelGGL(gq_merge<false>, dim3(B), dim3(64), 0, st, gx->hk.p, gx->hv.p, gx->hs.p, gx->nn_cnt.p, stride, K,
+                         d_oi, d_od, d_oc, (const int *)nullptr, (const int *)nullptr);
+    }
     HIP_CHECK(hipGetLastError());
     return;
   }

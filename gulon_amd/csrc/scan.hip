@@ -613,6 +613,13 @@ void launch_peel_finalize(const float *pv, const int *pi, int B, int cap, int K,
   HIP_CHECK(hipGetLastError());
 }
 
+void launch_peel_export(const float *pv, const int *pi, int B, int cap, int keff, float *out_v, int *out_i,
+                        hipStream_t st) {
+  hipLaunchKernelGGL(peel_export, dim3((unsigned)ceil_div((long long)B * keff, 256LL)), dim3(256), 0, st, pv, pi, B, cap,
+                     keff, out_v, out_i);
+  HIP_CHECK(hipGetLastError());
+}
+
 void launch_build_tables(int W, gulon_index *ix, const float *dQ, int B, int Bpad, float *tables, hipStream_t st,
                          const int *live_queries, float *mins) {
   long long total = (long long)(Bpad / W) * ix->m_pad * 256;

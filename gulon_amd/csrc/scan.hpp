@@ -16,11 +16,14 @@ void launch_merge(bool final_out, const float *in_v, const int *in_i, int lists,
                   int *out_flags, float *out_pv, int *out_pi, hipStream_t st);
 bool replay_enabled();
 // large-K peeling helpers (scan.hip): append a 64-entry round to [B][cap] and set the next lower bound;
-// then cut the concatenated list to [B][K] + count + tie flags
+// then cut the concatenated list to [B][K] + count + tie flags, or (a shard) copy its first keff = K + 1 entries
+// out as a partial list [B][keff]
 void launch_peel_update(const float *tv, const int *ti, int B, int round, int cap, float *pv, int *pi, float *lbv,
                         int *lbi, hipStream_t st);
 void launch_peel_finalize(const float *pv, const int *pi, int B, int cap, int K, int *out_idx, float *out_dist,
                           int *out_count, int *out_flags, hipStream_t st);
+void launch_peel_export(const float *pv, const int *pi, int B, int cap, int keff, float *out_v, int *out_i,
+                        hipStream_t st);
 }  // namespace gulon
 
 namespace gulon { struct ScanTuning; }

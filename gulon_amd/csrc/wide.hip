@@ -18,6 +18,12 @@
 //   merge    the common merge_lists of scan.hip; queries flagged with exact distance ties are then replayed with
 //            the literal TopKHeap like those of a byte-coded index (replay.hip: rp_scan_wide gathers the flagged
 //            query's table from global memory).
+//   K > 63   the result is peeled 64 entries per round like a byte-coded index's (scan.hip): scan_wide<.., PEEL> admits
+//            only rows after the query's lower bound in (distance, row id) order, the round's lists merge to one
+//            64-list, peel_update appends it and moves the bound; ceil((K + 1) / 64) rounds, then peel_finalize
+//            ([B][K], count, tie flags -- no replay) or peel_export (a shard's K + 1 smallest).  Sliced tables:
+//            the slices before the last run once, a round repeats the selecting launch over the parked sums.
+//            An LDS heap per wave does not fit next to the table: 8 x 1000 entries x 8 B + 128 KiB > 160 KiB.
 #include "scan.hpp"
 
 namespace gulon {
@@ -77,14 +83,18 @@ __global__ __launch_bounds__(256) void build_tables_wide(const float *__restrict
 // A table too large for LDS as a whole is walked in slices, one launch per slice: the running sums of
 // every (query, row) go through `partial` ([query][rows of the range], HBM) between the launches --
 // still the reference's order, j ascending -- and only the last launch selects.
-template <bool LDS_T, bool FIRST, bool LAST>
+// PEEL (k_nn > 63, run_wide_query): a round of 64 entries; only rows strictly after the query's lower bound
+// (lbv[q], lbi[q]) in (distance, row id) order are eligible -- the rule of scan.hip's peeling rounds.
+template <bool LDS_T, bool FIRST, bool LAST, bool PEEL = false>
 __global__ __launch_bounds__(WIDE_THREADS) void scan_wide(const uint16_t *__restrict__ codes, int m, int k,
                                                           const float *__restrict__ tables, int row_from,
                                                           int row_until, int row_base, int rb_begin, int rb_total,
                                                           int rb_per_chunk, int nchunks, int keff,
                                                           float *__restrict__ part_v, int *__restrict__ part_i,
                                                           int j0, int j1, float *__restrict__ partial,
-                                                          const int *__restrict__ enable /* per query; null: all */) {
+                                                          const int *__restrict__ enable /* per query; null: all */,
+                                                          const float *__restrict__ lbv, const int *__restrict__ lbi) {
+  static_assert(!PEEL || LAST, "only the selecting launch peels");
   extern __shared__ float wide_lds[];
   if (enable && enable[blockIdx.x] == 0) return;   // (wide_filter.hip: only the queries the filter gave up on)
   if (FIRST) j0 = 0;       // (constants for the optimiser: the one-slice instantiation is the plain scan)
@@ -101,6 +111,8 @@ __global__ __launch_bounds__(WIDE_THREADS) void scan_wide(const uint16_t *__rest
   const float *tab = LDS_T ? wide_lds : T + (size_t)j0 * k;     // tab[(j - j0) * k + c] for j in [j0, j1)
   constexpr bool first = FIRST, last = LAST;      // slice [0, ..) starts the sums, slice [.., m) selects
   float *pq = (first && last) ? nullptr : partial + (size_t)q * rb_total * 64;
+  const float lbq = PEEL ? lbv[q] : -1.f;
+  const int lbiq = PEEL ? lbi[q] : -1;
   WaveList wl;
   wl.init();
   int cnt = 0;
@@ -123,7 +135,8 @@ __global__ __launch_bounds__(WIDE_THREADS) void scan_wide(const uint16_t *__rest
       continue;
     }
     const int row = rb * 64 + lane;
-    const bool valid = row >= row_from && row < row_until;
+    bool valid = row >= row_from && row < row_until;
+    if (PEEL) valid = valid && (acc > lbq || (acc == lbq && row + row_base > lbiq));
     unsigned long long mk = __ballot(valid && acc <= wl.tau);
     while (mk) {
       const int l = __ffsll((long long)mk) - 1;
@@ -181,7 +194,7 @@ void launch_scan_wide_range(gulon_index *ix, int B, int K, int from, int until, 
                                     (int)lds_bytes));
     hipLaunchKernelGGL(kern, dim3(B, nchunks), dim3(WIDE_THREADS), lds_bytes, st, ix->wcodes.p, m, k, ix->tables.p,
                        from, until, ix->row_base, rb_begin, rb_total, rb_per_chunk, nchunks, K + 1, ix->part_v.p,
-                       ix->part_i.p, j0, j1, partial, enable);
+                       ix->part_i.p, j0, j1, partial, enable, (const float *)nullptr, (const int *)nullptr);
     HIP_CHECK(hipGetLastError());
   };
   if (table_bytes <= WIDE_LDS_TABLE) {
@@ -208,13 +221,17 @@ void launch_scan_wide_range(gulon_index *ix, int B, int K, int from, int until, 
 }
 
 // Table build + scan + merge of one batch over rows [from, until) of a wide index (run_query's contract).
+// k_nn > GULON_MAX_K: the result is peeled 64 entries at a time like a byte-coded index's (scan.hip): every round is the
+// exact scan restricted to the rows after the previous round's last entry, merged to one 64-list per query and
+// appended by peel_update; peel_finalize cuts the concatenation to [B][K] with its tie flags (no exact tie replay),
+// peel_export to the (K+1)-list of a shard.  With sliced tables the slices before the last do not depend on the bound:
+// they run once per sub-batch, and a round repeats only the last-slice launch over the parked sums.
 void run_wide_query(gulon_index *ix, const float *dQ, int B, int K, int from, int until, bool final_out, int *d_oi,
                     float *d_od, int *d_oc, int *d_of, float *d_pv, int *d_pi, hipStream_t st) {
-  GULON_UNSUPPORTED(K > GULON_MAX_K, "k_nn = %d > GULON_MAX_K = %d is not supported for k = %d centroids", K, GULON_MAX_K,
-                    ix->k);
-  const int keff = K + 1, m = ix->m, k = ix->k;
+  const bool peeled = K > GULON_MAX_K;            // results come 64 at a time
+  const int keff = peeled ? 64 : K + 1, m = ix->m, k = ix->k;
   const int rb_begin = from / 64, rb_total = ceil_div(until, 64) - rb_begin;
-  if (wide_filter_eligible(ix, B, K, rb_total)) {   // 8-bit lower bounds in front of the exact arithmetic (wide_filter.hip)
+  if (!peeled && wide_filter_eligible(ix, B, K, rb_total)) {   // 8-bit lower bounds in front of the exact arithmetic (wide_filter.hip)
     run_wide_filter_query(ix, dQ, B, K, from, until, final_out, d_oi, d_od, d_oc, d_of, d_pv, d_pi, st);
     return;
   }
@@ -238,6 +255,55 @@ void run_wide_query(gulon_index *ix, const float *dQ, int B, int K, int from, in
   ix->part_v.ensure((size_t)qb * lists * keff);
   ix->part_i.ensure((size_t)qb * lists * keff);
   if (passes > 1) ix->wpartial.ensure((size_t)qb * rows_pad);
+  // one launch over quantizers [j0, min(m, j0 + jp)) for the `nq` queries whose tables are in ix->tables;
+  // lbv / lbi: the peeling bounds of these queries (the selecting launch only)
+  auto launch_slice = [&](int nq, int j0, const float *lbv, const int *lbi) {
+    const int j1 = std::min(m, j0 + jp);
+    float *partial = passes > 1 ? ix->wpartial.p : nullptr;
+    const size_t lds_bytes = lds_t ? (size_t)(j1 - j0) * k * sizeof(float) : 0;
+    const bool first = j0 == 0, last = j1 == m, peel = lbv != nullptr;
+#define WIDE_GO(L, F, LA, P)                                                                                        \
+    {                                                                                                               \
+      auto kern = scan_wide<L, F, LA, P>;                                                                           \
+      if (lds_bytes)                                                                                                \
+        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                         \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));                 \
+      hipLaunchKernelGGL(kern, dim3(nq, nchunks), dim3(WIDE_THREADS), lds_bytes, st, ix->wcodes.p, m, k,             \
+                         ix->tables.p, from, until, ix->row_base, rb_begin, rb_total, rb_per_chunk, nchunks, keff,   \
+                         ix->part_v.p, ix->part_i.p, j0, j1, partial, (const int *)nullptr, lbv, lbi);              \
+    }
+    if (!lds_t) { if (peel) WIDE_GO(false, true, true, true) else WIDE_GO(false, true, true, false) }
+    else if (first && last) { if (peel) WIDE_GO(true, true, true, true) else WIDE_GO(true, true, true, false) }
+    else if (first) WIDE_GO(true, true, false, false)
+    else if (last) { if (peel) WIDE_GO(true, false, true, true) else WIDE_GO(true, false, true, false) }
+    else WIDE_GO(true, false, false, false)
+#undef WIDE_GO
+    HIP_CHECK(hipGetLastError());
+  };
+  if (peeled) {
+    const int rounds = ceil_div(K + 1, 64), cap = rounds * 64;
+    const int j_last = (passes - 1) * jp;           // first quantizer of the selecting launch
+    ix->peel_v.ensure((size_t)B * cap); ix->peel_i.ensure((size_t)B * cap);
+    ix->peel_tv.ensure((size_t)qb * 64); ix->peel_ti.ensure((size_t)qb * 64);
+    ix->peel_lbv.ensure((size_t)B); ix->peel_lbi.ensure((size_t)B);
+    HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)ix->peel_lbv.p, 0xBF800000 /* -1.0f */, (size_t)B, st));
+    HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)ix->peel_lbi.p, 0xFFFFFFFF /* -1 */, (size_t)B, st));
+    for (int q0 = 0; q0 < B; q0 += qb) {
+      const int nq = std::min(qb, B - q0);
+      launch_build_tables_wide(ix->cents.p, ix->from.p, ix->sdim.p, ix->d, m, k, dQ, q0, nq, ix->tables.p, st);
+      for (int j0 = 0; j0 < j_last; j0 += jp) launch_slice(nq, j0, nullptr, nullptr);   // parked sums: once per sub-batch
+      for (int r = 0; r < rounds; r++) {
+        launch_slice(nq, j_last, ix->peel_lbv.p + q0, ix->peel_lbi.p + q0);
+        launch_merge(false, ix->part_v.p, ix->part_i.p, lists, 64LL, (long long)lists * 64, nq, 63, nullptr, nullptr,
+                     nullptr, nullptr, ix->peel_tv.p, ix->peel_ti.p, st);
+        launch_peel_update(ix->peel_tv.p, ix->peel_ti.p, nq, r, cap, ix->peel_v.p + (size_t)q0 * cap,
+                           ix->peel_i.p + (size_t)q0 * cap, ix->peel_lbv.p + q0, ix->peel_lbi.p + q0, st);
+      }
+    }
+    if (final_out) launch_peel_finalize(ix->peel_v.p, ix->peel_i.p, B, cap, K, d_oi, d_od, d_oc, d_of, st);
+    else launch_peel_export(ix->peel_v.p, ix->peel_i.p, B, cap, K + 1, d_pv, d_pi, st);   // a shard's K+1 smallest
+    return;
+  }
   int *flags = d_of;
   if (final_out && replay_enabled() && flags == nullptr) {   // the replay needs the tie flags even if the caller does not
     ix->flags_scratch.ensure((size_t)B);
@@ -246,30 +312,7 @@ void run_wide_query(gulon_index *ix, const float *dQ, int B, int K, int from, in
   for (int q0 = 0; q0 < B; q0 += qb) {
     const int nq = std::min(qb, B - q0);
     launch_build_tables_wide(ix->cents.p, ix->from.p, ix->sdim.p, ix->d, m, k, dQ, q0, nq, ix->tables.p, st);
-    for (int j0 = 0; j0 < m; j0 += jp) {
-      const int j1 = std::min(m, j0 + jp);
-      float *partial = passes > 1 ? ix->wpartial.p : nullptr;
-      const size_t lds_bytes = lds_t ? (size_t)(j1 - j0) * k * sizeof(float) : 0;
-      const bool first = j0 == 0, last = j1 == m;
-#define WIDE_GO(L, F, LA)                                                                                          \
-      {                                                                                                             \
-        auto kern = scan_wide<L, F, LA>;                                                                            \
-        if (lds_bytes)                                                                                              \
-          HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                       \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));               \
-        hipLaunchKernelGGL(kern, dim3(nq, nchunks), dim3(WIDE_THREADS), lds_bytes, st, ix->wcodes.p, m, k,           \
-                           ix->tables.p, from, until, ix->row_base, rb_begin, rb_total, rb_per_chunk, nchunks, keff, \
-                           ix->part_v.p, ix->part_i.p, j0, j1, partial, (const int *)nullptr);                      \
-      }
-      if (!lds_t) WIDE_GO(false, true, true)
-      else if (first && last) WIDE_GO(true, true, true)
-      else if (first) WIDE_GO(true, true, false)
-      else if (last) WIDE_GO(true, false, true)
-      else WIDE_GO(true, false, false)
-#undef WIDE_GO
-      HIP_CHECK(hipGetLastError());
-    }
-    HIP_CHECK(hipGetLastError());
+    for (int j0 = 0; j0 < m; j0 += jp) launch_slice(nq, j0, nullptr, nullptr);
     launch_merge(final_out, ix->part_v.p, ix->part_i.p, lists, (long long)keff, (long long)lists * keff, nq, K,
                  final_out ? d_oi + (size_t)q0 * K : nullptr, final_out ? d_od + (size_t)q0 * K : nullptr,
                  final_out && d_oc ? d_oc + q0 : nullptr, final_out && flags ? flags + q0 : nullptr,

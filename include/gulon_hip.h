@@ -54,9 +54,9 @@ extern "C" {
 
 #define GULON_MAX_K 63 /* neighbours per query held by one wavefront list: fast path, exact tie replay,
                           sharded merge */
-#define GULON_MAX_K_PEELED 8191 /* larger k_nn (flat index, sharded or not; exact kNN): the result is peeled 64
-                                   entries per scan (a shard returns k_nn + 1 <= 8191 entries); ties keep the
-                                   (distance, row id) order + flags */
+#define GULON_MAX_K_PEELED 8191 /* larger k_nn (flat index of any code width, sharded or not; exact kNN): the result
+                                   is peeled 64 entries per scan (a shard returns k_nn + 1 <= 8191 entries); ties keep
+                                   the (distance, row id) order + flags */
 
 typedef struct gulon_dataset gulon_dataset; /* device-resident Matrix            */
 typedef struct gulon_index gulon_index;     /* device-resident PQIndex (codes+PQ) */
@@ -242,7 +242,9 @@ int32_t gulon_prepare_query(const float *cents, int32_t d, int32_t m, int32_t k,
  * to HBM.  row_base is added to every returned row id (row sharding).
  * Every code width of ProductQuantizer.coderFactory: k <= 256 (widths 0/2/4/8) runs the
  * byte-coded kernels; 256 < k <= 65536 (Coder.BytePlus, widths 10/12/16) the wide-code path
- * (exact scan, k_nn <= GULON_MAX_K, tie flags without GULON_FLAG_EXACT_REPLAY). */
+ * (wide.hip: exact scan behind a quantized filter, exact tie replay up to k_nn = GULON_MAX_K; larger k_nn up to
+ * GULON_MAX_K_PEELED peeled 64 entries per scan round like a byte-coded index: (distance, row id) order, tie flags
+ * without GULON_FLAG_EXACT_REPLAY; queries with NaN / +inf distances keep the (distance, row id) rule at every k_nn). */
 int32_t gulon_index_create(const uint8_t *codes, int32_t n, int32_t d, int32_t m, int32_t k,
                            const float *cents, int32_t row_base, gulon_index **out);
 int32_t gulon_index_destroy(gulon_index *idx);
@@ -362,8 +364,8 @@ int32_t gulon_sharded_index_info(const gulon_sharded_index *idx, int32_t *n_shar
  * equally distant coarse centroids included (they are common: WordVectors.grouped's leading empty
  * group repeats a centroid, WordVectors.scala:38-39): queries whose searched groups hang on such a tie
  * (or on a NaN distance) select their groups through the literal exactNearestNeighbours heap.
- * Groups may be empty (offsets may repeat).  k_nn <= GULON_MAX_K on the fast paths; up to 2048 (8-bit codes) through
- * the literal heaps alone, kept in LDS (Tests.scala asks for up to 1000 neighbours). */
+ * Groups may be empty (offsets may repeat).  k_nn <= GULON_MAX_K on the fast paths; up to 2048 (every code width)
+ * through the literal heaps alone, kept in LDS (Tests.scala asks for up to 1000 neighbours). */
 typedef struct gulon_grouped_index gulon_grouped_index;
 int32_t gulon_dataset_group_residuals(const gulon_dataset *ds, const int32_t *perm, const int32_t *group_of,
                                       const float *group_centroids, int32_t g, gulon_dataset **out);
