@@ -15,10 +15,12 @@ from .word_vectors import (DeviceWordVectors, GroupedWordVectors, KeyedIndex, Ke
 from .build import build_index
 from .word_index import WordIndex, WordResult
 from .refine import RefinedIndex, refine_topk
+from .expressions import Expression, Term, compose_reference, parse_expression, partition_by_operands
 
 __all__ = ["native", "GroupedIndex", "GroupedVectors", "LimitGroups", "LimitVectors", "group", "Coder", "width_for_clusters", "Index", "PQIndex", "Result", "SortedIndex",
            "exact_nearest_neighbours", "prepare_query", "tune_live", "KMeans", "KMeansConfig", "DeviceMatrix", "Matrix",
            "EncodedMatrix", "ProductQuantizer", "Quantizer", "ProductQuantizerConfig", "Vectors",
            "subvector_bounds", "subvectors", "GroupedWordVectors", "KeyedIndex", "KeyIndexGrouped", "KeyIndexSorted",
            "WordVectors", "read_word2vec", "WordIndex", "WordResult", "DeviceWordVectors", "read_word2vec_device",
-           "build_index", "RefinedIndex", "refine_topk"]
+           "build_index", "RefinedIndex", "refine_topk", "Expression", "Term", "compose_reference", "parse_expression",
+           "partition_by_operands"]

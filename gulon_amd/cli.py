@@ -5,7 +5,7 @@
                                        parsed on the device (word_vectors.read_word2vec_device) and every later stage
                                        runs there too (build.build_index)
 
-  query-words -i INDEX [-k N] [-v VECTORS [-c N]] [FILE]
+  query-words -i INDEX [-k N] [-x] [-v VECTORS [-c N]] [FILE]
                                        command/QueryWords.scala: one word per line of FILE (or stdin), printed as
                                        `word: w1,w2,...` or `word: not found`, in input order
   query -i INDEX [-k N] [-v VECTORS [-c N]] FILE
@@ -22,6 +22,14 @@ re-ranked by their exact distance to the original vectors of that word2vec text 
 (refine.RefinedIndex).  test -c N reports the recall of that refined index.  The recall harness asks ONE query per
 sampled vector at the largest k it kept and scores prefixes of the answer, so every R@k line is a prefix of one refined
 result -- the max(N, largest k) candidates re-ranked, the largest k kept -- not a refined query at that k.
+
+-x/--expressions on query-words (not in the reference): every line is an expression `word (op word)*`, split on
+whitespace, op one of the stand-alone tokens + and - (weights +1 and -1; a word may itself contain + or -, which is why
+this is opt-in).  The query is the sum of the index's vectors of the words with those weights (expressions.py), composed
+on the device; the words of the line are left out of its answer, so a line of one word prints that word's neighbours
+without the word itself.  A line is printed as `line: w1,w2,...`, `line: not found` if any of its words is absent, or
+`line: invalid expression` (an empty line, a leading or trailing operator, two operators or two words in a row).
+Works together with -v / -c.
 
 Input is UTF-8; lines end as java.io.BufferedReader.readLine ends them (\\n, \\r or \\r\\n).  Words are queried in
 batches; the output is the same as querying them one at a time."""
@@ -146,6 +154,11 @@ def _parser():
         s.add_argument("-c", "--candidates", type=_positive, default=None, metavar="num",
                        help="candidates taken from the index per query before re-ranking (needs --vectors; "
                             "default 10 * neighbours)")
+        if name == "query-words":
+            s.add_argument("-x", "--expressions", action="store_true",
+                           help="read every line as an expression `word (+|- word)*` (operators as stand-alone tokens): "
+                                "query with the sum of the words' vectors and leave the words themselves out of the "
+                                "answer")
         s.add_argument("file", nargs=None if need_file else "?", metavar="file")
     t = sub.add_parser("test", help="calculate recall of index", description="calculate recall of index")
     t.add_argument("-v", "--vectors", required=True, metavar="file", help="word2vec word vectors")
@@ -170,6 +183,22 @@ def query_words(index, k, lines, write):
         part = lines[s:s + CHUNK]
         for word, result in zip(part, index.batch_query_by_words(k, part)):
             write(_line(word, result) + "\n")
+
+
+def query_expressions(index, k, lines, write):
+    """query-words -x: every line an expression; invalid lines are answered without reaching the index."""
+    from .expressions import parse_expression
+    for s in range(0, len(lines), CHUNK):
+        part = lines[s:s + CHUNK]
+        parsed = []
+        for line in part:
+            try:
+                parsed.append(parse_expression(line))
+            except ValueError:
+                parsed.append(None)
+        results = iter(index.batch_query_expressions(k, [e for e in parsed if e is not None]))
+        for line, e in zip(part, parsed):
+            write((f"{line}: invalid expression" if e is None else _line(line, next(results))) + "\n")
 
 
 def query(index, k, vectors, write):
@@ -292,7 +321,7 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
         else:
             with open(args.file, "rb") as fh:
                 data = fh.read()
-        query_words(index, args.neighbours, read_lines(data), write)
+        (query_expressions if args.expressions else query_words)(index, args.neighbours, read_lines(data), write)
     else:
         from .word_vectors import read_word2vec
         queries = read_word2vec(args.file)

@@ -4,51 +4,13 @@
 //   MathUtils.normalize (MathUtils.scala:100-120), fused behind a flag        -- for cosine query-by-row
 //   ProductQuantizer.decode(EncodedMatrix) (ProductQuantizer.scala:58-78)  -- decode_range_kernel (bandwidth-bound)
 // A decoded coordinate is a copy of a codebook entry (plus one fp32 add for the grouped lookup), so results are
-// bit-exact by construction.  Codes are read in the layout the handle already keeps (scan.hip / wide.hip):
-//   byte codes (widths 0/2/4/8): codes[(((i >> 6) * ng + j / vec) * 64 + (i & 63)) * vec + j % vec]
-//   wide codes (10/12/16):       wcodes[((i >> 6) * m + j) * 64 + (i & 63)]
+// bit-exact by construction.  Codes are read in the layout the handle already keeps (row_decode.hpp, shared with
+// compose.hip).
 #include "normalize.hpp"
-#include "scan.hpp"
+#include "row_decode.hpp"
 
 namespace gulon {
 namespace {
-
-// Vectors.subvectors (Vectors.scala:84-104) inverted: the quantizer that coordinate e belongs to.  The first `full`
-// quantizers are `ideal` wide, the rest ideal - 1 (common.hpp subvectors, from which ix->from / ix->sdim are made).
-struct SubvectorMap {
-  int ideal, full;
-  __host__ __device__ SubvectorMap(int d, int m) : ideal((d + m - 1) / m), full(m - ((d + m - 1) / m * m - d)) {}
-  __device__ int quantizer(int e) const {
-    const int split = full * ideal;
-    return e < split ? e / ideal : full + (e - split) / (ideal - 1);
-  }
-  __device__ int from(int j) const { return j < full ? j * ideal : full * ideal + (j - full) * (ideal - 1); }
-  __device__ int sdim(int j) const { return j < full ? ideal : ideal - 1; }
-};
-
-struct CodeSrc {
-  const uint8_t *codes;     // byte layout (nullptr when wide)
-  const uint16_t *wcodes;   // wide layout
-  int ng, vec, m;
-  __device__ int code(long long i, int j) const {
-    if (wcodes) return wcodes[((size_t)(i >> 6) * m + j) * 64 + (i & 63)];
-    return codes[(((size_t)(i >> 6) * ng + j / vec) * 64 + (i & 63)) * vec + j % vec];
-  }
-};
-
-// java.util.Arrays.binarySearch(int[] a, int key), restated literally (an empty group repeats an offset: the
-// search may land on any of the equal entries, which is what the reference's lookup then uses).
-__device__ int java_binary_search(const int *__restrict__ a, int len, int key) {
-  int low = 0, high = len - 1;
-  while (low <= high) {
-    const int mid = (int)((unsigned)(low + high) >> 1);
-    const int v = a[mid];
-    if (v < key) low = mid + 1;
-    else if (v > key) high = mid - 1;
-    else return mid;
-  }
-  return -(low + 1);
-}
 
 // One workgroup (one wavefront) per requested row.  gcent != nullptr: GroupedIndex.lookup, base = the centroid of
 // the partition the reference's binarySearch over the raw offsets names, out = base + decode(row) (MathUtils.add,
@@ -128,14 +90,6 @@ __global__ __launch_bounds__(DR_THREADS) void decode_range_kernel(CodeSrc src, c
   } else {
     for (int f = tid; f < total; f += DR_THREADS) o[f] = value(l0 + f / d, f % d);
   }
-}
-
-CodeSrc code_src(const gulon_index *ix) {
-  CodeSrc s;
-  s.codes = ix->wide ? nullptr : ix->codes.p;
-  s.wcodes = ix->wide ? ix->wcodes.p : nullptr;
-  s.ng = ix->ng; s.vec = ix->vec; s.m = ix->m;
-  return s;
 }
 
 void check_rows_host(const gulon_index *ix, const int32_t *rows, int b) {

@@ -1588,6 +1588,12 @@ GULON_API int32_t gulon_grouped_index_query_rows(gulon_grouped_index *idx, const
   });
 }
 
+namespace gulon {
+GroupedParts grouped_parts(gulon_grouped_index *idx) {
+  return {idx->pq, idx->gcent.p, idx->bounds.p + 1, idx->g - 1, &idx->mu};
+}
+}  // namespace gulon
+
 GULON_API int32_t gulon_grouped_index_row_error(gulon_grouped_index *idx, int32_t *out) {
   return guarded([&] {
     GULON_REQUIRE(idx != nullptr && out != nullptr, "null argument");

@@ -26,7 +26,21 @@ void launch_peel_export(const float *pv, const int *pi, int B, int cap, int keff
                         hipStream_t st);
 }  // namespace gulon
 
-namespace gulon { struct ScanTuning; }
+namespace gulon {
+struct ScanTuning;
+// Workspace of the expression calls (compose.hip): the term lists, the composed vectors and the index's answer at
+// k_nn + extra before the operands are dropped.  `mu` is held for a whole call, so the three steps of a query -- compose,
+// the index's own *_dev query, drop -- see one set of buffers; it is taken before the handle's `mu`, never after.
+struct ExprWork {
+  DevBuf<int> off, rows;       // CSR term lists of the host-pointer forms
+  DevBuf<float> w, q;          // their weights; the composed vectors [b][d]
+  DevBuf<int> oi, oc;          // the answer at depth k_nn + extra
+  DevBuf<float> od;
+  DevBuf<int> fi, fc, ff;      // final lists of the host-pointer forms
+  DevBuf<float> fd;
+  std::mutex mu;
+};
+}
 // PQIndex on the device (opaque to C callers)
 using gulon::DevBuf;
 struct gulon_index {
@@ -57,6 +71,7 @@ struct gulon_index {
   DevBuf<int> flags_scratch;
   DevBuf<int> stage_rows;  // row ids of the host-pointer decode / query-by-row calls (decode.hip)
   DevBuf<int> row_err;     // set by the row decode when a *_dev call asked for a row outside [0, n)
+  gulon::ExprWork expr;    // expression queries (compose.hip)
   DevBuf<unsigned long long> dbg;   // GULON_REPLAY_STATS stamps (replay.hip)
   // large-K peeling rounds
   DevBuf<float> peel_v, peel_tv, peel_lbv;
@@ -268,4 +283,8 @@ void decode_rows_host(const gulon_index *ix, DevBuf<int> &rows_buf, DevBuf<float
                       const float *gcent, const int *offsets, int n_offsets, bool normalize, float *out, hipStream_t st);
 void ensure_row_err(gulon_index *ix);   // the handle's row_err word, allocated and zeroed on first use
 int take_row_err(gulon_index *ix);      // synchronises; returns and clears it
+// grouped.hip: what compose.hip needs of a GroupedIndex handle (the struct is private to grouped.hip) -- the residual
+// index, the group centroids, the raw offsets GroupedIndex.lookup searches, and the handle's mutex
+struct GroupedParts { gulon_index *pq; const float *gcent; const int *offsets; int n_offsets; std::mutex *mu; };
+GroupedParts grouped_parts(gulon_grouped_index *idx);
 }  // namespace gulon

@@ -1,0 +1,121 @@
+"""Expression queries: a weighted sum of stored rows as the query, the operands removed from its answer
+(csrc/compose.hip; DESIGN.md "Expression queries").
+
+An expression is a non-empty list of terms (key, weight): the key a row of the index -- or, at the WordIndex level, a
+word -- and the weight a binary32.  `king - man + woman` is [(king, 1), (man, -1), (woman, 1)]; a single term (w, 1) asks
+for the neighbours of w that are not w.
+
+The composed vector, with v_t = Index.lookup(row_t):
+  1. normalize_terms: v_t = MathUtils.normalize(v_t);
+  2. per coordinate acc = w_0 * v_0[e], then acc = acc + (w_t * v_t[e]) for t = 1, 2, ... in list order, every product
+     and every sum rounded to binary32 on its own;
+  3. normalize_query: MathUtils.normalize of the sum.
+A cosine index sets both flags, an l2 index neither.  `compose_reference` restates this in numpy, bit for bit.
+
+The answer to an expression at k: the index's answer to the composed vector at k + E, E = the number of DISTINCT term
+rows, with the term rows removed and the first k kept.  A batch is partitioned by E (`partition_by_operands`) and
+each part asked with extra = E, so an answer never depends on what else is in the batch."""
+from dataclasses import dataclass
+from typing import Dict, List, Sequence, Tuple, Union
+
+import numpy as np
+
+
+@dataclass(frozen=True)
+class Term:
+    """One operand: `key` is a row id (index level) or a word (WordIndex level)."""
+    key: Union[int, str]
+    weight: float = 1.0
+
+
+@dataclass(frozen=True)
+class Expression:
+    terms: Tuple[Term, ...]
+
+    def __post_init__(self):
+        if len(self.terms) == 0:
+            raise ValueError("requirement failed: an expression needs at least one term")
+
+    def __iter__(self):
+        return iter(self.terms)
+
+    def __len__(self):
+        return len(self.terms)
+
+
+def as_expression(e) -> Expression:
+    """An Expression, or any sequence of Terms / (key, weight) pairs."""
+    if isinstance(e, Expression):
+        return e
+    return Expression(tuple(t if isinstance(t, Term) else Term(t[0], float(t[1])) for t in e))
+
+
+def parse_expression(line: str) -> Expression:
+    """`word (op word)*` split on whitespace, op one of the stand-alone tokens + and -: weights +1 and -1.  ValueError
+    for an empty line, a leading or trailing operator, two operators in a row or two words in a row.  (A token such as
+    `e-mail` or `c++` is a word: only a token that IS + or - is an operator.)"""
+    tokens = line.split()
+    terms, sign, want_word = [], 1.0, True
+    for tok in tokens:
+        is_op = tok in ("+", "-")
+        if is_op == want_word:
+            raise ValueError("invalid expression")
+        if is_op:
+            sign = 1.0 if tok == "+" else -1.0
+        else:
+            terms.append(Term(tok, sign))
+        want_word = is_op
+    if want_word:                                   # nothing at all, or a trailing operator
+        raise ValueError("invalid expression")
+    return Expression(tuple(terms))
+
+
+def compose_reference(vectors, weights, normalize_terms=False, normalize_query=False) -> np.ndarray:
+    """The composed vector of one expression: vectors [T][d] = Index.lookup of its term rows, weights [T]."""
+    from .index import normalize
+    v = np.ascontiguousarray(vectors, np.float32)
+    w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+    if v.ndim != 2 or len(v) != len(w) or len(w) == 0:
+        raise ValueError("requirement failed: one weight per vector, at least one of them")
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        acc = None
+        for t in range(len(w)):
+            x = normalize(v[t]) if normalize_terms else v[t]
+            p = (w[t] * x).astype(np.float32)                       # one rounding per product
+            acc = p if acc is None else (acc + p).astype(np.float32)   # and one per sum
+        return normalize(acc) if normalize_query else acc
+
+
+def distinct_operands(expression) -> int:
+    return len({t.key for t in as_expression(expression)})
+
+
+def partition_by_operands(expressions) -> Dict[int, List[int]]:
+    """E -> the positions of the expressions with E distinct term keys, ascending E; a repeated operand counts once."""
+    parts: Dict[int, List[int]] = {}
+    for i, e in enumerate(expressions):
+        parts.setdefault(distinct_operands(e), []).append(i)
+    return dict(sorted(parts.items()))
+
+
+def to_csr(expressions):
+    """-> (term_offsets [b + 1], term_rows [T], term_weights [T]) for expressions over row ids."""
+    exprs = [as_expression(e) for e in expressions]
+    offsets = np.zeros(len(exprs) + 1, np.int32)
+    offsets[1:] = np.cumsum([len(e) for e in exprs])
+    rows = np.asarray([t.key for e in exprs for t in e], np.int32).reshape(-1)
+    weights = np.asarray([t.weight for e in exprs for t in e], np.float32).reshape(-1)
+    return offsets, rows, weights
+
+
+def query_partitioned(expressions: Sequence, call, columns):
+    """Runs call(part, extra) -> arrays (each with len(part) rows) once per partition of `expressions` by their number
+    of distinct operands, extra = that number, and puts the rows back in input order.  columns: per returned array its
+    (trailing shape, dtype, fill)."""
+    exprs = [as_expression(e) for e in expressions]
+    out = [np.full((len(exprs),) + tuple(shape), fill, dtype) for shape, dtype, fill in columns]
+    for extra, where in partition_by_operands(exprs).items():
+        got = call([exprs[i] for i in where], extra)
+        for dst, src in zip(out, got):
+            dst[where] = src
+    return out

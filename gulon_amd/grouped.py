@@ -169,6 +169,53 @@ class GroupedIndex:
         oi, od, oc = self.batch_query_rows_raw(k, rows)
         return [Result(oi[i, :oc[i]].copy(), od[i, :oc[i]].copy(), 0) for i in range(len(oc))]
 
+    def compose_rows(self, expressions, normalize_terms=None, normalize_query=None):
+        """The composed vector of every expression over grouped row positions (expressions.py), on the device
+        (gulon_grouped_index_compose_rows); the flags default to what the metric asks for.  -> [b][d] float32."""
+        from .expressions import to_csr
+        cosine = self.metric == "cosine"
+        nt = cosine if normalize_terms is None else bool(normalize_terms)
+        nq = cosine if normalize_query is None else bool(normalize_query)
+        off, rows, w = to_csr(expressions)
+        b = len(off) - 1
+        out = np.zeros((b, self.dimension), np.float32)
+        one_i, one_f = np.zeros(1, np.int32), np.zeros(1, np.float32)
+        N.check(N.lib().gulon_grouped_index_compose_rows(self._h, off, rows if b else one_i, w if b else one_f, b,
+                                                         int(nt), int(nq), out.reshape(-1) if out.size else one_f))
+        return out
+
+    def batch_query_terms_raw(self, k, expressions, extra):
+        """gulon_grouped_index_query_terms as it is: the answer at k + extra with every expression's term rows removed,
+        the first k kept.  -> (rows [b][k], distances [b][k], counts [b])."""
+        from .expressions import to_csr
+        off, rows, w = to_csr(expressions)
+        b = len(off) - 1
+        s, limit = self._strategy()
+        cosine = int(self.metric == "cosine")
+        oi = np.zeros((b, max(k, 1)), np.int32)
+        od = np.zeros((b, max(k, 1)), np.float32)
+        oc = np.zeros(max(b, 1), np.int32)
+        one_i, one_f = np.zeros(1, np.int32), np.zeros(1, np.float32)
+        N.check(N.lib().gulon_grouped_index_query_terms(self._h, off, rows if b else one_i, w if b else one_f, b, k,
+                                                        extra, cosine, cosine, s, limit, oi.reshape(-1), od.reshape(-1),
+                                                        oc))
+        return oi[:, :k], od[:, :k], oc[:b]
+
+    def batch_query_expressions_raw(self, k, expressions):
+        """batch_query_terms_raw per partition of the batch by its number E of distinct term rows, extra = E, in input
+        order: (rows [b][k] with -1 after a query's last entry, distances [b][k], counts [b], flags [b] = 0)."""
+        from .expressions import query_partitioned
+        oi, od, oc = query_partitioned(expressions, lambda part, extra: self.batch_query_terms_raw(k, part, extra),
+                                       (((k,), np.int32, -1), ((k,), np.float32, np.inf), ((), np.int32, 0)))
+        return oi, od, oc, np.zeros(len(oc), np.int32)
+
+    def batch_query_expressions(self, k, expressions):
+        """Per expression over grouped row positions the k nearest rows of its composed vector that are none of its
+        operands: GroupedIndex.batchQuery at k + E, the E distinct operands removed, the first k kept."""
+        from .index import Result
+        oi, od, oc, _ = self.batch_query_expressions_raw(k, expressions)
+        return [Result(oi[i, :oc[i]].copy(), od[i, :oc[i]].copy(), 0) for i in range(len(oc))]
+
     def close(self):
         if self._h is not None and self._h.value:
             N.lib().gulon_grouped_index_destroy(self._h)

@@ -168,6 +168,53 @@ class PQIndex:
         oi, od, oc, of = self.batch_query_rows_raw(k, rows, frm, until, normalize)
         return [Result(oi[i, :oc[i]].copy(), od[i, :oc[i]].copy(), int(of[i])) for i in range(len(oc))]
 
+    def compose_rows(self, expressions, normalize_terms=False, normalize_query=False):
+        """The composed vector of every expression over row ids (expressions.py), on the device
+        (gulon_index_compose_rows).  -> [len(expressions)][d] float32."""
+        from .expressions import to_csr
+        off, rows, w = to_csr(expressions)
+        b = len(off) - 1
+        out = np.zeros((b, self.dimension), np.float32)
+        one_i, one_f = np.zeros(1, np.int32), np.zeros(1, np.float32)
+        N.check(N.lib().gulon_index_compose_rows(self._h, off, rows if b else one_i, w if b else one_f, b,
+                                                 int(bool(normalize_terms)), int(bool(normalize_query)),
+                                                 out.reshape(-1) if out.size else one_f))
+        return out
+
+    def batch_query_terms_raw(self, k, expressions, extra, frm=0, until=None, normalize_terms=False,
+                              normalize_query=False):
+        """gulon_index_query_terms as it is: the answer at k + extra with every expression's term rows removed, the
+        first k kept.  -> (rows [b][k], distances [b][k], counts [b], flags [b])."""
+        from .expressions import to_csr
+        off, rows, w = to_csr(expressions)
+        b = len(off) - 1
+        until = self.length if until is None else until
+        oi = np.zeros((b, max(k, 1)), np.int32)
+        od = np.zeros((b, max(k, 1)), np.float32)
+        oc = np.zeros(max(b, 1), np.int32)
+        of = np.zeros(max(b, 1), np.int32)
+        one_i, one_f = np.zeros(1, np.int32), np.zeros(1, np.float32)
+        N.check(N.lib().gulon_index_query_terms(self._h, off, rows if b else one_i, w if b else one_f, b, k, extra,
+                                                int(bool(normalize_terms)), int(bool(normalize_query)), frm, until,
+                                                oi.reshape(-1), od.reshape(-1), oc, of))
+        return oi[:, :k], od[:, :k], oc[:b], of[:b]
+
+    def batch_query_terms_partitioned(self, k, expressions, frm=0, until=None, normalize_terms=False,
+                                      normalize_query=False):
+        """batch_query_terms_raw per partition of the batch by its number E of distinct term rows, extra = E, in input
+        order: (rows [b][k] with -1 after a query's last entry, distances [b][k], counts [b], flags [b])."""
+        from .expressions import query_partitioned
+        return query_partitioned(
+            expressions,
+            lambda part, extra: self.batch_query_terms_raw(k, part, extra, frm, until, normalize_terms, normalize_query),
+            (((k,), np.int32, -1), ((k,), np.float32, np.inf), ((), np.int32, 0), ((), np.int32, 0)))
+
+    def batch_query_terms(self, k, expressions, frm=0, until=None, normalize_terms=False, normalize_query=False):
+        """Per expression: batchQuery(k + E, composed vector) with the E distinct term rows removed and the first k
+        kept, without leaving the device between composing and the final list."""
+        oi, od, oc, of = self.batch_query_terms_partitioned(k, expressions, frm, until, normalize_terms, normalize_query)
+        return [Result(oi[i, :oc[i]].copy(), od[i, :oc[i]].copy(), int(of[i])) for i in range(len(oc))]
+
     def close(self):
         if self._h is not None and self._h.value:
             N.lib().gulon_index_destroy(self._h)
@@ -227,6 +274,22 @@ class SortedIndex:
         """Index.queryByWord (Index.scala:38-45) on row ids: query(k, lookup(row)) for every row, decoded (and for a
         cosine index normalised, Index.scala:324-331) on the device."""
         return self.vector_index.batch_query_rows(k, rows, normalize=self.metric == "cosine")
+
+    def compose_rows(self, expressions):
+        """The query vector of every expression over row ids as this index prepares it: terms and sum normalised for a
+        cosine index (expressions.py)."""
+        cosine = self.metric == "cosine"
+        return self.vector_index.compose_rows(expressions, cosine, cosine)
+
+    def batch_query_expressions_raw(self, k, expressions):
+        cosine = self.metric == "cosine"
+        return self.vector_index.batch_query_terms_partitioned(k, expressions, normalize_terms=cosine,
+                                                               normalize_query=cosine)
+
+    def batch_query_expressions(self, k, expressions):
+        """Per expression over row ids the k nearest rows of its composed vector that are none of its operands."""
+        cosine = self.metric == "cosine"
+        return self.vector_index.batch_query_terms(k, expressions, normalize_terms=cosine, normalize_query=cosine)
 
 
 class Index:

@@ -129,6 +129,18 @@ SIGNATURES = {
     "gulon_grouped_index_query_rows_dev": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "gulon_index_row_error": (_i32, [_vp, C.POINTER(_i32)]),
     "gulon_grouped_index_row_error": (_i32, [_vp, C.POINTER(_i32)]),
+    "gulon_index_compose_rows": (_i32, [_vp, _i32p, _i32p, _f32p, _i32, _i32, _i32, _f32p]),
+    "gulon_index_compose_rows_dev": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "gulon_grouped_index_compose_rows": (_i32, [_vp, _i32p, _i32p, _f32p, _i32, _i32, _i32, _f32p]),
+    "gulon_grouped_index_compose_rows_dev": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "gulon_index_query_terms": (_i32, [_vp, _i32p, _i32p, _f32p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32p, _f32p,
+                                       _i32p, _i32p]),
+    "gulon_index_query_terms_dev": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
+                                           _vp, _vp]),
+    "gulon_grouped_index_query_terms": (_i32, [_vp, _i32p, _i32p, _f32p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32p,
+                                               _f32p, _i32p]),
+    "gulon_grouped_index_query_terms_dev": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp,
+                                                   _vp, _vp]),
     "gulon_replay_pack_words": (C.c_int64, [_i32, _i32]),
     "gulon_index_replay_collect_dev": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp]),
     "gulon_replay_apply_dev": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),

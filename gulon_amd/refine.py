@@ -198,6 +198,30 @@ class RefinedIndex:
     def query_by_word(self, k, word, candidates=None) -> Optional[WordResult]:
         return self.batch_query_by_words(k, [word], candidates)[0]
 
+    def batch_query_expressions(self, k, expressions, candidates=None) -> List[Optional[WordResult]]:
+        """Expression queries (expressions.py), refined: the index answers every expression with `candidates` entries,
+        its operands already dropped; they are re-ranked by their exact distance from the composed vector -- as the
+        index prepares it, normalised for a cosine index -- to the original vectors, and the k nearest kept.  None for
+        an expression that names a word the index lacks."""
+        from .word_index import BATCH
+        c = self._candidates(k, candidates)
+        wi = self.word_index
+        resolved = wi.resolve_expressions(expressions)
+        present = [i for i, e in enumerate(resolved) if e is not None]
+        out: List[Optional[WordResult]] = [None] * len(resolved)
+        for s in range(0, len(present), BATCH):
+            part = present[s:s + BATCH]
+            exprs = [resolved[i] for i in part]
+            oi, _, oc, flags = wi.index.batch_query_expressions_raw(c, exprs)
+            prepared = wi.index.compose_rows(exprs)
+            cand = np.where(np.arange(c)[None, :] < oc[:, None], oi, -1).astype(np.int32)
+            for i, res in zip(part, self._results(*self._refine(k, prepared, cand), flags)):
+                out[i] = res
+        return out
+
+    def query_expression(self, k, expression, candidates=None) -> Optional[WordResult]:
+        return self.batch_query_expressions(k, [expression], candidates)[0]
+
     def close(self):
         """Frees the map and the workspace; the index and the vectors stay the caller's."""
         for a in [self._map] + self._work:

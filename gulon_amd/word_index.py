@@ -97,6 +97,34 @@ class WordIndex:
     def query_by_word(self, k, word) -> Optional[WordResult]:
         return self.batch_query_by_words(k, [word])[0]
 
+    def resolve_expressions(self, expressions):
+        """Expressions over words (Expression objects, sequences of Term / (word, weight), or text for
+        parse_expression) -> the same over row ids, None where a word is absent."""
+        from .expressions import Expression, Term, as_expression, parse_expression
+        out = []
+        for e in expressions:
+            e = parse_expression(e) if isinstance(e, str) else as_expression(e)
+            rows = [self.row_of(t.key) for t in e]
+            out.append(None if any(r is None for r in rows) else
+                       Expression(tuple(Term(r, t.weight) for r, t in zip(rows, e))))
+        return out
+
+    def batch_query_expressions(self, k, expressions) -> List[Optional[WordResult]]:
+        """Per expression over words (`king - man + woman`) the k nearest words of its composed vector that are none of
+        its operands, in input order; None for an expression that names a word the index lacks.  Composed, queried and
+        filtered on the device, up to BATCH expressions per batch."""
+        resolved = self.resolve_expressions(expressions)
+        present = [i for i, e in enumerate(resolved) if e is not None]
+        out: List[Optional[WordResult]] = [None] * len(resolved)
+        for s in range(0, len(present), BATCH):
+            part = present[s:s + BATCH]
+            for i, r in zip(part, self.index.batch_query_expressions(k, [resolved[i] for i in part])):
+                out[i] = self._result(r)
+        return out
+
+    def query_expression(self, k, expression) -> Optional[WordResult]:
+        return self.batch_query_expressions(k, [expression])[0]
+
     def batch_query(self, k, vectors) -> List[WordResult]:
         """Index.batchQuery (Index.scala:25-32) with the results' words."""
         q = np.ascontiguousarray(vectors, np.float32).reshape(-1, self.dimension)

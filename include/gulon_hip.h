@@ -423,6 +423,66 @@ int32_t gulon_grouped_index_query_rows_dev(gulon_grouped_index *idx, const int32
 int32_t gulon_index_row_error(gulon_index *idx, int32_t *out);
 int32_t gulon_grouped_index_row_error(gulon_grouped_index *idx, int32_t *out);
 
+/* ---- Expression queries: stored rows composed on the device, operands dropped (compose.hip) ------------------------
+ * An EXPRESSION is a non-empty list of terms (row, weight): LOCAL rows of the index (for a GroupedIndex: grouped row
+ * positions) and binary32 weights.  b expressions are given in CSR form: term_offsets[b + 1] (term_offsets[0] = 0,
+ * strictly ascending), term_rows[T] and term_weights[T] with T = term_offsets[b].  The composed vector of an expression:
+ *   v_t = Index.lookup(row_t) -- gulon_index_decode_rows / gulon_grouped_index_lookup_rows (the partition by the
+ *         reference's binarySearch rule) -- and, normalize_terms != 0, MathUtils.normalize(v_t);
+ *   per coordinate e: acc = w_0 * v_0[e]; acc = acc + (w_t * v_t[e]) for t = 1, 2, ... in list order, every product and
+ *         every sum rounded to binary32 on its own (no fma, no reassociation);
+ *   normalize_query != 0: MathUtils.normalize of the sum (SortedIndex.prepare, Index.scala:324-331).
+ * The handles carry no metric: a cosine index passes 1 for both flags, an l2 index 0 for both.  Nothing treats a zero
+ * vector specially: it is a legitimate l2 query, normalises to NaN on a cosine index, and a NaN query is answered as
+ * every NaN query is (GULON_FLAG_NONFINITE).  d * 4 <= 64 KiB, as for the row decode.
+ * The host-pointer forms check b, the offsets and every row before launching anything (GULON_ERR_INVALID_ARGUMENT).
+ * The _dev forms take device pointers and a stream, do not synchronise and cannot check: an expression without terms, or
+ * with a term row outside [0, n), comes back as an all-NaN vector (its query as the query of an all-NaN vector) and
+ * sets the handle's row-error word (gulon_index_row_error / gulon_grouped_index_row_error).
+ *
+ * gulon_*_compose_rows: the composed vectors, out [b][d]. */
+int32_t gulon_index_compose_rows(gulon_index *idx, const int32_t *term_offsets, const int32_t *term_rows,
+                                 const float *term_weights, int32_t b, int32_t normalize_terms,
+                                 int32_t normalize_query, float *out);
+int32_t gulon_index_compose_rows_dev(gulon_index *idx, const int32_t *d_term_offsets, const int32_t *d_term_rows,
+                                     const float *d_term_weights, int32_t b, int32_t normalize_terms,
+                                     int32_t normalize_query, float *d_out, void *stream);
+int32_t gulon_grouped_index_compose_rows(gulon_grouped_index *idx, const int32_t *term_offsets,
+                                         const int32_t *term_rows, const float *term_weights, int32_t b,
+                                         int32_t normalize_terms, int32_t normalize_query, float *out);
+int32_t gulon_grouped_index_compose_rows_dev(gulon_grouped_index *idx, const int32_t *d_term_offsets,
+                                             const int32_t *d_term_rows, const float *d_term_weights, int32_t b,
+                                             int32_t normalize_terms, int32_t normalize_query, float *d_out,
+                                             void *stream);
+/* gulon_*_query_terms: per expression (extra >= 0)
+ *   1. the index's own answer to the composed vector at depth k_nn + extra: what gulon_index_batch_query_dev /
+ *      gulon_grouped_index_batch_query_dev returns for it -- tie flags, the peeled (distance, row id) order above
+ *      GULON_MAX_K and the limits and errors of the index form (k_nn + extra counts against them) included;
+ *   2. every entry whose row is one of the expression's term rows is removed, the others keep their order;
+ *   3. the first k_nn are kept.
+ * Outputs as gulon_index_batch_query ([b][k_nn] idx/dist, -1 / +inf after the last entry; count[b]; flags[b], those of
+ * step 1, nullable) and gulon_grouped_index_batch_query.  With extra = the number of distinct term rows of every
+ * expression of the batch a full list can only fall short where step 1's does.  Everything runs on one stream (the
+ * _dev forms: the caller's); nothing returns to the host in between. */
+int32_t gulon_index_query_terms(gulon_index *idx, const int32_t *term_offsets, const int32_t *term_rows,
+                                const float *term_weights, int32_t b, int32_t k_nn, int32_t extra,
+                                int32_t normalize_terms, int32_t normalize_query, int32_t from, int32_t until,
+                                int32_t *out_idx, float *out_dist, int32_t *out_count, int32_t *out_flags);
+int32_t gulon_index_query_terms_dev(gulon_index *idx, const int32_t *d_term_offsets, const int32_t *d_term_rows,
+                                    const float *d_term_weights, int32_t b, int32_t k_nn, int32_t extra,
+                                    int32_t normalize_terms, int32_t normalize_query, int32_t from, int32_t until,
+                                    int32_t *d_out_idx, float *d_out_dist, int32_t *d_out_count, int32_t *d_out_flags,
+                                    void *stream);
+int32_t gulon_grouped_index_query_terms(gulon_grouped_index *idx, const int32_t *term_offsets, const int32_t *term_rows,
+                                        const float *term_weights, int32_t b, int32_t k_nn, int32_t extra,
+                                        int32_t normalize_terms, int32_t normalize_query, int32_t strategy,
+                                        int32_t limit, int32_t *out_idx, float *out_dist, int32_t *out_count);
+int32_t gulon_grouped_index_query_terms_dev(gulon_grouped_index *idx, const int32_t *d_term_offsets,
+                                            const int32_t *d_term_rows, const float *d_term_weights, int32_t b,
+                                            int32_t k_nn, int32_t extra, int32_t normalize_terms,
+                                            int32_t normalize_query, int32_t strategy, int32_t limit,
+                                            int32_t *d_out_idx, float *d_out_dist, int32_t *d_out_count, void *stream);
+
 /* Kernel timing for the roofline line of bench.py: when enabled, every scan-kernel
  * launch of this index is bracketed by hipEvents on the launch stream;
  * gulon_index_profile_read synchronises them and returns the summed duration. */
