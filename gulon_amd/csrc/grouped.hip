@@ -9,18 +9,21 @@
 // ARRAY order, so under distance ties the answer depends on the literal heaps.  Kernels:
 //   gq_cdist            query x centroid distances (MathUtils.distanceSq order), centroids transposed
 //   gq_nearest_groups   LimitGroups(<= 63): literal TopKHeap in registers (lane = slot) + deleteAll
-//   gq_sorted_groups    LimitVectors / larger limits: (distance, id) bitonic sort, cut by rows or count
-//   gq_group_scan       workgroup = 4 (query, searched group) pairs, one wave each: the residual's
-//                       m x k table in LDS (Index.prepareQuery arithmetic; each quantizer's codebook
-//                       staged once per workgroup, transposed), then the group's rows 64 at a time
-//                       (PQIndex.distances order).  Two instantiations:
-//                         fast     ascending (distance, row) list of K+1 entries per pair
-//                         literal  the reference's TopKHeap, fed in row order, stored in array order
-//   gq_merge_fast       merges the lists; a query whose K+1 best contain equal distances (or that
-//                       saw a NaN) is appended to a list ...
-//   gq_group_scan<literal> + gq_merge   ... and redone literally: TopKHeap.merge of the group heaps
-//                       in search order + Result.fromHeap.  Ids and order therefore equal the
-//                       reference's also under ties (GULON_GROUPED_LITERAL=1: every query).
+//   gq_select_groups    LimitGroups(> 63) of many groups: radix select of the limit-th distance, sort of the selected
+//   gq_sorted_groups    LimitVectors / the other limits: (distance, id) bitonic sort, cut by rows or count
+//   gq_literal_groups   the reference's heap for queries whose groups hang on equal centroid distances
+//   gq_approx_scan      (or the by-group filter of grouped_filter.hip) the 64 rows of a query's searched groups
+//                       with the smallest approximate distance, from one table per query ...
+//   gq_rerank           ... re-scored with the reference's arithmetic and certified; a query that is not
+//                       certified, has equal distances among its K+1 best or saw a NaN is appended to a list ...
+//   gq_group_scan + gq_merge   ... and redone literally.  Workgroup = 4 (query, searched group) pairs, one
+//                       wave each: the residual's m x k table in LDS (Index.prepareQuery arithmetic; each
+//                       quantizer's codebook staged once per workgroup, transposed), then the group's rows
+//                       64 at a time (PQIndex.distances order) through the reference's TopKHeap, fed in row
+//                       order, stored in array order; TopKHeap.merge of the group heaps in search order +
+//                       Result.fromHeap.  Ids and order therefore equal the reference's also under ties.
+//                       Every query takes this way for k_nn > 63, on an index without rows and with
+//                       GULON_GROUPED_LITERAL=1; gq_group_scan_wide does the same over 16-bit codes.
 #include "scan.hpp"
 
 #include "grouped_filter.hpp"
@@ -32,10 +35,9 @@ struct gulon_grouped_index {
   int32_t n = 0, d = 0, g = 0;
   DevBuf<float> gcent, gcent_t;    // [g][d] centroids of the non-empty groups, and the [d][g] transpose
   DevBuf<int> bounds;              // [g+1] first row of every group, then n
-  DevBuf<uint16_t> codes2;         // [n/64][ceil(m/2)][64]: the codes of quantizers 2h (low byte) and 2h+1 (gq_scan_qm)
   // scratch (grown on demand under mu)
   DevBuf<float> q_dev, cdist, hv, od;
-  DevBuf<int> nn, nn_cnt, hk, hs, oi, oc, qlist, qcount, sel_ok, nn_sized, lit_flag;
+  DevBuf<int> nn, nn_cnt, hk, hs, oi, oc, qlist, qcount, sel_ok, lit_flag;
   DevBuf<int> rows_dev;            // row ids of the host-pointer lookup / query-by-row calls
   DevBuf<float> lq;                // decoded queries of gulon_grouped_index_query_rows_dev
   DevBuf<float> wide_tables;       // k > 256: residual tables, one slot per workgroup of gq_group_scan_wide
@@ -359,14 +361,13 @@ __global__ __launch_bounds__(64) void gq_literal_groups(const float *__restrict_
 }
 
 // ---- one searched group of one query -------------------------------------------------------------
-// LITERAL = true: the group's literal TopKHeap, stored in array order (hk/hv/hs).  With a query list
-// (qlist/qcount on the device) only the listed queries are processed -- the tie-flagged ones.
-// LITERAL = false: the K+1 smallest (distance, row) pairs of the group as an ascending list
-// (hv/hk hold K+1 entries per pair, padded with (+inf, INT_MAX)); hs = 1 if a NaN distance was seen.
+// The group's literal TopKHeap, fed in row order and stored in array order: K entries per pair in hk/hv, the
+// heap's size in hs.  With a query list (qlist/qcount on the device) only the listed queries are processed --
+// the ones gq_rerank flagged.
 constexpr int GQ_WAVES = 4;    // (query, group) pairs per workgroup: they share the staged codebook slices
 constexpr int GQ_RPT = 8;      // centroid components prefetched per thread (sub-vectors up to 8 wide are fully overlapped)
 constexpr int GQ_PD = 4;       // quantizers whose codebooks are in flight
-template <int VEC, bool LITERAL, bool BIG = false /* k_nn > 63: the literal heap in LDS */>
+template <int VEC, bool BIG = false /* k_nn > 63: the literal heap in LDS */>
 __global__ __launch_bounds__(64 * GQ_WAVES) void gq_group_scan(const uint8_t *__restrict__ codes, int ng, int m, int m_pad, int k,
                                                     int d, const float *__restrict__ pq_cents,
                                                     const int *__restrict__ from, const int *__restrict__ sdim,
@@ -441,7 +442,6 @@ __global__ __launch_bounds__(64 * GQ_WAVES) void gq_group_scan(const uint8_t *__
   __syncthreads();
   if (!live) continue;
   const int row_from = bounds[c], row_until = bounds[c + 1];
-  const int keff = K + 1;
   // (BIG: the heaps sit behind the tables and the codebook slice)
   float *bigv = gq_lds + (size_t)GQ_WAVES * (m_pad * 256 + d) + slice_floats + (size_t)wave * (BIG ? K : 0);
   int *bigk = reinterpret_cast<int *>(gq_lds + (size_t)GQ_WAVES * (m_pad * 256 + d) + slice_floats + (size_t)GQ_WAVES * (BIG ? K : 0)) +
@@ -450,9 +450,6 @@ __global__ __launch_bounds__(64 * GQ_WAVES) void gq_group_scan(const uint8_t *__
     if constexpr (BIG) return LdsHeap(bigv, bigk, K, lane);
     else return RegHeap(K, lane);
   }();
-  WaveList wl;
-  wl.init();
-  int cnt = 0, saw_nan = 0;
   const Word *cw = reinterpret_cast<const Word *>(codes);
   // the first code words of the next GQ_PD row blocks stay in flight
   const int rb_first = row_from / 64, rb_end = (row_until + 63) / 64;
@@ -475,263 +472,31 @@ __global__ __launch_bounds__(64 * GQ_WAVES) void gq_group_scan(const uint8_t *__
     }
     const int row = rb * 64 + lane;
     const bool valid = row >= row_from && row < row_until;
-    if (LITERAL) {
-      // rows in ascending order through heap.update; the ballot only skips rows the heap would
-      // reject anyway (full and root <= value -- NaN compares false and is rejected like there)
-      unsigned long long mk = __ballot(valid && (h.size < K || h.val(0) > acc));
-      while (mk) {
-        const int l = __ffsll((long long)mk) - 1;
-        mk &= mk - 1;
-        const float x = readlane_f(acc, l);
-        if (h.would_insert(x)) h.update(rb * 64 + l, x);
-      }
-    } else {
-      if (__ballot(valid && acc != acc) != 0ull) saw_nan = 1;   // the heap keeps NaNs while it is not full
-      unsigned long long mk = __ballot(valid && (cnt < keff || wl.accepts(acc, row)));
-      while (mk) {
-        const int l = __ffsll((long long)mk) - 1;
-        mk &= mk - 1;
-        const float x = readlane_f(acc, l);
-        const int r = rb * 64 + l;
-        if (cnt < keff || wl.accepts(x, r)) {
-          wl.insert(x, r, keff, lane);
-          if (cnt < keff) cnt++;
-        }
-      }
+    // rows in ascending order through heap.update; the ballot only skips rows the heap would
+    // reject anyway (full and root <= value -- NaN compares false and is rejected like there)
+    unsigned long long mk = __ballot(valid && (h.size < K || h.val(0) > acc));
+    while (mk) {
+      const int l = __ffsll((long long)mk) - 1;
+      mk &= mk - 1;
+      const float x = readlane_f(acc, l);
+      if (h.would_insert(x)) h.update(rb * 64 + l, x);
     }
   }
   }
-  if (LITERAL) {
-    const size_t o = ((size_t)q * stride + t) * K;
-    if constexpr (BIG) {
-      for (int i = lane; i < h.size; i += 64) { hk[o + i] = h.key(i); hv[o + i] = h.val(i); }
-    } else {
-      if (lane < h.size) { hk[o + lane] = h.k; hv[o + lane] = h.v; }
-    }
-    if (lane == 0) hs[(size_t)q * stride + t] = h.size;
+  const size_t o = ((size_t)q * stride + t) * K;
+  if constexpr (BIG) {
+    for (int i = lane; i < h.size; i += 64) { hk[o + i] = h.key(i); hv[o + i] = h.val(i); }
   } else {
-    const size_t o = ((size_t)q * stride + t) * keff;
-    if (lane < keff) { hk[o + lane] = wl.i; hv[o + lane] = wl.v; }
-    if (lane == 0) hs[(size_t)q * stride + t] = saw_nan;
+    if (lane < h.size) { hk[o + lane] = h.k; hv[o + lane] = h.v; }
   }
-  }
-}
-
-// ---- the same (LITERAL = false) result, quantizer-major ------------------------------------------
-// gq_group_scan keeps a whole 16 KiB table per (query, group) pair in LDS: 8 waves per CU, one
-// workgroup barrier per quantizer for 4 pairs, and most of the time is latency.  Here a workgroup is 8
-// pairs (one wave each) and walks the quantizers two at a time: the two codebook slices are staged once
-// for all pairs of the workgroup (double-buffered, one barrier per step), every wave builds only the 2 x 256 table
-// entries of its pair for these two quantizers (2 KiB) and adds them straight onto per-row partial sums
-// held in registers -- up to 32 row blocks (2048 rows) of the group; longer groups take further passes.
-// The sums still grow in the reference's order (j ascending, unfused fp32).  52 KiB of LDS per workgroup
-// at d = 128: three workgroups = 24 waves per CU.  Codes come from a second layout with the bytes of
-// quantizers 2h and 2h + 1 of a row side by side (one 2-byte load per row and step).
-constexpr int QM_WAVES = 8;       // 76 VGPRs allow 6 waves per SIMD: three workgroups of 8 waves (52 KiB each at d = 128) per CU
-constexpr int QM_PARTS = QM_WAVES * 64 / 256;   // staging threads per centroid
-constexpr int QM_RB = 32;      // row blocks whose partial sums a wave holds
-constexpr int QM_LB = 8;       // code words in flight
-
-// The pairs of a workgroup walk the quantizers in lockstep (one barrier per step), so a workgroup is as slow
-// as its largest group: give it groups of similar size.  Per query, the searched groups sorted by their
-// number of row blocks, largest first (any order of the groups gives the same merged list).
-__global__ __launch_bounds__(256) void gq_sort_by_size(const int *__restrict__ nn, int nn_stride,
-                                                       const int *__restrict__ nn_cnt, const int *__restrict__ bounds,
-                                                       int npad /* power of two >= every count, <= 2048 */,
-                                                       int *__restrict__ out) {
-  extern __shared__ unsigned long long gs_keys[];
-  const int q = blockIdx.x, tid = threadIdx.x;
-  const int cnt = nn_cnt[q];
-  for (int e = tid; e < npad; e += 256) {
-    unsigned long long key = ~0ull;                      // padding sorts last
-    if (e < cnt) {
-      const int c = nn[(size_t)q * nn_stride + e];
-      const unsigned size = (unsigned)(bounds[c + 1] - bounds[c]);
-      key = ((unsigned long long)(0xFFFFFFFFu - size) << 32) | (unsigned)c;
-    }
-    gs_keys[e] = key;
-  }
-  __syncthreads();
-  for (int k2 = 2; k2 <= npad; k2 <<= 1)
-    for (int j = k2 >> 1; j >= 1; j >>= 1) {
-      for (int e = tid; e < npad; e += 256) {
-        const int p = e ^ j;
-        if (p > e) {
-          const unsigned long long a = gs_keys[e], b = gs_keys[p];
-          const bool up = (e & k2) == 0;
-          if ((a > b) == up) { gs_keys[e] = b; gs_keys[p] = a; }
-        }
-      }
-      __syncthreads();
-    }
-  for (int e = tid; e < cnt; e += 256) out[(size_t)q * nn_stride + e] = (int)(gs_keys[e] & 0xFFFFFFFFull);
-}
-
-__global__ void gq_pair_codes(const uint8_t *__restrict__ codes /*[n/64][ng][64][vec]*/, int ng, int vec, int m, int mh,
-                              uint16_t *__restrict__ out /*[n/64][mh][64]*/, long long total) {
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  const int lane = (int)(t & 63);
-  const long long bh = t >> 6;
-  const int h = (int)(bh % mh);
-  const long long rb = bh / mh;
-  auto byte_of = [&](int j) -> uint32_t {
-    if (j >= m) return 0u;
-    return codes[(((size_t)rb * ng + j / vec) * 64 + lane) * vec + j % vec];
-  };
-  out[t] = (uint16_t)(byte_of(2 * h) | (byte_of(2 * h + 1) << 8));
-}
-
-template <int XS>   // centroid components per staging thread and quantizer: sub-vectors up to QM_PARTS * XS wide
-__global__ __launch_bounds__(64 * QM_WAVES) void gq_scan_qm(
-    const uint16_t *__restrict__ codes2, int mh, int m, int k, int d, const float *__restrict__ pq_cents,
-    const int *__restrict__ from, const int *__restrict__ sdim, const float *__restrict__ gcent,
-    const int *__restrict__ bounds, const float *__restrict__ Q, const int *__restrict__ nn, int nn_stride,
-    const int *__restrict__ nn_cnt, int stride, int K, int *__restrict__ hk, float *__restrict__ hv,
-    int *__restrict__ hs, int smax) {
-  extern __shared__ float qm_lds[];
-  __shared__ int s_npass;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int cbq = smax * 256;                       // floats of one staged codebook slice, [x][256]
-  float *cb = qm_lds;                               // [2 buffers][2 quantizers][cbq]
-  float *T2 = qm_lds + 4 * (size_t)cbq + (size_t)wave * (512 + d);
-  float *res = T2 + 512;
-  const int q = blockIdx.y;
-  const int t = blockIdx.x * QM_WAVES + wave;       // searched-group slot of this wave
-  const bool live = t < nn_cnt[q];                  // wave-uniform; dead waves still help staging
-  const int c = live ? nn[(size_t)q * nn_stride + t] : 0;
-  const int row_from = live ? bounds[c] : 0, row_until = live ? bounds[c + 1] : 0;
-  const int rb_first = row_from / 64;
-  const int nrb_total = live ? (row_until + 63) / 64 - rb_first : 0;
-  if (tid == 0) s_npass = 0;
-  __syncthreads();
-  if (lane == 0 && nrb_total > 0) atomicMax(&s_npass, (nrb_total + QM_RB - 1) / QM_RB);
-  if (live)
-    for (int e = lane; e < d; e += 64) res[e] = Q[(size_t)q * d + e] - gcent[(size_t)c * d + e];   // MathUtils.subtract
-  __syncthreads();
-  const int npass = s_npass;
-  const int nsteps = (m + 1) / 2;
-  const int cc = tid & 255, part = tid >> 8;        // staging: centroid cc, components part, part + QM_PARTS, ...
-  auto fetch = [&](int step, float (&dst)[2][XS]) {
-#pragma unroll
-    for (int jj = 0; jj < 2; jj++) {
-      const int j = 2 * step + jj;
-      const int fr = j < m ? from[j] : 0, sj = j < m ? sdim[j] : 0;
-      const float *cent = pq_cents + (size_t)k * fr + (size_t)cc * sj;
-#pragma unroll
-      for (int u = 0; u < XS; u++) {
-        const int x = part + QM_PARTS * u;
-        dst[jj][u] = (cc < k && x < sj) ? cent[x] : 0.f;
-      }
-    }
-  };
-  auto store = [&](int buf, const float (&src)[2][XS]) {
-#pragma unroll
-    for (int jj = 0; jj < 2; jj++)
-#pragma unroll
-      for (int u = 0; u < XS; u++) {
-        const int x = part + QM_PARTS * u;
-        if (x < smax) cb[(size_t)(buf * 2 + jj) * cbq + x * 256 + cc] = src[jj][u];
-      }
-  };
-  const int keff = K + 1;
-  WaveList wl;
-  wl.init();
-  int cnt = 0, saw_nan = 0;
-  for (int pass = 0; pass < npass; pass++) {
-    const int rb0 = rb_first + pass * QM_RB;
-    const int nrb = min(max(nrb_total - pass * QM_RB, 0), QM_RB);
-    float acc[QM_RB];
-#pragma unroll
-    for (int i = 0; i < QM_RB; i++) acc[i] = 0.f;    // PQIndex.distances: j ascending, unfused fp32
-    float pre[2][XS];
-    fetch(0, pre);
-    store(0, pre);             // (every wave left the previous pass through its last barrier)
-    __syncthreads();
-    for (int step = 0; step < nsteps; step++) {
-      const int buf = step & 1;
-      if (step + 1 < nsteps) fetch(step + 1, pre);
-      if (nrb > 0) {
-        // Index.prepareQuery on the residual, quantizers 2 step and 2 step + 1:
-        // T[c'] = sum_e (r[from_j + e] - cent_j[c'][e])^2, e ascending, unfused
-#pragma unroll
-        for (int jj = 0; jj < 2; jj++) {
-          const int j = 2 * step + jj;
-          if (j < m) {
-            const int fr = from[j], sj = sdim[j];
-            const float *sl = cb + (size_t)(buf * 2 + jj) * cbq;
-            // centroids lane, lane + 64 | lane + 128, lane + 192: two per packed-fp32 instruction
-            // (v_pk_add_f32 / v_pk_mul_f32 round each half like the scalar instruction: still unfused)
-            typedef float f32x2 __attribute__((ext_vector_type(2)));
-            f32x2 a01 = {0.f, 0.f}, a23 = {0.f, 0.f};
-            for (int x = 0; x < sj; x++) {
-              const float rx = res[fr + x];
-              const f32x2 r2 = {rx, rx};
-              const f32x2 c01 = {sl[x * 256 + lane], sl[x * 256 + lane + 64]};
-              const f32x2 c23 = {sl[x * 256 + lane + 128], sl[x * 256 + lane + 192]};
-              const f32x2 d01 = r2 - c01, d23 = r2 - c23;
-              a01 += d01 * d01;
-              a23 += d23 * d23;
-            }
-            T2[jj * 256 + lane] = a01.x; T2[jj * 256 + lane + 64] = a01.y;
-            T2[jj * 256 + lane + 128] = a23.x; T2[jj * 256 + lane + 192] = a23.y;
-          }
-        }
-        const bool two = 2 * step + 1 < m;
-#pragma unroll
-        for (int b0 = 0; b0 < QM_RB; b0 += QM_LB) {
-          if (b0 < nrb) {
-            uint32_t w[QM_LB];
-#pragma unroll
-            for (int i = 0; i < QM_LB; i++)
-              w[i] = b0 + i < nrb ? (uint32_t)codes2[((size_t)(rb0 + b0 + i) * mh + step) * 64 + lane] : 0u;
-#pragma unroll
-            for (int i = 0; i < QM_LB; i++) {
-              if (b0 + i < nrb) {
-                acc[b0 + i] += T2[w[i] & 255u];
-                if (two) acc[b0 + i] += T2[256 + (w[i] >> 8)];
-              }
-            }
-          }
-        }
-      }
-      if (step + 1 < nsteps) store((step + 1) & 1, pre);
-      __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < QM_RB; i++) {
-      if (i < nrb) {
-        const int rb = rb0 + i;
-        const int row = rb * 64 + lane;
-        const bool valid = row >= row_from && row < row_until;
-        const float a = acc[i];
-        if (__ballot(valid && a != a) != 0ull) saw_nan = 1;   // the heap keeps NaNs while it is not full
-        unsigned long long mk = __ballot(valid && (cnt < keff || wl.accepts(a, row)));
-        while (mk) {
-          const int l = __ffsll((long long)mk) - 1;
-          mk &= mk - 1;
-          const float x = readlane_f(a, l);
-          const int r = rb * 64 + l;
-          if (cnt < keff || wl.accepts(x, r)) {
-            wl.insert(x, r, keff, lane);
-            if (cnt < keff) cnt++;
-          }
-        }
-      }
-    }
-  }
-  if (live) {
-    const size_t o = ((size_t)q * stride + t) * keff;
-    if (lane < keff) { hk[o + lane] = wl.i; hv[o + lane] = wl.v; }
-    if (lane == 0) hs[(size_t)q * stride + t] = saw_nan;
+  if (lane == 0) hs[(size_t)q * stride + t] = h.size;
   }
 }
 
 // ---- one searched group of one query over 16-bit codes (k > 256: Coder.BytePlus, wide.hip) ----------------
 // The residual's table is m * k floats (64 KiB at k = 1024, 4 MiB at k = 65 536): it is built in a slot of
 // global scratch (one slot per workgroup, which walks the (query, group) pairs), and the group's rows go through
-// the LITERAL TopKHeap in row order -- the same heaps, stored in array order, as gq_group_scan<.., true>, so
+// the LITERAL TopKHeap in row order -- the same heaps, stored in array order, as gq_group_scan's, so
 // that gq_merge folds them exactly as GroupedIndex.query does (Index.scala:265-282).  Generality over speed.
 // BIG (k_nn > 63): the pair's heap is an LdsHeap behind the residual (K values, then K keys), stored in the same
 // array order at stride K and folded by gq_merge<true>.
@@ -1033,55 +798,6 @@ __global__ __launch_bounds__(64) void gq_merge(const int *__restrict__ hk, const
   }
 }
 
-// Tie-free fast path: merge the groups' ascending (K+1)-lists under the (distance, row) order.
-// Wherever the K+1 smallest distances of the searched rows are pairwise different this IS the
-// reference's answer; a query with equal neighbours among them (or a NaN distance anywhere) is
-// appended to qlist and redone by the literal kernels.
-__global__ __launch_bounds__(64) void gq_merge_fast(const int *__restrict__ li, const float *__restrict__ lv,
-                                                    const int *__restrict__ nanflag,
-                                                    const int *__restrict__ nn_cnt, int stride, int K,
-                                                    int *__restrict__ out_idx, float *__restrict__ out_dist,
-                                                    int *__restrict__ out_count, int *__restrict__ qlist,
-                                                    int *__restrict__ qcount) {
-  const int q = blockIdx.x, lane = threadIdx.x;
-  const int keff = K + 1;
-  WaveList wl;
-  wl.init();
-  const int cnt = nn_cnt[q];
-  const int total = cnt * keff;
-  int nanany = 0;
-  for (int t = lane; t < cnt; t += 64) nanany |= nanflag[(size_t)q * stride + t];
-  nanany = __ballot(nanany != 0) != 0ull;
-  const size_t o = (size_t)q * stride * keff;
-  for (int base = 0; base < total; base += 64) {
-    const int e = base + lane;
-    const float cv = e < total ? lv[o + e] : INFINITY;
-    const int cr = e < total ? li[o + e] : INT_MAX;
-    unsigned long long mk = __ballot(cr != INT_MAX && wl.accepts(cv, cr));
-    while (mk) {
-      const int l = __ffsll((long long)mk) - 1;
-      mk &= mk - 1;
-      const float v = readlane_f(cv, l);
-      const int r = readlane_i(cr, l);
-      if (wl.accepts(v, r)) wl.insert(v, r, keff, lane);
-    }
-  }
-  const int live = __popcll(__ballot(lane < K && wl.i != INT_MAX));
-  if (lane < K) {
-    const bool ok = wl.i != INT_MAX;
-    out_idx[(size_t)q * K + lane] = ok ? wl.i : -1;
-    out_dist[(size_t)q * K + lane] = ok ? wl.v : INFINITY;
-  }
-  const float nv = __shfl_down(wl.v, 1);
-  const int ni = __shfl_down(wl.i, 1);
-  const bool tie = wl.i != INT_MAX && ni != INT_MAX && wl.v == nv && lane + 1 < keff;
-  const bool flagged = __ballot(tie) != 0ull || nanany;
-  if (lane == 0) {
-    if (out_count) out_count[q] = live;
-    if (flagged) qlist[atomicAdd(qcount, 1)] = q;
-  }
-}
-
 // residual dataset in grouped order: out[i] = X[perm[i]] - gcent[group_of[i]]
 __global__ void gq_residuals(const float *__restrict__ X, int d, const int *__restrict__ perm,
                              const int *__restrict__ group_of, const float *__restrict__ gcent, long long total,
@@ -1094,6 +810,253 @@ __global__ void gq_residuals(const float *__restrict__ X, int d, const int *__re
   }
 }
 
+// ---- the query driver: run_grouped_query and its stages ---------------------------------------------
+// The environment, read once per call (the tests set the variables after the library is loaded).
+struct GroupedKnobs {
+  bool literal = getenv("GULON_GROUPED_LITERAL") != nullptr;   // every query through the literal heaps: a testing aid
+  bool stats = getenv("GULON_GROUPED_STATS") != nullptr;       // synchronous statistics to stderr: a debugging aid
+};
+
+struct GroupedCall {   // one batch: the arguments of run_grouped_query
+  gulon_grouped_index *gx;
+  const float *dQ;
+  int B, K, strategy, limit;
+  int *d_oi;
+  float *d_od;
+  int *d_oc;
+  hipStream_t st;
+  bool big_k() const { return K > GULON_MAX_K; }   // the heaps in LDS (LdsHeap) instead of a wavefront's registers
+};
+
+struct CoarseResult {
+  int nn_stride;   // groups searched per query at most: the row length of nn
+  int stride;      // per-group heaps per query (<= nn_stride)
+  int lit_cap;     // > 0: group selection went through the (distance, id) sorts and the order-only ties (level 1) are
+                   // still to be redone for the listed queries; capacity of the literal heap
+};
+
+void launch_literal_groups(const GroupedCall &c, int nn_stride, int cap, int level, int grid, const int *qlist,
+                           const int *qcount) {
+  gulon_grouped_index *gx = c.gx;
+  hipLaunchKernelGGL(gq_literal_groups, dim3(grid), dim3(64), (size_t)cap * 8, c.st, gx->cdist.p, gx->g, cap, gx->bounds.p,
+                     c.strategy == 1, c.limit, gx->lit_flag.p, level, qlist, qcount, gx->nn.p, nn_stride, gx->nn_cnt.p);
+}
+
+// searchSpace (Index.scala:284-299): the groups every query searches, in gx->nn / gx->nn_cnt.
+// all_literal: every query's result will come from the literal heaps, merged in search order.
+CoarseResult coarse_stage(const GroupedCall &c, bool all_literal) {
+  gulon_grouped_index *gx = c.gx;
+  const int g = gx->g, B = c.B, strategy = c.strategy, limit = c.limit;
+  hipStream_t st = c.st;
+  // groups searched per query: at most `nn_stride` (LimitVectors: every non-empty group holds >= 1 row; the
+  // reference's leading empty group adds nothing to the count and is searched on top)
+  CoarseResult r;
+  r.nn_stride = std::max(1, (int)std::min<long long>((long long)limit + (strategy == 1 ? gx->n_empty : 0), g));
+  r.stride = r.nn_stride;
+  r.lit_cap = 0;
+  gx->cdist.ensure((size_t)B * g);
+  gx->nn.ensure((size_t)B * r.nn_stride);
+  gx->nn_cnt.ensure((size_t)B);
+  hipLaunchKernelGGL(gq_cdist, dim3(ceil_div(g, 256), ceil_div(B, CD_Q)), dim3(256), 0, st, gx->gcent_t.p, g, gx->d, c.dQ, B,
+                     gx->cdist.p);
+  if (strategy == 0 && limit <= GULON_MAX_K && limit >= 1) {
+    hipLaunchKernelGGL(gq_nearest_groups, dim3(B), dim3(64), 0, st, gx->cdist.p, g, limit, gx->nn.p, r.nn_stride,
+                       gx->nn_cnt.p);
+    HIP_CHECK(hipGetLastError());
+    return r;
+  }
+  int n2 = 64;
+  while (n2 < g) n2 <<= 1;
+  const size_t lds = (size_t)n2 * 8;
+  GULON_UNSUPPORTED(lds > 144 * 1024, "%d groups: ordering all of them needs %zu B of LDS (> 144 KiB)", g, lds);
+  HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gq_sorted_groups),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const int *done = nullptr;
+  gx->lit_flag.ensure((size_t)B);
+  if (strategy == 0 && limit >= 1 && limit * 4 <= g) {
+    // few of many: radix-select + sort of the selected; the full sort only runs for queries it gave up on
+    int cap = 256;
+    while (cap < limit + 128) cap <<= 1;
+    gx->sel_ok.ensure((size_t)B);
+    const size_t sel_lds = (size_t)cap * 8;
+    auto kern = g <= 256 * 8 ? gq_select_groups<8> : g <= 256 * 40 ? gq_select_groups<40> : gq_select_groups<0>;
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_lds));
+    hipLaunchKernelGGL(kern, dim3(B), dim3(256), sel_lds, st, gx->cdist.p, g, limit, cap, gx->nn.p,
+                       r.nn_stride, gx->nn_cnt.p, gx->sel_ok.p, gx->lit_flag.p);
+    done = gx->sel_ok.p;
+  }
+  hipLaunchKernelGGL(gq_sorted_groups, dim3(B), dim3(256), lds, st, gx->cdist.p, g, n2, gx->bounds.p, strategy == 1,
+                     limit, gx->nn.p, r.nn_stride, gx->nn_cnt.p, done, gx->lit_flag.p);
+  // queries whose answer hangs on equally distant centroids (or NaN distances): the reference's heap, literally
+  const int hcap = strategy == 1 ? g : std::min(limit, g);
+  if (hcap >= 1) {
+    const size_t hl = (size_t)hcap * 8;
+    GULON_UNSUPPORTED(hl > 144 * 1024, "%d groups: the literal heap needs %zu B of LDS (> 144 KiB)", hcap, hl);
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gq_literal_groups),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)hl));
+    launch_literal_groups(c, r.nn_stride, hcap, 2, B, nullptr, nullptr);
+    if (all_literal) launch_literal_groups(c, r.nn_stride, hcap, 1, B, nullptr, nullptr);   // the order-only ties as well
+    else r.lit_cap = hcap;
+  }
+  if (strategy == 1 && r.nn_stride > 64) {
+    // LimitVectors rarely needs more than a handful of groups: size the per-group heaps by the
+    // largest count of this batch (one small read-back) instead of by the worst case
+    std::vector<int> h((size_t)B);
+    HIP_CHECK(hipMemcpyAsync(h.data(), gx->nn_cnt.p, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    int mx = 1;
+    for (int v : h) mx = std::max(mx, v);
+    r.stride = mx;
+  }
+  HIP_CHECK(hipGetLastError());
+  return r;
+}
+
+void ensure_group_heaps(const GroupedCall &c, int stride) {
+  gulon_grouped_index *gx = c.gx;
+  gx->hk.ensure((size_t)c.B * stride * c.K);
+  gx->hv.ensure((size_t)c.B * stride * c.K);
+  gx->hs.ensure((size_t)c.B * stride);
+}
+
+// TopKHeap.merge of the stored group heaps + Result.fromHeap: of every query (grid = B), or of the listed ones
+void launch_gq_merge(const GroupedCall &c, int stride, int grid, const int *qlist, const int *qcount) {
+  gulon_grouped_index *gx = c.gx;
+  if (c.big_k())
+    hipLaunchKernelGGL(gq_merge<true>, dim3(grid), dim3(64), sizeof(float) * 2 * (size_t)c.K, c.st, gx->hk.p, gx->hv.p,
+                       gx->hs.p, gx->nn_cnt.p, stride, c.K, c.d_oi, c.d_od, c.d_oc, qlist, qcount);
+  else
+    hipLaunchKernelGGL(gq_merge<false>, dim3(grid), dim3(64), 0, c.st, gx->hk.p, gx->hv.p, gx->hs.p, gx->nn_cnt.p, stride,
+                       c.K, c.d_oi, c.d_od, c.d_oc, qlist, qcount);
+  HIP_CHECK(hipGetLastError());
+}
+
+// 16-bit codes: the literal heaps for every (query, group) pair, residual tables in global scratch (<= 1 GiB)
+void wide_scan(const GroupedCall &c, const CoarseResult &co) {
+  gulon_grouped_index *gx = c.gx;
+  gulon_index *ix = gx->pq;
+  const int B = c.B, K = c.K, stride = co.stride;
+  hipStream_t st = c.st;
+  ensure_group_heaps(c, stride);
+  const size_t slot = (size_t)ix->m * ix->k * sizeof(float);
+  const long long pairs = (long long)B * stride;
+  const int blocks = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(pairs, 4096),
+                                                                    std::max<long long>(64, (1ll << 30) / (long long)slot)));
+  gx->wide_tables.ensure((size_t)blocks * ix->m * ix->k);
+  HIP_CHECK(hipMemsetAsync(gx->hs.p, 0, sizeof(int) * (size_t)B * stride, st));
+  size_t lds = sizeof(float) * (size_t)ix->d;
+  auto kern = gq_group_scan_wide<false>;
+  if (c.big_k()) {   // the heaps in LDS (2 K words behind the residual), folded by the LDS merge
+    lds += sizeof(float) * 2 * (size_t)K;
+    GULON_UNSUPPORTED(lds > 160 * 1024, "grouped query needs %zu B of LDS (d = %d, k_nn = %d)", lds, ix->d, K);
+    kern = gq_group_scan_wide<true>;
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  }
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, st, ix->wcodes.p, ix->m, ix->k, ix->d, ix->cents.p, ix->from.p,
+                     ix->sdim.p, gx->gcent.p, gx->bounds.p, c.dQ, gx->nn.p, co.nn_stride, gx->nn_cnt.p, stride, B, K,
+                     gx->wide_tables.p, gx->hk.p, gx->hv.p, gx->hs.p);
+  launch_gq_merge(c, stride, B, nullptr, nullptr);
+}
+
+struct GroupScanLds { size_t bytes; int slice_floats; };
+
+// gq_group_scan's LDS: the four pairs' tables and residuals, one codebook slice, and for k_nn > 63 the four heaps
+GroupScanLds group_scan_lds(const GroupedCall &c) {
+  const gulon_index *ix = c.gx->pq;
+  int smax = 1;
+  std::vector<int> fr, un;
+  subvectors(ix->d, ix->m, fr, un);
+  for (int j = 0; j < ix->m; j++) smax = std::max(smax, un[j] - fr[j]);
+  GroupScanLds l;
+  l.slice_floats = 256 * smax;               // [x][256], transposed
+  l.bytes = ((size_t)GQ_WAVES * (ix->m_pad * 256 + ix->d) + (size_t)l.slice_floats + (c.big_k() ? (size_t)GQ_WAVES * 2 * c.K : 0)) *
+            sizeof(float);
+  GULON_UNSUPPORTED(l.bytes > 160 * 1024, "grouped query needs %zu B of LDS (m = %d, d = %d, k_nn = %d)", l.bytes, ix->m, ix->d,
+                    c.K);
+  return l;
+}
+
+// the literal heap of every (query, searched group) pair: of `gy` rows of queries, or of the listed queries
+void launch_group_scan(const GroupedCall &c, const CoarseResult &co, const GroupScanLds &l, int gy, const int *qlist,
+                       const int *qcount) {
+  gulon_grouped_index *gx = c.gx;
+  gulon_index *ix = gx->pq;
+  auto kern = c.big_k() ? (ix->vec == 16 ? gq_group_scan<16, true> : gq_group_scan<4, true>)
+                        : (ix->vec == 16 ? gq_group_scan<16> : gq_group_scan<4>);
+  HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.bytes));
+  hipLaunchKernelGGL(kern, dim3(ceil_div(co.stride, GQ_WAVES), gy), dim3(64 * GQ_WAVES), l.bytes, c.st, ix->codes.p, ix->ng, ix->m,
+                     ix->m_pad, ix->k, ix->d, ix->cents.p, ix->from.p, ix->sdim.p, gx->gcent.p, gx->bounds.p, c.dQ, gx->nn.p,
+                     co.nn_stride, gx->nn_cnt.p, co.stride, c.K, gx->hk.p, gx->hv.p, gx->hs.p, qlist, qcount, l.slice_floats);
+  HIP_CHECK(hipGetLastError());
+}
+
+// The queries gq_rerank listed, through the literal kernels: first the reference's heap order for those whose group
+// ORDER hangs on equal centroid distances, then the group heaps and their merge (usually the list is empty)
+void redo_flagged(const GroupedCall &c, const CoarseResult &co, const GroupScanLds &l) {
+  gulon_grouped_index *gx = c.gx;
+  const int fy = std::min(c.B, 16);
+  if (co.lit_cap > 0) {
+    launch_literal_groups(c, co.nn_stride, co.lit_cap, 1, fy, gx->qlist.p, gx->qcount.p);
+    HIP_CHECK(hipGetLastError());
+  }
+  launch_group_scan(c, co, l, fy, gx->qlist.p, gx->qcount.p);
+  launch_gq_merge(c, co.stride, fy, gx->qlist.p, gx->qcount.p);
+}
+
+void print_redo_stats(const GroupedCall &c) {   // GULON_GROUPED_STATS
+  HIP_CHECK(hipStreamSynchronize(c.st));
+  int nfl = 0;
+  HIP_CHECK(hipMemcpy(&nfl, c.gx->qcount.p, sizeof(int), hipMemcpyDeviceToHost));
+  fprintf(stderr, "[grouped] approximate pre-selection: %d of %d queries redone with literal heaps\n", nfl, c.B);
+}
+
+// approximate pre-selection with one table per query, exact re-ranking of 64 candidates, certificate: answers in
+// d_oi / d_od / d_oc, the queries to redo in gx->qlist / gx->qcount
+void approx_stage(const GroupedCall &c, const CoarseResult &co, const GroupedKnobs &knobs) {
+  gulon_grouped_index *gx = c.gx;
+  gulon_index *ix = gx->pq;
+  const int g = gx->g, B = c.B, nn_stride = co.nn_stride;
+  hipStream_t st = c.st;
+  gx->qlist.ensure((size_t)B);
+  gx->qcount.ensure(1);
+  HIP_CHECK(hipMemsetAsync(gx->qcount.p, 0, sizeof(int), st));
+  gx->ptab.ensure((size_t)B * ix->m_pad * 256);
+  gx->apv.ensure((size_t)B * GA_WAVES * GA_C); gx->api.ensure((size_t)B * GA_WAVES * GA_C);
+  gx->amv.ensure((size_t)B * GA_C); gx->ami.ensure((size_t)B * GA_C);
+  gx->anan.ensure((size_t)B * GA_WAVES);
+  // by group with 8-bit bound tables (grouped_filter.hip) where a query searches more than a handful of groups; else
+  // every searched row through gq_approx_scan
+  const bool by_group = gx->gfilter.built && group_filter_applies(ix->m, ix->m_pad, ix->ng, ix->vec, ix->k, ix->d) &&
+                        nn_stride > GF_SAMPLE_GROUPS && B <= 65535 &&   // (a grid's y extent carries the query)
+                        (long long)B * nn_stride <= (1ll << 28) &&      // (the pairs' tiles)
+                        (long long)B * g <= (1ll << 27);                // (the groups' query lists, room for all: 512 MiB at most)
+  if (by_group) {   // (this path builds the tables where it quantizes them)
+    group_filter_run(gx->gfilter, ix->codes.p, ix->ng, ix->vec, ix->m, ix->m_pad, ix->k, ix->d, gx->ptab.p, ix->cents.p,
+                     ix->from.p, ix->sdim.p, gx->xnorm.p, gx->xnmax,
+                     gx->gcent.p, gx->bounds.p, g, c.dQ, gx->cdist.p, gx->nn.p, nn_stride, gx->nn_cnt.p, B, gx->amv.p, gx->ami.p,
+                     gx->anan.p, st);
+  } else {
+    // the query's table and coordinates, (m_pad * 256 + d) floats: at most 40 KiB, since GQ_WAVES = 4 times as much
+    // (and a codebook slice) passed group_scan_lds' check against 160 KiB
+    const size_t lds_ga = ((size_t)ix->m_pad * 256 + ix->d) * sizeof(float);
+    auto kern = ix->vec == 16 ? gq_approx_scan<16> : gq_approx_scan<4>;
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds_ga));
+    hipLaunchKernelGGL(gq_ptables, dim3(ix->m_pad, B), dim3(256), 0, st, ix->cents.p, ix->from.p, ix->sdim.p, ix->d, ix->m,
+                       ix->m_pad, ix->k, c.dQ, gx->ptab.p);
+    hipLaunchKernelGGL(kern, dim3(B), dim3(64 * GA_WAVES), lds_ga, st, ix->codes.p, ix->ng, ix->m_pad, ix->d, gx->ptab.p,
+                       gx->xnorm.p, gx->gcent.p, gx->bounds.p, c.dQ, gx->nn.p, nn_stride, gx->nn_cnt.p, gx->apv.p, gx->api.p,
+                       gx->anan.p);
+    launch_merge(false, gx->apv.p, gx->api.p, GA_WAVES, (long long)GA_C, (long long)GA_WAVES * GA_C, B, GA_C - 1, nullptr,
+                 nullptr, nullptr, nullptr, gx->amv.p, gx->ami.p, st);
+  }
+  hipLaunchKernelGGL(gq_rerank, dim3(B), dim3(64), 0, st, ix->codes.p, ix->ng, ix->vec, ix->m, ix->k, ix->d, ix->cents.p,
+                     ix->from.p, ix->sdim.p, gx->gcent.p, gx->bounds.p, g, c.dQ, gx->amv.p, gx->ami.p, gx->anan.p, gx->xnmax,
+                     c.K, c.d_oi, c.d_od, c.d_oc, gx->qlist.p, gx->qcount.p);
+  HIP_CHECK(hipGetLastError());
+  if (knobs.stats) print_redo_stats(c);
+}
+
 void run_grouped_query(gulon_grouped_index *gx, const float *dQ, int B, int K, int strategy, int limit, int *d_oi,
                        float *d_od, int *d_oc, hipStream_t st) {
   GULON_REQUIRE(B >= 0 && K >= 0, "k and batch size must be non-negative");
@@ -1101,13 +1064,12 @@ void run_grouped_query(gulon_grouped_index *gx, const float *dQ, int B, int K, i
   GULON_REQUIRE(limit >= 0, "limit must be non-negative");
   // k_nn > GULON_MAX_K (Tests.scala asks for up to 1000): the literal kernels with the heaps in LDS, for every query
   constexpr int GROUPED_MAX_K_BIG = 2048;
-  const bool big_k = K > GULON_MAX_K;
   GULON_UNSUPPORTED(K > GROUPED_MAX_K_BIG, "k_nn = %d > %d is not supported by the grouped index", K, GROUPED_MAX_K_BIG);
   if (B == 0) return;
-  gulon_index *ix = gx->pq;
-  const int g = gx->g;
-  if (big_k) {   // the per-group heaps are B x groups x k_nn entries: batches of queries that keep them under 2 GiB
-    const long long per_query = (long long)std::max(1, std::min(strategy == 1 ? g : limit, g)) * K;
+  const GroupedKnobs knobs{};
+  const GroupedCall c{gx, dQ, B, K, strategy, limit, d_oi, d_od, d_oc, st};
+  if (c.big_k()) {   // the per-group heaps are B x groups x k_nn entries: batches of queries that keep them under 2 GiB
+    const long long per_query = (long long)std::max(1, std::min(strategy == 1 ? gx->g : limit, gx->g)) * K;
     const int sub = (int)std::max<long long>(1, std::min<long long>(B, (1ll << 28) / std::max<long long>(1, per_query)));
     if (sub < B) {
       for (int q0 = 0; q0 < B; q0 += sub) {
@@ -1122,281 +1084,41 @@ void run_grouped_query(gulon_grouped_index *gx, const float *dQ, int B, int K, i
     if (d_oc) HIP_CHECK(hipMemsetAsync(d_oc, 0, sizeof(int) * (size_t)B, st));
     return;
   }
-  // groups searched per query: at most `nn_stride` (LimitVectors: every non-empty group holds >= 1 row; the
-  // reference's leading empty group adds nothing to the count and is searched on top)
-  const int nn_stride = std::max(1, (int)std::min<long long>((long long)limit + (strategy == 1 ? gx->n_empty : 0), g));
-  int stride = nn_stride;
-  int lit_cap = 0;          // > 0: group selection went through the (distance, id) sorts; capacity of the literal heap
-  gx->cdist.ensure((size_t)B * g);
-  gx->nn.ensure((size_t)B * nn_stride);
-  gx->nn_cnt.ensure((size_t)B);
-  hipLaunchKernelGGL(gq_cdist, dim3(ceil_div(g, 256), ceil_div(B, CD_Q)), dim3(256), 0, st, gx->gcent_t.p, g, gx->d, dQ, B,
-                     gx->cdist.p);
-  if (strategy == 0 && limit <= GULON_MAX_K && limit >= 1) {
-    hipLaunchKernelGGL(gq_nearest_groups, dim3(B), dim3(64), 0, st, gx->cdist.p, g, limit, gx->nn.p, nn_stride,
-                       gx->nn_cnt.p);
-  } else {
-    int n2 = 64;
-    while (n2 < g) n2 <<= 1;
-    const size_t lds = (size_t)n2 * 8;
-    GULON_UNSUPPORTED(lds > 144 * 1024, "%d groups: ordering all of them needs %zu B of LDS (> 144 KiB)", g, lds);
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gq_sorted_groups),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int *done = nullptr;
-    gx->lit_flag.ensure((size_t)B);
-    if (strategy == 0 && limit >= 1 && limit * 4 <= g) {
-      // few of many: radix-select + sort of the selected; the full sort only runs for queries it gave up on
-      int cap = 256;
-      while (cap < limit + 128) cap <<= 1;
-      gx->sel_ok.ensure((size_t)B);
-      const size_t sel_lds = (size_t)cap * 8;
-      auto kern = g <= 256 * 8 ? gq_select_groups<8> : g <= 256 * 40 ? gq_select_groups<40> : gq_select_groups<0>;
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_lds));
-      hipLaunchKernelGGL(kern, dim3(B), dim3(256), sel_lds, st, gx->cdist.p, g, limit, cap, gx->nn.p,
-                         nn_stride, gx->nn_cnt.p, gx->sel_ok.p, gx->lit_flag.p);
-      done = gx->sel_ok.p;
-    }
-    hipLaunchKernelGGL(gq_sorted_groups, dim3(B), dim3(256), lds, st, gx->cdist.p, g, n2, gx->bounds.p, strategy == 1,
-                       limit, gx->nn.p, nn_stride, gx->nn_cnt.p, done, gx->lit_flag.p);
-    {
-      // queries whose answer hangs on equally distant centroids (or NaN distances): the reference's heap, literally
-      const int hcap = strategy == 1 ? g : std::min(limit, g);
-      if (hcap >= 1) {
-        const size_t hl = (size_t)hcap * 8;
-        GULON_UNSUPPORTED(hl > 144 * 1024, "%d groups: the literal heap needs %zu B of LDS (> 144 KiB)", hcap, hl);
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gq_literal_groups),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)hl));
-        hipLaunchKernelGGL(gq_literal_groups, dim3(B), dim3(64), hl, st, gx->cdist.p, g, hcap, gx->bounds.p, strategy == 1,
-                           limit, gx->lit_flag.p, 2, (const int *)nullptr, (const int *)nullptr, gx->nn.p, nn_stride,
-                           gx->nn_cnt.p);
-        lit_cap = hcap;
-        if (ix->wide || big_k || getenv("GULON_GROUPED_LITERAL") != nullptr) {
-          // every query's result comes from the literal heaps, merged in search order: the order-only ties as well
-          hipLaunchKernelGGL(gq_literal_groups, dim3(B), dim3(64), hl, st, gx->cdist.p, g, hcap, gx->bounds.p, strategy == 1,
-                             limit, gx->lit_flag.p, 1, (const int *)nullptr, (const int *)nullptr, gx->nn.p, nn_stride,
-                             gx->nn_cnt.p);
-          lit_cap = 0;
-        }
-      }
-    }
-    if (strategy == 1 && nn_stride > 64) {
-      // LimitVectors rarely needs more than a handful of groups: size the per-group heaps by the
-      // largest count of this batch (one small read-back) instead of by the worst case
-      std::vector<int> h((size_t)B);
-      HIP_CHECK(hipMemcpyAsync(h.data(), gx->nn_cnt.p, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, st));
-      HIP_CHECK(hipStreamSynchronize(st));
-      int mx = 1;
-      for (int v : h) mx = std::max(mx, v);
-      stride = mx;
-    }
-  }
-  HIP_CHECK(hipGetLastError());
-  const int keff = K + 1;
-  if (ix->wide) {
-    // 16-bit codes: the literal heaps for every (query, group) pair, residual tables in global scratch (<= 1 GiB)
-    gx->hk.ensure((size_t)B * stride * K);
-    gx->hv.ensure((size_t)B * stride * K);
-    gx->hs.ensure((size_t)B * stride);
-    const size_t slot = (size_t)ix->m * ix->k * sizeof(float);
-    const long long pairs = (long long)B * stride;
-    const int blocks = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(pairs, 4096),
-                                                                      std::max<long long>(64, (1ll << 30) / (long long)slot)));
-    gx->wide_tables.ensure((size_t)blocks * ix->m * ix->k);
-    HIP_CHECK(hipMemsetAsync(gx->hs.p, 0, sizeof(int) * (size_t)B * stride, st));
-    if (big_k) {   // the heaps in LDS (2 K words behind the residual), folded by the LDS merge
-      const size_t lds = sizeof(float) * ((size_t)ix->d + 2 * (size_t)K);
-      GULON_UNSUPPORTED(lds > 160 * 1024, "grouped query needs %zu B of LDS (d = %d, k_nn = %d)", lds, ix->d, K);
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gq_group_scan_wide<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(gq_group_scan_wide<true>, dim3(blocks), dim3(64), lds, st, ix->wcodes.p, ix->m, ix->k, ix->d,
-                         ix->cents.p, ix->from.p, ix->sdim.p, gx->gcent.p, gx->bounds.p, dQ, gx->nn.p, nn_stride,
-                         gx->nn_cnt.p, stride, B, K, gx->wide_tables.p, gx->hk.p, gx->hv.p, gx->hs.p);
-      hipLaunchKernelGGL(gq_merge<true>, dim3(B), dim3(64), sizeof(float) * 2 * (size_t)K, st, gx->hk.p, gx->hv.p, gx->hs.p,
-                         gx->nn_cnt.p, stride, K, d_oi, d_od, d_oc, (const int *)nullptr, (const int *)nullptr);
-    } else {
-      hipLaunchKernelGGL(gq_group_scan_wide<false>, dim3(blocks), dim3(64), sizeof(float) * (size_t)ix->d, st, ix->wcodes.p,
-                         ix->m, ix->k, ix->d, ix->cents.p, ix->from.p, ix->sdim.p, gx->gcent.p, gx->bounds.p, dQ, gx->nn.p,
-                         nn_stride, gx->nn_cnt.p, stride, B, K, gx->wide_tables.p, gx->hk.p, gx->hv.p, gx->hs.p);
-      hipLaunchKernelGGL(gq_merge<false>, dim3(B), dim3(64), 0, st, gx->hk.p, gx->hv.p, gx->hs.p, gx->nn_cnt.p, stride, K,
-                         d_oi, d_od, d_oc, (const int *)nullptr, (const int *)nullptr);
-    }
-    HIP_CHECK(hipGetLastError());
+  const bool wide = gx->pq->wide;
+  // Row norms exist for every 8-bit index that has rows (gulon_grouped_index_create); one without rows takes the
+  // literal kernels, which are the reference for any input
+  const bool literal_only = c.big_k() || knobs.literal || gx->xnorm.n == 0;
+  const CoarseResult co = coarse_stage(c, wide || literal_only);
+  if (wide) {
+    wide_scan(c, co);
     return;
   }
-  const bool literal_only = big_k || getenv("GULON_GROUPED_LITERAL") != nullptr;   // (the variable: a testing aid)
-  gx->hk.ensure((size_t)B * stride * keff);
-  gx->hv.ensure((size_t)B * stride * keff);
-  gx->hs.ensure((size_t)B * stride);
-  gx->qlist.ensure((size_t)B);
-  gx->qcount.ensure(1);
-  int smax = 1;
-  {
-    std::vector<int> fr, un;
-    subvectors(ix->d, ix->m, fr, un);
-    for (int j = 0; j < ix->m; j++) smax = std::max(smax, un[j] - fr[j]);
-  }
-  const int slice_floats = 256 * smax;               // [x][256], transposed
-  const size_t lds = ((size_t)GQ_WAVES * (ix->m_pad * 256 + ix->d) + (size_t)slice_floats + (big_k ? (size_t)GQ_WAVES * 2 * K : 0)) *
-                     sizeof(float);
-  GULON_UNSUPPORTED(lds > 160 * 1024, "grouped query needs %zu B of LDS (m = %d, d = %d, k_nn = %d)", lds, ix->m, ix->d, K);
-  auto scan = [&](bool literal, int gy, const int *qlist, const int *qcount) {
-#define GS3(V) GS_(V, true, true)
-#define GS(V, L) GS_(V, L, false)
-#define GS_(V, L, BG)                                                                                               \
-    {                                                                                                               \
-      auto kern = gq_group_scan<V, L, BG>;                                                                             \
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                           \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                         \
-      hipLaunchKernelGGL(kern, dim3(ceil_div(stride, GQ_WAVES), gy), dim3(64 * GQ_WAVES), lds, st, ix->codes.p, ix->ng, \
-                         ix->m, ix->m_pad, ix->k,                                                                  \
-                         ix->d, ix->cents.p, ix->from.p, ix->sdim.p, gx->gcent.p, gx->bounds.p, dQ, gx->nn.p,       \
-                         nn_stride, gx->nn_cnt.p, stride, K, gx->hk.p, gx->hv.p, gx->hs.p, qlist, qcount,          \
-                         slice_floats);                                                                            \
-    }
-    if (big_k) { if (ix->vec == 16) GS3(16) else GS3(4) }
-    else if (ix->vec == 16) { if (literal) GS(16, true) else GS(16, false) }
-    else               { if (literal) GS(4, true) else GS(4, false) }
-#undef GS
-#undef GS3
-    HIP_CHECK(hipGetLastError());
-  };
+  ensure_group_heaps(c, co.stride);
+  const GroupScanLds l = group_scan_lds(c);
   if (literal_only) {
-    scan(true, B, nullptr, nullptr);
-    if (big_k)
-      hipLaunchKernelGGL(gq_merge<true>, dim3(B), dim3(64), sizeof(float) * 2 * (size_t)K, st, gx->hk.p, gx->hv.p, gx->hs.p,
-                         gx->nn_cnt.p, stride, K, d_oi, d_od, d_oc, (const int *)nullptr, (const int *)nullptr);
-    else
-    hipLaunchKernelGGL(gq_merge<false>, dim3(B), dim3(64), 0, st, gx->hk.p, gx->hv.p, gx->hs.p, gx->nn_cnt.p, stride, K, d_oi,
-                       d_od, d_oc, (const int *)nullptr, (const int *)nullptr);
-    HIP_CHECK(hipGetLastError());
+    launch_group_scan(c, co, l, B, nullptr, nullptr);
+    launch_gq_merge(c, co.stride, B, nullptr, nullptr);
     return;
   }
-  // fast path for every query, then the literal heaps for the tie-flagged ones (usually none)
-  HIP_CHECK(hipMemsetAsync(gx->qcount.p, 0, sizeof(int), st));
-  static const bool approx_off = [] { const char *e = getenv("GULON_GROUPED_APPROX"); return e && atoi(e) == 0; }();
-  const size_t lds_ga = ((size_t)ix->m_pad * 256 + ix->d) * sizeof(float);
-  if (!approx_off && gx->xnorm.n > 0 && lds_ga <= 150 * 1024) {
-    // approximate pre-selection with one table per query, exact re-ranking of 64 candidates, certificate
-    gx->ptab.ensure((size_t)B * ix->m_pad * 256);
-    gx->apv.ensure((size_t)B * GA_WAVES * GA_C); gx->api.ensure((size_t)B * GA_WAVES * GA_C);
-    gx->amv.ensure((size_t)B * GA_C); gx->ami.ensure((size_t)B * GA_C);
-    gx->anan.ensure((size_t)B * GA_WAVES);
-    {
-      auto kern = ix->vec == 16 ? gq_approx_scan<16> : gq_approx_scan<4>;
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds_ga));
-      // by group with 8-bit bound tables (grouped_filter.hip) where a query searches more than a handful of groups; else
-      // every searched row through this kernel
-      const bool by_group = gx->gfilter.built && group_filter_applies(ix->m, ix->m_pad, ix->ng, ix->vec, ix->k, ix->d) &&
-                            nn_stride > GF_SAMPLE_GROUPS && B <= 65535 &&   // (a grid's y extent carries the query)
-                            (long long)B * nn_stride <= (1ll << 28) &&      // (the pairs' tiles)
-                            (long long)B * g <= (1ll << 27);                // (the groups' query lists, room for all: 512 MiB at most)
-      if (!by_group)   // (the by-group path builds the tables where it quantizes them)
-        hipLaunchKernelGGL(gq_ptables, dim3(ix->m_pad, B), dim3(256), 0, st, ix->cents.p, ix->from.p, ix->sdim.p, ix->d, ix->m,
-                           ix->m_pad, ix->k, dQ, gx->ptab.p);
-      if (by_group)
-        group_filter_run(gx->gfilter, ix->codes.p, ix->ng, ix->vec, ix->m, ix->m_pad, ix->k, ix->d, gx->ptab.p, ix->cents.p,
-                         ix->from.p, ix->sdim.p, gx->xnorm.p, gx->xnmax,
-                         gx->gcent.p, gx->bounds.p, g, dQ, gx->cdist.p, gx->nn.p, nn_stride, gx->nn_cnt.p, B, gx->amv.p, gx->ami.p,
-                         gx->anan.p, st);
-      else {
-        hipLaunchKernelGGL(kern, dim3(B), dim3(64 * GA_WAVES), lds_ga, st, ix->codes.p, ix->ng, ix->m_pad, ix->d, gx->ptab.p,
-                           gx->xnorm.p, gx->gcent.p, gx->bounds.p, dQ, gx->nn.p, nn_stride, gx->nn_cnt.p, gx->apv.p, gx->api.p,
-                           gx->anan.p);
-        launch_merge(false, gx->apv.p, gx->api.p, GA_WAVES, (long long)GA_C, (long long)GA_WAVES * GA_C, B, GA_C - 1, nullptr,
-                     nullptr, nullptr, nullptr, gx->amv.p, gx->ami.p, st);
-      }
-    }
-    hipLaunchKernelGGL(gq_rerank, dim3(B), dim3(64), 0, st, ix->codes.p, ix->ng, ix->vec, ix->m, ix->k, ix->d, ix->cents.p,
-                       ix->from.p, ix->sdim.p, gx->gcent.p, gx->bounds.p, g, dQ, gx->amv.p, gx->ami.p, gx->anan.p, gx->xnmax,
-                       K, d_oi, d_od, d_oc, gx->qlist.p, gx->qcount.p);
-    HIP_CHECK(hipGetLastError());
-    if (getenv("GULON_GROUPED_STATS")) {   // debugging aid
-      HIP_CHECK(hipStreamSynchronize(st));
-      int nfl = 0;
-      HIP_CHECK(hipMemcpy(&nfl, gx->qcount.p, sizeof(int), hipMemcpyDeviceToHost));
-      fprintf(stderr, "[grouped] approximate pre-selection: %d of %d queries redone with literal heaps\n", nfl, B);
-    }
-    if (lit_cap > 0) {   // listed queries whose group ORDER hangs on equal centroid distances: the reference's heap order
-      hipLaunchKernelGGL(gq_literal_groups, dim3(std::min(B, 16)), dim3(64), (size_t)lit_cap * 8, st, gx->cdist.p, g, lit_cap,
-                         gx->bounds.p, strategy == 1, limit, gx->lit_flag.p, 1, gx->qlist.p, gx->qcount.p, gx->nn.p, nn_stride,
-                         gx->nn_cnt.p);
-      HIP_CHECK(hipGetLastError());
-    }
-    const int fy = std::min(B, 16);
-    scan(true, fy, gx->qlist.p, gx->qcount.p);
-    hipLaunchKernelGGL(gq_merge<false>, dim3(fy), dim3(64), 0, st, gx->hk.p, gx->hv.p, gx->hs.p, gx->nn_cnt.p, stride, K, d_oi,
-                       d_od, d_oc, gx->qlist.p, gx->qcount.p);
-    HIP_CHECK(hipGetLastError());
-    return;
-  }
-  const size_t lds_qm = (4 * (size_t)smax * 256 + (size_t)QM_WAVES * (512 + ix->d)) * sizeof(float);
-  const char *qm_env = getenv("GULON_GROUPED_QM");   // testing aid: 0 = never, 1 = whenever it applies
-  const bool qm_off = qm_env && atoi(qm_env) == 0, qm_force = qm_env && atoi(qm_env) == 1;
-  // (from two workgroups of pairs per query on: 10 M rows / LimitGroups(500) 12.6 -> 8.4 ms per batch,
-  //  1 M rows / LimitGroups(50) 2.06 -> 1.92 ms)
-  if (!qm_off && (stride >= 2 * QM_WAVES || qm_force) && smax <= 16 && lds_qm <= 150 * 1024) {
-    const int mh = (ix->m + 1) / 2;
-    if (gx->codes2.n == 0) {   // second code layout, built once
-      const size_t nblk = (size_t)ceil_div(ix->n, 64);
-      const long long total = (long long)nblk * mh * 64;
-      const size_t padded = (size_t)total + (size_t)QM_RB * mh * 64;   // gq_scan_qm reads whole batches of row blocks
-      gx->codes2.alloc(padded);
-      HIP_CHECK(hipMemsetAsync(gx->codes2.p, 0, padded * sizeof(uint16_t), st));
-      if (total > 0) {
-        hipLaunchKernelGGL(gq_pair_codes, dim3((unsigned)ceil_div(total, 256LL)), dim3(256), 0, st, ix->codes.p, ix->ng,
-                           ix->vec, ix->m, mh, gx->codes2.p, total);
-        HIP_CHECK(hipGetLastError());
-      }
-    }
-    const int *nn_qm = gx->nn.p;
-    if (stride >= 2 * QM_WAVES && stride <= 2048) {   // several workgroups per query: size-sorted groups
-      int npad = 1;
-      while (npad < stride) npad <<= 1;
-      gx->nn_sized.ensure((size_t)B * nn_stride);
-      hipLaunchKernelGGL(gq_sort_by_size, dim3(B), dim3(256), (size_t)npad * sizeof(unsigned long long), st, gx->nn.p,
-                         nn_stride, gx->nn_cnt.p, gx->bounds.p, npad, gx->nn_sized.p);
-      HIP_CHECK(hipGetLastError());
-      nn_qm = gx->nn_sized.p;
-    }
-#define QM(X)                                                                                                        \
-    {                                                                                                               \
-      auto kern = gq_scan_qm<X>;                                                                                    \
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                           \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_qm));                      \
-      hipLaunchKernelGGL(kern, dim3(ceil_div(stride, QM_WAVES), B), dim3(64 * QM_WAVES), lds_qm, st, gx->codes2.p, mh, \
-                         ix->m, ix->k, ix->d, ix->cents.p, ix->from.p, ix->sdim.p, gx->gcent.p, gx->bounds.p, dQ,    \
-                         nn_qm, nn_stride, gx->nn_cnt.p, stride, K, gx->hk.p, gx->hv.p, gx->hs.p, smax);             \
-    }
-    if (smax <= 4) QM(2) else if (smax <= 8) QM(4) else if (smax <= 12) QM(6) else QM(8)
-#undef QM
-    HIP_CHECK(hipGetLastError());
-  } else {
-    scan(false, B, nullptr, nullptr);
-  }
-  hipLaunchKernelGGL(gq_merge_fast, dim3(B), dim3(64), 0, st, gx->hk.p, gx->hv.p, gx->hs.p, gx->nn_cnt.p, stride, K,
-                     d_oi, d_od, d_oc, gx->qlist.p, gx->qcount.p);
-  HIP_CHECK(hipGetLastError());
-  if (getenv("GULON_GROUPED_STATS")) {   // debugging aid
-    HIP_CHECK(hipStreamSynchronize(st));
-    int nfl = 0;
-    HIP_CHECK(hipMemcpy(&nfl, gx->qcount.p, sizeof(int), hipMemcpyDeviceToHost));
-    fprintf(stderr, "[grouped] %d of %d queries redone with literal heaps; %d groups searched per query at most\n", nfl, B,
-            stride);
-  }
-  {
-    if (lit_cap > 0) {   // listed queries whose group ORDER hangs on equal centroid distances: the reference's heap order
-      hipLaunchKernelGGL(gq_literal_groups, dim3(std::min(B, 16)), dim3(64), (size_t)lit_cap * 8, st, gx->cdist.p, g, lit_cap,
-                         gx->bounds.p, strategy == 1, limit, gx->lit_flag.p, 1, gx->qlist.p, gx->qcount.p, gx->nn.p, nn_stride,
-                         gx->nn_cnt.p);
-      HIP_CHECK(hipGetLastError());
-    }
-  }
-  const int fy = std::min(B, 16);
-  scan(true, fy, gx->qlist.p, gx->qcount.p);
-  hipLaunchKernelGGL(gq_merge<false>, dim3(fy), dim3(64), 0, st, gx->hk.p, gx->hv.p, gx->hs.p, gx->nn_cnt.p, stride, K, d_oi,
-                     d_od, d_oc, gx->qlist.p, gx->qcount.p);
-  HIP_CHECK(hipGetLastError());
+  // the pre-selection for every query, then the literal heaps for the ones it flagged
+  approx_stage(c, co, knobs);
+  redo_flagged(c, co, l);
+}
+
+// A query from host pointers, under idx->mu: `fill(st)` puts the b queries into idx->q_dev, then the query, the
+// download of the answers and the synchronise.
+template <class Fill>
+void query_from_host(gulon_grouped_index *idx, int b, int k_nn, int strategy, int limit, int32_t *out_idx, float *out_dist,
+                     int32_t *out_count, Fill fill) {
+  const size_t bk = (size_t)b * (size_t)k_nn;
+  idx->q_dev.ensure((size_t)b * idx->d + 1);
+  idx->oi.ensure(bk + 1); idx->od.ensure(bk + 1); idx->oc.ensure((size_t)b + 1);
+  hipStream_t st = nullptr;
+  if (b > 0) fill(st);
+  run_grouped_query(idx, idx->q_dev.p, b, k_nn, strategy, limit, idx->oi.p, idx->od.p, idx->oc.p, st);
+  if (bk) { idx->oi.download(out_idx, bk, st); idx->od.download(out_dist, bk, st); }
+  if (b > 0 && out_count) idx->oc.download(out_count, b, st);
+  HIP_CHECK(hipStreamSynchronize(st));
 }
 
 }  // namespace
@@ -1505,15 +1227,9 @@ GULON_API int32_t gulon_grouped_index_batch_query(gulon_grouped_index *idx, cons
     GULON_REQUIRE(idx != nullptr, "index is null");
     GULON_REQUIRE(b >= 0 && k_nn >= 0, "k and batch size must be non-negative");
     std::lock_guard<std::mutex> lock(idx->mu);
-    const size_t bk = (size_t)b * (size_t)k_nn;
-    idx->q_dev.ensure((size_t)b * idx->d + 1);
-    idx->oi.ensure(bk + 1); idx->od.ensure(bk + 1); idx->oc.ensure((size_t)b + 1);
-    hipStream_t st = nullptr;
-    if (b > 0) HIP_CHECK(hipMemcpyAsync(idx->q_dev.p, queries, sizeof(float) * (size_t)b * idx->d, hipMemcpyHostToDevice, st));
-    run_grouped_query(idx, idx->q_dev.p, b, k_nn, strategy, limit, idx->oi.p, idx->od.p, idx->oc.p, st);
-    if (bk) { idx->oi.download(out_idx, bk, st); idx->od.download(out_dist, bk, st); }
-    if (b > 0 && out_count) idx->oc.download(out_count, b, st);
-    HIP_CHECK(hipStreamSynchronize(st));
+    query_from_host(idx, b, k_nn, strategy, limit, out_idx, out_dist, out_count, [&](hipStream_t st) {
+      HIP_CHECK(hipMemcpyAsync(idx->q_dev.p, queries, sizeof(float) * (size_t)b * idx->d, hipMemcpyHostToDevice, st));
+    });
   });
 }
 
@@ -1571,20 +1287,12 @@ GULON_API int32_t gulon_grouped_index_query_rows(gulon_grouped_index *idx, const
     for (int r = 0; r < b; r++)   // checked before anything is launched
       GULON_REQUIRE(rows[r] >= 0 && rows[r] < idx->n, "row %d = %d outside [0, %d)", r, rows[r], idx->n);
     std::lock_guard<std::mutex> lock(idx->mu);
-    const size_t bk = (size_t)b * (size_t)k_nn;
-    idx->q_dev.ensure((size_t)b * idx->d + 1);
-    idx->rows_dev.ensure((size_t)b + 1);
-    idx->oi.ensure(bk + 1); idx->od.ensure(bk + 1); idx->oc.ensure((size_t)b + 1);
-    hipStream_t st = nullptr;
-    if (b > 0) {
+    query_from_host(idx, b, k_nn, strategy, limit, out_idx, out_dist, out_count, [&](hipStream_t st) {
+      idx->rows_dev.ensure((size_t)b + 1);
       HIP_CHECK(hipMemcpyAsync(idx->rows_dev.p, rows, sizeof(int32_t) * (size_t)b, hipMemcpyHostToDevice, st));
       launch_decode_rows(idx->pq, idx->rows_dev.p, b, idx->gcent.p, idx->bounds.p + 1, idx->g - 1, normalize != 0,
                          idx->q_dev.p, nullptr, st);
-    }
-    run_grouped_query(idx, idx->q_dev.p, b, k_nn, strategy, limit, idx->oi.p, idx->od.p, idx->oc.p, st);
-    if (bk) { idx->oi.download(out_idx, bk, st); idx->od.download(out_dist, bk, st); }
-    if (b > 0 && out_count) idx->oc.download(out_count, b, st);
-    HIP_CHECK(hipStreamSynchronize(st));
+    });
   });
 }
 

@@ -48,10 +48,15 @@ def _oracle_side(oracle, X, coarse, gv, pq, n):
     (20000, 32, 40, 8, 256, 17, 10, 0),
     (8000, 24, 10, 6, 64, 5, 10, 1500),          # duplicated rows: ties inside and across groups
 ])
-@pytest.mark.parametrize("qm", [False, True])
-def test_grouped_query_equals_reference(oracle, g, monkeypatch, n, d, groups, m, k, B, K, dup, strategy, limit, qm):
-    if qm:      # the quantizer-major kernel normally takes over from 16 searched groups per query on
-        monkeypatch.setenv("GULON_GROUPED_QM", "1")
+@pytest.mark.parametrize("literal", [False, True])
+def test_grouped_query_equals_reference(oracle, g, monkeypatch, capfd, n, d, groups, m, k, B, K, dup, strategy, limit,
+                                        literal):
+    """Every case twice: through the approximate pre-selection with the literal redo of what it flags, and, with
+    GULON_GROUPED_LITERAL=1, every (query, group) pair through the reference's TopKHeap in a wavefront's registers and
+    TopKHeap.merge in search order (Index.scala:265-282).  The statistics line shows which of the two ran."""
+    monkeypatch.setenv("GULON_GROUPED_STATS", "1")
+    if literal:
+        monkeypatch.setenv("GULON_GROUPED_LITERAL", "1")
     X, dm, coarse, gv, pq = _build(oracle, g, n, d, groups, m, k, seed=n + d, dup=dup)
     R, cents, offsets = _oracle_side(oracle, X, coarse, gv, pq, n)
     strat = g.LimitGroups(limit) if strategy == "groups" else g.LimitVectors(limit)
@@ -61,6 +66,7 @@ def test_grouped_query_equals_reference(oracle, g, monkeypatch, n, d, groups, m,
     rng = np.random.default_rng(1)
     Q = np.concatenate([X[rng.integers(0, n, B - 2)], (rng.standard_normal((2, d)) * 2).astype(np.float32)])
     oi, od, oc = index.batch_query_raw(K, Q)
+    assert ("approximate pre-selection" in capfd.readouterr().err) == (not literal)
     ei, ed, ec = oracle.grouped_query(codes, d, k, pq.flat_centroids(), cents, offsets, Q, K,
                                       0 if strategy == "groups" else 1, limit)
     assert np.array_equal(oc, ec)
@@ -71,14 +77,16 @@ def test_grouped_query_equals_reference(oracle, g, monkeypatch, n, d, groups, m,
 
 
 @pytest.mark.parametrize("n,d,groups,m,k,limit", [
-    (20000, 16, 3, 4, 256, 3),        # ~6700-row groups: several passes of 32 row blocks
-    (9000, 21, 30, 7, 40, 12),        # odd m: the last step has one quantizer; 3-wide sub-vectors
+    (20000, 16, 3, 4, 256, 3),        # ~6700-row groups
+    (9000, 21, 30, 7, 40, 12),        # odd m: a padding quantizer; 3-wide sub-vectors
     (6000, 50, 20, 5, 256, 20),       # 10-wide sub-vectors
     (6000, 64, 8, 4, 100, 8),         # 16-wide sub-vectors
-    (30000, 32, 200, 8, 256, 120),    # the regime where it is picked without being forced
+    (30000, 32, 200, 8, 256, 120),    # LimitGroups(> 63): the sorted group selection, the by-group filter
 ])
-def test_quantizer_major_scan_equals_reference(oracle, g, monkeypatch, n, d, groups, m, k, limit):
-    monkeypatch.setenv("GULON_GROUPED_QM", "1")
+def test_subvector_widths_equal_reference(oracle, g, monkeypatch, capfd, n, d, groups, m, k, limit):
+    """Odd m and sub-vectors 3, 10 and 16 wide, on duplicated rows, through the approximate pre-selection (the statistics
+    line shows that it ran) and the literal redo of the queries it flags."""
+    monkeypatch.setenv("GULON_GROUPED_STATS", "1")
     B, K = 7, 10
     X, dm, coarse, gv, pq = _build(oracle, g, n, d, groups, m, k, seed=n + m, dup=600, iters=2)
     R, cents, offsets = _oracle_side(oracle, X, coarse, gv, pq, n)
@@ -86,6 +94,7 @@ def test_quantizer_major_scan_equals_reference(oracle, g, monkeypatch, n, d, gro
     rng = np.random.default_rng(3)
     Q = np.concatenate([X[rng.integers(0, n, B - 1)], (rng.standard_normal((1, d)) * 2).astype(np.float32)])
     oi, od, oc = index.batch_query_raw(K, Q)
+    assert "approximate pre-selection" in capfd.readouterr().err
     ei, ed, ec = oracle.grouped_query(index.data.indices(), d, k, pq.flat_centroids(), cents, offsets, Q, K, 0, limit)
     assert np.array_equal(oc, ec)
     for q in range(B):
@@ -139,6 +148,23 @@ def test_bad_arguments(g):
     gc = np.zeros(2 * 8, np.float32)
     off = np.array([20], np.int32)                       # beyond n = 10
     assert N.lib().gulon_grouped_index_create(codes, 10, 8, 4, 256, cents, gc, off, 2, C.byref(h)) == -1
+
+
+@pytest.mark.parametrize("strategy,limit", [(0, 1), (1, 10)])
+def test_index_without_rows_answers_nothing(g, strategy, limit):
+    """n = 0 is a valid index (one group, no row norms): every query comes back with no neighbours."""
+    import ctypes as C
+    from gulon_amd import native as N
+    d, m, k, B, K = 8, 4, 16, 3, 5
+    h = C.c_void_p()
+    cents = np.random.default_rng(0).standard_normal(k * d).astype(np.float32)
+    assert N.lib().gulon_grouped_index_create(np.zeros(1, np.uint8), 0, d, m, k, cents, np.zeros(d, np.float32),
+                                              np.zeros(1, np.int32), 1, C.byref(h)) == 0      # GULON_OK
+    Q = np.random.default_rng(1).standard_normal(B * d).astype(np.float32)
+    oi, od, oc = np.zeros(B * K, np.int32), np.zeros(B * K, np.float32), np.full(B, -1, np.int32)
+    assert N.lib().gulon_grouped_index_batch_query(h, Q, B, K, strategy, limit, oi, od, oc) == 0
+    assert oc.tolist() == [0] * B
+    assert N.lib().gulon_grouped_index_destroy(h) == 0
 
 
 @pytest.mark.parametrize("n,d,groups,m,k,limit,dup,bad_query", [
