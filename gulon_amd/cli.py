@@ -154,6 +154,9 @@ def _parser():
         s.add_argument("-c", "--candidates", type=_positive, default=None, metavar="num",
                        help="candidates taken from the index per query before re-ranking (needs --vectors; "
                             "default 10 * neighbours)")
+        s.add_argument("-r", "--restrict", default=None, metavar="file",
+                       help="take the neighbours from the words of this file only (one word per line; words the index "
+                            "lacks are ignored and counted on stderr)")
         if name == "query-words":
             s.add_argument("-x", "--expressions", action="store_true",
                            help="read every line as an expression `word (+|- word)*` (operators as stand-alone tokens): "
@@ -277,10 +280,21 @@ def read_originals(path, normalize):
     return read_word2vec_device(path, normalize=normalize).sorted()
 
 
-def _refined(args, index, vectors):
-    """The loaded index, or with -v its refined form; -c needs -v."""
-    if args.vectors is None:
+def _restricted(args, index):
+    """The loaded index, or with -r its restriction to the words of that file."""
+    if args.restrict is None:
         return index
+    with open(args.restrict, "rb") as fh:
+        words = read_lines(fh.read())
+    index = index.restrict(words)
+    print(f"{index.ignored} of {len(words)} restriction words are not in the index", file=sys.stderr)
+    return index
+
+
+def _refined(args, index, vectors):
+    """The loaded index, or with -r its restriction, or with -v its refined form; -c needs -v."""
+    if args.vectors is None:
+        return _restricted(args, index)
     candidates = args.candidates if args.candidates is not None else 10 * args.neighbours
     return index.refined(vectors(args.vectors, index.metric == "cosine"), candidates)
 
@@ -295,6 +309,11 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
     args = parser.parse_args(argv)
     if args.command in ("query", "query-words") and args.candidates is not None and args.vectors is None:
         parser.error("--candidates is only applicable with --vectors")
+    if args.command in ("query", "query-words") and args.restrict is not None:
+        if args.vectors is not None:
+            parser.error("--restrict is not applicable with --vectors")
+        if getattr(args, "expressions", False):
+            parser.error("--restrict is not applicable with --expressions")
     vectors = vectors if vectors is not None else read_originals
     stdin = stdin if stdin is not None else sys.stdin.buffer
     stdout = stdout if stdout is not None else sys.stdout.buffer

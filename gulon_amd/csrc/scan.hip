@@ -997,16 +997,7 @@ GULON_API int32_t gulon_index_create(const uint8_t *codes, int32_t n, int32_t d,
                            ix->codes.p, total);
       HIP_CHECK(hipGetLastError());
       HIP_CHECK(hipDeviceSynchronize());
-      // the filter's conflict-ordered copy (one 16-byte code word per row; ranges the filter is never used for
-      // do not need one).  GULON_FILTER_ORDER = rounds of the ordering (0: no copy)
-      const int rounds = ix->tune->filter_order;
-      if (rounds > 0 && ix->vec == 16 && ix->ng == 1 && (long long)nblk >= ix->tune->filter_min_rb) {
-        ix->fcodes.alloc(nblk * 1024);
-        ix->fperm.alloc(nblk * 64);
-        launch_conflict_order(ix->codes.p, ix->fcodes.p, ix->fperm.p, (long long)nblk, FILTER_LDS_QUANTIZERS, rounds, 0);
-        ix->fwindow = conflict_order_windowed() ? 4 : 1;
-        HIP_CHECK(hipDeviceSynchronize());
-      }
+      build_filter_copy(ix.get());
     }
     HIP_CHECK(hipDeviceSynchronize());
     *out = ix.release();
@@ -1014,6 +1005,20 @@ GULON_API int32_t gulon_index_create(const uint8_t *codes, int32_t n, int32_t d,
 }
 
 namespace gulon {
+// the filter's conflict-ordered copy (one 16-byte code word per row; ranges the filter is never used for
+// do not need one).  GULON_FILTER_ORDER = rounds of the ordering (0: no copy)
+void build_filter_copy(gulon_index *ix) {
+  const size_t nblk = (size_t)ceil_div(ix->n, 64);
+  const int rounds = ix->tune->filter_order;
+  if (rounds > 0 && ix->vec == 16 && ix->ng == 1 && (long long)nblk >= ix->tune->filter_min_rb) {
+    ix->fcodes.alloc(nblk * 1024);
+    ix->fperm.alloc(nblk * 64);
+    launch_conflict_order(ix->codes.p, ix->fcodes.p, ix->fperm.p, (long long)nblk, FILTER_LDS_QUANTIZERS, rounds, 0);
+    ix->fwindow = conflict_order_windowed() ? 4 : 1;
+    HIP_CHECK(hipDeviceSynchronize());
+  }
+}
+
 gulon_index *make_context(gulon_index *parent) {
   std::unique_ptr<gulon_index> c(new gulon_index());
   c->n = parent->n; c->d = parent->d; c->m = parent->m; c->k = parent->k; c->row_base = parent->row_base;
@@ -1029,6 +1034,9 @@ gulon_index *make_context(gulon_index *parent) {
   c->cents.borrow(parent->cents);
   c->from.borrow(parent->from);
   c->sdim.borrow(parent->sdim);
+  c->is_view = parent->is_view;
+  c->view_base = parent->view_base;
+  c->vmap.borrow(parent->vmap);
   return c.release();
 }
 }  // namespace gulon
@@ -1086,17 +1094,27 @@ GULON_API int32_t gulon_index_context_create(gulon_index *parent, gulon_index **
   });
 }
 
+namespace gulon {
+void batch_query_dev_on(gulon_index *idx, const float *d_queries, int32_t b, int32_t k_nn, int32_t from, int32_t until,
+                        int32_t *d_out_idx, float *d_out_dist, int32_t *d_out_count, int32_t *d_out_flags,
+                        hipStream_t st, bool map_view) {
+  std::lock_guard<std::mutex> lock(idx->mu);
+  idx->pend_b = -1;
+  StreamOrder so(idx, st);
+  run_query(idx, d_queries, b, k_nn, from, until, true, d_out_idx, d_out_dist, d_out_count, d_out_flags, nullptr,
+            nullptr, st);
+  if (map_view) launch_map_rows(idx, d_out_idx, (long long)b * k_nn, st);
+  so.done();
+}
+}  // namespace gulon
+
 GULON_API int32_t gulon_index_batch_query_dev(gulon_index *idx, const float *d_queries, int32_t b, int32_t k_nn,
                                               int32_t from, int32_t until, int32_t *d_out_idx, float *d_out_dist,
                                               int32_t *d_out_count, int32_t *d_out_flags, void *stream) {
   return guarded([&] {
     GULON_REQUIRE(idx != nullptr, "index is null");
-    std::lock_guard<std::mutex> lock(idx->mu);
-    idx->pend_b = -1;
-    StreamOrder so(idx, (hipStream_t)stream);
-    run_query(idx, d_queries, b, k_nn, from, until, true, d_out_idx, d_out_dist, d_out_count, d_out_flags, nullptr,
-              nullptr, (hipStream_t)stream);
-    so.done();
+    batch_query_dev_on(idx, d_queries, b, k_nn, from, until, d_out_idx, d_out_dist, d_out_count, d_out_flags,
+                       (hipStream_t)stream, false);
   });
 }
 
@@ -1149,37 +1167,45 @@ GULON_API int32_t gulon_index_scan_partial_bounded_dev(gulon_index *idx, const f
   });
 }
 
+namespace gulon {
+void batch_query_host_on(gulon_index *idx, const float *queries, int32_t b, int32_t k_nn, int32_t from, int32_t until,
+                         int32_t *out_idx, float *out_dist, int32_t *out_count, int32_t *out_flags, bool map_view) {
+  GULON_REQUIRE(b >= 0 && k_nn >= 0, "k and batch size must be non-negative");
+  // concurrent callers (Tests.scala:109-122 queries from a thread pool) each get a workspace of their own
+  gulon_index *c = acquire_host_context(idx);
+  struct Release { gulon_index *i, *c; ~Release() { release_host_context(i, c); } } rel{idx, c};
+  std::lock_guard<std::mutex> lock(c->mu);
+  c->pend_b = -1;
+  size_t bk = (size_t)b * (size_t)k_nn;
+  c->stage_q.ensure((size_t)b * c->d + 1);
+  c->stage_oi.ensure(bk + 1);
+  c->stage_od.ensure(bk + 1);
+  c->stage_oc.ensure((size_t)b + 1);
+  c->stage_of.ensure((size_t)b + 1);
+  if (!c->host_stream) HIP_CHECK(hipStreamCreateWithFlags(&c->host_stream, hipStreamNonBlocking));
+  hipStream_t st = c->host_stream;
+  StreamOrder so(c, st);
+  if (b > 0) HIP_CHECK(hipMemcpyAsync(c->stage_q.p, queries, sizeof(float) * (size_t)b * c->d, hipMemcpyHostToDevice, st));
+  run_query(c, c->stage_q.p, b, k_nn, from, until, true, c->stage_oi.p, c->stage_od.p, c->stage_oc.p,
+            c->stage_of.p, nullptr, nullptr, st);
+  if (map_view) launch_map_rows(c, c->stage_oi.p, (long long)bk, st);   // the context borrows the view's map
+  if (bk) {
+    c->stage_oi.download(out_idx, bk, st);
+    c->stage_od.download(out_dist, bk, st);
+  }
+  if (b > 0 && out_count) c->stage_oc.download(out_count, b, st);
+  if (b > 0 && out_flags) c->stage_of.download(out_flags, b, st);
+  so.done();
+  HIP_CHECK(hipStreamSynchronize(st));
+}
+}  // namespace gulon
+
 GULON_API int32_t gulon_index_batch_query(gulon_index *idx, const float *queries, int32_t b, int32_t k_nn,
                                           int32_t from, int32_t until, int32_t *out_idx, float *out_dist,
                                           int32_t *out_count, int32_t *out_flags) {
   return guarded([&] {
     GULON_REQUIRE(idx != nullptr, "index is null");
-    GULON_REQUIRE(b >= 0 && k_nn >= 0, "k and batch size must be non-negative");
-    // concurrent callers (Tests.scala:109-122 queries from a thread pool) each get a workspace of their own
-    gulon_index *c = acquire_host_context(idx);
-    struct Release { gulon_index *i, *c; ~Release() { release_host_context(i, c); } } rel{idx, c};
-    std::lock_guard<std::mutex> lock(c->mu);
-    c->pend_b = -1;
-    size_t bk = (size_t)b * (size_t)k_nn;
-    c->stage_q.ensure((size_t)b * c->d + 1);
-    c->stage_oi.ensure(bk + 1);
-    c->stage_od.ensure(bk + 1);
-    c->stage_oc.ensure((size_t)b + 1);
-    c->stage_of.ensure((size_t)b + 1);
-    if (!c->host_stream) HIP_CHECK(hipStreamCreateWithFlags(&c->host_stream, hipStreamNonBlocking));
-    hipStream_t st = c->host_stream;
-    StreamOrder so(c, st);
-    if (b > 0) HIP_CHECK(hipMemcpyAsync(c->stage_q.p, queries, sizeof(float) * (size_t)b * c->d, hipMemcpyHostToDevice, st));
-    run_query(c, c->stage_q.p, b, k_nn, from, until, true, c->stage_oi.p, c->stage_od.p, c->stage_oc.p,
-              c->stage_of.p, nullptr, nullptr, st);
-    if (bk) {
-      c->stage_oi.download(out_idx, bk, st);
-      c->stage_od.download(out_dist, bk, st);
-    }
-    if (b > 0 && out_count) c->stage_oc.download(out_count, b, st);
-    if (b > 0 && out_flags) c->stage_of.download(out_flags, b, st);
-    so.done();
-    HIP_CHECK(hipStreamSynchronize(st));
+    batch_query_host_on(idx, queries, b, k_nn, from, until, out_idx, out_dist, out_count, out_flags, false);
   });
 }
 

@@ -60,6 +60,11 @@ struct gulon_index {
   DevBuf<uint32_t> wpark;  // wide filter, sliced 8-bit tables: byte sums [query group][row block][64 lanes] (wide_filter.hip)
   DevBuf<float> cents;     // k*d
   DevBuf<int> from, sdim;  // m
+  // a view (subset.hip): this index holds rows vmap[0] < vmap[1] < ... of another one -- local rows of the root, whose
+  // row_base is view_base.  The view-query entries answer view_base + vmap[p]; every other entry answers p.
+  bool is_view = false;
+  int view_base = 0;
+  DevBuf<int> vmap;        // n
   // scratch, grown on demand under `mu`
   DevBuf<float> tables;
   DevBuf<float> part_v;
@@ -142,6 +147,17 @@ struct gulon_index {
 namespace gulon {
 // a new workspace over `parent`'s read-only data (no reference counting: the caller keeps `parent` alive)
 gulon_index *make_context(gulon_index *parent);
+// scan.hip: the bodies of gulon_index_batch_query_dev / gulon_index_batch_query; map_view (a view only): the returned
+// positions are translated to the root's row ids on the same stream, inside the handle's StreamOrder
+void batch_query_dev_on(gulon_index *idx, const float *d_queries, int32_t b, int32_t k_nn, int32_t from, int32_t until,
+                        int32_t *d_out_idx, float *d_out_dist, int32_t *d_out_count, int32_t *d_out_flags,
+                        hipStream_t st, bool map_view);
+void batch_query_host_on(gulon_index *idx, const float *queries, int32_t b, int32_t k_nn, int32_t from, int32_t until,
+                         int32_t *out_idx, float *out_dist, int32_t *out_count, int32_t *out_flags, bool map_view);
+// scan.hip: the filter's conflict-ordered copy of ix->codes, where this handle's tuning and shape call for one
+void build_filter_copy(gulon_index *ix);
+// subset.hip: d_idx[0..count) positions of `view` -> row ids of its root, in place; negative entries stay
+void launch_map_rows(const gulon_index *view, int *d_idx, long long count, hipStream_t st);
 // RAII: order this call's device work after the previous call's on the same handle when the stream differs
 struct StreamOrder {
   gulon_index *ix;

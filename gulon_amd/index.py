@@ -215,6 +215,36 @@ class PQIndex:
         oi, od, oc, of = self.batch_query_terms_partitioned(k, expressions, frm, until, normalize_terms, normalize_query)
         return [Result(oi[i, :oc[i]].copy(), od[i, :oc[i]].copy(), int(of[i])) for i in range(len(oc))]
 
+    def select(self, rows=None, mask=None):
+        """The view of this index over a subset of its rows (gulon_index_select_*): an index of its own, gathered on
+        the device, that answers in THIS index's row ids.  Exactly one of `rows` (strictly ascending row numbers) and
+        `mask` (a bool array of length n, a packed uint64 array of ceil(n / 64) words -- bit r & 63 of word r >> 6 --
+        or a torch device tensor of uint64 / int64 words, used where it lies)."""
+        if (rows is None) == (mask is None):
+            raise ValueError("select takes exactly one of rows and mask")
+        h = C.c_void_p()
+        if rows is not None:
+            r = np.asarray(rows).reshape(-1)
+            if r.size and not np.issubdtype(r.dtype, np.integer):
+                raise ValueError("rows must be integers")
+            if r.size and (r.min() < -2 ** 31 or r.max() >= 2 ** 31):
+                bad = int(np.flatnonzero((r < -2 ** 31) | (r >= 2 ** 31))[0])
+                raise ValueError(f"requirement failed: rows[{bad}] = {int(r[bad])} outside [0, {self.length})")
+            r = N.i32(r)
+            N.check(N.lib().gulon_index_select_rows(self._h, r if r.size else np.zeros(1, np.int32), r.size,
+                                                    C.byref(h)))
+        elif hasattr(mask, "data_ptr"):
+            import torch
+            words = (self.length + 63) // 64
+            if not mask.is_cuda or mask.dtype not in (torch.uint64, torch.int64) or mask.numel() != words \
+                    or not mask.is_contiguous():
+                raise ValueError(f"a device mask is a contiguous uint64 / int64 tensor of {words} words")
+            torch.cuda.current_stream(mask.device).synchronize()      # the mask is read on the library's stream
+            N.check(N.lib().gulon_index_select_mask_dev(self._h, mask.data_ptr(), C.byref(h)))
+        else:
+            N.check(N.lib().gulon_index_select_mask(self._h, pack_mask(mask, self.length), C.byref(h)))
+        return PQIndexView(self, h)
+
     def close(self):
         if self._h is not None and self._h.value:
             N.lib().gulon_index_destroy(self._h)
@@ -225,6 +255,106 @@ class PQIndex:
             self.close()
         except Exception:
             pass
+
+
+def pack_mask(mask, n):
+    """A row mask as ceil(n / 64) uint64 words, bit r & 63 of word r >> 6 for row r: from a bool array of length n, or
+    from an array of that many words as it is."""
+    m = np.asarray(mask)
+    words = (n + 63) // 64
+    if m.dtype == np.bool_:
+        if m.shape != (n,):
+            raise ValueError(f"a bool mask has one entry per row: {m.shape} for {n} rows")
+        bits = np.zeros(words * 64, np.uint8)
+        bits[:n] = m
+        out = np.packbits(bits.reshape(words, 8, 8), axis=2, bitorder="little").reshape(words, 8)
+        return np.ascontiguousarray(out).view("<u8").reshape(-1).astype(np.uint64) if words else np.zeros(1, np.uint64)
+    if m.dtype not in (np.uint64, np.int64) or m.shape != (words,):
+        raise ValueError(f"a packed mask is {words} uint64 words for {n} rows")
+    return np.ascontiguousarray(m).view(np.uint64) if words else np.zeros(1, np.uint64)
+
+
+def mask_rows(mask, n):
+    """The rows a packed mask selects, ascending (bits at or above n ignored): the host statement of mask_to_rows."""
+    w = np.ascontiguousarray(mask, np.uint64)[:(n + 63) // 64]
+    bits = np.unpackbits(w.astype("<u8").view(np.uint8), bitorder="little")[:n]
+    return np.flatnonzero(bits).astype(np.int32)
+
+
+class PQIndexView(PQIndex):
+    """A view (PQIndex.select): the PQIndex over the selected rows of `source`, in ascending order, on the device.  Its
+    queries return row ids of the root index -- the index the first view was taken of; `positions_raw` the view's own
+    positions.  frm / until, and the rows of decode_rows / batch_query_rows, are positions of the view."""
+
+    def __init__(self, source, handle, _state=None):
+        self.product_quantizer = source.product_quantizer
+        self.row_base = 0
+        self._h = handle
+        # shared between a view and its contexts: the root's codes and the lazily downloaded rows
+        self._state = _state if _state is not None else {
+            "root": source._state["root"] if isinstance(source, PQIndexView) else source.data,
+            "root_base": source._state["root_base"] if isinstance(source, PQIndexView) else source.row_base,
+            "rows": None, "data": None}
+        _LIVE.add(self)
+
+    @property
+    def length(self):
+        s = C.c_int32(0)
+        N.check(N.lib().gulon_index_view_size(self._h, C.byref(s)))
+        return s.value
+
+    @property
+    def rows(self):
+        """The selected rows (local rows of the root index), ascending."""
+        if self._state["rows"] is None:
+            out = np.zeros(max(self.length, 1), np.int32)
+            N.check(N.lib().gulon_index_view_rows(self._h, out))
+            self._state["rows"] = out[:self.length]
+        return self._state["rows"]
+
+    @property
+    def data(self):
+        """The EncodedMatrix of the view: the root's columns at `rows`."""
+        if self._state["data"] is None:
+            from .coder import Coder
+            root = self._state["root"]
+            coder = Coder(root.coder.width, self.length)
+            self._state["data"] = EncodedMatrix(coder, [coder.build_code(ix[self.rows]) for ix in root.indices()])
+        return self._state["data"]
+
+    def context(self):
+        h = C.c_void_p()
+        N.check(N.lib().gulon_index_context_create(self._h, C.byref(h)))
+        return PQIndexView(self, h, _state=self._state)
+
+    def positions_raw(self, k, vectors, frm=0, until=None):
+        """batch_query_raw in the view's own positions."""
+        return PQIndex.batch_query_raw(self, k, vectors, frm, until)
+
+    def batch_query_raw(self, k, vectors, frm=0, until=None):
+        q = vectors.data if isinstance(vectors, Matrix) else N.f32(vectors)
+        q = N.f32(q).reshape(-1, self.dimension)
+        until = self.length if until is None else until
+        b = q.shape[0]
+        oi = np.zeros((b, max(k, 1)), np.int32)
+        od = np.zeros((b, max(k, 1)), np.float32)
+        oc = np.zeros(max(b, 1), np.int32)
+        of = np.zeros(max(b, 1), np.int32)
+        N.check(N.lib().gulon_index_view_batch_query(self._h, q.reshape(-1) if b else np.zeros(1, np.float32), b, k,
+                                                     frm, until, oi.reshape(-1), od.reshape(-1), oc, of))
+        return oi[:, :k], od[:, :k], oc[:b], of[:b]
+
+    def map_positions(self, positions):
+        """Positions of the view -> row ids of the root index; negative entries (padding) stay."""
+        p = N.i32(positions)
+        if not self.length:
+            return p
+        live = (p >= 0) & (p < self.length)
+        return np.where(live, self._state["root_base"] + self.rows[np.where(live, p, 0)], p).astype(np.int32)
+
+    def batch_query_rows_raw(self, k, rows, frm=0, until=None, normalize=False):
+        oi, od, oc, of = PQIndex.batch_query_rows_raw(self, k, rows, frm, until, normalize)
+        return self.map_positions(oi), od, oc, of
 
 
 def normalize(xs):
@@ -274,6 +404,11 @@ class SortedIndex:
         """Index.queryByWord (Index.scala:38-45) on row ids: query(k, lookup(row)) for every row, decoded (and for a
         cosine index normalised, Index.scala:324-331) on the device."""
         return self.vector_index.batch_query_rows(k, rows, normalize=self.metric == "cosine")
+
+    def select(self, rows=None, mask=None):
+        """A SortedIndex over the view of the selected rows (PQIndex.select), same metric: its results name rows of
+        this index."""
+        return SortedIndex(self.vector_index.select(rows, mask), self.metric)
 
     def compose_rows(self, expressions):
         """The query vector of every expression over row ids as this index prepares it: terms and sum normalised for a

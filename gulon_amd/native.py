@@ -50,6 +50,7 @@ class KMeansTraceTotals(C.Structure):
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
 _i64p = np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")
+_u64p = np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS")
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 _vp = C.c_void_p
 _i32 = C.c_int32
@@ -129,6 +130,15 @@ SIGNATURES = {
     "gulon_grouped_index_query_rows_dev": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "gulon_index_row_error": (_i32, [_vp, C.POINTER(_i32)]),
     "gulon_grouped_index_row_error": (_i32, [_vp, C.POINTER(_i32)]),
+    "gulon_index_select_rows": (_i32, [_vp, _i32p, _i32, C.POINTER(_vp)]),
+    "gulon_index_select_mask_dev": (_i32, [_vp, _vp, C.POINTER(_vp)]),
+    "gulon_index_select_mask": (_i32, [_vp, _u64p, C.POINTER(_vp)]),
+    "gulon_index_view_size": (_i32, [_vp, C.POINTER(_i32)]),
+    "gulon_index_view_rows": (_i32, [_vp, _i32p]),
+    "gulon_index_view_rows_dev": (_i32, [_vp, C.POINTER(_vp)]),
+    "gulon_index_view_batch_query": (_i32, [_vp, _f32p, _i32, _i32, _i32, _i32, _i32p, _f32p, _i32p, _i32p]),
+    "gulon_index_view_batch_query_dev": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "gulon_index_view_map_rows_dev": (_i32, [_vp, _vp, C.c_int64, _vp]),
     "gulon_index_compose_rows": (_i32, [_vp, _i32p, _i32p, _f32p, _i32, _i32, _i32, _f32p]),
     "gulon_index_compose_rows_dev": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "gulon_grouped_index_compose_rows": (_i32, [_vp, _i32p, _i32p, _f32p, _i32, _i32, _i32, _f32p]),

@@ -69,6 +69,15 @@ class WordIndex:
         from .refine import RefinedIndex
         return RefinedIndex(self, vectors, candidates)
 
+    def restrict(self, words):
+        """This index with its neighbours drawn from `words` only (PQIndex.select: a view gathered on the device, built
+        once for any number of queries).  Words the index lacks are ignored -- their number is `.ignored` -- and
+        duplicates count once.  Results carry this index's words and row ids; query_by_word looks its word up in this
+        index, so the query word need not be among `words`."""
+        if self._grouped:
+            raise NotImplementedError("restrict is not supported by the grouped index")
+        return RestrictedWordIndex(self, words)
+
     def row_of(self, word) -> Optional[int]:
         return self.key_index.lookup(word)
 
@@ -155,3 +164,55 @@ class WordIndex:
 
     def close(self):
         (self.index if self._grouped else self.index.vector_index).close()
+
+
+class RestrictedWordIndex(WordIndex):
+    """WordIndex.restrict: `parent`'s words and key index over a SortedIndex on the view of the listed words' rows."""
+
+    def __init__(self, parent, words):
+        rows = [parent.row_of(w) for w in words]
+        self.ignored = sum(r is None for r in rows)
+        self.parent = parent
+        self.words, self.key_index, self._grouped = parent.words, parent.key_index, False
+        self.index = parent.index.select(rows=np.unique(np.asarray([r for r in rows if r is not None], np.int64)))
+
+    @property
+    def restricted_size(self):
+        return self.index.size
+
+    def lookup(self, word):
+        return self.parent.lookup(word)
+
+    def batch_query_by_words(self, k, words) -> List[Optional[WordResult]]:
+        """queryByWord with the word's vector decoded from the PARENT and the neighbours taken from the restriction."""
+        words = list(words)
+        rows = [self.row_of(w) for w in words]
+        present = [i for i, r in enumerate(rows) if r is not None]
+        out: List[Optional[WordResult]] = [None] * len(words)
+        cosine = self.metric == "cosine"
+        for s in range(0, len(present), BATCH):
+            part = present[s:s + BATCH]
+            vectors = self.parent.index.vector_index.decode_rows(np.asarray([rows[i] for i in part], np.int32), cosine)
+            for i, r in zip(part, self.index.vector_index.batch_query(k, vectors)):
+                out[i] = self._result(r)
+        return out
+
+    def restrict(self, words):
+        """A restriction of a restriction: the listed words that are also in this one."""
+        inside = set(self.index.vector_index.rows.tolist())
+        rows = [self.row_of(w) for w in words]
+        out = self.parent.restrict([w for w, r in zip(words, rows) if r is not None and r in inside])
+        out.ignored = sum(r is None or r not in inside for r in rows)
+        return out
+
+    def refined(self, vectors, candidates):
+        raise NotImplementedError("refined is not supported by a restricted index")
+
+    def resolve_expressions(self, expressions):
+        raise NotImplementedError("expressions are not supported by a restricted index")
+
+    def batch_query_expressions(self, k, expressions):
+        raise NotImplementedError("expressions are not supported by a restricted index")
+
+    def close(self):
+        self.index.vector_index.close()

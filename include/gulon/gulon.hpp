@@ -211,10 +211,58 @@ class PQIndex {                       // Index.scala:385-441
   std::vector<Result> batchQuery(int k, const std::vector<float> &queries) const {
     return batchQuery(k, queries, 0, length_);
   }
+  gulon_index *handle() const { return h_; }
 
  private:
   gulon_index *h_ = nullptr;
   int dimension_, length_;
+};
+
+// A view (gulon_index_select_rows): the PQIndex over the chosen rows of another index -- strictly ascending local rows
+// -- gathered on the device; its results name rows of the index the first view was taken of.  from / until are
+// positions of the view.  The view owns what it reads: the source may be destroyed first.
+class IndexView {
+ public:
+  IndexView(const PQIndex &source, const std::vector<int32_t> &rows) : dimension_(source.dimension()) {
+    check(gulon_index_select_rows(source.handle(), rows.data(), (int32_t)rows.size(), &h_));
+    check(gulon_index_view_size(h_, &length_));
+  }
+  IndexView(const IndexView &source, const std::vector<int32_t> &positions) : dimension_(source.dimension_) {
+    check(gulon_index_select_rows(source.h_, positions.data(), (int32_t)positions.size(), &h_));
+    check(gulon_index_view_size(h_, &length_));
+  }
+  IndexView &operator=(const IndexView &) = delete;
+  ~IndexView() { if (h_) gulon_index_destroy(h_); }
+  int dimension() const { return dimension_; }
+  int length() const { return length_; }
+  std::vector<int32_t> rows() const {
+    std::vector<int32_t> out((size_t)length_ + 1);
+    check(gulon_index_view_rows(h_, out.data()));
+    out.resize((size_t)length_);
+    return out;
+  }
+  std::vector<Result> batchQuery(int k, const std::vector<float> &queries, int from, int until) const {
+    const int b = dimension_ ? (int)(queries.size() / dimension_) : 0;
+    std::vector<int32_t> idx((size_t)b * k + 1), cnt(b + 1), flg(b + 1);
+    std::vector<float> dist((size_t)b * k + 1);
+    check(gulon_index_view_batch_query(h_, queries.data(), b, k, from, until, idx.data(), dist.data(), cnt.data(),
+                                       flg.data()));
+    std::vector<Result> out(b);
+    for (int q = 0; q < b; q++) {
+      out[q].rows.assign(idx.begin() + (size_t)q * k, idx.begin() + (size_t)q * k + cnt[q]);
+      out[q].distances.assign(dist.begin() + (size_t)q * k, dist.begin() + (size_t)q * k + cnt[q]);
+      out[q].flags = flg[q];
+    }
+    return out;
+  }
+  std::vector<Result> batchQuery(int k, const std::vector<float> &queries) const {
+    return batchQuery(k, queries, 0, length_);
+  }
+
+ private:
+  gulon_index *h_ = nullptr;
+  int dimension_;
+  int32_t length_ = 0;
 };
 
 // WordVectors.Grouped without the keys (WordVectors.scala:24-58,118-138): rows regrouped by coarse

@@ -422,6 +422,40 @@ int32_t gulon_grouped_index_query_rows_dev(gulon_grouped_index *idx, const int32
                                            float *d_out_dist, int32_t *d_out_count, void *stream);
 int32_t gulon_index_row_error(gulon_index *idx, int32_t *out);
 int32_t gulon_grouped_index_row_error(gulon_grouped_index *idx, int32_t *out);
+/* ---- Index views: a chosen subset of an index's rows as an index of its own ------------------------
+ * A view of `idx` over rows r_0 < r_1 < ... < r_{s-1} (local rows, 0 <= r_i < n) is the PQIndex over the EncodedMatrix
+ * whose columns are those rows in that order, gathered on the device from the codes already in HBM.  Through every
+ * other entry point a view is an ordinary gulon_index of s rows that answers in positions p (from / until are
+ * positions; its row_base is 0); the gulon_index_view_* queries answer in the row ids of `idx`: every returned p >= 0
+ * becomes idx.row_base + r_p, padding, distances, counts and flags pass through.  The map ascends strictly, so the
+ * (distance, row id) order and the tie flags mean the same before and after it.  A view of a view takes positions of
+ * the view and names rows of the root.  s = 0 is a valid view.  A view owns all it reads (codes gathered, codebooks
+ * copied device to device): `idx` may be destroyed first, and a context of a view hangs off the view.  Destroy a view
+ * with gulon_index_destroy.
+ * gulon_index_select_rows: `rows` (host) is checked before anything is launched -- strictly ascending, every row in
+ * [0, n), else GULON_ERR_INVALID_ARGUMENT naming the first offending position. */
+int32_t gulon_index_select_rows(gulon_index *idx, const int32_t *rows, int32_t s, gulon_index **out);
+/* The rows as a bit mask of ceil(n / 64) 64-bit words in device memory: bit (r & 63) of word (r >> 6) selects row r,
+ * bits at or above n are ignored.  Synchronises once to learn s. */
+int32_t gulon_index_select_mask_dev(gulon_index *idx, const uint64_t *d_mask, gulon_index **out);
+/* The same with the mask in host memory. */
+int32_t gulon_index_select_mask(gulon_index *idx, const uint64_t *mask, gulon_index **out);
+/* s, the rows (s entries, local rows of the root index) to the host, and the device array they live in (valid until
+ * the view is destroyed).  On a handle that is not a view: GULON_ERR_INVALID_ARGUMENT. */
+int32_t gulon_index_view_size(gulon_index *view, int32_t *s);
+int32_t gulon_index_view_rows(gulon_index *view, int32_t *rows_out);
+int32_t gulon_index_view_rows_dev(gulon_index *view, const int32_t **d_rows);
+/* gulon_index_batch_query_dev / gulon_index_batch_query on the view (from / until are positions), the returned
+ * positions translated to the root's row ids on the same stream. */
+int32_t gulon_index_view_batch_query_dev(gulon_index *view, const float *d_queries, int32_t b, int32_t k_nn,
+                                         int32_t from, int32_t until, int32_t *d_out_idx, float *d_out_dist,
+                                         int32_t *d_out_count, int32_t *d_out_flags, void *stream);
+int32_t gulon_index_view_batch_query(gulon_index *view, const float *queries, int32_t b, int32_t k_nn, int32_t from,
+                                     int32_t until, int32_t *out_idx, float *out_dist, int32_t *out_count,
+                                     int32_t *out_flags);
+/* The translation alone, in place, for the answers of the other entry points (query by row, partial scans): every
+ * d_idx[i] in [0, s) becomes the root's row id, anything else (-1 padding, INT32_MAX) stays. */
+int32_t gulon_index_view_map_rows_dev(gulon_index *view, int32_t *d_idx, int64_t count, void *stream);
 
 /* ---- Expression queries: stored rows composed on the device, operands dropped (compose.hip) ------------------------
  * An EXPRESSION is a non-empty list of terms (row, weight): LOCAL rows of the index (for a GroupedIndex: grouped row
