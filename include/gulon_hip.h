@@ -47,7 +47,14 @@ extern "C" {
 #define GULON_FLAG_BOUNDARY_TIE 1 /* K-th and (K+1)-th smallest distances are equal */
 #define GULON_FLAG_INTERIOR_TIE 2 /* two equal distances inside the top K */
 #define GULON_FLAG_EXACT_REPLAY 4 /* tie resolved by replaying the reference heap's insertion history:
-                                     ids and order are exactly TopKHeap's (single, unsharded index only) */
+                                     ids and order are exactly TopKHeap's (single, unsharded index only).
+                                     A tie-flagged query is left unreplayed -- tie flags without this one, ids in
+                                     (distance, row id) order -- when the replay collects more than 8 192 candidate
+                                     rows for it (2 048 in one shard of a sharded index), when the reference heap
+                                     makes more than 2 048 successful insertions over the range, or at
+                                     k_nn > GULON_MAX_K.  Which queries reach a candidate limit depends on the launch
+                                     geometry, which follows the handle's recent batches: the same query may be
+                                     replayed in one batch and not in another; both answers hold this contract. */
 
 #define GULON_FLAG_NONFINITE 8    /* the query's distances can be NaN / +inf (NaN or huge query components, NaN
                                      centroids): result = the literal TopKHeap over all rows, TopKHeap.scala:69-79 */
