@@ -261,7 +261,8 @@ int32_t gulon_index_destroy(gulon_index *idx);
  *    belongs to the handle.  Calls on one handle may come from any thread and any stream: the host side is
  *    serialised by a mutex, and the DEVICE work of a call on another stream than the previous call's is
  *    ordered behind it with an event -- two batches "in flight" on one handle run one after the other,
- *    never on top of each other's scratch.
+ *    never on top of each other's scratch.  Results do not depend on the handle's earlier calls, and
+ *    gulon_index_tuning on a live handle changes the work a call does, never its results.
  *  - gulon_index_context_create gives another workspace over the SAME read-only codes and codebooks (no
  *    copy): one context per batch in flight (bench.py: one per stream) overlaps their device work.  A
  *    context is destroyed with gulon_index_destroy; the codes live until the index and all of its contexts
