@@ -15,6 +15,7 @@ from .word_vectors import (DeviceWordVectors, GroupedWordVectors, KeyedIndex, Ke
 from .build import build_index
 from .word_index import WordIndex, WordResult
 from .refine import RefinedIndex, refine_topk
+from .inspect import IndexReport, reference_quality
 from .expressions import Expression, Term, compose_reference, parse_expression, partition_by_operands
 
 __all__ = ["native", "GroupedIndex", "GroupedVectors", "LimitGroups", "LimitVectors", "group", "Coder", "width_for_clusters", "Index", "PQIndex", "PQIndexView", "Result", "SortedIndex",
@@ -23,4 +24,4 @@ __all__ = ["native", "GroupedIndex", "GroupedVectors", "LimitGroups", "LimitVect
            "subvector_bounds", "subvectors", "GroupedWordVectors", "KeyedIndex", "KeyIndexGrouped", "KeyIndexSorted",
            "WordVectors", "read_word2vec", "WordIndex", "WordResult", "DeviceWordVectors", "read_word2vec_device",
            "build_index", "RefinedIndex", "refine_topk", "Expression", "Term", "compose_reference", "parse_expression",
-           "partition_by_operands"]
+           "partition_by_operands", "IndexReport", "reference_quality"]

@@ -17,6 +17,14 @@
                                        k = 1 ... 1000 over SIZE sampled vectors (tests_recall.Tests; the vectors are
                                        read, the exact neighbours found and the results evaluated on the device)
 
+  inspect -i INDEX [-v VECTORS [-w N]]
+                                       (not in the reference) the diagnostics of an index file (inspect.IndexReport): its
+                                       shape and, per quantizer, how many centroids are used, the largest share of one
+                                       centroid and the entropy of the codes; with -v -- the word2vec text file it was
+                                       built from -- also the mean and relative squared error of its rows against their
+                                       original vectors, the mean error per quantizer and the N (default 10) words with
+                                       the largest error.  Counted and summed on the device (csrc/inspect.hip)
+
 -v VECTORS on the query commands (not in the reference): the index's N candidates per query (-c, default 10 * k) are
 re-ranked by their exact distance to the original vectors of that word2vec text file, and the k nearest are printed
 (refine.RefinedIndex).  test -c N reports the recall of that refined index.  The recall harness asks ONE query per
@@ -108,6 +116,13 @@ class RecallConfig:
     candidates: Optional[int] = None      # -c: the recall of the index refined over this many candidates
 
 
+@dataclass(frozen=True)
+class InspectConfig:
+    index: str
+    vectors: Optional[str] = None         # -v: compare the index with the vectors it was built from
+    worst: int = 10                       # -w: words with the largest error to list
+
+
 def _sample_size(s):                                         # Test.scala:24-28
     if _integer(s) <= 0:
         raise argparse.ArgumentTypeError("must be greater than 0")
@@ -174,6 +189,14 @@ def _parser():
                    help="report the recall of the index refined against the vectors: num candidates per query re-ranked "
                         "by exact distance.  Each R@k is a prefix of ONE refined result per query, over "
                         "max(num, largest k) candidates, not a refined query at that k")
+    i = sub.add_parser("inspect", help="report code usage and quantization error of an index",
+                       description="report code usage and quantization error of an index")
+    i.add_argument("-i", "--index", required=True, metavar="file", help="path to ANN index")
+    i.add_argument("-v", "--vectors", default=None, metavar="file",
+                   help="word2vec word vectors the index was built from: report the error of the index's rows "
+                        "against these")
+    i.add_argument("-w", "--worst", type=_positive, default=None, metavar="num",
+                   help="words with the largest error to list (needs --vectors; default 10)")
     return p
 
 
@@ -274,6 +297,15 @@ def print_results(recall, write):
         write(f"R@{k}: {java_float_to_string(stats.mean)} +/- {java_float_to_string(stats.std_dev)}\n")
 
 
+def run_inspect(config: InspectConfig, load, vectors):
+    """inspect between its argument handling and its lines -> inspect.IndexReport.  For a cosine index the vectors are
+    read normalised: they are what the index's rows approximate."""
+    index = load(config.index)
+    if config.vectors is None:
+        return index.inspect()
+    return index.inspect(vectors(config.vectors, index.metric == "cosine"), config.worst)
+
+
 def read_originals(path, normalize):
     """The -v vectors of the query commands: on the device, in word order (their key index resolves the index's words)."""
     from .word_vectors import read_word2vec_device
@@ -299,14 +331,18 @@ def _refined(args, index, vectors):
     return index.refined(vectors(args.vectors, index.metric == "cosine"), candidates)
 
 
-def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None, vectors=None):
+def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None, vectors=None, inspect=None):
     """Returns the exit code.  stdin / stdout: binary streams (default: the process's); load: path -> index with
     batch_query_by_words / batch_query (default WordIndex.load); build: (BuildConfig, write) -> None, the whole of
     build-index behind its argument handling (default run_build_index); recall: (RecallConfig, write, load) ->
     {k: SummaryStats}, the whole of test between its argument handling and its result lines (default run_recall);
-    vectors: (path, normalize) -> the word vectors behind -v of the query commands (default read_originals)."""
+    vectors: (path, normalize) -> the word vectors behind -v of the query commands (default read_originals); inspect:
+    (InspectConfig, load, vectors) -> IndexReport, the whole of inspect between its argument handling and its lines
+    (default run_inspect)."""
     parser = _parser()
     args = parser.parse_args(argv)
+    if args.command == "inspect" and args.worst is not None and args.vectors is None:
+        parser.error("--worst is only applicable with --vectors")
     if args.command in ("query", "query-words") and args.candidates is not None and args.vectors is None:
         parser.error("--candidates is only applicable with --vectors")
     if args.command in ("query", "query-words") and args.restrict is not None:
@@ -333,6 +369,10 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
     elif args.command == "test":
         config = RecallConfig(args.vectors, args.index, args.sample, args.error, args.candidates)
         print_results((recall if recall is not None else run_recall)(config, log, load), write)
+    elif args.command == "inspect":
+        config = InspectConfig(args.index, args.vectors, args.worst if args.worst is not None else 10)
+        for line in (inspect if inspect is not None else run_inspect)(config, load, vectors).lines():
+            write(line + "\n")
     elif args.command == "query-words":
         index = _refined(args, load(args.index), vectors)
         if args.file is None:

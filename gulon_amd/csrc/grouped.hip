@@ -1298,7 +1298,7 @@ GULON_API int32_t gulon_grouped_index_query_rows(gulon_grouped_index *idx, const
 
 namespace gulon {
 GroupedParts grouped_parts(gulon_grouped_index *idx) {
-  return {idx->pq, idx->gcent.p, idx->bounds.p + 1, idx->g - 1, &idx->mu};
+  return {idx->pq, idx->gcent.p, idx->bounds.p + 1, idx->g - 1, &idx->mu, idx->bounds.p, idx->g};
 }
 }  // namespace gulon
 

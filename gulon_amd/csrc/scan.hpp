@@ -300,7 +300,11 @@ void decode_rows_host(const gulon_index *ix, DevBuf<int> &rows_buf, DevBuf<float
 void ensure_row_err(gulon_index *ix);   // the handle's row_err word, allocated and zeroed on first use
 int take_row_err(gulon_index *ix);      // synchronises; returns and clears it
 // grouped.hip: what compose.hip needs of a GroupedIndex handle (the struct is private to grouped.hip) -- the residual
-// index, the group centroids, the raw offsets GroupedIndex.lookup searches, and the handle's mutex
-struct GroupedParts { gulon_index *pq; const float *gcent; const int *offsets; int n_offsets; std::mutex *mu; };
+// index, the group centroids, the raw offsets GroupedIndex.lookup searches, and the handle's mutex; for inspect.hip the
+// groups' row ranges: group c holds rows [bounds[c], bounds[c + 1]), c < g
+struct GroupedParts {
+  gulon_index *pq; const float *gcent; const int *offsets; int n_offsets; std::mutex *mu;
+  const int *bounds; int g;
+};
 GroupedParts grouped_parts(gulon_grouped_index *idx);
 }  // namespace gulon

@@ -150,6 +150,21 @@ class GroupedIndex:
     def lookup_row(self, row):
         return self.lookup_rows([row])[0]
 
+    def code_histogram(self, from_=0, until=None):
+        """H[j][c] = the number of rows in [from_, until) whose residual code at quantizer j is c, counted on the
+        device (gulon_grouped_index_code_histogram).  -> int64 [m][k]."""
+        from .inspect import code_histogram_raw
+        return code_histogram_raw(N.lib().gulon_grouped_index_code_histogram, self._h, len(self.quantizer.quantizers),
+                                  self.quantizer.num_clusters, self.size, from_, until)
+
+    def row_errors(self, matrix, row_map=None, from_=0, until=None, norms=False):
+        """As PQIndex.row_errors, against the vector a query compares with: the centroid of the row's OWN group
+        (cluster_of: the group whose row range holds it, which is where a query scans it) + decode(row).  Where
+        offsets repeat this is not always the group lookup_rows adds (the reference's binarySearch rule)."""
+        from .inspect import row_errors_raw
+        return row_errors_raw(N.lib().gulon_grouped_index_row_errors, self._h, len(self.quantizer.quantizers),
+                              self.size, matrix, row_map, from_, until, norms)
+
     def batch_query_rows_raw(self, k, rows):
         r = N.i32(rows).reshape(-1)
         b = r.size

@@ -150,6 +150,23 @@ class PQIndex:
         N.check(N.lib().gulon_index_decode_dataset(self._h, frm, until, C.byref(h)))
         return DeviceMatrix(h, until - frm, self.dimension)
 
+    def code_histogram(self, from_=0, until=None):
+        """H[j][c] = the number of rows in [from_, until) whose code at quantizer j is c, counted on the device
+        (gulon_index_code_histogram).  -> int64 [m][k]."""
+        from .inspect import code_histogram_raw
+        pq = self.product_quantizer
+        return code_histogram_raw(N.lib().gulon_index_code_histogram, self._h, len(pq.quantizers), pq.num_clusters,
+                                  self.length, from_, until)
+
+    def row_errors(self, matrix, row_map=None, from_=0, until=None, norms=False):
+        """MathUtils.distanceSq(matrix[row_map[r]], decode(r)) for every row r in [from_, until), on the device
+        (gulon_index_row_errors); row_map None: the identity.  -> (row_error [until - from_] float32,
+        quantizer_error [m] float64: the same sum restricted to each quantizer's coordinates, added over the rows)
+        and, norms=True, row_norm_sq [until - from_]: the squared norms of the originals."""
+        from .inspect import row_errors_raw
+        return row_errors_raw(N.lib().gulon_index_row_errors, self._h, len(self.product_quantizer.quantizers),
+                              self.length, matrix, row_map, from_, until, norms)
+
     def batch_query_rows_raw(self, k, rows, frm=0, until=None, normalize=False):
         r = N.i32(rows).reshape(-1)
         until = self.length if until is None else until
@@ -404,6 +421,12 @@ class SortedIndex:
         """Index.queryByWord (Index.scala:38-45) on row ids: query(k, lookup(row)) for every row, decoded (and for a
         cosine index normalised, Index.scala:324-331) on the device."""
         return self.vector_index.batch_query_rows(k, rows, normalize=self.metric == "cosine")
+
+    def code_histogram(self, from_=0, until=None):
+        return self.vector_index.code_histogram(from_, until)
+
+    def row_errors(self, matrix, row_map=None, from_=0, until=None, norms=False):
+        return self.vector_index.row_errors(matrix, row_map, from_, until, norms)
 
     def select(self, rows=None, mask=None):
         """A SortedIndex over the view of the selected rows (PQIndex.select), same metric: its results name rows of

@@ -50,6 +50,7 @@ class KMeansTraceTotals(C.Structure):
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
 _i64p = np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")
+_f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
 _u64p = np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS")
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 _vp = C.c_void_p
@@ -164,6 +165,12 @@ SIGNATURES = {
     "gulon_recall_counts": (_i32, [_vp, _f32p, _i32, _i32p, _i32, _i32p, _i32, _f32p, _i32p, _vp]),
     "gulon_refine_topk": (_i32, [_vp, _f32p, _i32, _i32p, _i32, _vp, _i32, _i32, _i32p, _f32p, _i32p]),
     "gulon_refine_topk_dev": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "gulon_index_code_histogram": (_i32, [_vp, _i32, _i32, _i64p]),
+    "gulon_grouped_index_code_histogram": (_i32, [_vp, _i32, _i32, _i64p]),
+    "gulon_index_row_errors": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _f64p]),
+    "gulon_index_row_errors_dev": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _f64p, _vp]),
+    "gulon_grouped_index_row_errors": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _f64p]),
+    "gulon_grouped_index_row_errors_dev": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _f64p, _vp]),
 }
 
 _lib = None

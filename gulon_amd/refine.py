@@ -62,6 +62,24 @@ class _DeviceArray:
         self.ptr, self.bytes = C.c_void_p(), 0
 
 
+def word_row_map(word_index, vectors):
+    """index row -> the row of `vectors` (DeviceWordVectors with a key index) that holds the same word: int32, one
+    entry per index row (one spare entry for an index without rows).  The vectors must have the index's dimension and
+    hold every word of the index."""
+    if vectors.dimension != word_index.dimension:
+        raise ValueError(f"vectors of dimension {vectors.dimension} for an index of dimension {word_index.dimension}")
+    if vectors.key_index is None:
+        raise ValueError("the word vectors need a key index (DeviceWordVectors.sorted())")
+    lookup = vectors.key_index.lookup
+    row_map = np.zeros(max(word_index.size, 1), np.int32)
+    for r, word in enumerate(word_index.words):
+        v = lookup(word)
+        if v is None:
+            raise LookupError(f"the index holds the word {word!r}, the word vectors do not")
+        row_map[r] = v
+    return row_map
+
+
 class RefinedIndex:
     """A WordIndex whose results are re-ranked against `vectors` (DeviceWordVectors with a key index, e.g.
     read_word2vec_device(...).sorted()): the query surface of WordIndex, each call taking `candidates` index results
@@ -72,17 +90,7 @@ class RefinedIndex:
         self.word_index, self.vectors, self.candidates = word_index, vectors, int(candidates)
         if self.candidates < 1:
             raise ValueError("candidates must be at least 1")
-        if vectors.dimension != word_index.dimension:
-            raise ValueError(f"vectors of dimension {vectors.dimension} for an index of dimension {word_index.dimension}")
-        if vectors.key_index is None:
-            raise ValueError("the word vectors need a key index (DeviceWordVectors.sorted())")
-        lookup = vectors.key_index.lookup
-        row_map = np.zeros(max(word_index.size, 1), np.int32)
-        for r, word in enumerate(word_index.words):
-            v = lookup(word)
-            if v is None:
-                raise LookupError(f"the index holds the word {word!r}, the word vectors do not")
-            row_map[r] = v
+        row_map = word_row_map(word_index, vectors)
         self._map, self._work = _DeviceArray(), [_DeviceArray() for _ in range(5)]
         self._map.upload(row_map)
 

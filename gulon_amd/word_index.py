@@ -69,6 +69,14 @@ class WordIndex:
         from .refine import RefinedIndex
         return RefinedIndex(self, vectors, candidates)
 
+    def inspect(self, vectors=None, worst=10):
+        """The diagnostics of this index (inspect.IndexReport): its shape and how its code books are used; with
+        `vectors` (DeviceWordVectors with a key index; the normalised reading for a cosine index), matched to the
+        index's words as `refined` matches them, also how far its rows lie from their originals and the `worst` words
+        with the largest error."""
+        from .inspect import inspect_word_index
+        return inspect_word_index(self, vectors, worst)
+
     def restrict(self, words):
         """This index with its neighbours drawn from `words` only (PQIndex.select: a view gathered on the device, built
         once for any number of queries).  Words the index lacks are ignored -- their number is `.ignored` -- and
@@ -207,6 +215,9 @@ class RestrictedWordIndex(WordIndex):
 
     def refined(self, vectors, candidates):
         raise NotImplementedError("refined is not supported by a restricted index")
+
+    def inspect(self, vectors=None, worst=10):
+        raise NotImplementedError("inspect is not supported by a restricted index")
 
     def resolve_expressions(self, expressions):
         raise NotImplementedError("expressions are not supported by a restricted index")

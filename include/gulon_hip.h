@@ -606,6 +606,48 @@ int32_t gulon_refine_topk_dev(const gulon_dataset *ds, const float *d_queries, i
                               int32_t k_nn, int32_t *d_out_idx, float *d_out_dist, int32_t *d_out_count,
                               void *stream);
 
+/* ---- Index diagnostics (inspect.hip; DESIGN.md "Index diagnostics") -------------------------------------------------
+ * Two computations over a device-resident index: how its code books are used, and how far its rows lie from the
+ * vectors they were built from.  Rows are LOCAL rows of the index (for a GroupedIndex: grouped row positions; for a
+ * view: its own positions), 0 <= from <= until <= n, else GULON_ERR_INVALID_ARGUMENT.  Both use scratch of their own
+ * and leave no trace on the handle.
+ *
+ * gulon_*_code_histogram: out[j * k + c] (host, m * k entries) = the number of rows in [from, until) whose code at
+ * quantizer j is c.  Integer arithmetic: exact; every quantizer's k counts sum to until - from. */
+int32_t gulon_index_code_histogram(gulon_index *idx, int32_t from, int32_t until, int64_t *out);
+int32_t gulon_grouped_index_code_histogram(gulon_grouped_index *idx, int32_t from, int32_t until, int64_t *out);
+/* gulon_*_row_errors: for every row r in [from, until), with x = vectors[row_map ? row_map[r] : r] and y = the vector
+ * the index's distances are about --
+ *   flat index:    ProductQuantizer.decode of row r (ProductQuantizer.scala:37-50);
+ *   grouped index: centroid(c) + decode(r), one fp32 add per coordinate (MathUtils.add, MathUtils.scala:63-71), c = the
+ *                  group whose row range holds r, i.e. the group a query scans the row in.  This is NOT the partition
+ *                  of gulon_grouped_index_lookup_rows: where offsets repeat (empty groups) the reference's binarySearch
+ *                  rule can name another group --
+ *   row_error[r - from]   = MathUtils.distanceSq(x, y) (MathUtils.scala:85-95): binary32, t = x_e - y_e; sum += t * t,
+ *                           unfused, e ascending, one running sum -- the summand of ProductQuantizerSpec.quality
+ *                           (ProductQuantizerSpec.scala:70-73);
+ *   row_norm_sq[r - from] = the same sum with y = 0 (nullable);
+ *   quantizer_error[j]    = the sum over those rows, in binary64, of the same binary32 sum restarted at 0 over the
+ *                           coordinates of quantizer j only (gulon_subvectors); [m], host memory in both forms.
+ * vectors->d must equal the index's; row_map (NULL: the identity, which needs vectors->n >= n) has map_len = n entries;
+ * an entry of [from, until) outside [0, vectors->n) is GULON_ERR_INVALID_ARGUMENT, found on the device (nothing is read
+ * for that row; the outputs are then undefined).  One 64-row block's codes must fit in LDS, as for
+ * gulon_index_decode_dataset.  Device form: row_map and the per-row outputs are device pointers, the work is enqueued on
+ * `stream` (hipStream_t), which is synchronised before the call returns (quantizer_error and the status come back). */
+int32_t gulon_index_row_errors(gulon_index *idx, const gulon_dataset *vectors, const int32_t *row_map, int32_t map_len,
+                               int32_t from, int32_t until, float *row_error, float *row_norm_sq,
+                               double *quantizer_error);
+int32_t gulon_index_row_errors_dev(gulon_index *idx, const gulon_dataset *vectors, const int32_t *d_row_map,
+                                   int32_t map_len, int32_t from, int32_t until, float *d_row_error,
+                                   float *d_row_norm_sq, double *quantizer_error, void *stream);
+int32_t gulon_grouped_index_row_errors(gulon_grouped_index *idx, const gulon_dataset *vectors, const int32_t *row_map,
+                                       int32_t map_len, int32_t from, int32_t until, float *row_error,
+                                       float *row_norm_sq, double *quantizer_error);
+int32_t gulon_grouped_index_row_errors_dev(gulon_grouped_index *idx, const gulon_dataset *vectors,
+                                           const int32_t *d_row_map, int32_t map_len, int32_t from, int32_t until,
+                                           float *d_row_error, float *d_row_norm_sq, double *quantizer_error,
+                                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif
