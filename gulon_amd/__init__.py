@@ -2,7 +2,7 @@
 Index / ProductQuantizer / KMeans API (host mirror over libgulon_hip.so)."""
 from . import native
 from .coder import Coder, width_for_clusters
-from .index import Index, PQIndex, PQIndexView, Result, SortedIndex, exact_nearest_neighbours, prepare_query, tune_live
+from .index import DevicePQIndex, Index, PQIndex, PQIndexView, Result, SortedIndex, exact_nearest_neighbours, prepare_query, tune_live
 from .grouped import GroupedIndex, GroupedVectors, LimitGroups, LimitVectors, group
 from .kmeans import KMeans
 from .kmeans import Config as KMeansConfig
@@ -16,12 +16,13 @@ from .build import build_index
 from .word_index import WordIndex, WordResult
 from .refine import RefinedIndex, refine_topk
 from .inspect import IndexReport, reference_quality
+from .update import UpdatePlan, plan_update
 from .expressions import Expression, Term, compose_reference, parse_expression, partition_by_operands
 
-__all__ = ["native", "GroupedIndex", "GroupedVectors", "LimitGroups", "LimitVectors", "group", "Coder", "width_for_clusters", "Index", "PQIndex", "PQIndexView", "Result", "SortedIndex",
+__all__ = ["native", "GroupedIndex", "GroupedVectors", "LimitGroups", "LimitVectors", "group", "Coder", "width_for_clusters", "Index", "PQIndex", "PQIndexView", "DevicePQIndex", "Result", "SortedIndex",
            "exact_nearest_neighbours", "prepare_query", "tune_live", "KMeans", "KMeansConfig", "DeviceMatrix", "Matrix",
            "EncodedMatrix", "ProductQuantizer", "Quantizer", "ProductQuantizerConfig", "Vectors",
            "subvector_bounds", "subvectors", "GroupedWordVectors", "KeyedIndex", "KeyIndexGrouped", "KeyIndexSorted",
            "WordVectors", "read_word2vec", "WordIndex", "WordResult", "DeviceWordVectors", "read_word2vec_device",
            "build_index", "RefinedIndex", "refine_topk", "Expression", "Term", "compose_reference", "parse_expression",
-           "partition_by_operands", "IndexReport", "reference_quality"]
+           "partition_by_operands", "IndexReport", "reference_quality", "UpdatePlan", "plan_update"]

@@ -1,4 +1,4 @@
-"""`python -m gulon_amd`: the reference's four commands (command/Main.scala:7-11).
+"""`python -m gulon_amd`: the reference's four commands (command/Main.scala:7-11), `inspect` and `update`.
 
   build-index -d l2|cosine -o INDEX [-k N] [-m N] [-n N] [-p [--partitions N] [-l N]] FILE
                                        command/BuildIndex.scala: a word2vec text file -> an index file; the text is
@@ -24,6 +24,14 @@
                                        built from -- also the mean and relative squared error of its rows against their
                                        original vectors, the mean error per quantizer and the N (default 10) words with
                                        the largest error.  Counted and summed on the device (csrc/inspect.hip)
+
+  update -i INDEX -o OUTPUT [-a VECTORS] [-x WORDS]
+                                       (not in the reference) add, replace and remove words of an index file without
+                                       retraining (update.py, csrc/update.hip): the words of WORDS (one per line) are
+                                       removed first, then every word of the word2vec text file VECTORS is added, or
+                                       replaced if the index still has it -- encoded by the index's own code books on the
+                                       device, read normalised for a cosine index.  Kept words keep their codes.  Not for
+                                       a partitioned (grouped) index
 
 -v VECTORS on the query commands (not in the reference): the index's N candidates per query (-c, default 10 * k) are
 re-ranked by their exact distance to the original vectors of that word2vec text file, and the k nearest are printed
@@ -123,6 +131,14 @@ class InspectConfig:
     worst: int = 10                       # -w: words with the largest error to list
 
 
+@dataclass(frozen=True)
+class UpdateConfig:
+    index: str
+    output: str
+    add: Optional[str] = None             # -a: word2vec text of the words to add or replace
+    remove: Optional[str] = None          # -x: one word per line to remove
+
+
 def _sample_size(s):                                         # Test.scala:24-28
     if _integer(s) <= 0:
         raise argparse.ArgumentTypeError("must be greater than 0")
@@ -197,6 +213,14 @@ def _parser():
                         "against these")
     i.add_argument("-w", "--worst", type=_positive, default=None, metavar="num",
                    help="words with the largest error to list (needs --vectors; default 10)")
+    u = sub.add_parser("update", help="add, replace and remove words of an index without retraining",
+                       description="add, replace and remove words of an index without retraining")
+    u.add_argument("-i", "--index", required=True, metavar="file", help="path to ANN index")
+    u.add_argument("-o", "--output", required=True, metavar="file", help="index output file")
+    u.add_argument("-a", "--add", default=None, metavar="file",
+                   help="word2vec word vectors to add; a word the index already has is replaced")
+    u.add_argument("-x", "--remove", default=None, metavar="file",
+                   help="words to remove, one per line (words the index lacks are ignored and counted)")
     return p
 
 
@@ -306,6 +330,41 @@ def run_inspect(config: InspectConfig, load, vectors):
     return index.inspect(vectors(config.vectors, index.metric == "cosine"), config.worst)
 
 
+class UpdateError(Exception):
+    """What `update` reports and exits on: a grouped index file, vectors of another dimension, a word listed twice."""
+
+
+def run_update(config: UpdateConfig, write, load):
+    """update behind its argument handling: load, read (normalised for a cosine index), WordIndex.update, write.
+    -> the updated WordIndex."""
+    from .build import log_task
+    from .index_file import dump_index
+    from .word_vectors import read_word2vec_device
+    index = log_task(write, f"Reading index from {config.index}", lambda: load(config.index),
+                     lambda i: f"Read index of {i.size} words")
+    add = remove = None
+    if config.add is not None:
+        add = log_task(write, "Reading word vectors",
+                       lambda: read_word2vec_device(config.add, normalize=index.metric == "cosine"),
+                       lambda v: f"Read {v.size} word vectors")
+    if config.remove is not None:
+        with open(config.remove, "rb") as fh:
+            remove = read_lines(fh.read())
+    try:
+        updated = log_task(write, "Updating index", lambda: index.update(add=add, remove=remove),
+                           lambda i: f"Updated index to {i.size} words")
+    except NotImplementedError as e:
+        raise UpdateError(f"{config.index}: {e}")
+    except ValueError as e:
+        raise UpdateError(str(e))
+
+    def dump():
+        with open(config.output, "wb") as fh:
+            fh.write(dump_index(updated.index, updated.words))
+    log_task(write, f"Writing index to {config.output}", dump, f"Wrote index to {config.output}")
+    return updated
+
+
 def read_originals(path, normalize):
     """The -v vectors of the query commands: on the device, in word order (their key index resolves the index's words)."""
     from .word_vectors import read_word2vec_device
@@ -331,16 +390,20 @@ def _refined(args, index, vectors):
     return index.refined(vectors(args.vectors, index.metric == "cosine"), candidates)
 
 
-def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None, vectors=None, inspect=None):
+def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None, vectors=None, inspect=None,
+         update=None):
     """Returns the exit code.  stdin / stdout: binary streams (default: the process's); load: path -> index with
     batch_query_by_words / batch_query (default WordIndex.load); build: (BuildConfig, write) -> None, the whole of
     build-index behind its argument handling (default run_build_index); recall: (RecallConfig, write, load) ->
     {k: SummaryStats}, the whole of test between its argument handling and its result lines (default run_recall);
     vectors: (path, normalize) -> the word vectors behind -v of the query commands (default read_originals); inspect:
     (InspectConfig, load, vectors) -> IndexReport, the whole of inspect between its argument handling and its lines
-    (default run_inspect)."""
+    (default run_inspect); update: (UpdateConfig, write, load) -> the updated index with its four counters, the whole
+    of update behind its argument handling (default run_update)."""
     parser = _parser()
     args = parser.parse_args(argv)
+    if args.command == "update" and args.add is None and args.remove is None:
+        parser.error("at least one of --add and --remove is required")
     if args.command == "inspect" and args.worst is not None and args.vectors is None:
         parser.error("--worst is only applicable with --vectors")
     if args.command in ("query", "query-words") and args.candidates is not None and args.vectors is None:
@@ -373,6 +436,15 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
         config = InspectConfig(args.index, args.vectors, args.worst if args.worst is not None else 10)
         for line in (inspect if inspect is not None else run_inspect)(config, load, vectors).lines():
             write(line + "\n")
+    elif args.command == "update":
+        config = UpdateConfig(args.index, args.output, args.add, args.remove)
+        try:
+            u = (update if update is not None else run_update)(config, log, load)
+        except UpdateError as e:
+            stdout.flush()
+            print(f"error: {e}", file=sys.stderr)
+            return 1
+        write(f"{u.added} added, {u.replaced} replaced, {u.removed} removed, {u.ignored} ignored\n")
     elif args.command == "query-words":
         index = _refined(args, load(args.index), vectors)
         if args.file is None:

@@ -1779,6 +1779,18 @@ GULON_API int32_t gulon_pq_encode_range(const gulon_dataset *ds, int32_t m, int3
   return guarded([&] { pq_encode_range(ds, m, k, cents, j_begin, j_end, codes_out); });
 }
 
+namespace gulon {
+// One quantizer of ProductQuantizer.encode (ProductQuantizer.scala:25-35): the serial KMeans.assign of every row's slice
+// [from, from + s) against dC [k][s], its Random(0) stream over the rows in order, into d_assign [n].
+void pq_assign_quantizer(KmeansWorkspace &ws, PackedSlice &packed, const float *dX, int n, int ld, int from, int s,
+                         const float *dC, int k, int *d_assign) {
+  HIP_CHECK(hipMemset(d_assign, 0, sizeof(int) * (size_t)n));
+  const bool mf = mfma_assign_supported(s, k);
+  if (mf) pack_slice(dX, n, ld, from, s, k, packed, nullptr);
+  kmeans_assign_dev(ws, dX, n, ld, from, s, dC, k, 0, d_assign, nullptr, mf ? &packed : nullptr);   // serial assign
+}
+}  // namespace gulon
+
 static void pq_encode_range(const gulon_dataset *ds, int m, int k, const float *cents, int j_begin, int j_end,
                             uint8_t *codes_out) {
   {
@@ -1802,10 +1814,7 @@ static void pq_encode_range(const gulon_dataset *ds, int m, int k, const float *
     for (int j = j_begin; j < j_end; j++) {
       const int s = until[j] - from[j];
       dc.upload(cents + (size_t)k * from[j], (size_t)k * s);
-      HIP_CHECK(hipMemset(da.p, 0, sizeof(int) * (size_t)n));
-      const bool mf = mfma_assign_supported(s, k);
-      if (mf) pack_slice(ds->x.p, n, ds->d, from[j], s, k, packed, nullptr);
-      kmeans_assign_dev(ws, ds->x.p, n, ds->d, from[j], s, dc.p, k, 0, da.p, nullptr, mf ? &packed : nullptr);   // serial assign
+      pq_assign_quantizer(ws, packed, ds->x.p, n, ds->d, from[j], s, dc.p, k, da.p);
       uint8_t *out = codes_out + (size_t)(j - j_begin) * bytes;
       if (width == 8) {                                                                   // Coder8: idx.toByte
         hipLaunchKernelGGL(narrow_assign_u8, dim3(ceil_div(n, 256)), dim3(256), 0, 0, da.p, (long long)n, d8.p);

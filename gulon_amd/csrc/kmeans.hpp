@@ -107,6 +107,10 @@ void assign_stage3(AssignJob &j);
 // exact re-check of the flagged rows; without it every row takes the exact VALU kernel.
 void kmeans_assign_dev(KmeansWorkspace &ws, const float *dX, int n, int ld, int from, int s, const float *dC, int k,
                        int rng_batch, int *d_assign, hipStream_t st, const PackedSlice *ps = nullptr);
+// kmeans.hip: one quantizer of ProductQuantizer.encode -- d_assign zeroed, the slice packed where the MFMA filter takes
+// it, then the serial kmeans_assign_dev (gulon_pq_encode* and gulon_index_encode_dataset share it)
+void pq_assign_quantizer(KmeansWorkspace &ws, PackedSlice &packed, const float *dX, int n, int ld, int from, int s,
+                         const float *dC, int k, int *d_assign);
 #ifdef __HIPCC__
 // RN(1 / n) for an integer n < 2^24 whose significand is not all ones: the hardware reciprocal (1 ulp) and one
 // fma-corrected Newton step (Markstein).  Checked against 1.0f / n for EVERY such n by gulon_selftest_mean_division.

@@ -4,6 +4,10 @@
 // that order: its code buffers are gathered from P's, it owns a copy of the codebooks, and it keeps the map p -> r_p so
 // that the view-query entries can answer in P's row ids.  No scan kernel knows about views.
 //
+// A view gathers from one parent, in ascending order.  update.hip has the rest: gulon_index_merge gathers from two
+// sources in any order into a root index, gulon_index_encode_dataset fills a code buffer from new vectors, and
+// gulon_index_get_codes is the accessor for an index's plain code buffer (a view's included).
+//
 // Kernels
 //   mask_to_rows_count    bit mask -> per word the prefix of its popcount inside its 64-word group, per group the sum
 //   mask_to_rows_groups   exclusive scan over the group sums (one workgroup), and the total s

@@ -262,6 +262,43 @@ class PQIndex:
             N.check(N.lib().gulon_index_select_mask(self._h, pack_mask(mask, self.length), C.byref(h)))
         return PQIndexView(self, h)
 
+    def indices(self, frm=0, until=None):
+        """EncodedMatrix.indices of rows [frm, until) read back from the device (gulon_index_get_codes): the centroid
+        ids of the index's plain code buffer, un-blocked in HBM and copied down once.  -> int32 [m][until - frm].  A
+        view answers in its own positions."""
+        until = self.length if until is None else until
+        m = len(self.product_quantizer.quantizers)
+        out = np.zeros(max(m * max(until - frm, 0), 1), np.uint16)
+        N.check(N.lib().gulon_index_get_codes(self._h, frm, until, out))
+        return out[:m * (until - frm)].reshape(m, until - frm).astype(np.int32)
+
+    def encode(self, matrix):
+        """PQIndex(pq, pq.encode(matrix)) with pq the quantizer this index holds in HBM (gulon_index_encode_dataset):
+        the rows of `matrix` (a DeviceMatrix is used where it lies) encoded in their order -- that order fixes the
+        tie-break stream -- and written straight into a new index on the device.  -> a root index of matrix.rows rows."""
+        dm = as_device(matrix)
+        if dm.cols != self.dimension:
+            raise ValueError(f"requirement failed: the vectors have {dm.cols} dimensions, the index {self.dimension}")
+        h = C.c_void_p()
+        N.check(N.lib().gulon_index_encode_dataset(self._h, dm._h, C.byref(h)))
+        return DevicePQIndex(self.product_quantizer, h, dm.rows)
+
+    def merged(self, other, take):
+        """A new root index of len(take) rows gathered on the device (gulon_index_merge): row p carries the code of this
+        index's row take[p] when take[p] >= 0, of `other`'s row -1 - take[p] otherwise; any order, repeats allowed.
+        `other` (None: every entry is >= 0) must have this index's shape and bitwise equal code books."""
+        t = np.asarray(take).reshape(-1)
+        if t.size and not np.issubdtype(t.dtype, np.integer):
+            raise ValueError("take must be integers")
+        if t.size and (t.min() < -2 ** 31 or t.max() >= 2 ** 31):
+            bad = int(np.flatnonzero((t < -2 ** 31) | (t >= 2 ** 31))[0])
+            raise ValueError(f"requirement failed: take[{bad}] = {int(t[bad])} outside the int32 range")
+        t = N.i32(t)
+        h = C.c_void_p()
+        N.check(N.lib().gulon_index_merge(self._h, other._h if other is not None else None,
+                                          t if t.size else np.zeros(1, np.int32), t.size, C.byref(h)))
+        return DevicePQIndex(self.product_quantizer, h, t.size)
+
     def close(self):
         if self._h is not None and self._h.value:
             N.lib().gulon_index_destroy(self._h)
@@ -272,6 +309,35 @@ class PQIndex:
             self.close()
         except Exception:
             pass
+
+
+class DevicePQIndex(PQIndex):
+    """An index made on the device (PQIndex.encode / PQIndex.merged): an ordinary root index whose codes exist in HBM
+    only.  `data`, its EncodedMatrix, is read back through `indices` the first time it is asked for (dump_index)."""
+
+    def __init__(self, product_quantizer, handle, length, _state=None):
+        self.product_quantizer = product_quantizer
+        self.row_base = 0
+        self._h = handle
+        self._length = length
+        self._state = _state if _state is not None else {"data": None}      # shared with the contexts
+        _LIVE.add(self)
+
+    @property
+    def length(self):
+        return self._length
+
+    @property
+    def data(self):
+        if self._state["data"] is None:
+            coder = self.product_quantizer.coder_factory(self._length)
+            self._state["data"] = EncodedMatrix(coder, [coder.build_code(ix) for ix in self.indices()])
+        return self._state["data"]
+
+    def context(self):
+        h = C.c_void_p()
+        N.check(N.lib().gulon_index_context_create(self._h, C.byref(h)))
+        return DevicePQIndex(self.product_quantizer, h, self._length, _state=self._state)
 
 
 def pack_mask(mask, n):
@@ -432,6 +498,17 @@ class SortedIndex:
         """A SortedIndex over the view of the selected rows (PQIndex.select), same metric: its results name rows of
         this index."""
         return SortedIndex(self.vector_index.select(rows, mask), self.metric)
+
+    def updated(self, take, added=None):
+        """A SortedIndex over take's rows (PQIndex.merged), same metric: take[p] >= 0 keeps this index's row take[p] with
+        its code, take[p] < 0 is row -1 - take[p] of `added` -- a matrix encoded in its row order by this index's own
+        quantizer (PQIndex.encode; for a cosine index the rows are normalised already).  This index is untouched."""
+        new = self.vector_index.encode(added) if added is not None else None
+        try:
+            return SortedIndex(self.vector_index.merged(new, take), self.metric)
+        finally:
+            if new is not None:
+                new.close()
 
     def compose_rows(self, expressions):
         """The query vector of every expression over row ids as this index prepares it: terms and sum normalised for a

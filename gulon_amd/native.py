@@ -53,6 +53,7 @@ _i64p = np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")
 _f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
 _u64p = np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS")
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
+_u16p = np.ctypeslib.ndpointer(np.uint16, flags="C_CONTIGUOUS")
 _vp = C.c_void_p
 _i32 = C.c_int32
 
@@ -140,6 +141,9 @@ SIGNATURES = {
     "gulon_index_view_batch_query": (_i32, [_vp, _f32p, _i32, _i32, _i32, _i32, _i32p, _f32p, _i32p, _i32p]),
     "gulon_index_view_batch_query_dev": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gulon_index_view_map_rows_dev": (_i32, [_vp, _vp, C.c_int64, _vp]),
+    "gulon_index_encode_dataset": (_i32, [_vp, _vp, C.POINTER(_vp)]),
+    "gulon_index_merge": (_i32, [_vp, _vp, _i32p, _i32, C.POINTER(_vp)]),
+    "gulon_index_get_codes": (_i32, [_vp, _i32, _i32, _u16p]),
     "gulon_index_compose_rows": (_i32, [_vp, _i32p, _i32p, _f32p, _i32, _i32, _i32, _f32p]),
     "gulon_index_compose_rows_dev": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "gulon_grouped_index_compose_rows": (_i32, [_vp, _i32p, _i32p, _f32p, _i32, _i32, _i32, _f32p]),

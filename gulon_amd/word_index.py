@@ -86,6 +86,25 @@ class WordIndex:
             raise NotImplementedError("restrict is not supported by the grouped index")
         return RestrictedWordIndex(self, words)
 
+    def update(self, add=None, remove=None):
+        """A new WordIndex with words removed, replaced and added, built on the device without retraining (update.py,
+        csrc/update.hip); this index is untouched.  remove: an iterable of words, applied first -- words the index lacks
+        are ignored.  add: DeviceWordVectors as read (for a cosine index the normalised reading, which is what
+        build-index feeds); a word the index still has is replaced, any other added, each encoded by this index's own
+        quantizer in the order `add` gives them.  A kept word keeps its code.  The result's words are in String.compareTo
+        order; it carries the counters .added, .replaced, .removed, .ignored.  A word twice in `add`: ValueError."""
+        from .update import plan_update
+        if self._grouped:
+            raise NotImplementedError("update is not supported by the grouped index")
+        add_words = list(add.words) if add is not None else []
+        if add_words and add.dimension != self.dimension:
+            raise ValueError(f"requirement failed: the added vectors have {add.dimension} dimensions, the index "
+                             f"{self.dimension}")
+        plan = plan_update(self.words, add_words, remove if remove is not None else ())
+        out = WordIndex(plan.words, self.index.updated(plan.take, add.matrix if add_words else None))
+        out.added, out.replaced, out.removed, out.ignored = plan.added, plan.replaced, plan.removed, plan.ignored
+        return out
+
     def row_of(self, word) -> Optional[int]:
         return self.key_index.lookup(word)
 
@@ -212,6 +231,9 @@ class RestrictedWordIndex(WordIndex):
         out = self.parent.restrict([w for w, r in zip(words, rows) if r is not None and r in inside])
         out.ignored = sum(r is None or r not in inside for r in rows)
         return out
+
+    def update(self, add=None, remove=None):
+        raise NotImplementedError("update is not supported by a restricted index")
 
     def refined(self, vectors, candidates):
         raise NotImplementedError("refined is not supported by a restricted index")

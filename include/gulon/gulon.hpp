@@ -188,6 +188,8 @@ class PQIndex {                       // Index.scala:385-441
     check(gulon_index_create(data.packed.data(), data.length, pq.dimension, pq.numQuantizers, pq.numClusters,
                              pq.centroids.data(), rowBase, &h_));
   }
+  // takes over an index made on the device (Index::encode, Index::merge)
+  PQIndex(gulon_index *adopted, int dimension, int length) : h_(adopted), dimension_(dimension), length_(length) {}
   PQIndex(const PQIndex &) = delete;
   PQIndex &operator=(const PQIndex &) = delete;
   ~PQIndex() { if (h_) gulon_index_destroy(h_); }
@@ -348,6 +350,26 @@ inline std::unique_ptr<GroupedIndex> grouped(const GroupedVectors &gv, const Pro
 // Index.sorted (Index.scala:107-114): encode, then wrap.
 inline std::unique_ptr<PQIndex> sorted(const Matrix &vectors, const ProductQuantizer &pq) {
   return std::unique_ptr<PQIndex>(new PQIndex(pq, pq.encode(vectors)));
+}
+// Index updates (gulon_index_encode_dataset / gulon_index_merge / gulon_index_get_codes): not in the reference, stated
+// through it.  encode: PQIndex(pq, pq.encode(vectors)) with the quantizer `index` holds on the device.
+inline std::unique_ptr<PQIndex> encode(const PQIndex &index, const Matrix &vectors) {
+  gulon_index *h = nullptr;
+  check(gulon_index_encode_dataset(index.handle(), vectors.handle(), &h));
+  return std::unique_ptr<PQIndex>(new PQIndex(h, index.dimension(), vectors.rows()));
+}
+// merge: row p of the result is a's row take[p] when take[p] >= 0, b's row -1 - take[p] otherwise (b may be null).
+inline std::unique_ptr<PQIndex> merge(const PQIndex &a, const PQIndex *b, const std::vector<int32_t> &take) {
+  gulon_index *h = nullptr;
+  check(gulon_index_merge(a.handle(), b ? b->handle() : nullptr, take.data(), (int32_t)take.size(), &h));
+  return std::unique_ptr<PQIndex>(new PQIndex(h, a.dimension(), (int)take.size()));
+}
+// codes: EncodedMatrix.indices of rows [from, until), [numQuantizers][until - from].
+inline std::vector<uint16_t> codes(const PQIndex &index, int numQuantizers, int from, int until) {
+  std::vector<uint16_t> out((size_t)numQuantizers * (until > from ? until - from : 0) + 1);
+  check(gulon_index_get_codes(index.handle(), from, until, out.data()));
+  out.pop_back();
+  return out;
 }
 // Index.exactNearestNeighbours (Index.scala:209-229) for a batch of queries.
 inline std::vector<Result> exactNearestNeighbours(const Matrix &vectors, int from, int until,

@@ -465,6 +465,26 @@ int32_t gulon_index_view_batch_query(gulon_index *view, const float *queries, in
  * d_idx[i] in [0, s) becomes the root's row id, anything else (-1 padding, INT32_MAX) stays. */
 int32_t gulon_index_view_map_rows_dev(gulon_index *view, int32_t *d_idx, int64_t count, void *stream);
 
+/* ---- Index updates (update.hip): new root indexes from an index's quantizer and from existing codes --------
+ * The reference has no mutation: an updated index is the PQIndex it would hold over the merged EncodedMatrix.  Both
+ * entries below give an ordinary root index (row_base 0, not a view) that owns all it reads -- codebooks copied device to
+ * device -- so the sources may be destroyed first.  Sources may be views or contexts: they are read as the indexes they are.
+ *
+ * gulon_index_encode_dataset: PQIndex(pq, pq.encode(ds)) where pq is the quantizer `idx` holds in HBM
+ * (ProductQuantizer.scala:25-35: per quantizer the serial KMeans.assign, one java.util.Random(0) stream over the rows of
+ * `ds` in their order -- the path of gulon_pq_encode), the codes written straight into the device layout.  ds->d must
+ * equal the index's d; ds->n = 0 is valid.  Nothing but the status reaches the host. */
+int32_t gulon_index_encode_dataset(gulon_index *idx, const gulon_dataset *ds, gulon_index **out);
+/* A root index of s rows: row p carries the code of a's row take[p] when take[p] >= 0, of b's row -1 - take[p]
+ * otherwise -- any order, repeats allowed.  b may be NULL (then every entry is >= 0).  `take` (host) is checked before
+ * anything is launched: every entry in range for its source, a and b equal in d, m, k and bitwise equal codebooks, else
+ * GULON_ERR_INVALID_ARGUMENT (for an entry: naming the first offending position). */
+int32_t gulon_index_merge(gulon_index *a, gulon_index *b, const int32_t *take, int32_t s, gulon_index **out);
+/* EncodedMatrix.indices of local rows [from, until): out[j * (until - from) + (r - from)] = the code of row r at
+ * quantizer j, for every code layout; a view answers in its own positions.  Un-blocked on the device from the plain code
+ * buffer (never the filter's reordered copy), copied down once. */
+int32_t gulon_index_get_codes(gulon_index *idx, int32_t from, int32_t until, uint16_t *out);
+
 /* ---- Expression queries: stored rows composed on the device, operands dropped (compose.hip) ------------------------
  * An EXPRESSION is a non-empty list of terms (row, weight): LOCAL rows of the index (for a GroupedIndex: grouped row
  * positions) and binary32 weights.  b expressions are given in CSR form: term_offsets[b + 1] (term_offsets[0] = 0,
