@@ -141,9 +141,12 @@ __global__ __launch_bounds__(256) void conflict_order(const uint4 *__restrict__ 
 // (0 .. 255): a byte still.  A last window of fewer than four blocks orders its rows among the blocks it has.
 // What this asks of the readers of the copy: a block holds rows of its whole window, so a row range is scanned in
 // whole windows (filter.hip rounds its block range outwards and tests every reported row against the range).
-template <int NQ>
+// SORTED (the key-sorted copy below): window position p holds row order[p] of `src` (p < n; the rest of the last window
+// is padding: zero code words, row id -1), every window is whole, and `perm` takes 32-bit row ids instead of place bytes.
+template <int NQ, bool SORTED = false>
 __global__ __launch_bounds__(256) void conflict_order_window(const uint4 *__restrict__ src, uint4 *__restrict__ dst,
-                                                             uint8_t *__restrict__ perm, long long nblk, int rounds) {
+                                                             uint8_t *__restrict__ perm, long long nblk, int rounds,
+                                                             const uint32_t *__restrict__ order = nullptr, int n = 0) {
   __shared__ uint32_t cnt_s[16 * 16 * 4];        // [group (16)][quantizer (16)][column] bytes, four columns per word
   __shared__ uint16_t st_s[16 * 16];             // [group][quantizer] fullest column | number of such columns << 8
   __shared__ uint8_t grp_s[256];                 // group of every row
@@ -156,7 +159,12 @@ __global__ __launch_bounds__(256) void conflict_order_window(const uint4 *__rest
   const bool live = t < nrows;
   uint8_t *cb = reinterpret_cast<uint8_t *>(cnt_s);
   uint4 w = make_uint4(0, 0, 0, 0);
-  if (live) w = src[wb * 64 + t];
+  int id = -1;
+  if constexpr (SORTED) {
+    if (wb * 64 + t < n) { id = (int)order[wb * 64 + t]; w = src[id]; }
+  } else {
+    if (live) w = src[wb * 64 + t];
+  }
   const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
   unsigned long long cols = 0;
 #pragma unroll
@@ -260,7 +268,67 @@ __global__ __launch_bounds__(256) void conflict_order_window(const uint4 *__rest
   if (live) {
     const long long slot = (wb + (grp >> 2)) * 64 + lds_lane_of_group(grp & 3, below + within);
     dst[slot] = w;
-    perm[slot] = (uint8_t)t;
+    if constexpr (SORTED) reinterpret_cast<int *>(perm)[slot] = id;
+    else perm[slot] = (uint8_t)t;
+  }
+}
+
+// ---- the key-sorted copy ------------------------------------------------------------------------------------------------
+// The filter stages that cover a whole index read a copy whose rows are in stable ascending order of the key
+// (code 15 << 8) | code 14 -- the two quantizers the kernel takes through the vector L1 first: a 256-row window then
+// holds a handful of values of them, and a gather whose lanes touch few 128-byte lines costs the L1 half of a random
+// one (scripts/micro/l1_gather.hip).  A stable counting sort in two passes, code 14 then code 15, 256 bins each: per
+// 1024-row chunk a histogram, one exclusive prefix over [bin][chunk], and a scatter whose rank inside the chunk counts
+// the equal digits before the row -- stable, so the result is THE ascending order, whatever the launch shape.
+constexpr int SORT_CHUNK = 1024;
+__device__ __forceinline__ uint32_t sort_digit(const uint4 w, int pass) { return (w.w >> (pass ? 24 : 16)) & 255u; }
+
+template <int PASS>
+__global__ __launch_bounds__(SORT_CHUNK) void sort_count(const uint4 *__restrict__ codes, const uint32_t *__restrict__ ids,
+                                                         int n, int nchunks, uint32_t *__restrict__ counts /*[256][nchunks]*/) {
+  __shared__ uint32_t h[256];
+  const int t = threadIdx.x, i = blockIdx.x * SORT_CHUNK + t;
+  if (t < 256) h[t] = 0;
+  __syncthreads();
+  if (i < n) atomicAdd(&h[sort_digit(codes[PASS ? ids[i] : (uint32_t)i], PASS)], 1u);
+  __syncthreads();
+  if (t < 256) counts[(size_t)t * nchunks + blockIdx.x] = h[t];
+}
+
+// counts[0 .. total) -> their exclusive prefix sums, in place; one workgroup
+__global__ __launch_bounds__(1024) void sort_scan(uint32_t *__restrict__ counts, int total) {
+  __shared__ uint32_t part[1024];
+  const int t = threadIdx.x, per = (total + 1023) / 1024;
+  const int lo = min(total, t * per), hi = min(total, lo + per);
+  uint32_t s = 0;
+  for (int i = lo; i < hi; i++) s += counts[i];
+  part[t] = s;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {
+    const uint32_t v = t >= o ? part[t - o] : 0u;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  uint32_t run = part[t] - s;
+  for (int i = lo; i < hi; i++) { const uint32_t c = counts[i]; counts[i] = run; run += c; }
+}
+
+template <int PASS>
+__global__ __launch_bounds__(SORT_CHUNK) void sort_scatter(const uint4 *__restrict__ codes, const uint32_t *__restrict__ ids,
+                                                           int n, int nchunks, const uint32_t *__restrict__ base,
+                                                           uint32_t *__restrict__ out /*[n]*/) {
+  __shared__ uint8_t dg[SORT_CHUNK];
+  const int t = threadIdx.x, i = blockIdx.x * SORT_CHUNK + t;
+  const bool live = i < n;
+  const uint32_t row = live ? (PASS ? ids[i] : (uint32_t)i) : 0u;
+  const uint32_t d = live ? sort_digit(codes[row], PASS) : 0u;
+  dg[t] = (uint8_t)d;
+  __syncthreads();
+  if (live) {   // (the rows behind n sit behind every live row of the last chunk: they change no rank)
+    uint32_t rank = 0;
+    for (int j = 0; j < t; j++) rank += dg[j] == d;
+    out[base[(size_t)d * nchunks + blockIdx.x] + rank] = row;
   }
 }
 
@@ -281,6 +349,24 @@ void launch_conflict_order(const uint8_t *src, uint8_t *dst, uint8_t *perm, long
   else
     hipLaunchKernelGGL(conflict_order<FILTER_LDS_QUANTIZERS>, grid, dim3(256), 0, st, s4, d4, perm, nblk, rounds);
   HIP_CHECK(hipGetLastError());
+}
+
+void launch_sorted_copy(const uint8_t *codes, int n, uint8_t *dst, int *ids, int rounds, hipStream_t st) {
+  if (n <= 0) return;
+  const int nchunks = ceil_div(n, SORT_CHUNK);
+  const long long nwin = ceil_div((long long)n, 256LL);
+  DevBuf<uint32_t> counts((size_t)256 * nchunks), a((size_t)n), b((size_t)n);
+  const auto c4 = reinterpret_cast<const uint4 *>(codes);
+  hipLaunchKernelGGL(sort_count<0>, dim3(nchunks), dim3(SORT_CHUNK), 0, st, c4, (const uint32_t *)nullptr, n, nchunks, counts.p);
+  hipLaunchKernelGGL(sort_scan, dim3(1), dim3(1024), 0, st, counts.p, 256 * nchunks);
+  hipLaunchKernelGGL(sort_scatter<0>, dim3(nchunks), dim3(SORT_CHUNK), 0, st, c4, (const uint32_t *)nullptr, n, nchunks, counts.p, a.p);
+  hipLaunchKernelGGL(sort_count<1>, dim3(nchunks), dim3(SORT_CHUNK), 0, st, c4, a.p, n, nchunks, counts.p);
+  hipLaunchKernelGGL(sort_scan, dim3(1), dim3(1024), 0, st, counts.p, 256 * nchunks);
+  hipLaunchKernelGGL(sort_scatter<1>, dim3(nchunks), dim3(SORT_CHUNK), 0, st, c4, a.p, n, nchunks, counts.p, b.p);
+  hipLaunchKernelGGL((conflict_order_window<FILTER_SORT_LDS_QUANTIZERS, true>), dim3((unsigned)nwin), dim3(256), 0, st, c4,
+                     reinterpret_cast<uint4 *>(dst), reinterpret_cast<uint8_t *>(ids), nwin * 4, rounds, b.p, n);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(st));   // the temporaries go with this scope
 }
 
 bool conflict_order_windowed() {
@@ -305,6 +391,25 @@ GULON_API int32_t gulon_selftest_conflict_order(const uint8_t *codes, int64_t n_
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(codes_out, dst.p, (size_t)n_blocks * 1024, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(place_out, place.p, (size_t)n_blocks * 64, hipMemcpyDeviceToHost));
+  });
+}
+
+// the key-sorted copy of n rows ([ceil(n/64) * 64] 16-byte code words): codes_out / ids_out [ceil(n/256) * 256].
+// (Declared here and bound by its test, tests/test_gpu_filter_sort.py: the header's list of hooks is pinned by test_abi.)
+GULON_API int32_t gulon_selftest_filter_sort(const uint8_t *codes, int64_t n, int32_t rounds, uint8_t *codes_out,
+                                                        int32_t *ids_out) {
+  return guarded([&] {
+    GULON_REQUIRE(codes != nullptr && codes_out != nullptr && ids_out != nullptr && n >= 0 && n <= INT_MAX - 256 &&
+                  rounds >= 0 && rounds <= 8, "bad arguments");
+    if (n == 0) return;
+    const size_t nblk = (size_t)ceil_div(n, (int64_t)64), npad = (size_t)ceil_div(n, (int64_t)256) * 256;
+    DevBuf<uint8_t> src, dst(npad * 16);
+    DevBuf<int> ids(npad);
+    src.upload(codes, nblk * 1024);
+    launch_sorted_copy(src.p, (int)n, dst.p, ids.p, rounds, 0);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(codes_out, dst.p, npad * 16, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(ids_out, ids.p, npad * sizeof(int), hipMemcpyDeviceToHost));
   });
 }
 #endif

@@ -436,7 +436,8 @@ template <> struct QEntry<8> { using type = uint2; };
 template <> struct QEntry<4> { using type = uint32_t; };
 
 template <int QW, int NQG, int VEC, int NADD, int MAIN,
-          int NG1 /* 1: a single code word per row (ng == 1); 2: and `codes` is the conflict-ordered copy, `perm` its row order */>
+          int NG1 /* 1: a single code word per row (ng == 1); 2: and `codes` is the conflict-ordered copy, `perm` its row order;
+                     3: and `codes` is the key-sorted copy, `perm` its 32-bit row ids (conflict_order.hip) */>
 __global__ __launch_bounds__(FILTER_THREADS) void filter_kernel(
     const uint8_t *__restrict__ codes, const uint8_t *__restrict__ perm, int ng, int m_pad, const uint8_t *__restrict__ qtab, int row_from, int row_until,
     int rb_begin, int e_count, int e_per_chunk, RbMap mp, int *__restrict__ cnt, int *__restrict__ queue, int cap /* entries per sub-queue */,
@@ -454,7 +455,16 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_kernel(
   // of up front: 3.21, 3.23, 3.36; five 3.96, eight 5.58 -- the L1 path saturates quickly).  It pays only where
   // LDS is the one busy pipe: 16-byte entries, four entries summed per widening, two workgroups per CU (m <= 16);
   // with 4-byte code words, wider indexes (m = 32, 64, 100) or the 7-bit levels it measured 2-50 % slower.
-  constexpr int GLB = (QW == 16 && NQG == 1 && VEC == 16 && NADD == 4 && NG1) ? GULON_FILTER_GLB : 0;
+  // What the L1 path carries (scripts/micro/l1_gather.hip): a 16-byte gather returns 64 bytes per
+  // cycle at best -- 16.5 cycles per wave-instruction whenever its lanes touch up to 16 distinct 128-byte lines or
+  // equal lines sit in neighbouring lanes -- and 32 cycles for 64 random entries of a 4 KiB table; the coalesced code
+  // word costs another 16.  Three random look-ups and the code word are 112 cycles of the ~118 a row block takes: that
+  // is why a fourth never paid.  In the key-sorted copy (NG1 == 3) a row block holds one value of code 15 and a few of
+  // code 14, so those two cost 16.5 cycles each and a FOURTH look-up fits (2 x 32 + 2 x 16.5 + 16 = 113) -- one LDS
+  // gather fewer per block.  Measured per batch at 10 M rows: 2.33 ms window-ordered, 2.26 with 3 L1 look-ups in the
+  // sorted copy, 2.24 with 4, 2.66 with 5.
+  constexpr bool SORTED = NG1 == 3;
+  constexpr int GLB = (QW == 16 && NQG == 1 && VEC == 16 && NADD == 4 && NG1) ? (SORTED ? GULON_FILTER_SORT_GLB : GULON_FILTER_GLB) : 0;
   using Word = typename CodeWord<VEC>::type;
   using QE = typename QEntry<QW>::type;
   extern __shared__ uint4 qlds_raw[];
@@ -486,7 +496,9 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_kernel(
   {
     const int n16 = NQG * tab * QW / 16;   // 16-byte units (tab * QW is a multiple of 16)
     const uint4 *src = reinterpret_cast<const uint4 *>(qtab) + (size_t)tile * n16;
-    for (int e = tid; e < n16; e += FILTER_THREADS) qlds_raw[e] = src[e];
+    // (the key-sorted form never reads the LDS copy of its L1-served quantizers: the last of the one group's table)
+    const int n16_lds = SORTED ? (VEC - GLB) * 256 * QW / 16 : n16;
+    for (int e = tid; e < n16_lds; e += FILTER_THREADS) qlds_raw[e] = src[e];
     if (tid == 0) *reinterpret_cast<int *>(qlds_raw + n16) = NW;   // run counter: the first NW runs are the waves' own
   }
   __syncthreads();
@@ -568,9 +580,10 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_kernel(
       const uint8_t *tj_glb = qtab + ((size_t)tile * NQG * tab + (decltype(G0)::value ? 0 : g * VEC * 256)) * sizeof(QE);
       QE gl[GLB > 0 ? GLB : 1][NQG];
 #pragma unroll
-      for (int a = 0; a < GLB; a++)
+      for (int a0 = 0; a0 < GLB; a0++)
 #pragma unroll
         for (int s = 0; s < NQG; s++) {
+          const int a = SORTED ? GLB - 1 - a0 : a0;   // the sorted quantizers (the word's last two) first
           const uint8_t *base = tj_glb + ((size_t)(VEC - GLB + a) * 256 + (size_t)s * tab) * sizeof(QE);
           const uint32_t off = code_byte<VEC>(w, VEC - GLB + a) * (uint32_t)sizeof(QE);
           gl[a][s] = *reinterpret_cast<const QE *>(base + off);
@@ -662,7 +675,7 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_kernel(
 #pragma unroll
       for (int dd = 0; dd < DW; dd++) acc[s][2 * dd] -= acc[s][2 * dd + 1] << 8;
     // conflict-ordered copy: which row a lane holds is only looked up (one byte) when a lane has something to report
-    constexpr bool PERM = NG1 == 2;
+    constexpr bool PERM = NG1 >= 2;
     int row = rb * 64 + lane;
     bool valid = PERM || (row >= row_from && row < row_until);
     uint32_t any = 0;
@@ -685,7 +698,8 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_kernel(
         const uint8_t *perm_l = perm;
         int pwin_l = pwin;
         asm volatile("" : "+s"(perm_l), "+s"(pwin_l));
-        row = (rb & ~pwin_l) * 64 + perm_l[(size_t)rb * 64 + lane];
+        if constexpr (SORTED) row = reinterpret_cast<const int *>(perm_l)[(size_t)rb * 64 + lane];   // (-1: padding)
+        else row = (rb & ~pwin_l) * 64 + perm_l[(size_t)rb * 64 + lane];
         valid = row >= row_from && row < row_until;
       }
 #pragma unroll
@@ -841,7 +855,7 @@ __global__ __launch_bounds__(64 * SV_WAVES * 4) void survivors_kernel(
 
 template <int QW, int NQG, int VEC, int NADD>
 void launch_filter_t(gulon_index *ix, int ftiles, int nchunks, int rb_begin, int e_count, int e_per_chunk, RbMap mp,
-                     int from, int until, int cap, int stage, int B, hipStream_t st, int *fb, int qt) {
+                     int from, int until, int cap, int stage, int B, hipStream_t st, int *fb, int qt, bool sorted) {
   const int W_fp32 = ix->w;
   const size_t lds_bytes = (size_t)NQG * ix->m_pad * 256 * QW + 16;   // tables + the run counter
   // (the single-word form only for the instantiation the headline index runs on: m = 16, two workgroups per CU)
@@ -860,6 +874,12 @@ void launch_filter_t(gulon_index *ix, int ftiles, int nchunks, int rb_begin, int
         HIP_CHECK(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k)));
         if (fa.sharedSizeBytes != 0) return false;
       }
+    if constexpr (one_word_form)
+      for (auto k : {filter_kernel<QW, NQG, VEC, NADD, 0, 3>, filter_kernel<QW, NQG, VEC, NADD, 1, 3>}) {
+        hipFuncAttributes fa;
+        HIP_CHECK(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k)));
+        if (fa.sharedSizeBytes != 0) return false;
+      }
     return true;
   }();
   GULON_REQUIRE(lds_at_zero, "internal: the filter kernels address their tables from LDS offset 0");
@@ -873,11 +893,20 @@ void launch_filter_t(gulon_index *ix, int ftiles, int nchunks, int rb_begin, int
       perm = ix->fperm.p;
     }
   }
+  if (sorted) {   // the key-sorted copy: the whole-index launches of the short and the main stage
+    GULON_REQUIRE(one_word_form && ix->ng == 1 && ix->scodes.p && ix->sids.p && stage != 2,
+                  "internal: no key-sorted form of this filter launch");
+    if constexpr (one_word_form) {
+      kern = stage == 1 ? filter_kernel<QW, NQG, VEC, NADD, 1, 3> : filter_kernel<QW, NQG, VEC, NADD, 0, 3>;
+      codes = ix->scodes.p;
+      perm = reinterpret_cast<const uint8_t *>(ix->sids.p);
+    }
+  }
   HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds_bytes));
   hipLaunchKernelGGL(kern, stage == 2 ? dim3(nchunks, ftiles) : dim3(ftiles, nchunks), dim3(FILTER_THREADS), lds_bytes, st, codes, perm, ix->ng, ix->m_pad,
                      ix->qtab.p, from, until, rb_begin, e_count, e_per_chunk, mp, ix->sv_cnt.p, ix->sv_queue.p, cap,
-                     fb ? fb : ix->fb_tile.p, fb ? qt : W_fp32 * ix->nsub, B, perm ? ix->fwindow - 1 : 0);
+                     fb ? fb : ix->fb_tile.p, fb ? qt : W_fp32 * ix->nsub, B, sorted ? 3 : perm ? ix->fwindow - 1 : 0);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -958,9 +987,10 @@ FilterShape filter_shape(const gulon_index *ix) {
 
 void launch_filter(gulon_index *ix, int qw, int nqg, int nadd, int ftiles, int nchunks, int rb_begin, int e_count,
                    int e_per_chunk, RbMap mp, int from, int until, int cap, int stage, int B, hipStream_t st,
-                   int *fb = nullptr /* tile flags other than the index's own, one per `qt` queries */, int qt = 1) {
+                   int *fb = nullptr /* tile flags other than the index's own, one per `qt` queries */, int qt = 1,
+                   bool sorted = false /* read the key-sorted copy (the launch covers every row of the index) */) {
 #define GO(W_, Q, V, A) \
-  launch_filter_t<W_, Q, V, A>(ix, ftiles, nchunks, rb_begin, e_count, e_per_chunk, mp, from, until, cap, stage, B, st, fb, qt)
+  launch_filter_t<W_, Q, V, A>(ix, ftiles, nchunks, rb_begin, e_count, e_per_chunk, mp, from, until, cap, stage, B, st, fb, qt, sorted)
 #define GO_QV(W_, Q, V) do { if (nadd == 4) GO(W_, Q, V, 4); else GO(W_, Q, V, 2); } while (0)
 #define GO_W(W_) do {                                                  \
     if (ix->vec == 16) { if (nqg == 2) GO_QV(W_, 2, 16); else GO_QV(W_, 1, 16); } \
@@ -1147,6 +1177,13 @@ void run_filter_query(gulon_index *ix, const float *dQ, int B, int K, int from, 
   const int rb_total = ceil_div(until, 64) - rb_begin;
   int frb_begin = rb_begin, frb_total = rb_total;        // what the filter launches scan (whole ordering windows)
   filter_block_range(ix, qw, nqg, nadd, from, until, frb_begin, frb_total);
+  // the stages of a query over every row of the index read the key-sorted copy, whole 256-row windows of it
+  const bool sorted = ix->scodes.p && ix->sids.p && t.filter_sort > 0 && ix->ng == 1 && ix->vec == 16 && qw == 16 &&
+                      nqg == 1 && nadd == 4 && from == 0 && until == ix->n;
+  if (sorted) {
+    frb_begin = 0;
+    frb_total = ceil_div(ix->n, 256) * 4;
+  }
   const int P = t.filter_period;
   const int s0 = std::min(std::max(t.filter_stage0, 0), P - 2);
   const int s1 = std::min(std::max(t.filter_stage1, 1), P - 1 - s0);
@@ -1270,7 +1307,8 @@ void run_filter_query(gulon_index *ix, const float *dQ, int B, int K, int from, 
       const bool turns = (long long)rb_total * 64 >= (2ll << 20);
       if (main_stage && !fresh && turns) HIP_CHECK(hipStreamWaitEvent(st, lane_ev, 0));
       if (timed) HIP_CHECK(hipEventRecord(ev0, st));         // after the wait: the kernel's own duration
-      launch_filter(ix, qw, nqg, nadd, ftiles, nc, frb_begin, en, per, mp, from, until, cap, main_stage ? 1 : 0, B, st);
+      launch_filter(ix, qw, nqg, nadd, ftiles, nc, frb_begin, en, per, mp, from, until, cap, main_stage ? 1 : 0, B, st,
+                    nullptr, 1, sorted);
       if (main_stage) HIP_CHECK(hipEventRecord(lane_ev, st));
     }
     if (stats) {   // debugging aid (GULON_FILTER_STATS=1): synchronous survivor statistics

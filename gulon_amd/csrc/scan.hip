@@ -636,7 +636,7 @@ ScanTuning::ScanTuning() {
   static const char *keys[] = {"GULON_SCAN_BLOCKS", "GULON_SCAN_PRUNE", "GULON_SCAN_PRUNE_FROM", "GULON_SCAN_FILTER",
                                "GULON_FILTER_MIN_RB", "GULON_FILTER_PERIOD", "GULON_FILTER_STAGE1", "GULON_FILTER_CAP",
                                "GULON_FILTER_NADD", "GULON_FILTER_SAMPLE", "GULON_FILTER_STAGE0", "GULON_FILTER_BLOCKS",
-                               "GULON_FILTER_SHARED_STAGE1", "GULON_FILTER_ORDER"};
+                               "GULON_FILTER_SHARED_STAGE1", "GULON_FILTER_ORDER", "GULON_FILTER_SORT"};
   for (const char *k : keys)
     if (const char *e = getenv(k)) set(k, atoi(e));
 }
@@ -657,6 +657,7 @@ bool ScanTuning::set(const char *key, int v) {
   else if (k == "GULON_FILTER_BLOCKS") { if (v >= 1) filter_blocks = v; }
   else if (k == "GULON_FILTER_SHARED_STAGE1") { if (v >= -1 && v <= 1) filter_shared_stage1 = v; }
   else if (k == "GULON_FILTER_ORDER") { if (v >= 0 && v <= 8) filter_order = v; }
+  else if (k == "GULON_FILTER_SORT") filter_sort = v != 0;
   else return false;
   return true;
 }
@@ -1017,6 +1018,14 @@ void build_filter_copy(gulon_index *ix) {
     ix->fwindow = conflict_order_windowed() ? 4 : 1;
     HIP_CHECK(hipDeviceSynchronize());
   }
+  // the key-sorted copy (GULON_FILTER_SORT): 16 bytes of codes + a 32-bit row id per row
+  if (ix->tune->filter_sort > 0 && ix->vec == 16 && ix->ng == 1 && (long long)nblk >= ix->tune->filter_min_rb) {
+    const size_t nwin = (size_t)ceil_div(ix->n, 256);
+    ix->scodes.alloc(nwin * 4096);
+    ix->sids.alloc(nwin * 256);
+    launch_sorted_copy(ix->codes.p, ix->n, ix->scodes.p, ix->sids.p, std::max(1, rounds), 0);
+    HIP_CHECK(hipDeviceSynchronize());
+  }
 }
 
 gulon_index *make_context(gulon_index *parent) {
@@ -1030,6 +1039,8 @@ gulon_index *make_context(gulon_index *parent) {
   c->fcodes.borrow(parent->fcodes);
   c->fperm.borrow(parent->fperm);
   c->fwindow = parent->fwindow;
+  c->scodes.borrow(parent->scodes);
+  c->sids.borrow(parent->sids);
   c->wcodes.borrow(parent->wcodes);
   c->cents.borrow(parent->cents);
   c->from.borrow(parent->from);

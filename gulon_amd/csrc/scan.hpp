@@ -54,6 +54,11 @@ struct gulon_index {
   // conflicts of its table gathers (conflict_order.hip), and each lane's place in the block's row order
   DevBuf<uint8_t> fcodes, fperm;   // [n/64][64][16], [n/64][64]
   int fwindow = 1;                 // blocks per ordering window of fcodes (4: fperm = place in a 256-row window; 1: in the block)
+  // a third copy for the filter stages that cover the whole index: rows in stable ascending order of
+  // (code 15 << 8) | code 14, cut into 256-row windows that are dealt to lane groups like fcodes' (conflict_order.hip);
+  // sids = the row behind every lane position (-1: padding of the last window)
+  DevBuf<uint8_t> scodes;          // [ceil(n/256) * 4][64][16]
+  DevBuf<int> sids;                // [ceil(n/256) * 4][64]
   bool wide = false;       // k > 256: 16-bit codes, tables in HBM (wide.hip)
   DevBuf<uint16_t> wcodes; // wide: [n/64][m][64]
   DevBuf<float> wpartial;  // wide, sliced tables: running sums [queries of the sub-batch][rows]
@@ -192,6 +197,12 @@ inline int rbmap_count(int rb_total, RbMap mp) {
 #define GULON_FILTER_GLB 3
 #endif
 constexpr int FILTER_LDS_QUANTIZERS = 16 - GULON_FILTER_GLB;
+// the same for the key-sorted copy, where the look-ups of the two sorted quantizers cost the vector L1 half of a random
+// one (scripts/micro/l1_gather.hip): one more goes through it
+#ifndef GULON_FILTER_SORT_GLB
+#define GULON_FILTER_SORT_GLB 4
+#endif
+constexpr int FILTER_SORT_LDS_QUANTIZERS = 16 - GULON_FILTER_SORT_GLB;
 
 struct ScanTuning {
   int threads = 1024;        // workgroup size (16 waves hide the pruning checkpoints' LDS drain)
@@ -210,6 +221,7 @@ struct ScanTuning {
   int filter_blocks = 4096;         // workgroups aimed for by a filter launch
   int filter_shared_stage1 = -1;    // bounds shared across shards: run the short first stage? (-1: by sample size)
   int filter_order = 1;             // conflict-ordered code copy: built at index creation (the environment's value) / used (per handle)
+  int filter_sort = 1;              // key-sorted code copy: built at index creation (the environment's value) / used (per handle)
   ScanTuning();
   bool set(const char *key, int v);
 };
@@ -287,6 +299,8 @@ void run_tie_replay(gulon_index *ix, const float *dQ, int B, int K, int from, in
 void launch_conflict_order(const uint8_t *src, uint8_t *dst, uint8_t *perm, long long nblk, int nq, int rounds,
                            hipStream_t st);
 bool conflict_order_windowed();   // the ordering spans windows of four blocks (default) or single blocks
+// conflict_order.hip: the key-sorted copy of n one-word rows -- dst [ceil(n/256) * 256] code words, ids [the same] rows
+void launch_sorted_copy(const uint8_t *codes, int n, uint8_t *dst, int *ids, int rounds, hipStream_t st);
 // decode.hip: rows of the index back into vectors (ProductQuantizer.decode, GroupedIndex.lookup).  gcent != nullptr:
 // out = gcent[partition] + decode(row), the partition by Arrays.binarySearch over offsets[0..n_offsets); normalize:
 // MathUtils.normalize of the result.  d_rows / d_out are device pointers; rows outside [0, n) give NaN rows and set

@@ -565,7 +565,10 @@ int32_t gulon_index_filter_stats(gulon_index *idx, int32_t *query_tiles, int32_t
  * from it afterwards); there is no process-wide setter.  Results never depend on them.
  * "GULON_FILTER_ORDER" (default 1): an index of one-word codes (m <= 16) created while the environment's value is
  * non-zero keeps a second, conflict-ordered copy of its codes for the filter kernel (+ 17 bytes per row; the value =
- * rounds of the ordering); per handle 0 makes the filter read the plain copy again. */
+ * rounds of the ordering); per handle 0 makes the filter read the plain copy again.
+ * "GULON_FILTER_SORT" (default 1): such an index also keeps a copy of its codes sorted by the last two quantizers'
+ * codes with a 32-bit row id per row (+ 20 bytes per row), which the filter reads for queries over the index's whole
+ * row range; per handle 0 makes those queries read the other copies again. */
 int32_t gulon_index_tuning(gulon_index *idx, const char *key, int32_t value);
 /* TopKHeap.merge semantics (TopKHeap.scala:44-53, used at Index.scala:279) under
  * the deterministic (distance, row id) order: merges `lists` partial lists per
