@@ -1,17 +1,17 @@
-"""`python -m gulon_amd`: the reference's four commands (command/Main.scala:7-11), `inspect` and `update`.
+"""`python -m gulon_amd`: the reference's four commands (command/Main.scala:7-11), `inspect`, `update` and `build-fine`.
 
   build-index -d l2|cosine -o INDEX [-k N] [-m N] [-n N] [-p [--partitions N] [-l N]] FILE
                                        command/BuildIndex.scala: a word2vec text file -> an index file; the text is
                                        parsed on the device (word_vectors.read_word2vec_device) and every later stage
                                        runs there too (build.build_index)
 
-  query-words -i INDEX [-k N] [-x] [-v VECTORS [-c N]] [FILE]
+  query-words -i INDEX [-k N] [-x] [-v VECTORS | -f FINE] [-c N] [FILE]
                                        command/QueryWords.scala: one word per line of FILE (or stdin), printed as
                                        `word: w1,w2,...` or `word: not found`, in input order
-  query -i INDEX [-k N] [-v VECTORS [-c N]] FILE
+  query -i INDEX [-k N] [-v VECTORS | -f FINE] [-c N] FILE
                                        command/Query.scala: a word2vec text file of query vectors, printed as
                                        `key: w1,w2,...`
-  test -v VECTORS -i INDEX [-s SIZE] [-e ERROR] [-c N]
+  test -v VECTORS -i INDEX [-s SIZE] [-e ERROR] [[-f FINE] -c N]
                                        command/Test.scala: the recall of an index file against the exact neighbours in
                                        the word2vec text file it was built from, `R@k: mean +/- stdDev` for
                                        k = 1 ... 1000 over SIZE sampled vectors (tests_recall.Tests; the vectors are
@@ -32,6 +32,17 @@
                                        replaced if the index still has it -- encoded by the index's own code books on the
                                        device, read normalised for a cosine index.  Kept words keep their codes.  Not for
                                        a partitioned (grouped) index
+
+  build-fine -i INDEX -v VECTORS -o OUTPUT [-k N] [-m N] [-n N]
+                                       (not in the reference) the fine index of an index file (fine.py, csrc/fine.hip): a
+                                       second quantizer over the residuals the index leaves against the word2vec text
+                                       file VECTORS it was built from (read normalised for a cosine index), written as an
+                                       ordinary sorted l2 index file.  -k / -m / -n as for build-index
+
+-f FINE on the query commands and on test (not in the reference): as -v / -c, but the candidates are re-ranked by their
+distance to the index's row plus the fine index's row of the same word (fine.FineRefinedIndex) -- no original vectors in
+memory.  FINE is a file written by build-fine.  Not together with -v (on the query commands) or -r; works with -x.  On
+test, -f needs -c, and the R@k lines are prefixes of one result per query exactly as described for -c below.
 
 -v VECTORS on the query commands (not in the reference): the index's N candidates per query (-c, default 10 * k) are
 re-ranked by their exact distance to the original vectors of that word2vec text file, and the k nearest are printed
@@ -122,6 +133,18 @@ class RecallConfig:
     sample_size: int
     epsilon: float
     candidates: Optional[int] = None      # -c: the recall of the index refined over this many candidates
+    fine: Optional[str] = None            # -f: refined against this fine index file instead of the vectors
+
+
+@dataclass(frozen=True)
+class FineConfig:
+    """build-fine: the index file, the word2vec text it was built from, the output, and build-index's quantizer options."""
+    index: str
+    vectors: str
+    output: str
+    num_clusters: int = 256
+    num_quantizers: int = 25
+    max_iterations: int = 100
 
 
 @dataclass(frozen=True)
@@ -173,6 +196,18 @@ def _parser():
     b.add_argument("-l", "--limit", type=_integer, default=None, metavar="num", help="number of partitions to search")
     b.add_argument("-o", "--output", required=True, metavar="file", help="index output file")
     b.add_argument("file", metavar="file")
+    bf = sub.add_parser("build-fine", help="build the fine index of a nearest neighbour index",
+                        description="build the fine index of a nearest neighbour index: a second quantizer over the "
+                                    "residuals the index leaves")
+    bf.add_argument("-i", "--index", required=True, metavar="file", help="path to ANN index")
+    bf.add_argument("-v", "--vectors", required=True, metavar="file",
+                    help="word2vec word vectors the index was built from")
+    bf.add_argument("-k", "--clusters", type=_clusters, default=256, metavar="num_clusters",
+                    help="clusters per quantizer, between 1 and 65536")
+    bf.add_argument("-m", "--quantizers", type=_integer, default=25, metavar="num", help="number of quantizers used")
+    bf.add_argument("-n", "--max-iters", type=_integer, default=100, metavar="iterations",
+                    help="maximum number of iterations per quantizer")
+    bf.add_argument("-o", "--output", required=True, metavar="file", help="fine index output file")
     for name, help_, need_file in (("query-words", "query nearest neighbour index by word", False),
                                    ("query", "query nearest neighbour index", True)):
         s = sub.add_parser(name, help=help_, description=help_)
@@ -183,8 +218,11 @@ def _parser():
                        help="word2vec word vectors the index was built from: re-rank the index's candidates by their "
                             "exact distance to these")
         s.add_argument("-c", "--candidates", type=_positive, default=None, metavar="num",
-                       help="candidates taken from the index per query before re-ranking (needs --vectors; "
+                       help="candidates taken from the index per query before re-ranking (needs --vectors or --fine; "
                             "default 10 * neighbours)")
+        s.add_argument("-f", "--fine", default=None, metavar="file",
+                       help="fine index of the index (build-fine): re-rank the index's candidates by their distance to "
+                            "the two-level reconstruction")
         s.add_argument("-r", "--restrict", default=None, metavar="file",
                        help="take the neighbours from the words of this file only (one word per line; words the index "
                             "lacks are ignored and counted on stderr)")
@@ -205,6 +243,9 @@ def _parser():
                    help="report the recall of the index refined against the vectors: num candidates per query re-ranked "
                         "by exact distance.  Each R@k is a prefix of ONE refined result per query, over "
                         "max(num, largest k) candidates, not a refined query at that k")
+    t.add_argument("-f", "--fine", default=None, metavar="file",
+                   help="report the recall of the index refined against this fine index (build-fine) instead of the "
+                        "vectors; needs --candidates")
     i = sub.add_parser("inspect", help="report code usage and quantization error of an index",
                        description="report code usage and quantization error of an index")
     i.add_argument("-i", "--index", required=True, metavar="file", help="path to ANN index")
@@ -294,7 +335,8 @@ def run_recall(config: RecallConfig, write, load):
     An index form that cannot answer k = 1000 fails here with the library's message; k is never clamped.
     config.candidates: the recall of RefinedIndex(index, vectors, candidates) instead.  Its vectors are what the index
     prepares its queries for -- a NORMALISED reading of the same file for a cosine index -- while the queries and the
-    recall distances stay on the raw vectors."""
+    recall distances stay on the raw vectors.  config.fine: the recall of FineRefinedIndex(index, that fine index file,
+    candidates) instead; the vectors then serve the exact neighbours only."""
     from .build import log_task
     from .tests_recall import Tests
     from .word_vectors import read_word2vec_device
@@ -302,7 +344,9 @@ def run_recall(config: RecallConfig, write, load):
                        lambda v: f"Read {v.size} word vectors")
     index = load(config.index)
     raw = vectors.sorted()
-    if config.candidates is not None:
+    if config.fine is not None:
+        index = index.fine_refined(load(config.fine), config.candidates)
+    elif config.candidates is not None:
         cosine = index.metric == "cosine"
         originals = read_word2vec_device(config.vectors, normalize=True).sorted() if cosine else raw
         index = index.refined(originals, config.candidates)
@@ -365,6 +409,28 @@ def run_update(config: UpdateConfig, write, load):
     return updated
 
 
+def run_build_fine(config: FineConfig, write, load):
+    """build-fine behind its argument handling: load the index, read the vectors (normalised for a cosine index), build
+    the fine index on the device, write it."""
+    from .build import log_task
+    from .fine import build_fine_index
+    from .index_file import dump_index
+    from .product_quantizer import Config
+    from .word_vectors import read_word2vec_device
+    index = log_task(write, f"Reading index from {config.index}", lambda: load(config.index),
+                     lambda i: f"Read index of {i.size} words")
+    vectors = log_task(write, "Reading word vectors",
+                       lambda: read_word2vec_device(config.vectors, normalize=index.metric == "cosine").sorted(),
+                       lambda v: f"Read {v.size} word vectors")
+    fine = build_fine_index(index, vectors, Config(config.num_clusters, config.num_quantizers, config.max_iterations),
+                            write)
+
+    def dump():
+        with open(config.output, "wb") as fh:
+            fh.write(dump_index(fine.index, fine.words))
+    log_task(write, f"Writing index to {config.output}", dump, f"Wrote index to {config.output}")
+
+
 def read_originals(path, normalize):
     """The -v vectors of the query commands: on the device, in word order (their key index resolves the index's words)."""
     from .word_vectors import read_word2vec_device
@@ -382,16 +448,18 @@ def _restricted(args, index):
     return index
 
 
-def _refined(args, index, vectors):
-    """The loaded index, or with -r its restriction, or with -v its refined form; -c needs -v."""
-    if args.vectors is None:
+def _refined(args, index, vectors, load):
+    """The loaded index, or with -r its restriction, or with -v / -f its refined form; -c needs one of those."""
+    if args.vectors is None and args.fine is None:
         return _restricted(args, index)
     candidates = args.candidates if args.candidates is not None else 10 * args.neighbours
+    if args.fine is not None:
+        return index.fine_refined(load(args.fine), candidates)
     return index.refined(vectors(args.vectors, index.metric == "cosine"), candidates)
 
 
 def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None, vectors=None, inspect=None,
-         update=None):
+         update=None, fine=None):
     """Returns the exit code.  stdin / stdout: binary streams (default: the process's); load: path -> index with
     batch_query_by_words / batch_query (default WordIndex.load); build: (BuildConfig, write) -> None, the whole of
     build-index behind its argument handling (default run_build_index); recall: (RecallConfig, write, load) ->
@@ -399,15 +467,24 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
     vectors: (path, normalize) -> the word vectors behind -v of the query commands (default read_originals); inspect:
     (InspectConfig, load, vectors) -> IndexReport, the whole of inspect between its argument handling and its lines
     (default run_inspect); update: (UpdateConfig, write, load) -> the updated index with its four counters, the whole
-    of update behind its argument handling (default run_update)."""
+    of update behind its argument handling (default run_update); fine: (FineConfig, write, load) -> None, the whole of
+    build-fine behind its argument handling (default run_build_fine).  The fine index behind -f is read with `load`."""
     parser = _parser()
     args = parser.parse_args(argv)
     if args.command == "update" and args.add is None and args.remove is None:
         parser.error("at least one of --add and --remove is required")
     if args.command == "inspect" and args.worst is not None and args.vectors is None:
         parser.error("--worst is only applicable with --vectors")
-    if args.command in ("query", "query-words") and args.candidates is not None and args.vectors is None:
-        parser.error("--candidates is only applicable with --vectors")
+    if args.command in ("query", "query-words") and args.candidates is not None and args.vectors is None \
+            and args.fine is None:
+        parser.error("--candidates is only applicable with --vectors or --fine")
+    if args.command in ("query", "query-words") and args.fine is not None:
+        if args.vectors is not None:
+            parser.error("--fine is not applicable with --vectors")
+        if args.restrict is not None:
+            parser.error("--fine is not applicable with --restrict")
+    if args.command == "test" and args.fine is not None and args.candidates is None:
+        parser.error("--fine needs --candidates")
     if args.command in ("query", "query-words") and args.restrict is not None:
         if args.vectors is not None:
             parser.error("--restrict is not applicable with --vectors")
@@ -429,8 +506,11 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
 
     if args.command == "build-index":
         (build if build is not None else run_build_index)(build_config(parser, args), log)
+    elif args.command == "build-fine":
+        config = FineConfig(args.index, args.vectors, args.output, args.clusters, args.quantizers, args.max_iters)
+        (fine if fine is not None else run_build_fine)(config, log, load)
     elif args.command == "test":
-        config = RecallConfig(args.vectors, args.index, args.sample, args.error, args.candidates)
+        config = RecallConfig(args.vectors, args.index, args.sample, args.error, args.candidates, args.fine)
         print_results((recall if recall is not None else run_recall)(config, log, load), write)
     elif args.command == "inspect":
         config = InspectConfig(args.index, args.vectors, args.worst if args.worst is not None else 10)
@@ -446,7 +526,7 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
             return 1
         write(f"{u.added} added, {u.replaced} replaced, {u.removed} removed, {u.ignored} ignored\n")
     elif args.command == "query-words":
-        index = _refined(args, load(args.index), vectors)
+        index = _refined(args, load(args.index), vectors, load)
         if args.file is None:
             data = stdin.read()
         else:
@@ -456,7 +536,7 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
     else:
         from .word_vectors import read_word2vec
         queries = read_word2vec(args.file)
-        index = _refined(args, load(args.index), vectors)
+        index = _refined(args, load(args.index), vectors, load)
         query(index, args.neighbours, queries, write)
     stdout.flush()
     return 0

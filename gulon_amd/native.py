@@ -175,6 +175,14 @@ SIGNATURES = {
     "gulon_index_row_errors_dev": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _f64p, _vp]),
     "gulon_grouped_index_row_errors": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _f64p]),
     "gulon_grouped_index_row_errors_dev": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _f64p, _vp]),
+    "gulon_index_row_residuals": (_i32, [_vp, _vp, _i32p, _i32p, _i32, C.POINTER(_vp)]),
+    "gulon_grouped_index_row_residuals": (_i32, [_vp, _vp, _i32p, _i32p, _i32, C.POINTER(_vp)]),
+    "gulon_index_refine_codes_topk": (_i32, [_vp, _vp, _f32p, _i32, _i32p, _i32, _vp, _i32, _i32, _i32p, _f32p, _i32p]),
+    "gulon_index_refine_codes_topk_dev": (_i32, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "gulon_grouped_index_refine_codes_topk": (_i32, [_vp, _vp, _f32p, _i32, _i32p, _i32, _vp, _i32, _i32, _i32p, _f32p,
+                                                     _i32p]),
+    "gulon_grouped_index_refine_codes_topk_dev": (_i32, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp,
+                                                         _vp]),
 }
 
 _lib = None

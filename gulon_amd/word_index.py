@@ -69,6 +69,13 @@ class WordIndex:
         from .refine import RefinedIndex
         return RefinedIndex(self, vectors, candidates)
 
+    def fine_refined(self, fine, candidates):
+        """This index with its results re-ranked against its fine index `fine` (fine.FineRefinedIndex; a WordIndex from
+        fine.build_fine_index or the build-fine command): `candidates` index results per query, the k nearest of them by
+        their distance to the two-level reconstruction.  No original vectors are needed."""
+        from .fine import FineRefinedIndex
+        return FineRefinedIndex(self, fine, candidates)
+
     def inspect(self, vectors=None, worst=10):
         """The diagnostics of this index (inspect.IndexReport): its shape and how its code books are used; with
         `vectors` (DeviceWordVectors with a key index; the normalised reading for a cosine index), matched to the
@@ -237,6 +244,9 @@ class RestrictedWordIndex(WordIndex):
 
     def refined(self, vectors, candidates):
         raise NotImplementedError("refined is not supported by a restricted index")
+
+    def fine_refined(self, fine, candidates):
+        raise NotImplementedError("fine_refined is not supported by a restricted index")
 
     def inspect(self, vectors=None, worst=10):
         raise NotImplementedError("inspect is not supported by a restricted index")

@@ -671,6 +671,54 @@ int32_t gulon_grouped_index_row_errors_dev(gulon_grouped_index *idx, const gulon
                                            float *d_row_error, float *d_row_norm_sq, double *quantizer_error,
                                            void *stream);
 
+/* ---- Fine codes (fine.hip; DESIGN.md "Fine codes") -------------------------------------------------------------------
+ * A second quantizer over the residuals an index leaves, and the index's candidates re-ranked against the two-level
+ * reconstruction.  y_r is the vector the index's distances are about for row r, exactly as for gulon_*_row_errors: the
+ * decode of row r for a flat index, centroid(g) + decode(r) for a grouped one (MathUtils.add, MathUtils.scala:63-71; g
+ * the group whose row range holds r).  Rows are LOCAL rows (a view: its own positions).  Both calls use scratch of their
+ * own and leave no trace on the handles.
+ *
+ * gulon_*_row_residuals: *out = a new device dataset of s x d with
+ *   out[t][e] = vectors[vector_rows[t]][e] - y_{rows[t]}[e]     (MathUtils.subtract, MathUtils.scala:74-83: one binary32
+ *                                                                subtraction per coordinate), t < s.
+ * rows / vector_rows: host arrays of s entries, any order, repeats allowed.  Every entry is checked before anything is
+ * launched: an entry outside [0, n) resp. [0, vectors->n) is GULON_ERR_INVALID_ARGUMENT, the message naming the first
+ * offending position.  vectors->d must equal the index's.  s = 0 gives an empty dataset. */
+int32_t gulon_index_row_residuals(gulon_index *idx, const gulon_dataset *vectors, const int32_t *rows,
+                                  const int32_t *vector_rows, int32_t s, gulon_dataset **out);
+int32_t gulon_grouped_index_row_residuals(gulon_grouped_index *idx, const gulon_dataset *vectors, const int32_t *rows,
+                                          const int32_t *vector_rows, int32_t s, gulon_dataset **out);
+/* gulon_*_refine_codes_topk: gulon_refine_topk with the two-level reconstruction in the place of the original vectors --
+ * per query
+ *   heap = TopKHeap(k_nn); for p = 0 .. c-1, in that order, with id = cand_rows[q][p] >= 0:
+ *     z[e] = y_id[e] + decode_fine(fine_map ? fine_map[id] : id)[e]     (y_id[e] formed first, the fine coordinate added
+ *                                                                        last: one binary32 add each)
+ *     heap.update(id, MathUtils.distanceSq(query_q, z));   Result.fromHeap(heap)
+ * (TopKHeap.scala:69-79, MathUtils.scala:85-95 -- the sum of (z_e - q_e)^2, e ascending, unfused -- Index.scala:83-94).
+ * `fine` is an ordinary flat index over the residuals; the two handles must agree in d and in nothing else (m, k and code
+ * layout are independent).  Arguments, outputs and conventions are those of gulon_refine_topk: negative candidates are
+ * padding, 1 <= k_nn <= c <= GULON_MAX_K_PEELED (a larger c: GULON_ERR_UNSUPPORTED), out_idx the candidates' own ids,
+ * -1 / 0 after a query's last entry.  A candidate outside the coarse index or the map, or whose fine row is outside
+ * `fine`, is GULON_ERR_INVALID_ARGUMENT (found on the device; the outputs are then undefined).  Device form: every
+ * pointer but the handles is a device pointer, the work is enqueued on `stream` and not synchronised, nothing is
+ * allocated; a query with such a candidate gets d_out_count[q] = -1. */
+int32_t gulon_index_refine_codes_topk(gulon_index *coarse, gulon_index *fine, const float *queries, int32_t b,
+                                      const int32_t *cand_rows, int32_t c, const int32_t *fine_map, int32_t map_len,
+                                      int32_t k_nn, int32_t *out_idx, float *out_dist, int32_t *out_count);
+int32_t gulon_index_refine_codes_topk_dev(gulon_index *coarse, gulon_index *fine, const float *d_queries, int32_t b,
+                                          const int32_t *d_cand_rows, int32_t c, const int32_t *d_fine_map,
+                                          int32_t map_len, int32_t k_nn, int32_t *d_out_idx, float *d_out_dist,
+                                          int32_t *d_out_count, void *stream);
+int32_t gulon_grouped_index_refine_codes_topk(gulon_grouped_index *coarse, gulon_index *fine, const float *queries,
+                                              int32_t b, const int32_t *cand_rows, int32_t c, const int32_t *fine_map,
+                                              int32_t map_len, int32_t k_nn, int32_t *out_idx, float *out_dist,
+                                              int32_t *out_count);
+int32_t gulon_grouped_index_refine_codes_topk_dev(gulon_grouped_index *coarse, gulon_index *fine,
+                                                  const float *d_queries, int32_t b, const int32_t *d_cand_rows,
+                                                  int32_t c, const int32_t *d_fine_map, int32_t map_len, int32_t k_nn,
+                                                  int32_t *d_out_idx, float *d_out_dist, int32_t *d_out_count,
+                                                  void *stream);
+
 #ifdef __cplusplus
 }
 #endif
