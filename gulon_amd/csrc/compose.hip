@@ -1,7 +1,7 @@
 // Expression queries (DESIGN.md "Expression queries"): a weighted sum of stored rows as the query, and the operands
 // removed from its answer, without leaving the device.
 //   compose_rows_kernel   term lists (CSR: offsets, rows, weights) -> query vectors.  Per term Index.lookup(row) --
-//                         the decode of decode.hip, with the group base for a GroupedIndex -- optionally
+//                         row_decode.hpp's decoded_coordinate, with lookup_base for a GroupedIndex -- optionally
 //                         MathUtils.normalize (MathUtils.scala:100-120); per coordinate
 //                           acc = w_0 * v_0[e];  acc = acc + (w_t * v_t[e])  for t = 1, 2, ... in list order,
 //                         every product and every sum a binary32 operation of its own; optionally MathUtils.normalize

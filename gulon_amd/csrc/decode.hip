@@ -4,8 +4,9 @@
 //   MathUtils.normalize (MathUtils.scala:100-120), fused behind a flag        -- for cosine query-by-row
 //   ProductQuantizer.decode(EncodedMatrix) (ProductQuantizer.scala:58-78)  -- decode_range_kernel (bandwidth-bound)
 // A decoded coordinate is a copy of a codebook entry (plus one fp32 add for the grouped lookup), so results are
-// bit-exact by construction.  Codes are read in the layout the handle already keeps (row_decode.hpp, shared with
-// compose.hip).
+// bit-exact by construction.  Codes are read in the layout the handle already keeps, through row_decode.hpp (shared with
+// compose.hip, inspect.hip and fine.hip): decode_rows_kernel reads single codes (CodeSrc), decode_range_kernel a block
+// staged in LDS (StagedCodes).  Neither clamps a code to the code book.
 #include "normalize.hpp"
 #include "row_decode.hpp"
 
@@ -30,16 +31,8 @@ __global__ __launch_bounds__(64) void decode_rows_kernel(CodeSrc src, const floa
     return;
   }
   const SubvectorMap sv(d, src.m);
-  const float *base = nullptr;
-  if (gcent) {
-    const int i = java_binary_search(offsets, n_offsets, row);
-    base = gcent + (size_t)(i < 0 ? -i - 1 : i + 1) * d;
-  }
-  for (int e = lane; e < d; e += 64) {
-    const int j = sv.quantizer(e), fr = sv.from(j), sj = sv.sdim(j);
-    const float c = cents[(size_t)k * fr + (size_t)src.code(row, j) * sj + (e - fr)];
-    xs[e] = base ? base[e] + c : c;
-  }
+  const float *base = gcent ? lookup_base(gcent, offsets, n_offsets, row, d) : nullptr;
+  for (int e = lane; e < d; e += 64) xs[e] = decoded_coordinate(src, sv, cents, k, row, e, base);
   if (!normalize) {
     for (int e = lane; e < d; e += 64) o[e] = xs[e];
     return;
@@ -49,7 +42,7 @@ __global__ __launch_bounds__(64) void decode_rows_kernel(CodeSrc src, const floa
 }
 
 // Rows [from, until) into out[(i - from) * d + e].  One workgroup per 64-row block: the block's codes are staged in LDS
-// once (16-byte loads), then the block's slice of the output -- contiguous in row-major order -- is written with
+// once (StagedCodes), then the block's slice of the output -- contiguous in row-major order -- is written with
 // 16-byte stores, consecutive lanes on consecutive addresses (VEC4: d % 4 == 0, so a float4 never spans two rows and
 // every row starts 16-byte aligned).  Centroids are read through the caches (k * d * 4 bytes).
 constexpr int DR_THREADS = 256;
@@ -61,21 +54,14 @@ __global__ __launch_bounds__(DR_THREADS) void decode_range_kernel(CodeSrc src, c
   const int rb = rb0 + blockIdx.x;
   const int tid = threadIdx.x;
   const int m = src.m;
-  // stage: byte layout [ng][64][vec] bytes, wide [m][64] uint16 -- both contiguous per block, multiples of 16 bytes
-  const int chunk = WIDE ? m * 128 : src.ng * 64 * src.vec;
-  const uint4 *gsrc = WIDE ? (const uint4 *)(src.wcodes + (size_t)rb * m * 64)
-                           : (const uint4 *)(src.codes + (size_t)rb * chunk);
-  for (int t = tid; t < chunk / 16; t += DR_THREADS) ((uint4 *)lcode)[t] = gsrc[t];
+  const StagedCodes<WIDE> staged{lcode, src.vec};
+  staged.stage(src, rb, tid, DR_THREADS);
   __syncthreads();
   const int r_lo = max(rb * 64, from), r_hi = min(rb * 64 + 64, until);
   const SubvectorMap sv(d, m);
-  auto code_of = [&](int l, int j) -> int {
-    if (WIDE) return ((const uint16_t *)lcode)[j * 64 + l];
-    return lcode[(j / src.vec) * 64 * src.vec + l * src.vec + j % src.vec];
-  };
   auto value = [&](int l, int e) -> float {
     const int j = sv.quantizer(e), fr = sv.from(j), sj = sv.sdim(j);
-    return cents[(size_t)k * fr + (size_t)code_of(l, j) * sj + (e - fr)];
+    return cents[(size_t)k * fr + (size_t)staged.code(l, j) * sj + (e - fr)];
   };
   float *o = out + (size_t)(r_lo - from) * d;
   const int total = (r_hi - r_lo) * d;          // floats of this block's output
@@ -129,14 +115,12 @@ void launch_decode_range(const gulon_index *ix, int from, int until, float *d_ou
   GULON_REQUIRE(0 <= from && from <= until && until <= ix->n, "expected: 0 <= from <= until <= length");
   if (from == until) return;
   const int rb0 = from / 64, nrb = ceil_div(until, 64) - rb0;
-  const size_t lds = ix->wide ? (size_t)ix->m * 128 : (size_t)ix->ng * 64 * ix->vec;
+  const size_t lds = block_code_bytes(ix);
   GULON_UNSUPPORTED(lds > 64 * 1024, "m = %d: one row block's codes do not fit in LDS", ix->m);
-  const bool v4 = ix->d % 4 == 0;
-#define DR(W, V) hipLaunchKernelGGL((decode_range_kernel<W, V>), dim3(nrb), dim3(DR_THREADS), lds, st, code_src(ix), \
-                                    ix->cents.p, ix->d, ix->k, from, until, rb0, d_out)
-  if (ix->wide) { if (v4) DR(true, true); else DR(true, false); }
-  else { if (v4) DR(false, true); else DR(false, false); }
-#undef DR
+  dispatch_flags(ix->wide, ix->d % 4 == 0, [&](auto wide, auto vec4) {
+    hipLaunchKernelGGL((decode_range_kernel<wide.value, vec4.value>), dim3(nrb), dim3(DR_THREADS), lds, st, code_src(ix),
+                       ix->cents.p, ix->d, ix->k, from, until, rb0, d_out);
+  });
   HIP_CHECK(hipGetLastError());
 }
 

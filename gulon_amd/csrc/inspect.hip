@@ -7,13 +7,14 @@
 //                    of quantizer j (Vectors.subvectors ranges)                                  -- row_errors_kernel
 // y_r is the vector the index's distances are about.  Flat index: ProductQuantizer.decode of row r
 // (ProductQuantizer.scala:37-50).  Grouped index: centroid(c) + decode(r), one fp32 add per coordinate (MathUtils.add),
-// c = the group whose range [bounds[c], bounds[c + 1]) holds r -- the group a query scans the row in.  That is
-// deliberately NOT the partition GroupedIndex.lookup finds with Arrays.binarySearch over the raw offsets
-// (gulon_grouped_index_lookup_rows): where offsets repeat (empty groups) that rule can name another group, whose
-// centroid no query ever pairs with the row.
-// Codes are read in the layout the handle keeps (row_decode.hpp); nothing decoded is written to HBM.  The calls use
-// scratch of their own: a handle keeps no trace of them.
+// c = the group whose range [bounds[c], bounds[c + 1]) holds r -- row_decode.hpp's group_centroid, deliberately NOT the
+// partition of GroupedIndex.lookup (the two rules are set side by side there).
+// Codes are read in the layout the handle keeps: the row errors walk a staged block (row_decode.hpp StagedCodes, RowWalk,
+// clamped to the code book) beside the gathered tile of the originals (row_tile.hpp); the histogram reads whole code
+// words itself, every quantizer of a word unrolled.  Nothing decoded is written to HBM.  The calls use scratch of their
+// own: a handle keeps no trace of them.
 #include "row_decode.hpp"
+#include "row_tile.hpp"
 
 namespace gulon {
 namespace {
@@ -76,8 +77,9 @@ __global__ __launch_bounds__(IH_THREADS) void code_histogram_kernel(CodeSrc src,
   }
 }
 
-// out (host): [m][k] int64; mu: the lock of the handle the caller was given
-void code_histogram(gulon_index *ix, std::mutex &mu, int from, int until, int64_t *out) {
+// out (host): [m][k] int64
+void code_histogram(const IndexRef &r, int from, int until, int64_t *out) {
+  gulon_index *ix = r.ix;
   GULON_REQUIRE(out != nullptr, "out is null");
   GULON_REQUIRE(0 <= from && from <= until && until <= ix->n, "expected: 0 <= from <= until <= length");
   const size_t cells = (size_t)ix->m * ix->k;
@@ -86,8 +88,8 @@ void code_histogram(gulon_index *ix, std::mutex &mu, int from, int until, int64_
     memset(out, 0, cells * sizeof(int64_t));
     return;
   }
-  GULON_REQUIRE(ix->vec == 4 || ix->vec == 16 || ix->wide, "unexpected code word of %d bytes", ix->vec);
-  std::lock_guard<std::mutex> lock(mu);
+  require_code_layout(ix);
+  std::lock_guard<std::mutex> lock(*r.mu);
   DevBuf<unsigned long long> d_out(cells);
   StreamOrder so(ix, nullptr);
   HIP_CHECK(hipMemsetAsync(d_out.p, 0, cells * sizeof(unsigned long long), nullptr));
@@ -96,11 +98,10 @@ void code_histogram(gulon_index *ix, std::mutex &mu, int from, int until, int64_
   // few workgroups, many blocks each: every workgroup clears and flushes m * k counters
   const int grid = std::max(1, std::min(1024, ceil_div(nrb, IH_WAVES * 16)));
   const size_t lds = in_lds ? cells * sizeof(unsigned) : 0;
-#define IH(W, L) hipLaunchKernelGGL((code_histogram_kernel<W, L>), dim3(grid), dim3(IH_THREADS), lds, nullptr, \
-                                    code_src(ix), ix->k, from, until, rb0, nrb, d_out.p)
-  if (ix->wide) { if (in_lds) IH(true, true); else IH(true, false); }
-  else { if (in_lds) IH(false, true); else IH(false, false); }
-#undef IH
+  dispatch_flags(ix->wide, in_lds, [&](auto wide, auto lds_counts) {
+    hipLaunchKernelGGL((code_histogram_kernel<wide.value, lds_counts.value>), dim3(grid), dim3(IH_THREADS), lds, nullptr,
+                       code_src(ix), ix->k, from, until, rb0, nrb, d_out.p);
+  });
   HIP_CHECK(hipGetLastError());
   so.done();
   static_assert(sizeof(unsigned long long) == sizeof(int64_t), "counts are downloaded as they are");
@@ -110,35 +111,28 @@ void code_histogram(gulon_index *ix, std::mutex &mu, int from, int until, int64_
 
 // ---- row errors --------------------------------------------------------------------------------------------------
 // One wavefront per 64-row block, lane = row: MathUtils.distanceSq is one running binary32 sum over e ascending, so a
-// row's coordinates are never reduced across lanes.  The block's codes are staged in LDS once (16-byte loads, as
-// decode_range_kernel does); the 64 originals V[map[r]] go through an LDS tile RE_DT coordinates at a time (row_tile.hpp's
-// scheme: eight lanes read the 128 bytes of one row with a 16-byte load each, so the loads are coalesced per row
-// although the map scatters the rows; the tile is padded to RE_DT + 1 floats for the lane = row reads).  Code-book
+// row's coordinates are never reduced across lanes.  The block's codes are staged in LDS once (StagedCodes, as
+// decode_range_kernel does) and walked per lane by a RowWalk; the 64 originals V[map[r]] go through the gathered tile
+// (row_tile.hpp tile_load), so the loads are coalesced per row although the map scatters the rows.  Code-book
 // entries come through the caches.  One pass gives row_error, row_norm_sq and the per-quantizer sums p[r][j]; at the end
 // of every quantizer's coordinates the wave adds its 64 p up in binary64 and stores the block's partial sum
 // (qpart[block][j]); quantizer_error_kernel then adds the blocks up, in a fixed order: the result is deterministic.
 // A lane whose row is outside [from, until) takes no part; a map entry outside [0, vn) sets *bad and nothing is read for
 // that row.
-constexpr int RE_DT = 32;
-
 template <bool WIDE, bool VEC4>
 __global__ __launch_bounds__(64) void row_errors_kernel(CodeSrc src, const float *__restrict__ cents, int d, int k,
                                                         const float *__restrict__ X, int vn,
-                                                        const int *__restrict__ row_map, const float *__restrict__ gcent,
-                                                        const int *__restrict__ bounds, int g, int from, int until,
-                                                        int rb0, float *__restrict__ row_error,
+                                                        const int *__restrict__ row_map, GroupBase gb, int from,
+                                                        int until, int rb0, float *__restrict__ row_error,
                                                         float *__restrict__ row_norm_sq, double *__restrict__ qpart,
                                                         int *__restrict__ bad) {
-  __shared__ float xs[64 * (RE_DT + 1)];
+  __shared__ float xs[tile_floats(64)];
   __shared__ int rs[64];
   extern __shared__ __attribute__((aligned(16))) uint8_t re_code[];
   const int lane = threadIdx.x, m = src.m;
   const int rb = rb0 + blockIdx.x;
-  // stage: byte layout [ng][64][vec] bytes, wide [m][64] uint16 -- both contiguous per block, multiples of 16 bytes
-  const int chunk = WIDE ? m * 128 : src.ng * 64 * src.vec;
-  const uint4 *gsrc = WIDE ? (const uint4 *)(src.wcodes + (size_t)rb * m * 64)
-                           : (const uint4 *)(src.codes + (size_t)rb * chunk);
-  for (int t = lane; t < chunk / 16; t += 64) ((uint4 *)re_code)[t] = gsrc[t];
+  const StagedCodes<WIDE> staged{re_code, src.vec};
+  staged.stage(src, rb, lane, 64);
   const int row = rb * 64 + lane;
   const bool inside = row >= from && row < until;
   int vrow = -1;
@@ -148,72 +142,42 @@ __global__ __launch_bounds__(64) void row_errors_kernel(CodeSrc src, const float
   }
   rs[lane] = vrow;
   const bool active = vrow >= 0;
-  const float *base = nullptr;                  // grouped: the centroid of the row's own group
-  if (active && gcent) {
-    int lo = 0, hi = g;                         // largest c with bounds[c] <= row: [bounds[c], bounds[c + 1]) holds it
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (bounds[mid] <= row) lo = mid; else hi = mid; }
-    base = gcent + (size_t)lo * d;
-  }
+  const float *base = (active && gb.gcent) ? group_centroid(gb, row, d) : nullptr;   // the row's own group
   __syncthreads();
-  auto code_of = [&](int j) -> int {
-    const int c = WIDE ? ((const uint16_t *)re_code)[j * 64 + lane]
-                       : re_code[(j / src.vec) * 64 * src.vec + lane * src.vec + j % src.vec];
-    return min(c, k - 1);
-  };
-  const SubvectorMap sv(d, m);
+  RowWalk<StagedRow<WIDE>> y(StagedRow<WIDE>{staged, lane}, cents, d, m, k, k - 1);   // a code >= k reads as k - 1
+  y.enter_next();                               // quantizer 0
   double *qp = qpart + (size_t)blockIdx.x * m;
-  auto flush = [&](int j, float p) {            // all 64 lanes: the block's binary64 sum of p[r][j]
+  float err = 0.f, nrm = 0.f, p = 0.f;
+  auto flush = [&](int j) {                     // all 64 lanes: the block's binary64 sum of p[r][j]; p starts again
     double v = active ? (double)p : 0.0;
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
     if (lane == 0) qp[j] = v;
+    p = 0.f;
   };
-  int j = 0, jfrom = 0, jend = sv.sdim(0);
-  const float *cj = active ? cents + (size_t)code_of(0) * sv.sdim(0) : nullptr;   // entry of quantizer j for this row
-  float err = 0.f, nrm = 0.f, p = 0.f;
-  for (int d0 = 0; d0 < d; d0 += RE_DT) {
+  for (int d0 = 0; d0 < d; d0 += RC_DT) {
     __syncthreads();                            // the previous step's tile has been read
-    if (VEC4) {
-      for (int e = lane; e < 64 * (RE_DT / 4); e += 64) {
-        const int r = e / (RE_DT / 4), c = (e % (RE_DT / 4)) * 4;
-        const int rr = rs[r];
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (rr >= 0 && d0 + c < d) v = *(const f32x4 *)(X + (size_t)rr * d + d0 + c);
-        float *o = xs + r * (RE_DT + 1) + c;
-        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-      }
-    } else {
-      for (int e = lane; e < 64 * RE_DT; e += 64) {
-        const int r = e / RE_DT, c = e % RE_DT;
-        const int rr = rs[r];
-        xs[r * (RE_DT + 1) + c] = (rr >= 0 && d0 + c < d) ? X[(size_t)rr * d + d0 + c] : 0.f;
-      }
-    }
+    tile_load<64, VEC4>(xs, rs, X, d, d0, d);
     __syncthreads();
-    const int dl = min(RE_DT, d - d0);
+    const int dl = min(RC_DT, d - d0);
     for (int c = 0; c < dl; c++) {
       const int e = d0 + c;
-      while (e == jend && j + 1 < m) {          // (wave-uniform) quantizer j is complete
-        flush(j, p);
-        p = 0.f;
-        j++;
-        jfrom = jend;
-        jend += sv.sdim(j);
-        if (active) cj = cents + (size_t)k * jfrom + (size_t)code_of(j) * sv.sdim(j);
+      if (y.behind(e)) {                        // (wave-uniform) quantizer y.j is complete
+        flush(y.j);
+        y.enter_next();
       }
       if (active) {
-        const float x = xs[lane * (RE_DT + 1) + c];
-        const float ce = cj[e - jfrom];
-        const float y = base ? base[e] + ce : ce;           // MathUtils.add
-        const float t = x - y;                              // MathUtils.distanceSq: unfused, e ascending
+        const float x = tile_at(xs, lane, c);
+        const float ce = y.at(e);
+        const float yv = base ? base[e] + ce : ce;          // MathUtils.add
+        const float t = x - yv;                             // MathUtils.distanceSq: unfused, e ascending
         err += t * t;
         p += t * t;
         nrm += x * x;
       }
     }
   }
-  flush(j, p);
-  for (int jj = j + 1; jj < m; jj++) flush(jj, 0.f);        // quantizers without coordinates (d < m)
+  flush(y.j);
   if (inside) {
     row_error[row - from] = err;
     if (row_norm_sq) row_norm_sq[row - from] = nrm;
@@ -237,8 +201,6 @@ __global__ __launch_bounds__(256) void quantizer_error_kernel(const double *__re
   if (tid == 0) out[j] = acc[0];
 }
 
-struct GroupBase { const float *gcent; const int *bounds; int g; };
-
 void check_row_error_args(const gulon_index *ix, const gulon_dataset *ds, bool have_map, int map_len, int from,
                           int until, const double *quantizer_error) {
   GULON_REQUIRE(ds != nullptr, "vectors is null");
@@ -256,20 +218,20 @@ void run_row_errors(gulon_index *ix, const gulon_dataset *ds, const int *d_map, 
   for (int j = 0; j < m; j++) quantizer_error[j] = 0.0;
   if (from == until) return;
   GULON_REQUIRE(d_err != nullptr, "row_error is null");
-  const size_t lds = ix->wide ? (size_t)m * 128 : (size_t)ix->ng * 64 * ix->vec;
-  GULON_UNSUPPORTED(lds + sizeof(float) * 64 * (RE_DT + 2) > 64 * 1024, "m = %d: one row block's codes do not fit in LDS", m);
+  const size_t lds = block_code_bytes(ix);
+  GULON_UNSUPPORTED(lds + sizeof(float) * (tile_floats(64) + 64) > 64 * 1024,
+                    "m = %d: one row block's codes do not fit in LDS", m);
   const int rb0 = from / 64, nrb = ceil_div(until, 64) - rb0;
   DevBuf<double> qpart((size_t)nrb * m), qsum((size_t)m);
   DevBuf<int> bad(1);
   StreamOrder so(ix, st);
   HIP_CHECK(hipMemsetAsync(bad.p, 0, sizeof(int), st));
   const bool v4 = ix->d % 4 == 0 && (uintptr_t)ds->x.p % 16 == 0;
-#define RE(W, V) hipLaunchKernelGGL((row_errors_kernel<W, V>), dim3(nrb), dim3(64), lds, st, code_src(ix), ix->cents.p, \
-                                    ix->d, ix->k, ds->x.p, ds->n, d_map, gb.gcent, gb.bounds, gb.g, from, until, rb0,   \
-                                    d_err, d_norm, qpart.p, bad.p)
-  if (ix->wide) { if (v4) RE(true, true); else RE(true, false); }
-  else { if (v4) RE(false, true); else RE(false, false); }
-#undef RE
+  dispatch_flags(ix->wide, v4, [&](auto wide, auto vec4) {
+    hipLaunchKernelGGL((row_errors_kernel<wide.value, vec4.value>), dim3(nrb), dim3(64), lds, st, code_src(ix),
+                       ix->cents.p, ix->d, ix->k, ds->x.p, ds->n, d_map, gb, from, until, rb0, d_err, d_norm, qpart.p,
+                       bad.p);
+  });
   HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(quantizer_error_kernel, dim3(m), dim3(256), 0, st, qpart.p, nrb, m, qsum.p);
   HIP_CHECK(hipGetLastError());
@@ -281,26 +243,25 @@ void run_row_errors(gulon_index *ix, const gulon_dataset *ds, const int *d_map, 
   GULON_REQUIRE(!h_bad, "a row map entry of rows [%d, %d) lies outside the %d vectors", from, until, ds->n);
 }
 
-void row_errors_dev(gulon_index *ix, std::mutex &mu, GroupBase gb, const gulon_dataset *ds, const int *d_map,
-                    int map_len, int from, int until, float *d_err, float *d_norm, double *quantizer_error,
-                    hipStream_t st) {
-  check_row_error_args(ix, ds, d_map != nullptr, map_len, from, until, quantizer_error);
-  std::lock_guard<std::mutex> lock(mu);
-  run_row_errors(ix, ds, d_map, gb, from, until, d_err, d_norm, quantizer_error, st);
+void row_errors_dev(const IndexRef &r, const gulon_dataset *ds, const int *d_map, int map_len, int from, int until,
+                    float *d_err, float *d_norm, double *quantizer_error, hipStream_t st) {
+  check_row_error_args(r.ix, ds, d_map != nullptr, map_len, from, until, quantizer_error);
+  std::lock_guard<std::mutex> lock(*r.mu);
+  run_row_errors(r.ix, ds, d_map, r.gb, from, until, d_err, d_norm, quantizer_error, st);
 }
 
-void row_errors_host(gulon_index *ix, std::mutex &mu, GroupBase gb, const gulon_dataset *ds, const int *row_map,
-                     int map_len, int from, int until, float *row_error, float *row_norm_sq,
-                     double *quantizer_error) {
+void row_errors_host(const IndexRef &r, const gulon_dataset *ds, const int *row_map, int map_len, int from, int until,
+                     float *row_error, float *row_norm_sq, double *quantizer_error) {
+  gulon_index *ix = r.ix;
   check_row_error_args(ix, ds, row_map != nullptr, map_len, from, until, quantizer_error);
   const size_t rows = (size_t)(until - from);
   GULON_REQUIRE(rows == 0 || row_error != nullptr, "row_error is null");
-  std::lock_guard<std::mutex> lock(mu);
+  std::lock_guard<std::mutex> lock(*r.mu);
   DevBuf<int> dmap;
   DevBuf<float> derr(rows), dnorm(row_norm_sq ? rows : 0);
   if (row_map && map_len) dmap.upload(row_map, (size_t)map_len);
   try {
-    run_row_errors(ix, ds, row_map ? dmap.p : nullptr, gb, from, until, derr.p, row_norm_sq ? dnorm.p : nullptr,
+    run_row_errors(ix, ds, row_map ? dmap.p : nullptr, r.gb, from, until, derr.p, row_norm_sq ? dnorm.p : nullptr,
                    quantizer_error, nullptr);
   } catch (const DeviceError &e) {
     if (e.code == GULON_ERR_INVALID_ARGUMENT && row_map)   // the device found it: name the offender
@@ -314,36 +275,25 @@ void row_errors_host(gulon_index *ix, std::mutex &mu, GroupBase gb, const gulon_
   HIP_CHECK(hipStreamSynchronize(nullptr));
 }
 
-GroupBase group_base(const GroupedParts &gp) { return {gp.gcent, gp.bounds, gp.g}; }
-
 }  // namespace
 }  // namespace gulon
 
 using namespace gulon;
 
 GULON_API int32_t gulon_index_code_histogram(gulon_index *idx, int32_t from, int32_t until, int64_t *out) {
-  return guarded([&] {
-    GULON_REQUIRE(idx != nullptr, "index is null");
-    code_histogram(idx, idx->mu, from, until, out);
-  });
+  return guarded([&] { code_histogram(index_ref(idx), from, until, out); });
 }
 
 GULON_API int32_t gulon_grouped_index_code_histogram(gulon_grouped_index *idx, int32_t from, int32_t until,
                                                      int64_t *out) {
-  return guarded([&] {
-    GULON_REQUIRE(idx != nullptr, "index is null");
-    const GroupedParts gp = grouped_parts(idx);
-    code_histogram(gp.pq, *gp.mu, from, until, out);
-  });
+  return guarded([&] { code_histogram(index_ref(idx), from, until, out); });
 }
 
 GULON_API int32_t gulon_index_row_errors(gulon_index *idx, const gulon_dataset *vectors, const int32_t *row_map,
                                          int32_t map_len, int32_t from, int32_t until, float *row_error,
                                          float *row_norm_sq, double *quantizer_error) {
   return guarded([&] {
-    GULON_REQUIRE(idx != nullptr, "index is null");
-    row_errors_host(idx, idx->mu, GroupBase{nullptr, nullptr, 0}, vectors, row_map, map_len, from, until, row_error,
-                    row_norm_sq, quantizer_error);
+    row_errors_host(index_ref(idx), vectors, row_map, map_len, from, until, row_error, row_norm_sq, quantizer_error);
   });
 }
 
@@ -351,9 +301,8 @@ GULON_API int32_t gulon_index_row_errors_dev(gulon_index *idx, const gulon_datas
                                              int32_t map_len, int32_t from, int32_t until, float *d_row_error,
                                              float *d_row_norm_sq, double *quantizer_error, void *stream) {
   return guarded([&] {
-    GULON_REQUIRE(idx != nullptr, "index is null");
-    row_errors_dev(idx, idx->mu, GroupBase{nullptr, nullptr, 0}, vectors, d_row_map, map_len, from, until, d_row_error,
-                   d_row_norm_sq, quantizer_error, (hipStream_t)stream);
+    row_errors_dev(index_ref(idx), vectors, d_row_map, map_len, from, until, d_row_error, d_row_norm_sq, quantizer_error,
+                   (hipStream_t)stream);
   });
 }
 
@@ -361,10 +310,7 @@ GULON_API int32_t gulon_grouped_index_row_errors(gulon_grouped_index *idx, const
                                                  const int32_t *row_map, int32_t map_len, int32_t from, int32_t until,
                                                  float *row_error, float *row_norm_sq, double *quantizer_error) {
   return guarded([&] {
-    GULON_REQUIRE(idx != nullptr, "index is null");
-    const GroupedParts gp = grouped_parts(idx);
-    row_errors_host(gp.pq, *gp.mu, group_base(gp), vectors, row_map, map_len, from, until, row_error, row_norm_sq,
-                    quantizer_error);
+    row_errors_host(index_ref(idx), vectors, row_map, map_len, from, until, row_error, row_norm_sq, quantizer_error);
   });
 }
 
@@ -373,9 +319,7 @@ GULON_API int32_t gulon_grouped_index_row_errors_dev(gulon_grouped_index *idx, c
                                                      int32_t until, float *d_row_error, float *d_row_norm_sq,
                                                      double *quantizer_error, void *stream) {
   return guarded([&] {
-    GULON_REQUIRE(idx != nullptr, "index is null");
-    const GroupedParts gp = grouped_parts(idx);
-    row_errors_dev(gp.pq, *gp.mu, group_base(gp), vectors, d_row_map, map_len, from, until, d_row_error, d_row_norm_sq,
-                   quantizer_error, (hipStream_t)stream);
+    row_errors_dev(index_ref(idx), vectors, d_row_map, map_len, from, until, d_row_error, d_row_norm_sq, quantizer_error,
+                   (hipStream_t)stream);
   });
 }

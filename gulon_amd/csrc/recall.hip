@@ -1,7 +1,7 @@
 // Tests.recallOf (Tests.scala:18-41), the per-batch part: for every query the exact MathUtils.distanceSq
 // (MathUtils.scala:85-95) to each returned row of the dataset and, for every k of the caller's list, the number of
-// entries among the first k whose distance is <= that k's cutoff.  One workgroup per query; the B x max_k distances
-// stay on the device unless the caller asks for them.
+// entries among the first k whose distance is <= that k's cutoff.  One workgroup per query, its rows gathered through
+// row_tile.hpp's tile; the B x max_k distances stay on the device unless the caller asks for them.
 #include "row_tile.hpp"
 
 namespace gulon {

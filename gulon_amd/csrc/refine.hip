@@ -3,13 +3,14 @@
 //   Result.fromHeap(heap)
 // (TopKHeap.scala:69-79, MathUtils.scala:85-95, Index.scala:83-94).  One workgroup per query: all of it gathers the
 // candidates' rows and sums their distances (row_tile.hpp, the bits of gulon_recall_counts), the c distances stay in
-// LDS, and the workgroup's first wave then replays them through the reference's heap in candidate order.
+// LDS, and the workgroup's first wave then replays them through the reference's heap in candidate order
+// (refine_replay.hpp, shared with fine.hip: resolve_candidate, the replay and its stores, the argument checks).
 #include "row_tile.hpp"
 #include "refine_replay.hpp"
 
 namespace gulon {
 
-// dyn: the query's c distances, then (k > GULON_MAX_K) the LdsHeap's k values and k keys.
+// dyn: refine_dyn_lds.
 // out_count[q] = the result's length, or -1 when a candidate of the query has no row in X (see gulon_hip.h).
 template <bool VEC4>
 __global__ __launch_bounds__(RC_THREADS) void refine_topk_kernel(
@@ -30,52 +31,22 @@ __global__ __launch_bounds__(RC_THREADS) void refine_topk_kernel(
   for (int p0 = 0; p0 < c; p0 += RC_THREADS) {
     const int p = p0 + tid;
     const int id = p < c ? qcand[p] : -1;
-    int row = id;
-    bool outside = false;
-    if (id >= 0) {
-      if (row_map != nullptr) {
-        outside = id >= map_len;
-        row = outside ? -1 : row_map[id];
-      }
-      outside = outside || row < 0 || row >= n;
-      if (outside) row = -1;                       // reported below; the entry is not read
-    }
-    const float acc = tile_distance_sq<VEC4>(tile, X, d, query, row, !whole_query || p0 == 0);
-    if (outside) bad = 1;
+    const Candidate cd = resolve_candidate(id, row_map, map_len, n);   // outside: reported below, not read
+    const float acc = tile_distance_sq<VEC4>(tile, X, d, query, cd.row, !whole_query || p0 == 0);
+    if (cd.outside) bad = 1;
     if (p < c) sd[p] = acc;
   }
   __syncthreads();
   if (wave != 0) return;
 
-  int *oi = out_idx + (size_t)q * k;
-  float *od = out_dist + (size_t)q * k;
-  int count;
-  auto put = [&](int i, int kk, float x) {
-    if (lane == 0) { oi[i] = kk; od[i] = x; }
-  };
-  if (k <= GULON_MAX_K) {
-    RegHeap h(k, lane);
-    refine_replay(h, qcand, sd, c, lane);
-    count = h.size;
-    h.drain(put);
-  } else {
-    LdsHeap h(rf_dyn + c, (int *)(rf_dyn + c + k), k, lane);
-    refine_replay(h, qcand, sd, c, lane);
-    count = h.size;
-    h.drain(put);
-  }
-  for (int i = count + lane; i < k; i += 64) { oi[i] = -1; od[i] = 0.f; }
-  if (lane == 0) out_count[q] = bad ? -1 : count;
+  refine_replay_store(qcand, sd, c, k, lane, bad != 0, out_idx + (size_t)q * k, out_dist + (size_t)q * k,
+                      out_count + q);
 }
-
-static size_t refine_dyn_lds(int c, int k) { return sizeof(float) * ((size_t)c + (k > GULON_MAX_K ? 2 * (size_t)k : 0)); }
 
 static void check_refine_args(const gulon_dataset *ds, int32_t b, int32_t c, const int32_t *row_map, int32_t map_len,
                               int32_t k_nn) {
   GULON_REQUIRE(ds != nullptr, "dataset is null");
-  GULON_REQUIRE(b >= 0 && k_nn >= 1 && c >= k_nn, "bad arguments b=%d c=%d k_nn=%d (1 <= k_nn <= c)", b, c, k_nn);
-  GULON_REQUIRE(row_map == nullptr || map_len >= 0, "map_len = %d", map_len);
-  GULON_UNSUPPORTED(c > GULON_MAX_K_PEELED, "c = %d > %d", c, GULON_MAX_K_PEELED);
+  check_refine_shape(b, c, row_map != nullptr, map_len, k_nn);
   // the tile, the c distances and the heap of k > GULON_MAX_K share one workgroup's LDS (160 KiB on gfx950)
   static_assert(sizeof(RowTile) + 64 + sizeof(float) * 3 * (size_t)GULON_MAX_K_PEELED <= 160 * 1024, "LDS");
 }
@@ -109,32 +80,16 @@ GULON_API int32_t gulon_refine_topk(const gulon_dataset *ds, const float *querie
                                     float *out_dist, int32_t *out_count) {
   return guarded([&] {
     check_refine_args(ds, b, c, row_map, map_len, k_nn);
-    if (b == 0) return;
-    GULON_REQUIRE(queries && cand_rows && out_idx && out_dist && out_count, "null argument");
-    const size_t bc = (size_t)b * c, bk = (size_t)b * k_nn;
-    DevBuf<float> dq, dod(bk);
-    DevBuf<int> dc, dmap, doi(bk), doc((size_t)b);
-    dq.upload(queries, (size_t)b * ds->d);
-    dc.upload(cand_rows, bc);
-    if (row_map != nullptr) dmap.upload(row_map, (size_t)map_len);
-    // (an empty map still has to read as a map: every candidate is then outside it)
-    const int32_t *map_arg = row_map == nullptr ? nullptr : (map_len ? dmap.p : (const int32_t *)dc.p);
-    const int32_t rc = gulon_refine_topk_dev(ds, dq.p, b, dc.p, c, map_arg, map_len, k_nn, doi.p, dod.p, doc.p, nullptr);
-    if (rc != GULON_OK) throw DeviceError{rc};
-    doi.download(out_idx, bk);
-    dod.download(out_dist, bk);
-    doc.download(out_count, (size_t)b);
-    HIP_CHECK(hipDeviceSynchronize());
-    for (int q = 0; q < b; q++) {
-      if (out_count[q] >= 0) continue;
-      for (int p = 0; p < c; p++) {                // name the offender
-        const int id = cand_rows[(size_t)q * c + p];
-        if (id < 0) continue;
-        GULON_REQUIRE(row_map == nullptr || id < map_len, "candidate row %d outside the row map [0,%d)", id, map_len);
-        const int row = row_map ? row_map[id] : id;
-        GULON_REQUIRE(row >= 0 && row < ds->n, "row %d out of range [0,%d)", row, ds->n);
-      }
-      GULON_REQUIRE(false, "query %d has a candidate row outside the dataset", q);
-    }
+    refine_host_form(ds->d, queries, b, cand_rows, c, row_map, map_len, k_nn, out_idx, out_dist, out_count,
+                     [&](const float *dq, const int *dc, const int *dmap, int *doi, float *dod, int *doc) {
+                       const int32_t rc =
+                           gulon_refine_topk_dev(ds, dq, b, dc, c, dmap, map_len, k_nn, doi, dod, doc, nullptr);
+                       if (rc != GULON_OK) throw DeviceError{rc};
+                     });
+    name_refine_offender(out_count, cand_rows, b, c, "dataset", [&](int id) {
+      GULON_REQUIRE(row_map == nullptr || id < map_len, "candidate row %d outside the row map [0,%d)", id, map_len);
+      const int row = row_map ? row_map[id] : id;
+      GULON_REQUIRE(row >= 0 && row < ds->n, "row %d out of range [0,%d)", row, ds->n);
+    });
   });
 }

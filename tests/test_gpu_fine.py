@@ -304,6 +304,8 @@ RERANK_CASES = [
     (48, 17, 100, 10, "vec4", "vec16"), (48, 17, 100, 10, "vec16", "ng"), (48, 17, 100, 10, "ng", "vec16x2"),
     (48, 17, 100, 10, "vec16x2", "vec4"), (48, 17, 100, 10, "wide", "vec4"), (48, 17, 100, 10, "grouped", "wide"),
     (7, 17, 63, 10, "grouped", "ng"), (48, 17, 1000, 64, "grouped", "vec4"),
+    # two walks of different layouts in one lane at d % 4 != 0; one pass of 256 lanes, 186 of them without a candidate
+    (26, 3, 70, 5, "wide", "vec4"),
 ]
 
 
