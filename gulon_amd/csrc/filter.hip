@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "scan.hpp"
+#include "select.hpp"
 
 namespace gulon {
 
@@ -37,12 +38,6 @@ constexpr size_t FILTER_LDS_BUDGET = 144 * 1024;
 constexpr int FILTER_THREADS = GULON_FILTER_THREADS;   // filter_kernel's workgroup
 constexpr int BOUND_THREADS = 1024;                     // bound_tables' workgroup
 constexpr int NSLOT = 16;   // survivor sub-queues per query (workgroups of different chunks use different ones)
-
-__device__ inline uint32_t pk_sub_sat_u16(uint32_t a, uint32_t b) {   // per 16-bit half: max(a - b, 0)
-  uint32_t d;
-  asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(d) : "v"(a), "v"(b));
-  return d;
-}
 
 // fp32 table entry (j, c) of query q; W queries are interleaved per entry (scan.hip build_tables)
 __device__ inline float table_at(const float *__restrict__ tables, int W, int m_pad, int q, int j, int c) {
@@ -151,59 +146,7 @@ __global__ __launch_bounds__(256) void qt_quantize(const float *__restrict__ tab
 // to K+1 distinct rows, so the (K+1)-th smallest group minimum bounds the final (K+1)-th
 // distance from above; with 1024 groups it is almost always the sample's own (K+1)-th distance.
 // Selection = one 64-lane bitonic sort per wave and query, then a sorted merge of the 16 waves.
-__device__ inline float sort64_asc(float x, int lane) {
-#pragma unroll
-  for (int k = 2; k <= 64; k <<= 1)
-#pragma unroll
-    for (int j = k >> 1; j >= 1; j >>= 1) {
-      const float y = __shfl_xor(x, j);
-      const bool up = (lane & k) == 0, lower = (lane & j) == 0;
-      x = (lower == up) ? fminf(x, y) : fmaxf(x, y);
-    }
-  return x;
-}
-// a, b ascending: the 64 smallest of both, ascending
-__device__ inline float merge64_asc(float a, float b, int lane) {
-  float x = fminf(a, __shfl(b, 63 - lane));   // bitonic sequence holding the 64 smallest
-#pragma unroll
-  for (int j = 32; j >= 1; j >>= 1) {
-    const float y = __shfl_xor(x, j);
-    x = (lane & j) == 0 ? fminf(x, y) : fmaxf(x, y);
-  }
-  return x;
-}
-
-// the same two networks for 64-bit keys (the survivor pass orders (distance bits << 32) | row id)
-__device__ inline unsigned long long shfl_u64(unsigned long long x, int src) {
-  const unsigned lo = (unsigned)__shfl((int)(unsigned)x, src), hi = (unsigned)__shfl((int)(unsigned)(x >> 32), src);
-  return ((unsigned long long)hi << 32) | lo;
-}
-__device__ inline unsigned long long shfl_xor_u64(unsigned long long x, int m) {
-  const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)x, m), hi = (unsigned)__shfl_xor((int)(unsigned)(x >> 32), m);
-  return ((unsigned long long)hi << 32) | lo;
-}
-__device__ inline unsigned long long sort64_u64(unsigned long long x, int lane) {
-#pragma unroll
-  for (int k = 2; k <= 64; k <<= 1)
-#pragma unroll
-    for (int j = k >> 1; j >= 1; j >>= 1) {
-      const unsigned long long y = shfl_xor_u64(x, j);
-      const bool up = (lane & k) == 0, lower = (lane & j) == 0;
-      x = (lower == up) ? (x < y ? x : y) : (x < y ? y : x);
-    }
-  return x;
-}
-// a, b ascending: the 64 smallest of both, ascending
-__device__ inline unsigned long long merge64_u64(unsigned long long a, unsigned long long b, int lane) {
-  const unsigned long long br = shfl_u64(b, 63 - lane);
-  unsigned long long x = a < br ? a : br;      // bitonic sequence holding the 64 smallest
-#pragma unroll
-  for (int j = 32; j >= 1; j >>= 1) {
-    const unsigned long long y = shfl_xor_u64(x, j);
-    x = (lane & j) == 0 ? (x < y ? x : y) : (x < y ? y : x);
-  }
-  return x;
-}
+// (sort64_asc / merge64_asc: select.hpp.)
 
 template <int W> struct FTab;
 template <> struct FTab<4> { using type = float4; };
@@ -403,8 +346,7 @@ __global__ __launch_bounds__(256) void shared_tau(const float *__restrict__ all 
   const int n = lists * keff;
   auto key_at = [&](int i) {
     const int l = i / keff, e = i - l * keff;
-    const uint32_t u = __float_as_uint(all[((size_t)l * B + q) * keff + e]);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);          // unsigned order = float order
+    return ordered_key(all[((size_t)l * B + q) * keff + e]);    // unsigned order = float order
   };
   constexpr int R = 4;                                           // values per lane held in registers
   uint32_t held[R];
@@ -422,7 +364,7 @@ __global__ __launch_bounds__(256) void shared_tau(const float *__restrict__ all 
     if (c < keff) t = cand;                                      // fewer than keff values below: go up
   }
   if (lane == 0) {
-    const float v = __uint_as_float((t & 0x80000000u) ? (t & 0x7FFFFFFFu) : ~t);
+    const float v = ordered_float(t);
     if (v == v) tau0[q] = fminf(tau0[q], v);
   }
 }
@@ -711,18 +653,7 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_kernel(
           const int q0 = (tile_l * NQG + s) * QW + 4 * (x >> 1) + (x & 1);
           // a full sub-queue means the bound separates nothing for this query: flag its tile at once, so that
           // the workgroups of the tile that have not started yet return immediately (the exact scan redoes it)
-          if (l & 0xFFFFu) {
-            const int sq = q0 * NSLOT + slot_l;
-            const int pos = atomicAdd(&cnt_l[sq], 1);
-            if (pos < cap) queue_l[(size_t)sq * cap + pos] = row;
-            else fb_l[q0 / qt] = 1;
-          }
-          if (l >> 16) {
-            const int sq = (q0 + 2) * NSLOT + slot_l;
-            const int pos = atomicAdd(&cnt_l[sq], 1);
-            if (pos < cap) queue_l[(size_t)sq * cap + pos] = row;
-            else fb_l[(q0 + 2) / qt] = 1;
-          }
+          enqueue_halves<NSLOT>(l, q0, slot_l, row, cnt_l, queue_l, cap, [&](int q) -> int & { return fb_l[q / qt]; });
         }
     }
   }
@@ -759,21 +690,15 @@ __global__ __launch_bounds__(64 * SV_WAVES * 4) void survivors_kernel(
       for (int e = tid; e < n16; e += 64 * SV_WAVES * W) dst[e] = __builtin_nontemporal_load(src + e);
   }
   // sub-queue fill levels -> exclusive offsets of a flat numbering of this query's survivors
-  int mine = lane < NSLOT ? cnt[q * NSLOT + lane] : 0;
+  SurvivorQueues<NSLOT> sq(cnt, q, lane);
   __syncthreads();                                  // every wave has read the counters; the table is in LDS
-  if (wave == 0 && lane < NSLOT) cnt[q * NSLOT + lane] = 0;
+  sq.clear(wave == 0);
   bool active = q < B;                              // (uniform per query; no early return: barriers below)
-  if (active && __ballot(mine > cap) != 0ull) {
+  if (active && sq.overflowed(cap)) {
     if (wave == 0 && lane == 0) fb_tile[q / qt] = 1;   // a sub-queue overflowed: the exact scan redoes this query tile
-    mine = min(mine, cap);
+    sq.clamp(cap);
   }
-  int incl = mine;
-#pragma unroll
-  for (int o = 1; o < NSLOT; o <<= 1) {
-    const int up = __shfl_up(incl, o);
-    if (lane >= o) incl += up;
-  }
-  int n = readlane_i(incl, NSLOT - 1);
+  int n = sq.count();
   if (active && give_up > 0 && n > give_up) {
     // the bound lets too many rows through for this query (data without a tail of near rows):
     // filtering the rest would cost more than it saves -- its tile goes to the exact scan
@@ -781,18 +706,7 @@ __global__ __launch_bounds__(64 * SV_WAVES * 4) void survivors_kernel(
     active = false;
   }
   if (!active) n = 0;
-  int start[NSLOT];
-#pragma unroll
-  for (int sl = 0; sl < NSLOT; sl++) start[sl] = readlane_i(incl - mine, sl);
-  auto entry = [&](int e) {   // e-th survivor of the query, e < n
-    int sl = 0;
-#pragma unroll
-    for (int x = 1; x < NSLOT; x++) sl += e >= start[x];
-    int off = start[0];
-#pragma unroll
-    for (int x = 1; x < NSLOT; x++) off = sl == x ? start[x] : off;
-    return queue[((size_t)q * NSLOT + sl) * cap + (e - off)];
-  };
+  auto entry = [&](int e) { return sq.entry(queue, q, cap, e); };   // e-th survivor of the query, e < n
 
   // The running list and every candidate as ONE 64-bit key, (distance bits << 32) | row id: distances are sums of
   // squares (>= +0, or NaN, which sorts behind +inf and never enters), so the unsigned order of the key is the
@@ -1077,39 +991,22 @@ __global__ __launch_bounds__(256) void rp_filter_emit(const uint8_t *__restrict_
   using Word = typename CodeWord<VEC>::type;
   // compact position fc (queues, bounds, flags) -> slot f (tables, candidate pool)
   const int fc = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-  int mine = lane < NSLOT ? cnt[fc * NSLOT + lane] : 0;
+  SurvivorQueues<NSLOT> sq(cnt, fc, lane);
   __syncthreads();                                  // every wave has read the counters
-  if (tid < NSLOT) cnt[fc * NSLOT + tid] = 0;
+  sq.clear(tid < NSLOT);
   if (fc >= min(*count, F)) return;
   const int f = order[fc];
   if (fb[fc] != 0) {
     if (tid == 0) scanme[f] = fb[fc] == 1;
     return;
   }
-  if (__ballot(mine > cap) != 0ull) {
+  if (sq.overflowed(cap)) {
     if (tid == 0) { fb[fc] = 1; scanme[f] = 1; }    // a sub-queue overflowed
     return;
   }
   if (tid == 0) scanme[f] = 0;
-  int incl = mine;
-#pragma unroll
-  for (int o = 1; o < NSLOT; o <<= 1) {
-    const int up = __shfl_up(incl, o);
-    if (lane >= o) incl += up;
-  }
-  const int n = readlane_i(incl, NSLOT - 1);
-  int start[NSLOT];
-#pragma unroll
-  for (int sl = 0; sl < NSLOT; sl++) start[sl] = readlane_i(incl - mine, sl);
-  auto entry = [&](int e) {
-    int sl = 0;
-#pragma unroll
-    for (int x = 1; x < NSLOT; x++) sl += e >= start[x];
-    int off = start[0];
-#pragma unroll
-    for (int x = 1; x < NSLOT; x++) off = sl == x ? start[x] : off;
-    return queue[((size_t)fc * NSLOT + sl) * cap + (e - off)];
-  };
+  const int n = sq.count();
+  auto entry = [&](int e) { return sq.entry(queue, fc, cap, e); };
   const float bound = tau[fc];
   const float *tq = tables + (size_t)f * m_pad * 256;
   const Word *cw = reinterpret_cast<const Word *>(codes);

@@ -27,6 +27,7 @@
 #include "scan.hpp"
 
 #include "grouped_filter.hpp"
+#include "select.hpp"
 #include "topk_heap.hpp"
 using gulon::DevBuf;
 
@@ -183,14 +184,14 @@ __global__ __launch_bounds__(256) void gq_select_groups(const float *__restrict_
   extern __shared__ float sel_lds[];
   float *sv = sel_lds;                                     // [cap]
   int *si = reinterpret_cast<int *>(sel_lds + cap);        // [cap]
-  __shared__ unsigned hist[256], hsub[256 * 8];   // (eight sub-counters per bin: centroid distances share their high bytes,
-  __shared__ unsigned s_prefix, s_remaining;      //  and 10 000 atomics on one or two LDS words serialise)
+  __shared__ unsigned hist[256], hsub[256 * 8];
+  __shared__ RadixSelectState s_sel;
   __shared__ int s_count, s_lit;
   const int q = blockIdx.x, tid = threadIdx.x;
   const float *dq = cdist + (size_t)q * g;
   auto keyof = [&](int c) { const float v = dq[c]; return v != v ? 0x7F800000u : __float_as_uint(v); };   // NaN orders last
   const int want = min(limit, g);
-  if (tid == 0) { s_prefix = 0u; s_remaining = (unsigned)want; s_count = 0; s_lit = 0; }
+  if (tid == 0) { s_count = 0; s_lit = 0; }
   constexpr int KRN = KR > 0 ? KR : 1;
   unsigned kreg[KRN];                                      // key of centroid tid + 256 r (0xFFFFFFFF: none)
   bool any_nan = false;
@@ -204,81 +205,25 @@ __global__ __launch_bounds__(256) void gq_select_groups(const float *__restrict_
     }
   }
   __syncthreads();
-  unsigned mask = 0u;
-  for (int shift = 24; shift >= 0; shift -= 8) {
-    for (int e = tid; e < 256 * 8; e += 256) hsub[e] = 0u;
-    __syncthreads();
-    const unsigned prefix = s_prefix;
+  auto each = [&](auto f) __attribute__((always_inline)) {   // f(key, centroid) for every key of this thread
     if (KR > 0) {
 #pragma unroll
-      for (int r = 0; r < KRN; r++) {
-        const unsigned key = kreg[r];
-        if (key != 0xFFFFFFFFu && (key & mask) == prefix) atomicAdd(&hsub[((key >> shift) & 255u) * 8 + (tid & 7)], 1u);
-      }
+      for (int r = 0; r < KRN; r++)
+        if (kreg[r] != 0xFFFFFFFFu) f(kreg[r], tid + 256 * r);
     } else {
-      for (int c = tid; c < g; c += 256) {
-        const unsigned key = keyof(c);
-        if ((key & mask) == prefix) atomicAdd(&hsub[((key >> shift) & 255u) * 8 + (tid & 7)], 1u);
-      }
+      for (int c = tid; c < g; c += 256) f(keyof(c), c);
     }
-    __syncthreads();
-    {
-      unsigned h = 0;
-#pragma unroll
-      for (int x = 0; x < 8; x++) h += hsub[tid * 8 + x];
-      hist[tid] = h;
+  };
+  auto keys = [&](auto f) __attribute__((always_inline)) { each([&](unsigned key, int) __attribute__((always_inline)) { f(key); }); };
+  const unsigned thr = block_radix_select<256>(keys, (unsigned)want, hsub, hist, s_sel);   // key of the want-th smallest distance
+  if (KR > 0 && any_nan) s_lit = 2;                        // NaN distance: literal heap (gq_literal_groups)
+  each([&](unsigned key, int c) __attribute__((always_inline)) {
+    if (KR == 0 && dq[c] != dq[c]) s_lit = 2;
+    if (key <= thr) {
+      const int p = atomicAdd(&s_count, 1);
+      if (p < cap) { sv[p] = __uint_as_float(key); si[p] = c; }
     }
-    __syncthreads();
-    if (tid < 64) {
-      // the bin in which the running count reaches `remaining`: four bins per lane, a prefix sum over the lanes
-      const unsigned h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
-      const unsigned mine = h0 + h1 + h2 + h3;
-      unsigned incl = mine;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned up = __shfl_up(incl, o);
-        if (tid >= o) incl += up;
-      }
-      const unsigned rem = s_remaining;
-      const unsigned long long reach = __ballot(incl >= rem);
-      // (the serial walk stopped at bin 255 at the latest: a total below `remaining` cannot happen -- every pass keeps
-      // at least `remaining` keys -- but the last lane takes it then, as the walk did)
-      const int first = reach ? __ffsll((long long)reach) - 1 : 63;
-      if (tid == first) {
-        unsigned cum = incl - mine;
-        int b = 4 * tid;
-        if (cum + h0 >= rem) { }
-        else if (cum + h0 + h1 >= rem) { cum += h0; b += 1; }
-        else if (cum + h0 + h1 + h2 >= rem) { cum += h0 + h1; b += 2; }
-        else { cum += h0 + h1 + h2; b += 3; }
-        s_remaining = rem - cum;
-        s_prefix = prefix | ((unsigned)b << shift);
-      }
-    }
-    mask |= 255u << shift;
-    __syncthreads();
-  }
-  const unsigned thr = s_prefix;                           // key of the want-th smallest distance
-  if (KR > 0) {
-    if (any_nan) s_lit = 2;                                // NaN distance: literal heap (gq_literal_groups)
-#pragma unroll
-    for (int r = 0; r < KRN; r++) {
-      const unsigned key = kreg[r];
-      if (key != 0xFFFFFFFFu && key <= thr) {
-        const int p = atomicAdd(&s_count, 1);
-        if (p < cap) { sv[p] = __uint_as_float(key); si[p] = tid + 256 * r; }
-      }
-    }
-  } else {
-    for (int c = tid; c < g; c += 256) {
-      const unsigned key = keyof(c);
-      if (dq[c] != dq[c]) s_lit = 2;                       // NaN distance: literal heap (gq_literal_groups)
-      if (key <= thr) {
-        const int p = atomicAdd(&s_count, 1);
-        if (p < cap) { sv[p] = __uint_as_float(key); si[p] = c; }
-      }
-    }
-  }
+  });
   __syncthreads();
   const int cnt = s_count;
   if (cnt > cap) {                                         // a huge tie at the threshold
@@ -602,12 +547,7 @@ __global__ __launch_bounds__(256) void gq_ptables(const float *__restrict__ pq_c
                                                   const float *__restrict__ Q, float *__restrict__ P) {
   const int c = threadIdx.x, j = blockIdx.x, q = blockIdx.y;
   float acc = 0.f;
-  if (j < m && c < k) {
-    const int fr = from[j], sj = sdim[j];
-    const float *cc = pq_cents + (size_t)k * fr + (size_t)c * sj;
-    for (int t = 0; t < sj; t++) acc += Q[(size_t)q * d + fr + t] * cc[t];
-    acc *= -2.0f;
-  }
+  if (j < m && c < k) acc = ptable_entry(Q, (size_t)q * d, pq_cents, from, sdim, k, j, c);
   P[((size_t)q * m_pad + j) * 256 + c] = acc;
 }
 
@@ -631,8 +571,7 @@ __global__ __launch_bounds__(64 * GA_WAVES) void gq_approx_scan(const uint8_t *_
   __syncthreads();
   float qq = 0.f;
   for (int e = lane; e < d; e += 64) qq += qv[e] * qv[e];
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) qq += __shfl_xor(qq, o);
+  qq = wave_sum(qq);
   WaveList wl;
   wl.init();
   int cnt = 0, saw_nan = 0;
@@ -643,8 +582,7 @@ __global__ __launch_bounds__(64 * GA_WAVES) void gq_approx_scan(const uint8_t *_
     const int row_from = bounds[c], row_until = bounds[c + 1];
     float qg = 0.f;
     for (int e = lane; e < d; e += 64) qg += qv[e] * gcent[(size_t)c * d + e];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) qg += __shfl_xor(qg, o);
+    qg = wave_sum(qg);
     const float base = qq - 2.0f * qg;
     const int rb_first = row_from >> 6, rb_end = (row_until + 63) >> 6;
     Word wnext{};
@@ -654,13 +592,9 @@ __global__ __launch_bounds__(64 * GA_WAVES) void gq_approx_scan(const uint8_t *_
       if (rb + 1 < rb_end) wnext = cw[((size_t)(rb + 1) * ng) * 64 + lane];
       const int row = rb * 64 + lane;
       const bool valid = row >= row_from && row < row_until;
-      float acc = base + (valid ? xnorm[row] : 0.f);
-      for (int gi = 0; gi < ng; gi++) {
-        const Word w = gi == 0 ? w0 : cw[((size_t)rb * ng + gi) * 64 + lane];
-        const float *tj = tab + gi * VEC * 256;
-#pragma unroll
-        for (int b = 0; b < VEC; b++) acc += tj[b * 256 + code_byte<VEC>(w, b)];
-      }
+      const float acc = approx_row_sum<VEC>(base + (valid ? xnorm[row] : 0.f), tab, ng, [=](int gi) {
+        return gi == 0 ? w0 : cw[((size_t)rb * ng + gi) * 64 + lane];
+      });
       if (__ballot(valid && acc != acc) != 0ull) saw_nan = 1;
       unsigned long long mk = __ballot(valid && (cnt < GA_C || wl.accepts(acc, row)));
       while (mk) {
@@ -681,7 +615,8 @@ __global__ __launch_bounds__(64 * GA_WAVES) void gq_approx_scan(const uint8_t *_
   if (lane == 0) nanflag[q * GA_WAVES + wave] = saw_nan;
 }
 
-// 64-lane bitonic sort of (value, id) pairs, ascending by (value, id); padding = (+inf, INT_MAX)
+// 64-lane bitonic sort of (value, id) pairs, ascending by (value, id); padding = (+inf, INT_MAX).  (select.hpp's network
+// with a step for pairs compiles gq_rerank to other code than this loop does: it keeps its own.)
 __device__ inline void sort64_pairs(float &v, int &id, int lane) {
 #pragma unroll
   for (int k = 2; k <= 64; k <<= 1)
@@ -714,8 +649,7 @@ __global__ __launch_bounds__(64) void gq_rerank(const uint8_t *__restrict__ code
   const float a_last = readlane_f(approx, GA_C - 1);          // the largest kept D~ (every other row's is >= it)
   float qq = 0.f;
   for (int e = lane; e < d; e += 64) { const float x = Q[(size_t)q * d + e]; qq += x * x; }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) qq += __shfl_xor(qq, o);
+  qq = wave_sum(qq);
   float D = INFINITY;
   if (have) {
     int lo = 0, hi = g;

@@ -26,6 +26,7 @@
 #include "grouped_filter.hpp"
 
 #include "scan.hpp"
+#include "select.hpp"
 
 namespace gulon {
 namespace {
@@ -40,32 +41,6 @@ constexpr float GF_SHRINK = 0.99999905f;        // 1 - 2^-20: a product of two r
 constexpr int GF_NADD = GULON_GF_NADD;          // table entries summed as bytes before a widening: 4 (6-bit levels), 2 (7-bit) or 1 (8-bit)
 constexpr int GF_SAT = 255 / GF_NADD;           // a saturated level: alone it exceeds any budget (63 / 127 / 255)
 constexpr float GF_LEVELS = (float)(GF_SAT - 3); // the largest budget in steps (two steps of slack below saturation)
-
-__device__ inline uint32_t gf_pk_sub_sat_u16(uint32_t a, uint32_t b) {   // per 16-bit half: max(a - b, 0)
-  uint32_t d;
-  asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(d) : "v"(a), "v"(b));
-  return d;
-}
-
-__device__ inline float gf_wave_sum(float x) {                          // gq_approx_scan's reduction order
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
-
-// the 16 code bytes of row `row` as four words: one 16-byte word per row (VEC = 16), or ng <= 4 four-byte words in
-// scan.hip's [row block][word][lane] layout (VEC = 4; quantizers from 4 ng on read as code 0: their tables are zero)
-template <int VEC>
-__device__ inline uint4 gf_row_words(const uint8_t *__restrict__ codes, int ng, int row) {
-  if constexpr (VEC == 16) return reinterpret_cast<const uint4 *>(codes)[row];
-  const uint32_t *cw = reinterpret_cast<const uint32_t *>(codes);
-  const size_t o = ((size_t)(row >> 6) * ng) * 64 + (row & 63);
-  uint4 w = uint4{cw[o], 0u, 0u, 0u};
-  if (ng > 1) w.y = cw[o + 64];
-  if (ng > 2) w.z = cw[o + 128];
-  if (ng > 3) w.w = cw[o + 192];
-  return w;
-}
 
 // ---- per index: 8-bit levels of the row norms above their group's smallest ----------------------------
 // (per group: |x^|^2 = |g|^2 + 2 g.r^ + |r^|^2 moves with the group; against one floor for the whole index most of a
@@ -103,7 +78,7 @@ __global__ void gf_gnorm(const float *__restrict__ gcent, int g, int d, float *_
   if (c >= g) return;
   float a = 0.f;
   for (int e = lane; e < d; e += 64) { const float v = gcent[(size_t)c * d + e]; a += v * v; }
-  a = gf_wave_sum(a);
+  a = wave_sum(a);
   if (lane == 0) { gnorm[c] = a; atomicMax(mx, __float_as_uint(a == a && a < INFINITY ? a : INFINITY)); }
 }
 
@@ -183,22 +158,18 @@ __global__ __launch_bounds__(256) void gf_quant(float *__restrict__ P /* out: th
   float *qv = gq_sm, *tab = gq_sm + d, *vals = tab + m_pad * 256;
   __shared__ float s_lo[16], s_mb[4], s_sbase[GF_SAMPLE_GROUPS];
   __shared__ int s_bad, s_sc[GF_SAMPLE_GROUPS], s_sr0[GF_SAMPLE_GROUPS], s_soff[GF_SAMPLE_GROUPS + 1], s_ns;
-  __shared__ unsigned s_hist[256], s_prefix, s_remaining;
+  __shared__ unsigned s_hist[256];
+  __shared__ RadixSelectState s_sel;
   const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   float *Pq = P + (size_t)q * m_pad * 256;
   for (int e = tid; e < d; e += 256) qv[e] = Q[(size_t)q * d + e];
   if (tid == 0) s_bad = 0;
   __syncthreads();
-  // the query's table P[j][c] = -2 (q_j . c_j[c]) -- gq_ptables' arithmetic, term by term -- into LDS and out to memory
-  // (gf_survivors reads it there): thread = centroid
+  // the query's table P[j][c] = -2 (q_j . c_j[c]) -- gq_ptables' -- into LDS and out to memory (gf_survivors reads it
+  // there): thread = centroid
   for (int j = 0; j < m_pad; j++) {
     float acc = 0.f;
-    if (j < m && tid < k) {
-      const int fr = from[j], sj = sdim[j];
-      const float *cc = pq_cents + (size_t)k * fr + (size_t)tid * sj;
-      for (int t = 0; t < sj; t++) acc += qv[fr + t] * cc[t];
-      acc *= -2.0f;
-    }
+    if (j < m && tid < k) acc = ptable_entry(qv, 0, pq_cents, from, sdim, k, j, tid);
     tab[j * 256 + tid] = acc;
     Pq[j * 256 + tid] = acc;
   }
@@ -221,7 +192,7 @@ __global__ __launch_bounds__(256) void gf_quant(float *__restrict__ P /* out: th
   __syncthreads();
   float qq = 0.f;
   for (int e = lane; e < d; e += 64) qq += qv[e] * qv[e];
-  qq = gf_wave_sum(qq);
+  qq = wave_sum(qq);
   bool bad = false;
   for (int j = wave; j < 16; j += 4) {         // the smallest entry of every table (entries from k on are never looked up)
     float lo = INFINITY;
@@ -239,11 +210,11 @@ __global__ __launch_bounds__(256) void gf_quant(float *__restrict__ P /* out: th
   for (int t = wave; t < ns; t += 4) {         // the sampled groups' bases, gq_approx_scan's arithmetic
     float qg = 0.f;
     for (int e = lane; e < d; e += 64) qg += qv[e] * gcent[(size_t)s_sc[t] * d + e];
-    qg = gf_wave_sum(qg);
+    qg = wave_sum(qg);
     if (lane == 0) s_sbase[t] = qq - 2.0f * qg;
   }
   __syncthreads();
-  // D~ of the sampled rows (gq_approx_scan's sum, term by term), as order-preserving keys in registers: up to
+  // D~ of the sampled rows (gq_approx_scan's sum: approx_row_sum), as order-preserving keys in registers: up to
   // GF_SAMPLE_ROWS / 256 = 8 per thread
   constexpr int SR = GF_SAMPLE_ROWS / 256;
   unsigned skey[SR];
@@ -256,70 +227,22 @@ __global__ __launch_bounds__(256) void gf_quant(float *__restrict__ P /* out: th
       while (t + 1 < ns && i >= s_soff[t + 1]) t++;
       const int row = s_sr0[t] + (i - s_soff[t]);
       const uint4 w = gf_row_words<VEC>(codes, ng, row);
-      float acc = s_sbase[t] + xnorm[row];
-      for (int j = 0; j < m_pad; j++) {
-        const uint32_t x = j < 4 ? w.x : j < 8 ? w.y : j < 12 ? w.z : w.w;
-        acc += tab[j * 256 + ((x >> (8 * (j & 3))) & 0xFFu)];
-      }
+      float acc = approx_row_sum<VEC>(s_sbase[t] + xnorm[row], tab, VEC == 16 ? 1 : ng /* (one 16-byte word) */, gf_word_at<VEC>(w));
       bad = bad || acc != acc;
       if (acc != acc) acc = INFINITY;
-      const unsigned u = __float_as_uint(acc);
-      skey[r] = (u & 0x80000000u) ? ~u : (u | 0x80000000u);     // unsigned order = float order
+      skey[r] = ordered_key(acc);                // unsigned order = float order
     }
   }
   // the 64th smallest of them (+inf with fewer than 64 rows: keep every row): a four-pass radix select over the keys in
-  // registers -- 16 barriers where the bitonic sort of up to 2048 values in LDS took 66 (gq_select_groups' scheme: eight
-  // sub-counters per bin, the bins walked by a prefix sum over one wavefront)
+  // registers -- 16 barriers where the bitonic sort of up to 2048 values in LDS took 66
   float tq = INFINITY;
   if (total >= GF_LIST) {                      // (uniform over the workgroup)
-    unsigned *hsub = reinterpret_cast<unsigned *>(vals);          // [256][8]: GF_SAMPLE_ROWS words
-    if (tid == 0) { s_prefix = 0u; s_remaining = (unsigned)GF_LIST; }
-    unsigned mask = 0u;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-      for (int e = tid; e < 256 * 8; e += 256) hsub[e] = 0u;
-      __syncthreads();
-      const unsigned prefix = s_prefix;
+    auto keys = [&](auto f) __attribute__((always_inline)) {
 #pragma unroll
-      for (int r = 0; r < SR; r++) {
-        const unsigned key = skey[r];
-        if (key != 0xFFFFFFFFu && (key & mask) == prefix) atomicAdd(&hsub[((key >> shift) & 255u) * 8 + (tid & 7)], 1u);
-      }
-      __syncthreads();
-      {
-        unsigned h = 0;
-#pragma unroll
-        for (int x = 0; x < 8; x++) h += hsub[tid * 8 + x];
-        s_hist[tid] = h;
-      }
-      __syncthreads();
-      if (tid < 64) {
-        const unsigned h0 = s_hist[4 * tid], h1 = s_hist[4 * tid + 1], h2 = s_hist[4 * tid + 2], h3 = s_hist[4 * tid + 3];
-        const unsigned mine = h0 + h1 + h2 + h3;
-        unsigned incl = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const unsigned up = __shfl_up(incl, o);
-          if (tid >= o) incl += up;
-        }
-        const unsigned rem = s_remaining;
-        const unsigned long long reach = __ballot(incl >= rem);
-        const int first = reach ? __ffsll((long long)reach) - 1 : 63;
-        if (tid == first) {
-          unsigned cum = incl - mine;
-          int bin = 4 * tid;
-          if (cum + h0 >= rem) { }
-          else if (cum + h0 + h1 >= rem) { cum += h0; bin += 1; }
-          else if (cum + h0 + h1 + h2 >= rem) { cum += h0 + h1; bin += 2; }
-          else { cum += h0 + h1 + h2; bin += 3; }
-          s_remaining = rem - cum;
-          s_prefix = prefix | ((unsigned)bin << shift);
-        }
-      }
-      mask |= 255u << shift;
-      __syncthreads();
-    }
-    const unsigned t = s_prefix;
-    tq = __uint_as_float((t & 0x80000000u) ? (t & 0x7FFFFFFFu) : ~t);
+      for (int r = 0; r < SR; r++)
+        if (skey[r] != 0xFFFFFFFFu) f(skey[r]);
+    };
+    tq = ordered_float(block_radix_select<256>(keys, (unsigned)GF_LIST, reinterpret_cast<unsigned *>(vals) /* GF_SAMPLE_ROWS words */, s_hist, s_sel));
   }
   // a lower bound of |q|^2 - 2 q.g over the searched groups, from the centroid distances the group selection already
   // has: |q - g|^2 - |g|^2, less what the two roundings can differ by (it only sizes the step; the budgets themselves
@@ -476,8 +399,8 @@ __global__ __launch_bounds__(GF_THREADS) void gf_filter(const uint8_t *__restric
           qg += x * gcent[(size_t)c * d + e];
         }
       }
-      qq = gf_wave_sum(qq);
-      qg = gf_wave_sum(qg);
+      qq = wave_sum(qq);
+      qg = wave_sum(qg);
       const float base = qq - 2.0f * qg;
       int lim;                                 // a row survives with a level sum below lim
       if (i >= nq) lim = 0;
@@ -553,7 +476,7 @@ __global__ __launch_bounds__(GF_THREADS) void gf_filter(const uint8_t *__restric
         // and 4 dd + 3 (read per block: eight registers the next tile's loads need more)
         const int dd_ = x >> 1, o_ = x & 1;
         const uint32_t limp = s_lim[4 * dd_ + o_] | (s_lim[4 * dd_ + o_ + 2] << 16);
-        left[x] = gf_pk_sub_sat_u16(limp, acc[x]);              // non-zero half <=> that query keeps this row
+        left[x] = pk_sub_sat_u16(limp, acc[x]);              // non-zero half <=> that query keeps this row
         any |= left[x];
       }
       if (__ballot(valid && any != 0) == 0ull) continue;
@@ -588,7 +511,8 @@ __global__ __launch_bounds__(64 * GF_WAVES) void gf_survivors(const uint8_t *__r
                                                               int *__restrict__ nanflag) {
   // The GF_LIST smallest (D~, row) of the query's survivors, ascending.  Every survivor is scored into a register (an
   // order-preserving key and the row: up to GF_CAP / 1024 = 16 per thread, usually one); the GF_LIST-th smallest key is
-  // found by a four-pass radix select over those registers (gf_quant's, gq_select_groups' scheme), the entries at or
+  // found by a four-pass radix select over those registers (block_radix_select's scheme, in this kernel's own copy: through
+  // the shared routine the kernel took 36.8 us instead of 30.7 at 1 M rows / LimitGroups(50)), the entries at or
   // below it are compacted into LDS and each of them finds its place by counting the entries below it.  (Sixteen wave
   // lists -- serial insertions -- and a bitonic sort of their 1024 entries, 55 barriers of a 1024-thread workgroup, before.)
   extern __shared__ float tab[];               // m_pad * 256 table entries; afterwards the select's counters and the compacted entries
@@ -626,8 +550,7 @@ __global__ __launch_bounds__(64 * GF_WAVES) void gf_survivors(const uint8_t *__r
           }
         }
         if (acc != acc) { nanv = true; acc = INFINITY; }
-        const unsigned u = __float_as_uint(acc);
-        key[h] = (u & 0x80000000u) ? ~u : (u | 0x80000000u);      // unsigned order = float order
+        key[h] = ordered_key(acc);                                 // unsigned order = float order
         rowv[h] = row;
       }
     }
@@ -708,7 +631,7 @@ __global__ __launch_bounds__(64 * GF_WAVES) void gf_survivors(const uint8_t *__r
         place += (kj < k || (kj == k && rj < r)) ? 1 : 0;
       }
       if (place < GF_LIST) {
-        lv[(size_t)q * GF_LIST + place] = __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+        lv[(size_t)q * GF_LIST + place] = ordered_float(k);
         li[(size_t)q * GF_LIST + place] = r;
       }
     }
@@ -717,6 +640,40 @@ __global__ __launch_bounds__(64 * GF_WAVES) void gf_survivors(const uint8_t *__r
   // an overflowing queue has lost rows, a NaN value or more ties at the cut than the placing holds: the literal kernels
   if (tid < GF_WAVES) nanflag[q * GF_WAVES + tid] = tid == 0 ? ((s_nan != 0 || total > GF_CAP || c > GF_PLACED) ? 1 : 0) : 0;
 }
+
+#ifdef GULON_TEST_HOOKS
+// block_radix_select on its own, one workgroup.  PER > 0: thread t holds keys t, t + NT, ... in registers (0xFFFFFFFF:
+// none, skipped here as in gf_quant / gf_survivors / gq_select_groups<KR > 0>); PER = 0: streamed (gq_select_groups<0>).
+template <int NT, int PER>
+__global__ __launch_bounds__(NT) void selftest_select(const uint32_t *__restrict__ keys, int n, unsigned want,
+                                                      uint32_t *__restrict__ threshold, long long *__restrict__ at_or_below) {
+  __shared__ unsigned hsub[256 * 8];
+  __shared__ unsigned s_hist[256];
+  __shared__ RadixSelectState s_sel;
+  __shared__ int s_cnt;
+  const int tid = threadIdx.x;
+  constexpr int NR = PER > 0 ? PER : 1;
+  unsigned kreg[NR];
+#pragma unroll
+  for (int r = 0; r < NR; r++) kreg[r] = PER > 0 && tid + NT * r < n ? keys[tid + NT * r] : 0xFFFFFFFFu;
+  if (tid == 0) s_cnt = 0;
+  auto each = [&](auto f) __attribute__((always_inline)) {
+    if (PER > 0) {
+#pragma unroll
+      for (int r = 0; r < NR; r++)
+        if (kreg[r] != 0xFFFFFFFFu) f(kreg[r]);
+    } else {
+      for (int e = tid; e < n; e += NT) f(keys[e]);
+    }
+  };
+  const unsigned thr = block_radix_select<NT>(each, want, hsub, s_hist, s_sel);
+  int c = 0;
+  each([&](unsigned key) __attribute__((always_inline)) { c += key <= thr ? 1 : 0; });
+  atomicAdd(&s_cnt, c);
+  __syncthreads();
+  if (tid == 0) { *threshold = thr; *at_or_below = s_cnt; }
+}
+#endif
 
 }  // namespace
 
@@ -814,3 +771,28 @@ void group_filter_run(GroupFilter &gf, const uint8_t *codes, int ng, int vec, in
 }
 
 }  // namespace gulon
+
+#ifdef GULON_TEST_HOOKS
+using namespace gulon;
+
+// The `want`-th smallest of n keys (none 0xFFFFFFFF) by block_radix_select, and how many keys lie at or below it.  form 0:
+// 256 threads, keys in registers, n <= 2048; 1: 1024 threads, registers, n <= 16384; 2: 256 threads, keys streamed.
+// (Declared here and bound by its test, tests/test_gpu_select.py: the header's list of hooks is pinned by test_abi.)
+GULON_API int32_t gulon_selftest_block_select(const uint32_t *keys, int64_t n, int32_t want, int32_t form, uint32_t *threshold,
+                                              int64_t *at_or_below) {
+  return guarded([&] {
+    GULON_REQUIRE(keys != nullptr && threshold != nullptr && at_or_below != nullptr && form >= 0 && form <= 2, "bad arguments");
+    GULON_REQUIRE(n >= 1 && n <= (form == 0 ? 2048 : form == 1 ? 16384 : INT_MAX) && want >= 1 && want <= n, "bad sizes");
+    DevBuf<uint32_t> dk, dt(1);
+    DevBuf<long long> dc(1);
+    dk.upload(keys, (size_t)n);
+    if (form == 0) hipLaunchKernelGGL((selftest_select<256, 8>), dim3(1), dim3(256), 0, 0, dk.p, (int)n, (unsigned)want, dt.p, dc.p);
+    else if (form == 1) hipLaunchKernelGGL((selftest_select<1024, 16>), dim3(1), dim3(1024), 0, 0, dk.p, (int)n, (unsigned)want, dt.p, dc.p);
+    else hipLaunchKernelGGL((selftest_select<256, 0>), dim3(1), dim3(256), 0, 0, dk.p, (int)n, (unsigned)want, dt.p, dc.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(threshold, dt.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(at_or_below, dc.p, sizeof(int64_t), hipMemcpyDeviceToHost));
+  });
+}
+#endif

@@ -55,3 +55,57 @@ void group_filter_run(GroupFilter &gf, const uint8_t *codes, int ng, int vec, in
                       const int *nn_cnt, int B, float *amv, int *ami, int *anan, hipStream_t st);
 
 }  // namespace gulon
+
+#ifdef __HIPCC__
+#include "scan.hpp"
+
+namespace gulon {
+// ---- the approximate distance D~ = base + xnorm[row] + sum_j P[j][code_j]: ONE copy of its arithmetic -----------------
+// gq_approx_scan (grouped.hip) and the by-group filter (gf_quant's sample, gf_survivors) must produce the same bits:
+// the filter's lists are gq_approx_scan's only while the table entries and the order of the adds are these.
+// P[j][c] = -2 (q_j . c_j[c]): entry c of quantizer j (< m) of the table of the query whose d coordinates start at Q[q0]
+__device__ inline float ptable_entry(const float *Q, size_t q0, const float *pq_cents,
+                                              const int *from, const int *sdim, int k, int j, int c) {
+  const int fr = from[j], sj = sdim[j];
+  const float *cc = pq_cents + (size_t)k * fr + (size_t)c * sj;
+  float acc = 0.f;
+  for (int t = 0; t < sj; t++) acc += Q[q0 + fr + t] * cc[t];
+  return acc * -2.0f;
+}
+
+// acc + the table entries of a row in quantizer order 0 .. ng VEC - 1 (= m_pad - 1); word_at(gi): the row's gi-th code
+// word (CodeWord<VEC>), tab: [m_pad][256]
+template <int VEC, class WordAt>
+__device__ __forceinline__ float approx_row_sum(float acc, const float *tab, int ng, const WordAt &word_at) {
+  for (int gi = 0; gi < ng; gi++) {
+    const typename CodeWord<VEC>::type w = word_at(gi);
+    const float *tj = tab + gi * VEC * 256;
+#pragma unroll
+    for (int b = 0; b < VEC; b++) acc += tj[b * 256 + code_byte<VEC>(w, b)];
+  }
+  return acc;
+}
+
+// the 16 code bytes of row `row` as four words: one 16-byte word per row (VEC = 16), or ng <= 4 four-byte words in
+// scan.hip's [row block][word][lane] layout (VEC = 4; quantizers from 4 ng on read as code 0: their tables are zero)
+template <int VEC>
+__device__ inline uint4 gf_row_words(const uint8_t *__restrict__ codes, int ng, int row) {
+  if constexpr (VEC == 16) return reinterpret_cast<const uint4 *>(codes)[row];
+  const uint32_t *cw = reinterpret_cast<const uint32_t *>(codes);
+  const size_t o = ((size_t)(row >> 6) * ng) * 64 + (row & 63);
+  uint4 w = uint4{cw[o], 0u, 0u, 0u};
+  if (ng > 1) w.y = cw[o + 64];
+  if (ng > 2) w.z = cw[o + 128];
+  if (ng > 3) w.w = cw[o + 192];
+  return w;
+}
+// ... and approx_row_sum's word_at over them
+template <int VEC>
+__device__ __forceinline__ auto gf_word_at(const uint4 &w) {
+  return [w](int gi) __attribute__((always_inline)) {
+    if constexpr (VEC == 16) return w;
+    else return gi == 0 ? w.x : gi == 1 ? w.y : gi == 2 ? w.z : w.w;
+  };
+}
+}  // namespace gulon
+#endif

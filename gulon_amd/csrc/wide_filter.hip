@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "scan.hpp"
+#include "select.hpp"
 
 namespace gulon {
 
@@ -33,12 +34,6 @@ constexpr int WF_NW = WF_THREADS / 64;
 constexpr int WF_NSLOT = 16;                 // survivor sub-queues per query
 constexpr size_t WF_LDS_BUDGET = 144 * 1024;
 constexpr int WF_NADD = 4, WF_QMAX = 255 / WF_NADD;   // 6-bit levels: four entries summed per byte
-
-__device__ inline uint32_t wf_pk_sub_sat_u16(uint32_t a, uint32_t b) {   // per 16-bit half: max(a - b, 0)
-  uint32_t d;
-  asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(d) : "v"(a), "v"(b));
-  return d;
-}
 
 __global__ void wf_reset(int *__restrict__ fb, int n_fb, int *__restrict__ cnt, int n_cnt) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -243,7 +238,7 @@ __global__ __launch_bounds__(WF_THREADS) void wf_filter(const uint16_t *__restri
     uint32_t any = 0, left[2 * DW];
 #pragma unroll
     for (int x = 0; x < 2 * DW; x++) {
-      left[x] = wf_pk_sub_sat_u16(QMAXP, acc[x]);     // non-zero half <=> that query keeps this row
+      left[x] = pk_sub_sat_u16(QMAXP, acc[x]);     // non-zero half <=> that query keeps this row
       any |= left[x];
     }
     if (__ballot(valid && any != 0) != 0ull) {        // rare path
@@ -252,18 +247,8 @@ __global__ __launch_bounds__(WF_THREADS) void wf_filter(const uint16_t *__restri
         const uint32_t l = valid ? left[x] : 0u;
         if (__ballot(l != 0) == 0ull) continue;
         const int q0 = tile * QW + 4 * (x >> 1) + (x & 1);   // low half: query q0, high half: q0 + 2
-        if (l & 0xFFFFu) {
-          const int sq = q0 * WF_NSLOT + slot;
-          const int pos = atomicAdd(&cnt[sq], 1);
-          if (pos < cap) queue[(size_t)sq * cap + pos] = row;
-          else fb[q0] = 1;                              // (padding queries are all-QMAX: they never get here)
-        }
-        if (l >> 16) {
-          const int sq = (q0 + 2) * WF_NSLOT + slot;
-          const int pos = atomicAdd(&cnt[sq], 1);
-          if (pos < cap) queue[(size_t)sq * cap + pos] = row;
-          else fb[q0 + 2] = 1;
-        }
+        // (padding queries are all-QMAX: they never get here)
+        enqueue_halves<WF_NSLOT>(l, q0, slot, row, cnt, queue, cap, [&](int q) -> int & { return fb[q]; });
       }
     }
   }
@@ -281,33 +266,16 @@ __global__ __launch_bounds__(64 * WF_SV_WAVES) void wf_survivors(const uint16_t 
   __shared__ int mi[(WF_SV_WAVES - 1) * 64];
   const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int mine = lane < WF_NSLOT ? cnt[q * WF_NSLOT + lane] : 0;
+  SurvivorQueues<WF_NSLOT> sq(cnt, q, lane);
   __syncthreads();                                  // every wave has read the counters
-  if (wave == 0 && lane < WF_NSLOT) cnt[q * WF_NSLOT + lane] = 0;
+  sq.clear(wave == 0);
   if (q >= B) return;
-  if (__ballot(mine > cap) != 0ull) {
+  if (sq.overflowed(cap)) {
     if (tid == 0) fb[q] = 1;             // a sub-queue overflowed: the exact scan redoes this query
-    mine = min(mine, cap);
+    sq.clamp(cap);
   }
-  int incl = mine;
-#pragma unroll
-  for (int o = 1; o < WF_NSLOT; o <<= 1) {
-    const int up = __shfl_up(incl, o);
-    if (lane >= o) incl += up;
-  }
-  const int n = readlane_i(incl, WF_NSLOT - 1);
-  int start[WF_NSLOT];
-#pragma unroll
-  for (int sl = 0; sl < WF_NSLOT; sl++) start[sl] = readlane_i(incl - mine, sl);
-  auto entry = [&](int e) {   // e-th survivor of the query, e < n
-    int sl = 0;
-#pragma unroll
-    for (int x = 1; x < WF_NSLOT; x++) sl += e >= start[x];
-    int off = start[0];
-#pragma unroll
-    for (int x = 1; x < WF_NSLOT; x++) off = sl == x ? start[x] : off;
-    return queue[((size_t)q * WF_NSLOT + sl) * cap + (e - off)];
-  };
+  const int n = sq.count();
+  auto entry = [&](int e) { return sq.entry(queue, q, cap, e); };   // e-th survivor of the query, e < n
   const float fv = lane < keff ? fin_v[(size_t)q * keff + lane] : INFINITY;
   const int fi = lane < keff ? fin_i[(size_t)q * keff + lane] : INT_MAX;
   const float bound_v = readlane_f(fv, keff - 1);

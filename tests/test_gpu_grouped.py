@@ -172,6 +172,7 @@ def test_index_without_rows_answers_nothing(g, strategy, limit):
     (60000, 24, 300, 8, 64, 90, 3000, False),      # duplicated rows: equal D~ at the cut, ties in the re-ranking
     (60000, 16, 250, 4, 16, 250, 0, True),         # every group searched; a NaN query and a far-away query
     (66000, 8, 11000, 4, 16, 100, 0, False),       # more groups than the group selection keeps keys in registers for
+    (66000, 8, 3000, 4, 16, 100, 0, False),        # 2048 < groups <= 10240: the group selection with 40 keys per thread
     (90000, 16, 600, 8, 64, 40, 2500, False),      # LimitGroups(<= 63) over many groups (the wavefront heap), duplicated rows
 ])
 def test_by_group_filter_equals_reference(oracle, g, monkeypatch, capfd, n, d, groups, m, k, limit, dup, bad_query):
@@ -181,6 +182,8 @@ def test_by_group_filter_equals_reference(oracle, g, monkeypatch, capfd, n, d, g
     monkeypatch.setenv("GULON_GROUPED_STATS", "1")
     B, K = 40, 10
     X, dm, coarse, gv, pq = _build(oracle, g, n, d, groups, m, k, seed=n + groups, dup=dup, iters=2)
+    if groups == 3000:
+        assert 2048 < len(gv.centroids) <= 10240          # gq_select_groups<40>'s range (grouped.hip, coarse_stage)
     R, cents, offsets = _oracle_side(oracle, X, coarse, gv, pq, n)
     index = g.Index.grouped(gv, pq, g.LimitGroups(limit))
     rng = np.random.default_rng(5)
