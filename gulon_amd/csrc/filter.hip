@@ -11,6 +11,8 @@
 //        q_j[c] = min(QMAX, floor((T_j[c] - min_j) / delta)),  delta = (tau' - sum_j min_j) / QL,
 //      where tau' = tau * (1 + 2 m u), u = 2^-24, covers the rounding of the reference's
 //      sequential fp32 sum D against the real sum R (all terms >= 0: D >= R (1 - m u)).
+//      (As evaluated, in fp64: tau' = tau * (1 + 2 m_pad * 5.97e-8) * (1 + 1e-9) -- m and u rounded up, and a margin
+//      for the fp64 arithmetic itself; wf_quantize of wide_filter.hip: the same with its m.)
 //      Then  sum_j min_j + delta * sum_j q_j[c_j]  <=  R,  and a row with  sum_j q_j > QL  has
 //      R > tau', hence D > tau: it cannot be among the K+1 smallest and is dropped;
 //   3. the (few) surviving (query, row) pairs are queued and re-evaluated with the exact fp32
@@ -105,9 +107,11 @@ __global__ __launch_bounds__(256) void qt_quantize(const float *__restrict__ tab
       }
     }
     s_dead[c] = dead;
-    // 1 / delta for the fp32 levels below: rounded to fp32 (<= 2^-24 relative), then shrunk by 2^-21; a delta so
-    // small that the reciprocal overflows fp32 leaves +inf -> every entry above its minimum gets the top level (valid:
-    // levels only ever round down from x / delta, and the top level is what min(QMAX, .) would give)
+    // 1 / delta for the fp32 levels below: rounded to fp32 (<= 2^-24 relative), then shrunk by 2^-21; for a delta so
+    // small that the reciprocal overflows fp32 the largest finite value short of it, 3.0e38, stands in (+inf would turn
+    // an entry AT its minimum, x = 0, into 0 * inf = NaN and that into the top level): the levels then come out far
+    // below x / delta -- 0 for every x below 1 / 3.0e38 -- which is valid (levels only ever round down) and filters
+    // little; entries from about QMAX / 3.0e38 up still get the top level
     float inv32 = (float)(1.0 / delta);
     inv32 = inv32 < INFINITY ? inv32 * (1.0f - 4.76837158e-7f) : 3.0e38f;
     s_inv32[c] = inv32;
@@ -1326,3 +1330,130 @@ bool replay_level2_filtered(gulon_index *ix, int F, int K, int rb_lo, int rb_hi,
 }
 
 }  // namespace gulon
+
+#ifdef GULON_TEST_HOOKS
+using namespace gulon;
+
+// ONE filter stage on its own, over every row block of [from, until), for tests/test_gpu_filter_stage.py: what the stage
+// queues per query and the levels it quantized, against bounds the caller chooses.  The hook builds its own index (handle
+// and hook share this library's statics) and runs the production kernels as run_filter_query launches them --
+// bound_tables (tables, minima, counters; the bound of its sample is overwritten with `tau`, the running lists stay
+// empty), qt_quantize, launch_filter with every block -- and no survivors kernel.  copy: 0 the plain codes, 1 the
+// conflict-ordered copy, 2 the key-sorted copy (one-word codes with nadd = 4 only; 2: the whole row range only).
+// rows_out [b][16 cap]: the queued rows of a query, ascending (entries beyond a full sub-queue are lost, as in
+// production); counts_out [b][16]: the sub-queues' fill counters, unclamped; flagged_out [b]: the flag of the query's
+// tile; levels_out [b][m][k]: the 8-bit levels of the real quantizers and centroids; info: qmax, m_pad, queries per
+// flag, queries per table entry, entry groups per workgroup, chunks launched.
+// (Declared here and bound by its test: the header's list of hooks is pinned by test_abi.)
+GULON_API int32_t gulon_selftest_filter_stage(const uint8_t *codes, int32_t n, int32_t d, int32_t m, int32_t k,
+                                              const float *cents, const float *queries, int32_t b, int32_t from,
+                                              int32_t until, const float *tau, int32_t copy, int32_t nadd, int32_t cap,
+                                              int32_t main_stage, int32_t *rows_out, int32_t *counts_out,
+                                              int32_t *flagged_out, uint8_t *levels_out, int32_t *info) {
+  gulon_index *raw = nullptr;
+  const int32_t rc = guarded([&] {
+    GULON_REQUIRE(codes && cents && queries && tau && rows_out && counts_out && flagged_out && levels_out && info, "null argument");
+    GULON_REQUIRE(k >= 1 && k <= 256 && b >= 1 && b <= 4096 && from >= 0 && from < until && until <= n && copy >= 0 && copy <= 2 &&
+                  (nadd == 2 || nadd == 4) && cap >= 1 && cap <= (1 << 16), "bad arguments");
+    GULON_REQUIRE(gulon_index_create(codes, n, d, m, k, cents, 0, &raw) == GULON_OK && raw, "no index");
+    gulon_index *ix = raw;
+    GULON_REQUIRE((size_t)ix->m_pad * 256 * 4 <= FILTER_LDS_BUDGET, "no filter for m = %d", m);
+    ScanTuning &t = *ix->tune;
+    t.filter_nadd = nadd;
+    t.filter_min_rb = 4;
+    t.filter_order = copy == 1 ? std::max(1, t.filter_order) : 0;
+    t.filter_sort = copy == 2;
+    if (copy != 0) {
+      GULON_REQUIRE(ix->vec == 16 && ix->ng == 1 && nadd == 4, "no ordered copy of this index");
+      GULON_REQUIRE(copy == 1 || (from == 0 && until == n), "the key-sorted copy serves the whole range only");
+      build_filter_copy(ix);
+    }
+    hipStream_t st = nullptr;
+    const int B = b, keff = 11, W = ix->w, QT = W * ix->nsub, ntiles = ceil_div(B, QT), Bp = ntiles * QT;
+    const FilterShape fs = filter_shape(ix);
+    const int qw = fs.qw, nqg = fs.nqg, qmax = fs.qmax;
+    GULON_REQUIRE(fs.nadd == nadd, "internal: nadd");
+    const int ftiles = ceil_div(B, qw * nqg), Bq = ceil_div(ftiles * nqg * qw, 16) * 16;
+    const int rb_begin = from / 64, rb_total = ceil_div(until, 64) - rb_begin;
+    int frb_begin = rb_begin, frb_total = rb_total;
+    filter_block_range(ix, qw, nqg, nadd, from, until, frb_begin, frb_total);
+    const bool sorted = copy == 2;
+    if (sorted) { frb_begin = 0; frb_total = ceil_div(ix->n, 256) * 4; }
+    const int NW = t.threads / 64;
+    ix->tables.ensure((size_t)Bp * ix->m_pad * 256);
+    ix->gtau.ensure((size_t)Bp);
+    ix->fin_v.ensure((size_t)Bq * keff); ix->fin_i.ensure((size_t)Bq * keff);
+    ix->qmins.ensure((size_t)Bq * ix->m_pad);
+    ix->qtab.ensure((size_t)Bq * ix->m_pad * 256);
+    ix->sv_cnt.ensure((size_t)Bq * NSLOT);
+    ix->sv_queue.ensure((size_t)Bq * NSLOT * cap);
+    ix->fb_tile.ensure((size_t)ntiles);
+    ix->tau0.ensure((size_t)Bp);
+    DevBuf<float> dQ;
+    dQ.upload(queries, (size_t)B * d, st);
+    {   // run_filter_query's first launch, phase 0
+      const int srows = std::max(4096, std::min(t.filter_sample, (int)(17.0 * std::sqrt((double)rb_total * 64.0))));
+      const int sblocks = std::max(NW, std::min(rb_total, ceil_div(srows, 64)));
+      const RbMap smap{std::max(1, rb_total / sblocks), 0, 1};
+      const int se = rbmap_count(rb_total, smap);
+      const size_t lds_bytes = std::max((size_t)ix->m_pad * 256 * 4 * W, (size_t)W * NW * 64 * 4);
+      const bool ordered = ix->fcodes.p && ix->ng == 1 && ix->vec == 16 && t.filter_order > 0;
+      const uint8_t *scodes = ordered ? ix->fcodes.p : ix->codes.p, *sperm = ordered ? ix->fperm.p : nullptr;
+#define BS(V, W_)                                                                                                   \
+      {                                                                                                             \
+        auto kern = bound_tables<V, W_>;                                                                            \
+        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                         \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));                 \
+        hipLaunchKernelGGL(kern, dim3(Bp / W_), dim3(BOUND_THREADS), lds_bytes, st, ix->cents.p, ix->from.p,        \
+                           ix->sdim.p, ix->d, ix->m, ix->k, dQ.p, ix->tables.p, ix->qmins.p, scodes, sperm,         \
+                           ordered ? ix->fwindow - 1 : 0, ix->ng, ix->m_pad, from, until, rb_begin, se, smap, B, keff, \
+                           ix->tau0.p, ix->fin_v.p, ix->fin_i.p, (float *)nullptr, ix->gtau.p, Bp, ix->fb_tile.p,    \
+                           ntiles, ix->sv_cnt.p, Bq * NSLOT);                                                       \
+      }
+      if (ix->vec == 16) { if (W == 4) BS(16, 4) else if (W == 2) BS(16, 2) else BS(16, 1) }
+      else               { if (W == 4) BS(4, 4) else if (W == 2) BS(4, 2) else BS(4, 1) }
+#undef BS
+      HIP_CHECK(hipGetLastError());
+    }
+    HIP_CHECK(hipMemcpyAsync(ix->tau0.p, tau, sizeof(float) * (size_t)B, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(qt_quantize, dim3(Bq / 4, ix->m_pad), dim3(256), 0, st, ix->tables.p, W, Bp, ix->m_pad, ix->k,
+                       B, ix->qmins.p, ix->fin_v.p, ix->fin_i.p, ix->tau0.p, keff, qmax, qw, ix->qtab.p,
+                       ix->fb_tile.p, QT);
+    HIP_CHECK(hipGetLastError());
+    const RbMap all{1, 0, 1};
+    const int en = frb_total;
+    // the main-stage tag: chunks long enough for every wave to draw runs (all sixteen sub-queues fill, as in production);
+    // the short-stage tag: many short chunks, whose first few waves take all the runs
+    int nc = std::max(1, std::min(ceil_div(fs.slots, ftiles), en / (main_stage ? 4 * NW : NW)));
+    const int per = ceil_div(en, nc);
+    nc = ceil_div(en, per);
+    launch_filter(ix, qw, nqg, nadd, ftiles, nc, frb_begin, en, per, all, from, until, cap, main_stage ? 1 : 0, B, st,
+                  nullptr, 1, sorted);
+    HIP_CHECK(hipStreamSynchronize(st));
+    std::vector<int> cnt((size_t)Bq * NSLOT), queue((size_t)Bq * NSLOT * cap), fb((size_t)ntiles);
+    std::vector<uint8_t> qt((size_t)Bq * ix->m_pad * 256);
+    HIP_CHECK(hipMemcpy(cnt.data(), ix->sv_cnt.p, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(queue.data(), ix->sv_queue.p, sizeof(int) * queue.size(), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(fb.data(), ix->fb_tile.p, sizeof(int) * fb.size(), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(qt.data(), ix->qtab.p, qt.size(), hipMemcpyDeviceToHost));
+    for (int q = 0; q < B; q++) {
+      int32_t *out = rows_out + (size_t)q * NSLOT * cap;
+      size_t fill = 0;
+      for (int sl = 0; sl < NSLOT; sl++) {
+        const int c = cnt[(size_t)q * NSLOT + sl];
+        counts_out[(size_t)q * NSLOT + sl] = c;
+        for (int e = 0; e < std::min(c, (int)cap); e++) out[fill++] = queue[((size_t)q * NSLOT + sl) * cap + e] + ix->row_base;
+      }
+      std::sort(out, out + fill);
+      for (size_t e = fill; e < (size_t)NSLOT * cap; e++) out[e] = -1;
+      flagged_out[q] = fb[q / QT];
+      for (int j = 0; j < m; j++)      // entry (j, c) of query q: byte q % QW of entry [q / QW][j][c] (qt_quantize)
+        for (int c = 0; c < k; c++)
+          levels_out[((size_t)q * m + j) * k + c] = qt[((((size_t)(q / qw)) * ix->m_pad + j) * 256 + c) * qw + q % qw];
+    }
+    info[0] = qmax; info[1] = ix->m_pad; info[2] = QT; info[3] = qw; info[4] = nqg; info[5] = nc;
+  });
+  if (raw) (void)gulon_index_destroy(raw);
+  return rc;
+}
+#endif

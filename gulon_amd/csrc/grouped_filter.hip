@@ -673,6 +673,45 @@ __global__ __launch_bounds__(NT) void selftest_select(const uint32_t *__restrict
   __syncthreads();
   if (tid == 0) { *threshold = thr; *at_or_below = s_cnt; }
 }
+
+// The rest of select.hpp, one wavefront per 64 inputs (workgroup x: elements 64 x .. 64 x + 63; what = 6: query x).
+// what 0: a = floats -> out[e] = ordered_key, out[n + e] = the bits of ordered_float(ordered_key);  1: pk_sub_sat_u16(a, b);
+// 2: sort64_asc(a);  3: merge64_asc(a, b);  4: sort64_u64(a);  5: merge64_u64(a, b) (64-bit elements);
+// 6: SurvivorQueues<16> over the fill levels a [queries][16] and the queues b [queries][16][cap]:
+//    out[q][0] = count() after clamp(cap), out[q][1] = overflowed(cap), out[q][2 + e] = entry(e), e < count.
+__global__ __launch_bounds__(64) void selftest_select_parts(int what, const void *__restrict__ a, const void *__restrict__ b,
+                                                            long long n, int cap, void *__restrict__ out) {
+  const int lane = threadIdx.x;
+  const long long e = (long long)blockIdx.x * 64 + lane;
+  const uint32_t *a32 = static_cast<const uint32_t *>(a), *b32 = static_cast<const uint32_t *>(b);
+  const unsigned long long *a64 = static_cast<const unsigned long long *>(a), *b64 = static_cast<const unsigned long long *>(b);
+  uint32_t *o32 = static_cast<uint32_t *>(out);
+  unsigned long long *o64 = static_cast<unsigned long long *>(out);
+  if (what == 0) {
+    const unsigned key = ordered_key(__uint_as_float(a32[e]));
+    o32[e] = key;
+    o32[n + e] = __float_as_uint(ordered_float(key));
+  } else if (what == 1) {
+    o32[e] = pk_sub_sat_u16(a32[e], b32[e]);
+  } else if (what == 2) {
+    o32[e] = __float_as_uint(sort64_asc(__uint_as_float(a32[e]), lane));
+  } else if (what == 3) {
+    o32[e] = __float_as_uint(merge64_asc(__uint_as_float(a32[e]), __uint_as_float(b32[e]), lane));
+  } else if (what == 4) {
+    o64[e] = sort64_u64(a64[e], lane);
+  } else if (what == 5) {
+    o64[e] = merge64_u64(a64[e], b64[e], lane);
+  } else {
+    const int q = blockIdx.x;
+    int *o = static_cast<int *>(out) + (size_t)q * (2 + 16 * (size_t)cap);
+    SurvivorQueues<16> sq(const_cast<int *>(static_cast<const int *>(a)), q, lane);
+    const bool over = sq.overflowed(cap);
+    sq.clamp(cap);
+    const int cnt = sq.count();
+    if (lane == 0) { o[0] = cnt; o[1] = over ? 1 : 0; }
+    for (int i = lane; i < cnt; i += 64) o[2 + i] = sq.entry(static_cast<const int *>(b), q, cap, i);
+  }
+}
 #endif
 
 }  // namespace
@@ -793,6 +832,34 @@ GULON_API int32_t gulon_selftest_block_select(const uint32_t *keys, int64_t n, i
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(threshold, dt.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(at_or_below, dc.p, sizeof(int64_t), hipMemcpyDeviceToHost));
+  });
+}
+
+// selftest_select_parts over host data.  what 0-5: n elements (a multiple of 64) of a_bytes / b_bytes / out_bytes bytes
+// in all; what 6: n queries.  (Bound by tests/test_gpu_select.py, like the hook above.)
+GULON_API int32_t gulon_selftest_select_parts(int32_t what, const void *a, int64_t a_bytes, const void *b, int64_t b_bytes,
+                                              int64_t n, int32_t cap, void *out, int64_t out_bytes) {
+  return guarded([&] {
+    GULON_REQUIRE(what >= 0 && what <= 6 && a != nullptr && out != nullptr && n >= 1 && n <= (1 << 24) && a_bytes >= 0 &&
+                  b_bytes >= 0 && out_bytes >= 0 && (b != nullptr) == (b_bytes > 0), "bad arguments");
+    const int64_t el = what >= 4 ? 8 : 4;
+    if (what <= 5) {
+      const bool two = what == 1 || what == 3 || what == 5;
+      GULON_REQUIRE(n % 64 == 0 && a_bytes == n * el && b_bytes == (two ? n * el : 0) && out_bytes == (what == 0 ? 2 : 1) * n * el,
+                    "bad sizes");
+    } else {
+      GULON_REQUIRE(cap >= 1 && cap <= 4096 && a_bytes == n * 16 * 4 && b_bytes == n * 16 * (int64_t)cap * 4 &&
+                    out_bytes == n * (2 + 16 * (int64_t)cap) * 4, "bad sizes");
+    }
+    DevBuf<uint8_t> da, db, dout((size_t)out_bytes);
+    da.upload(static_cast<const uint8_t *>(a), (size_t)a_bytes);
+    if (b_bytes) db.upload(static_cast<const uint8_t *>(b), (size_t)b_bytes);
+    HIP_CHECK(hipMemset(dout.p, 0xEE, (size_t)out_bytes));
+    hipLaunchKernelGGL(selftest_select_parts, dim3((unsigned)(what <= 5 ? n / 64 : n)), dim3(64), 0, 0, what, (const void *)da.p,
+                       (const void *)db.p, (long long)n, cap, (void *)dout.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(out, dout.p, (size_t)out_bytes, hipMemcpyDeviceToHost));
   });
 }
 #endif

@@ -454,3 +454,119 @@ void run_wide_filter_query(gulon_index *ix, const float *dQ, int B, int K, int f
 }
 
 }  // namespace gulon
+
+#ifdef GULON_TEST_HOOKS
+using namespace gulon;
+
+// The wide counterpart of gulon_selftest_filter_stage (filter.hip): ONE stage of run_wide_filter_query over every row
+// block of [from, until) -- the fp32 tables, wf_table_mins, wf_quantize, wf_filter (whole table or sliced, as wf_slice
+// decides) -- against the caller's bounds, which stand as the last entry of a full running list, where wf_quantize reads
+// them; no wf_survivors.  Outputs as the flat hook's (flagged_out: the query's own flag); info: QMAX, queries per table
+// entry, quantizers per launch, chunks launched.  Returns GULON_SELFTEST_WIDE_REFUSED (77) where wf_qw refuses the code
+// book (not even one quantizer's entries fit LDS).
+// (Declared here and bound by its test: the header's list of hooks is pinned by test_abi.)
+GULON_API int32_t gulon_selftest_wide_filter_stage(const uint8_t *codes, int32_t n, int32_t d, int32_t m, int32_t k,
+                                                   const float *cents, const float *queries, int32_t b, int32_t from,
+                                                   int32_t until, const float *tau, int32_t cap, int32_t *rows_out,
+                                                   int32_t *counts_out, int32_t *flagged_out, uint8_t *levels_out,
+                                                   int32_t *info) {
+  gulon_index *raw = nullptr;
+  bool refused = false;
+  const int32_t rc = guarded([&] {
+    GULON_REQUIRE(codes && cents && queries && tau && rows_out && counts_out && flagged_out && levels_out && info, "null argument");
+    GULON_REQUIRE(k > 256 && b >= 1 && b <= 4096 && from >= 0 && from < until && until <= n && cap >= 1 && cap <= (1 << 16),
+                  "bad arguments");
+    GULON_REQUIRE(gulon_index_create(codes, n, d, m, k, cents, 0, &raw) == GULON_OK && raw, "no index");
+    gulon_index *ix = raw;
+    const int QW = wf_qw(ix);
+    if (QW == 0) { refused = true; return; }
+    hipStream_t st = nullptr;
+    const int B = b, keff = 11;
+    const int ngrp = ceil_div(B, QW), Bq = ngrp * QW;
+    const int sb = from / 64, sc = ceil_div(until, 64) - sb;
+    const size_t tstride = ((size_t)m * k * QW + 15) & ~(size_t)15;
+    ix->tables.ensure((size_t)B * m * k);
+    ix->fin_v.ensure((size_t)Bq * keff); ix->fin_i.ensure((size_t)Bq * keff);
+    ix->qmins.ensure((size_t)B * m);
+    ix->qtab.ensure((size_t)ngrp * tstride);
+    ix->sv_cnt.ensure((size_t)Bq * WF_NSLOT);
+    ix->sv_queue.ensure((size_t)Bq * WF_NSLOT * cap);
+    ix->fb_tile.ensure((size_t)Bq);
+    DevBuf<float> dQ;
+    dQ.upload(queries, (size_t)B * d, st);
+    {   // full lists whose last entry is the caller's bound
+      std::vector<float> fv((size_t)Bq * keff, 0.f);
+      std::vector<int> fi((size_t)Bq * keff, 0);
+      for (int q = 0; q < B; q++) fv[(size_t)q * keff + keff - 1] = tau[q];
+      HIP_CHECK(hipMemcpy(ix->fin_v.p, fv.data(), sizeof(float) * fv.size(), hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(ix->fin_i.p, fi.data(), sizeof(int) * fi.size(), hipMemcpyHostToDevice));
+    }
+    hipLaunchKernelGGL(wf_reset, dim3(ceil_div(Bq * WF_NSLOT, 256)), dim3(256), 0, st, ix->fb_tile.p, Bq, ix->sv_cnt.p,
+                       Bq * WF_NSLOT);
+    launch_build_tables_wide(ix->cents.p, ix->from.p, ix->sdim.p, ix->d, m, k, dQ.p, 0, B, ix->tables.p, st);
+    hipLaunchKernelGGL(wf_table_mins, dim3(m, B), dim3(256), 0, st, ix->tables.p, m, k, ix->qmins.p);
+    HIP_CHECK(hipGetLastError());
+    // from here on: one turn of run_wide_filter_query's stage loop
+    const int jp = wf_slice(ix);
+    const size_t lds_bytes = jp < m ? (size_t)jp * k * QW : tstride;
+    int cus = 256;
+    { int dev = 0; HIP_CHECK(hipGetDevice(&dev)); HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)); }
+    const int resident = std::max(1, (int)(160 * 1024 / lds_bytes));
+    if (QW == 8)
+      hipLaunchKernelGGL(wf_quantize<8>, dim3(ceil_div(k, 256), m, ngrp), dim3(256), 0, st, ix->tables.p, m, k, B, ix->qmins.p,
+                         ix->fin_v.p, ix->fin_i.p, keff, ix->qtab.p, tstride, ix->fb_tile.p);
+    else
+      hipLaunchKernelGGL(wf_quantize<4>, dim3(ceil_div(k, 256), m, ngrp), dim3(256), 0, st, ix->tables.p, m, k, B, ix->qmins.p,
+                         ix->fin_v.p, ix->fin_i.p, keff, ix->qtab.p, tstride, ix->fb_tile.p);
+    HIP_CHECK(hipGetLastError());
+    int nchunks = std::max(1, std::min(ceil_div(cus * resident * 2, ngrp), sc / (4 * WF_NW)));
+    const int per = ceil_div(sc, nchunks);
+    nchunks = ceil_div(sc, per);
+    auto go = [&](auto kern) {
+      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)lds_bytes));
+      hipLaunchKernelGGL(kern, dim3(ngrp, nchunks), dim3(WF_THREADS), lds_bytes, st, ix->wcodes.p, m, k, ix->qtab.p, tstride,
+                         from, until, sb, sc, per, ix->sv_cnt.p, ix->sv_queue.p, cap, ix->fb_tile.p, B, 0, 0, (uint32_t *)nullptr);
+    };
+    const int mq = ceil_div(m, 4);
+    if (jp < m) {
+      ix->wpark.ensure((size_t)ngrp * sc * 64);
+      auto kern = jp <= 4 ? wf_filter<4, 1, true> : wf_filter<4, 2, true>;
+      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)lds_bytes));
+      for (int j0 = 0; j0 < m; j0 += jp)
+        hipLaunchKernelGGL(kern, dim3(ngrp, nchunks), dim3(WF_THREADS), lds_bytes, st, ix->wcodes.p, m, k, ix->qtab.p, tstride,
+                           from, until, sb, sc, per, ix->sv_cnt.p, ix->sv_queue.p, cap, ix->fb_tile.p, B, j0,
+                           std::min(m, j0 + jp), ix->wpark.p);
+    }
+    else if (QW == 8) { if (mq <= 2) go(wf_filter<8, 2>); else if (mq <= 4) go(wf_filter<8, 4>); else go(wf_filter<8, 0>); }
+    else              { if (mq <= 2) go(wf_filter<4, 2>); else if (mq <= 4) go(wf_filter<4, 4>); else go(wf_filter<4, 0>); }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(st));
+    std::vector<int> cnt((size_t)Bq * WF_NSLOT), queue((size_t)Bq * WF_NSLOT * cap), fb((size_t)Bq);
+    std::vector<uint8_t> qt((size_t)ngrp * tstride);
+    HIP_CHECK(hipMemcpy(cnt.data(), ix->sv_cnt.p, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(queue.data(), ix->sv_queue.p, sizeof(int) * queue.size(), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(fb.data(), ix->fb_tile.p, sizeof(int) * fb.size(), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(qt.data(), ix->qtab.p, qt.size(), hipMemcpyDeviceToHost));
+    for (int q = 0; q < B; q++) {
+      int32_t *out = rows_out + (size_t)q * WF_NSLOT * cap;
+      size_t fill = 0;
+      for (int sl = 0; sl < WF_NSLOT; sl++) {
+        const int c = cnt[(size_t)q * WF_NSLOT + sl];
+        counts_out[(size_t)q * WF_NSLOT + sl] = c;
+        for (int e = 0; e < std::min(c, (int)cap); e++) out[fill++] = queue[((size_t)q * WF_NSLOT + sl) * cap + e] + ix->row_base;
+      }
+      std::sort(out, out + fill);
+      for (size_t e = fill; e < (size_t)WF_NSLOT * cap; e++) out[e] = -1;
+      flagged_out[q] = fb[q];
+      for (int j = 0; j < m; j++)      // entry (j, c) of query q: byte q % QW of entry [j][c] of group q / QW (wf_quantize)
+        for (int c = 0; c < k; c++)
+          levels_out[((size_t)q * m + j) * k + c] = qt[(size_t)(q / QW) * tstride + ((size_t)j * k + c) * QW + q % QW];
+    }
+    info[0] = WF_QMAX; info[1] = QW; info[2] = jp; info[3] = nchunks;
+  });
+  if (raw) (void)gulon_index_destroy(raw);
+  return rc != GULON_OK ? rc : refused ? 77 : GULON_OK;
+}
+#endif

@@ -3,6 +3,7 @@ bit for bit on small inputs (both are written from the Scala source)."""
 import numpy as np
 import pytest
 
+import filter_stage_ref as fs
 import value_regimes as vr
 from conftest import bits
 from oracle import py_oracle as po
@@ -166,3 +167,44 @@ def test_tight_rows_of_the_exact_knn_case(oracle):
     n, d = vr.KNN_SHAPE
     cents, idx, Q = vr.query_case(oracle, "tight", n, d, *vr.KNN_TIGHT_MK, 12)
     vr.query_predicate(oracle, "tight", cents, idx, Q, d, *vr.KNN_TIGHT_MK, K=10)
+
+
+@pytest.mark.parametrize("form,regime", fs.CASES)
+def test_filter_stage_cases_meet_their_preconditions(oracle, form, regime):
+    """What test_gpu_filter_stage.py needs of its data, from the oracle alone: for every bound of every case the rows a
+    sound and tight stage may keep (the upper set) are at most a quarter of the range and fit one survivor sub-queue
+    -- but for the combinations filter_stage_ref.LOOSE names -- and a faithful numpy model of the stage passes every
+    check of the GPU test."""
+    ref = fs.reference(oracle, form, regime)
+    wide = form in fs.WIDE_FORMS
+    for frm, until in fs.ranges():
+        tau = ref.taus(frm, until)
+        for nadd in ((4,) if wide else (4, 2)):
+            qmax = fs.qmax_of(form, nadd)
+            ref.preconditions(frm, until, tau, qmax)
+            levels = fs.model_levels(ref, tau, qmax, wide=wide)
+            fs.check_stage(ref, frm, until, tau, qmax, fs.CAP, *fs.model_stage(ref, frm, until, levels, qmax), levels)
+
+
+@pytest.mark.parametrize("form,regime,nadd,broken", [
+    ("m16", "tight", 4, "widen"), ("m100", "tight", 2, "widen"), ("m16", "offset", 4, "widen"), ("k5", "tight", 4, "widen"),
+    ("m16", "large", 4, "shrink"), ("m16", "mixed_mild", 4, "shrink"), ("m16", "mixed_mild", 2, "shrink"),
+    ("m16", "mixed", 4, "budget"), ("k5", "tight", 2, "budget")])
+def test_filter_stage_checks_reject_a_broken_stage(oracle, form, regime, nadd, broken):
+    """The checks are not vacuous: a model of qt_quantize without the 2 m_pad u widening of tau, without the 2^-21 shrink of
+    the reciprocal (at the bounds of reciprocal_edge_taus), or with a budget test off by one in the generous direction
+    fails them, and the faithful model passes at the same bounds."""
+    ref = fs.reference(oracle, form, regime)
+    frm, until = fs.ranges()[0]
+    qmax = fs.qmax_of(form, nadd)
+    tau = ref.taus(frm, until)
+    if broken == "shrink":
+        tau, found = fs.reciprocal_edge_taus(ref, qmax, frm, until)
+        assert found.sum() >= 6
+
+    def run(extra=0, **mutation):
+        levels = fs.model_levels(ref, tau, qmax, **mutation)
+        fs.check_stage(ref, frm, until, tau, qmax, fs.CAP, *fs.model_stage(ref, frm, until, levels, qmax, extra), levels)
+    run()
+    with pytest.raises(AssertionError):
+        run(**({"extra": -1} if broken == "budget" else {broken: False}))
