@@ -944,26 +944,28 @@ void print_redo_stats(const GroupedCall &c) {   // GULON_GROUPED_STATS
   fprintf(stderr, "[grouped] approximate pre-selection: %d of %d queries redone with literal heaps\n", nfl, c.B);
 }
 
-// approximate pre-selection with one table per query, exact re-ranking of 64 candidates, certificate: answers in
-// d_oi / d_od / d_oc, the queries to redo in gx->qlist / gx->qcount
-void approx_stage(const GroupedCall &c, const CoarseResult &co, const GroupedKnobs &knobs) {
+// by group with 8-bit bound tables (grouped_filter.hip) where a query searches more than a handful of groups; else
+// every searched row through gq_approx_scan
+bool by_group_applies(const GroupedCall &c, const CoarseResult &co) {
+  gulon_grouped_index *gx = c.gx;
+  gulon_index *ix = gx->pq;
+  return gx->gfilter.built && group_filter_applies(ix->m, ix->m_pad, ix->ng, ix->vec, ix->k, ix->d) &&
+         co.nn_stride > GF_SAMPLE_GROUPS && c.B <= 65535 &&          // (a grid's y extent carries the query)
+         (long long)c.B * co.nn_stride <= (1ll << 28) &&             // (the pairs' tiles)
+         (long long)c.B * gx->g <= (1ll << 27);                      // (the groups' query lists, room for all: 512 MiB at most)
+}
+
+// The pre-selection alone: per query the GA_C smallest (D~, row) of its searched rows in gx->amv / gx->ami, the flags in
+// gx->anan and the queries' tables in gx->ptab -- by group, or every searched row through gq_approx_scan
+void preselect(const GroupedCall &c, const CoarseResult &co, bool by_group) {
   gulon_grouped_index *gx = c.gx;
   gulon_index *ix = gx->pq;
   const int g = gx->g, B = c.B, nn_stride = co.nn_stride;
   hipStream_t st = c.st;
-  gx->qlist.ensure((size_t)B);
-  gx->qcount.ensure(1);
-  HIP_CHECK(hipMemsetAsync(gx->qcount.p, 0, sizeof(int), st));
   gx->ptab.ensure((size_t)B * ix->m_pad * 256);
   gx->apv.ensure((size_t)B * GA_WAVES * GA_C); gx->api.ensure((size_t)B * GA_WAVES * GA_C);
   gx->amv.ensure((size_t)B * GA_C); gx->ami.ensure((size_t)B * GA_C);
   gx->anan.ensure((size_t)B * GA_WAVES);
-  // by group with 8-bit bound tables (grouped_filter.hip) where a query searches more than a handful of groups; else
-  // every searched row through gq_approx_scan
-  const bool by_group = gx->gfilter.built && group_filter_applies(ix->m, ix->m_pad, ix->ng, ix->vec, ix->k, ix->d) &&
-                        nn_stride > GF_SAMPLE_GROUPS && B <= 65535 &&   // (a grid's y extent carries the query)
-                        (long long)B * nn_stride <= (1ll << 28) &&      // (the pairs' tiles)
-                        (long long)B * g <= (1ll << 27);                // (the groups' query lists, room for all: 512 MiB at most)
   if (by_group) {   // (this path builds the tables where it quantizes them)
     group_filter_run(gx->gfilter, ix->codes.p, ix->ng, ix->vec, ix->m, ix->m_pad, ix->k, ix->d, gx->ptab.p, ix->cents.p,
                      ix->from.p, ix->sdim.p, gx->xnorm.p, gx->xnmax,
@@ -984,10 +986,28 @@ void approx_stage(const GroupedCall &c, const CoarseResult &co, const GroupedKno
     launch_merge(false, gx->apv.p, gx->api.p, GA_WAVES, (long long)GA_C, (long long)GA_WAVES * GA_C, B, GA_C - 1, nullptr,
                  nullptr, nullptr, nullptr, gx->amv.p, gx->ami.p, st);
   }
-  hipLaunchKernelGGL(gq_rerank, dim3(B), dim3(64), 0, st, ix->codes.p, ix->ng, ix->vec, ix->m, ix->k, ix->d, ix->cents.p,
-                     ix->from.p, ix->sdim.p, gx->gcent.p, gx->bounds.p, g, c.dQ, gx->amv.p, gx->ami.p, gx->anan.p, gx->xnmax,
+}
+
+// gq_rerank over the lists in gx->amv / gx->ami / gx->anan: answers in d_oi / d_od / d_oc, the queries to redo appended
+// to gx->qlist / gx->qcount
+void launch_rerank(const GroupedCall &c) {
+  gulon_grouped_index *gx = c.gx;
+  gulon_index *ix = gx->pq;
+  hipLaunchKernelGGL(gq_rerank, dim3(c.B), dim3(64), 0, c.st, ix->codes.p, ix->ng, ix->vec, ix->m, ix->k, ix->d, ix->cents.p,
+                     ix->from.p, ix->sdim.p, gx->gcent.p, gx->bounds.p, gx->g, c.dQ, gx->amv.p, gx->ami.p, gx->anan.p, gx->xnmax,
                      c.K, c.d_oi, c.d_od, c.d_oc, gx->qlist.p, gx->qcount.p);
   HIP_CHECK(hipGetLastError());
+}
+
+// approximate pre-selection with one table per query, exact re-ranking of 64 candidates, certificate: answers in
+// d_oi / d_od / d_oc, the queries to redo in gx->qlist / gx->qcount
+void approx_stage(const GroupedCall &c, const CoarseResult &co, const GroupedKnobs &knobs) {
+  gulon_grouped_index *gx = c.gx;
+  gx->qlist.ensure((size_t)c.B);
+  gx->qcount.ensure(1);
+  HIP_CHECK(hipMemsetAsync(gx->qcount.p, 0, sizeof(int), c.st));
+  preselect(c, co, by_group_applies(c, co));
+  launch_rerank(c);
   if (knobs.stats) print_redo_stats(c);
 }
 
@@ -1243,3 +1263,104 @@ GULON_API int32_t gulon_grouped_index_row_error(gulon_grouped_index *idx, int32_
     *out = take_row_err(idx->pq);
   });
 }
+
+#ifdef GULON_TEST_HOOKS
+// The grouped pre-selection on its own (tests/test_gpu_grouped_stage.py, tests/grouped_stage_ref.py).  Builds a grouped
+// index from gulon_grouped_index_create's arguments, runs coarse_stage as run_grouped_query does and then, on the same
+// nn lists, preselect BOTH ways -- by group (group_filter_run) and through gq_ptables + gq_approx_scan + launch_merge --
+// each followed by gq_rerank.  Returns GULON_SELFTEST_GROUPED_REFUSED (78) where the production driver would not take the
+// by-group path for this index and batch (by_group_applies), or would not pre-select at all.
+// out[]: 0 nn [b][nn_stride], 1 nn_cnt [b], 2 cdist [b][g], 3 xnorm [n], 4 xnlo [g], 5 xcode [ceil(n / 64) 64] bytes,
+//   6 gnorm [g], 7 {xnmax, xn_step, gnmax}, 8 P [b][m_pad][256], 9 qs [b][4], 10 qb [b][GF_NT][256] bytes, 11 gcnt [g],
+//   12 tiles [meta[0]] GfTile records (room for b nn_stride / 16 + g + 1), 13 meta [4], 14 qcnt [b],
+//   15 queue [b][GF_CAP] (row, bits of the base): the first min(qcnt, GF_CAP) of a query, sorted by (row, base),
+//   16-18 amv [b][64], ami [b][64], anan [b][16] of the by-group path, 19-21 of the scan path,
+//   22-26 out_idx [b][k_nn], out_dist [b][k_nn], out_count [b], redo count [1], redo list [b] of the by-group path,
+//   27-31 of the scan path.
+// info: nn_stride, m_pad, vec, ng, GF_CAP, GF_PLACED.
+// (Declared here and bound by its test: the header's list of hooks is pinned by test_abi.)
+GULON_API int32_t gulon_selftest_grouped_stage(const uint8_t *codes, int32_t n, int32_t d, int32_t m, int32_t k,
+                                               const float *pq_cents, const float *group_centroids, const int32_t *offsets,
+                                               int32_t g, const float *queries, int32_t b, int32_t k_nn, int32_t strategy,
+                                               int32_t limit, void **out, int32_t *info) {
+  gulon_grouped_index *gx = nullptr;
+  bool refused = false;
+  const int32_t rc = guarded([&] {
+    GULON_REQUIRE(codes && pq_cents && group_centroids && queries && out && info, "null argument");
+    GULON_REQUIRE(n >= 1 && b >= 1 && b <= 4096 && k_nn >= 1 && k_nn <= GULON_MAX_K && (strategy == 0 || strategy == 1) && limit >= 1,
+                  "bad arguments");
+    for (int i = 0; i < 32; i++) GULON_REQUIRE(out[i] != nullptr, "out[%d] is null", i);
+    GULON_REQUIRE(gulon_grouped_index_create(codes, n, d, m, k, pq_cents, group_centroids, offsets, g, &gx) == GULON_OK && gx, "no index");
+    gulon_index *ix = gx->pq;
+    GroupFilter &gf = gx->gfilter;
+    if (ix->wide || gx->xnorm.n == 0 || !gf.built) { refused = true; return; }
+    hipStream_t st = nullptr;
+    const int B = b, K = k_nn;
+    gx->q_dev.upload(queries, (size_t)B * d, st);
+    DevBuf<int> oi((size_t)B * K), oc((size_t)B);
+    DevBuf<float> od((size_t)B * K);
+    const GroupedCall c{gx, gx->q_dev.p, B, K, strategy, limit, oi.p, od.p, oc.p, st};
+    const CoarseResult co = coarse_stage(c, false);
+    if (!by_group_applies(c, co)) { refused = true; return; }
+    const int nn_stride = co.nn_stride;
+    gx->qlist.ensure((size_t)B);
+    gx->qcount.ensure(1);
+    auto get = [&](int slot, const void *dev, size_t bytes) {
+      if (bytes) HIP_CHECK(hipMemcpy(out[slot], dev, bytes, hipMemcpyDeviceToHost));
+    };
+    for (int path = 0; path < 2; path++) {   // 0: by group, 1: gq_approx_scan
+      HIP_CHECK(hipMemsetAsync(gx->qcount.p, 0, sizeof(int), st));
+      HIP_CHECK(hipMemsetAsync(gx->qlist.p, 0xFF, sizeof(int) * (size_t)B, st));
+      preselect(c, co, path == 0);
+      launch_rerank(c);
+      HIP_CHECK(hipStreamSynchronize(st));
+      const int l0 = 16 + 3 * path, r0 = 22 + 5 * path;
+      get(l0, gx->amv.p, sizeof(float) * (size_t)B * GA_C);
+      get(l0 + 1, gx->ami.p, sizeof(int) * (size_t)B * GA_C);
+      get(l0 + 2, gx->anan.p, sizeof(int) * (size_t)B * GA_WAVES);
+      get(r0, oi.p, sizeof(int) * (size_t)B * K);
+      get(r0 + 1, od.p, sizeof(float) * (size_t)B * K);
+      get(r0 + 2, oc.p, sizeof(int) * (size_t)B);
+      get(r0 + 3, gx->qcount.p, sizeof(int));
+      get(r0 + 4, gx->qlist.p, sizeof(int) * (size_t)B);
+      if (path == 0) {   // the by-group path's state, before the other path overwrites the tables
+        get(8, gx->ptab.p, sizeof(float) * (size_t)B * ix->m_pad * 256);
+        get(9, gf.qs.p, sizeof(float) * (size_t)B * 4);
+        get(10, gf.qb.p, (size_t)B * GF_NT * 256);
+        get(11, gf.gcnt.p, sizeof(int) * (size_t)g);
+        int meta[4];
+        HIP_CHECK(hipMemcpy(meta, gf.meta.p, sizeof(meta), hipMemcpyDeviceToHost));
+        memcpy(out[13], meta, sizeof(meta));
+        const size_t tiles_room = (size_t)B * nn_stride / GF_QT + (size_t)g + 1;
+        GULON_REQUIRE(meta[0] >= 0 && (size_t)meta[0] <= tiles_room, "internal: %d tiles", meta[0]);
+        get(12, gf.tiles.p, sizeof(GfTile) * (size_t)meta[0]);
+        std::vector<int> qcnt((size_t)B);
+        HIP_CHECK(hipMemcpy(qcnt.data(), gf.qcnt.p, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost));
+        memcpy(out[14], qcnt.data(), sizeof(int) * (size_t)B);
+        std::vector<unsigned long long> ent((size_t)GF_CAP);
+        for (int q = 0; q < B; q++) {
+          const size_t cnt = (size_t)std::min(std::max(qcnt[q], 0), GF_CAP);
+          if (cnt) HIP_CHECK(hipMemcpy(ent.data(), gf.queue.p + (size_t)q * GF_CAP, sizeof(uint2) * cnt, hipMemcpyDeviceToHost));
+          std::vector<std::pair<uint32_t, uint32_t>> pr(cnt);
+          for (size_t e = 0; e < cnt; e++) pr[e] = {(uint32_t)(ent[e] & 0xFFFFFFFFull), (uint32_t)(ent[e] >> 32)};
+          std::sort(pr.begin(), pr.end());
+          uint32_t *o = static_cast<uint32_t *>(out[15]) + (size_t)q * GF_CAP * 2;
+          for (size_t e = 0; e < cnt; e++) { o[2 * e] = pr[e].first; o[2 * e + 1] = pr[e].second; }
+        }
+      }
+    }
+    get(0, gx->nn.p, sizeof(int) * (size_t)B * nn_stride);
+    get(1, gx->nn_cnt.p, sizeof(int) * (size_t)B);
+    get(2, gx->cdist.p, sizeof(float) * (size_t)B * g);
+    get(3, gx->xnorm.p, sizeof(float) * (size_t)n);
+    get(4, gf.xnlo.p, sizeof(float) * (size_t)g);
+    get(5, gf.xcode.p, (size_t)ceil_div(n, 64) * 64);
+    get(6, gf.gnorm.p, sizeof(float) * (size_t)g);
+    const float sc[3] = {gx->xnmax, gf.xn_step, gf.gnmax};
+    memcpy(out[7], sc, sizeof(sc));
+    info[0] = nn_stride; info[1] = ix->m_pad; info[2] = ix->vec; info[3] = ix->ng; info[4] = GF_CAP; info[5] = GF_PLACED;
+  });
+  if (gx) (void)gulon_grouped_index_destroy(gx);
+  return rc != GULON_OK ? rc : refused ? 78 : GULON_OK;
+}
+#endif

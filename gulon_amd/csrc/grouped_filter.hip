@@ -33,7 +33,6 @@ namespace {
 
 constexpr int GF_THREADS = 512;
 constexpr int GF_NW = GF_THREADS / 64;
-constexpr int GF_NT = 17;                       // tables per query: 16 quantizers and the row norm
 constexpr float GF_SHRINK = 0.99999905f;        // 1 - 2^-20: a product of two roundings stays below the real product
 #ifndef GULON_GF_NADD
 #define GULON_GF_NADD 1

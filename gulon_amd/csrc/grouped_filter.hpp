@@ -5,6 +5,7 @@
 
 namespace gulon {
 
+constexpr int GF_NT = 17;       // tables per query: 16 quantizers and the row norm
 constexpr int GF_QT = 16;       // queries per tile: one 16-byte table entry holds their bytes
 constexpr int GF_CAP = 16384;   // survivors kept per query (more: the query goes to the literal kernels)
 constexpr int GF_WAVES = 16;    // per-query lists written by gf_survivors (= gq_approx_scan's)

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import filter_stage_ref as fs
+import grouped_stage_ref as gs
 import value_regimes as vr
 from conftest import bits
 from oracle import py_oracle as po
@@ -208,3 +209,30 @@ def test_filter_stage_checks_reject_a_broken_stage(oracle, form, regime, nadd, b
     run()
     with pytest.raises(AssertionError):
         run(**({"extra": -1} if broken == "budget" else {broken: False}))
+
+
+@pytest.mark.parametrize("name", gs.FINITE)
+def test_grouped_stage_cases_meet_their_preconditions(oracle, name):
+    """What test_gpu_grouped_stage.py needs of its data, without a GPU: on a numpy model of the pre-selection every query's
+    upper set holds at most a third of its searched rows (but for grouped_stage_ref.LOOSE) and fewer than GF_CAP rows,
+    every regular case has a query with 64 searched rows, no certificate sits on its edge, and the model passes every
+    check of the GPU test."""
+    cs = gs.case(oracle, name)
+    out = gs.stage_model(cs)
+    gs.preconditions(cs, out)
+    stats, worst, certified, edges = gs.check_stage(cs, out, oracle)
+    assert edges == 0 and worst <= 1.0
+    assert name not in gs.REGULAR or name in gs.LOOSE + ("k63",) or certified[0] > 0      # (K = 63: ek IS the 64th distance)
+
+
+@pytest.mark.parametrize("name,broken", [("m3", "lim")] + [(n, "margin") for n in ("m16", "m5", "g90", "b17")]
+                         + [(n, "padding") for n in ("m16", "g90", "b17")])
+def test_grouped_stage_checks_reject_a_broken_stage(oracle, name, broken):
+    """The checks are not vacuous: a model of gf_filter whose limit lacks its `+ 2`, of gf_quant whose budget lacks the
+    margin, or of gf_filter with a limit for a tile's padding slots fails them.  (The limit: on m3 alone.  A row's m + 1 levels
+    are rounded down, half a step each on average, so with more tables no row the checks insist on comes within reach of
+    a limit two steps lower.)"""
+    cs = gs.case(oracle, name)
+    mutation = {"lim": dict(lim_plus=0), "margin": dict(with_margin=False), "padding": dict(pad_limit=1)}[broken]
+    with pytest.raises(AssertionError):
+        gs.check_stage(cs, gs.stage_model(cs, **mutation), oracle)
