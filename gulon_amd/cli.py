@@ -1,6 +1,7 @@
 """`python -m gulon_amd`: the reference's four commands (command/Main.scala:7-11), `inspect`, `update` and `build-fine`.
 
-  build-index -d l2|cosine -o INDEX [-k N] [-m N] [-n N] [-p [--partitions N] [-l N]] FILE
+  build-index -d l2|cosine -o INDEX [-k N] [-m N] [-n N] [-p [--partitions N] [-l N]] [-R ROTATION [--rotation-rounds N]]
+              FILE
                                        command/BuildIndex.scala: a word2vec text file -> an index file; the text is
                                        parsed on the device (word_vectors.read_word2vec_device) and every later stage
                                        runs there too (build.build_index)
@@ -58,6 +59,13 @@ without the word itself.  A line is printed as `line: w1,w2,...`, `line: not fou
 `line: invalid expression` (an empty line, a leading or trailing operator, two operators or two words in a row).
 Works together with -v / -c.
 
+-R/--rotation FILE (not in the reference; rotation.py, csrc/rotate.hip): an orthogonal rotation learned before quantizing.
+build-index -R FILE [--rotation-rounds N] learns it on the vectors as read (N refinement rounds, default 4; with -p too it
+is learned for the flat quantizer), writes it to FILE, rotates the vectors on the device and builds the index over them.
+The query commands take the same -R FILE: the loaded index is wrapped (rotation.RotatedWordIndex) before -v, -f, -r and -x
+apply, so query vectors are rotated on their way in and -v's vectors once on the device.  On test, inspect, build-fine and
+update, -R FILE rotates the vectors file (-a for update) after reading it; the index file is used as it is.
+
 Input is UTF-8; lines end as java.io.BufferedReader.readLine ends them (\\n, \\r or \\r\\n).  Words are queried in
 batches; the output is the same as querying them one at a time."""
 import argparse
@@ -101,6 +109,8 @@ class BuildConfig:
     partitioned: Optional[object]
     output: str
     input: str
+    rotation: Optional[str] = None        # -R: learn a rotation first and write it to this file
+    rotation_rounds: int = 4              # --rotation-rounds: refinement rounds after the initial rotation
 
 
 def _integer(s):
@@ -134,6 +144,7 @@ class RecallConfig:
     epsilon: float
     candidates: Optional[int] = None      # -c: the recall of the index refined over this many candidates
     fine: Optional[str] = None            # -f: refined against this fine index file instead of the vectors
+    rotation: Optional[str] = None        # -R: the index was built over vectors rotated by this file
 
 
 @dataclass(frozen=True)
@@ -145,6 +156,7 @@ class FineConfig:
     num_clusters: int = 256
     num_quantizers: int = 25
     max_iterations: int = 100
+    rotation: Optional[str] = None        # -R: the index was built over vectors rotated by this file
 
 
 @dataclass(frozen=True)
@@ -152,6 +164,7 @@ class InspectConfig:
     index: str
     vectors: Optional[str] = None         # -v: compare the index with the vectors it was built from
     worst: int = 10                       # -w: words with the largest error to list
+    rotation: Optional[str] = None        # -R: the index was built over vectors rotated by this file
 
 
 @dataclass(frozen=True)
@@ -160,6 +173,7 @@ class UpdateConfig:
     output: str
     add: Optional[str] = None             # -a: word2vec text of the words to add or replace
     remove: Optional[str] = None          # -x: one word per line to remove
+    rotation: Optional[str] = None        # -R: the index was built over vectors rotated by this file
 
 
 def _sample_size(s):                                         # Test.scala:24-28
@@ -179,6 +193,28 @@ def _epsilon(s):                                             # Test.scala:29-33
     return v
 
 
+def _rounds(s):
+    v = _integer(s)
+    if v < 0:
+        raise argparse.ArgumentTypeError("must not be negative")
+    return v
+
+
+_ROTATED_VECTORS = ("rotation file the index was built with (build-index -R): the vectors are rotated on the device after "
+                    "they are read")
+
+
+def _rotated(path, vectors):
+    """The word vectors as read, or with -R rotated on the device by that file (the unrotated matrix is freed)."""
+    if path is None:
+        return vectors
+    from .rotation import Rotation
+    rotated = Rotation.load(path).rotate_word_vectors(vectors)
+    if vectors.matrix is not None:
+        vectors.matrix.close()
+    return rotated
+
+
 def _parser():
     p = argparse.ArgumentParser(prog="python -m gulon_amd",
                                 description="build and query a Gulon nearest neighbour index")
@@ -195,6 +231,12 @@ def _parser():
     b.add_argument("--partitions", type=_integer, default=None, metavar="num", help="set fixed number of partitions")
     b.add_argument("-l", "--limit", type=_integer, default=None, metavar="num", help="number of partitions to search")
     b.add_argument("-o", "--output", required=True, metavar="file", help="index output file")
+    b.add_argument("-R", "--rotation", default=None, metavar="file",
+                   help="learn an orthogonal rotation on the vectors as read, write it to this file and build the index "
+                        "over the rotated vectors; with --partitioned too the rotation is learned for the flat quantizer, "
+                        "not for the partitions' residuals")
+    b.add_argument("--rotation-rounds", type=_rounds, default=None, metavar="num",
+                   help="refinement rounds after the initial rotation (needs --rotation; default 4)")
     b.add_argument("file", metavar="file")
     bf = sub.add_parser("build-fine", help="build the fine index of a nearest neighbour index",
                         description="build the fine index of a nearest neighbour index: a second quantizer over the "
@@ -208,6 +250,7 @@ def _parser():
     bf.add_argument("-n", "--max-iters", type=_integer, default=100, metavar="iterations",
                     help="maximum number of iterations per quantizer")
     bf.add_argument("-o", "--output", required=True, metavar="file", help="fine index output file")
+    bf.add_argument("-R", "--rotation", default=None, metavar="file", help=_ROTATED_VECTORS)
     for name, help_, need_file in (("query-words", "query nearest neighbour index by word", False),
                                    ("query", "query nearest neighbour index", True)):
         s = sub.add_parser(name, help=help_, description=help_)
@@ -226,6 +269,9 @@ def _parser():
         s.add_argument("-r", "--restrict", default=None, metavar="file",
                        help="take the neighbours from the words of this file only (one word per line; words the index "
                             "lacks are ignored and counted on stderr)")
+        s.add_argument("-R", "--rotation", default=None, metavar="file",
+                       help="rotation file the index was built with (build-index -R): query vectors, and the vectors of "
+                            "--vectors, are rotated before they reach the index")
         if name == "query-words":
             s.add_argument("-x", "--expressions", action="store_true",
                            help="read every line as an expression `word (+|- word)*` (operators as stand-alone tokens): "
@@ -246,6 +292,7 @@ def _parser():
     t.add_argument("-f", "--fine", default=None, metavar="file",
                    help="report the recall of the index refined against this fine index (build-fine) instead of the "
                         "vectors; needs --candidates")
+    t.add_argument("-R", "--rotation", default=None, metavar="file", help=_ROTATED_VECTORS)
     i = sub.add_parser("inspect", help="report code usage and quantization error of an index",
                        description="report code usage and quantization error of an index")
     i.add_argument("-i", "--index", required=True, metavar="file", help="path to ANN index")
@@ -254,6 +301,7 @@ def _parser():
                         "against these")
     i.add_argument("-w", "--worst", type=_positive, default=None, metavar="num",
                    help="words with the largest error to list (needs --vectors; default 10)")
+    i.add_argument("-R", "--rotation", default=None, metavar="file", help=_ROTATED_VECTORS + " (needs --vectors)")
     u = sub.add_parser("update", help="add, replace and remove words of an index without retraining",
                        description="add, replace and remove words of an index without retraining")
     u.add_argument("-i", "--index", required=True, metavar="file", help="path to ANN index")
@@ -262,6 +310,7 @@ def _parser():
                    help="word2vec word vectors to add; a word the index already has is replaced")
     u.add_argument("-x", "--remove", default=None, metavar="file",
                    help="words to remove, one per line (words the index lacks are ignored and counted)")
+    u.add_argument("-R", "--rotation", default=None, metavar="file", help=_ROTATED_VECTORS + " (needs --add)")
     return p
 
 
@@ -307,7 +356,12 @@ def build_config(parser, args):
         partitioned = None
     else:
         parser.error("--partitions and --limit are only applicable with --partitioned")
-    return BuildConfig(args.metric, args.clusters, args.quantizers, args.max_iters, partitioned, args.output, args.file)
+    if args.rotation is None:
+        if args.rotation_rounds is not None:
+            parser.error("--rotation-rounds is only applicable with --rotation")
+        return BuildConfig(args.metric, args.clusters, args.quantizers, args.max_iters, partitioned, args.output, args.file)
+    return BuildConfig(args.metric, args.clusters, args.quantizers, args.max_iters, partitioned, args.output, args.file,
+                       args.rotation, args.rotation_rounds if args.rotation_rounds is not None else 4)
 
 
 def run_build_index(config: BuildConfig, write):
@@ -319,8 +373,16 @@ def run_build_index(config: BuildConfig, write):
     vectors = log_task(write, "Reading word vectors",
                        lambda: read_word2vec_device(config.input, normalize=config.metric == "cosine"),
                        lambda v: f"Read {v.size} word vectors")             # CommandUtils.scala:112-115
-    words, index = build_index(vectors, config.metric, config.partitioned,
-                               Config(config.num_clusters, config.num_quantizers, config.max_iterations), write)
+    pq_config = Config(config.num_clusters, config.num_quantizers, config.max_iterations)
+    if config.rotation is not None:
+        from .rotation import train_rotation
+        rotation, _ = train_rotation(vectors.matrix, pq_config, config.rotation_rounds, write)
+        log_task(write, f"Writing rotation to {config.rotation}", lambda: rotation.save(config.rotation),
+                 f"Wrote rotation to {config.rotation}")
+        rotated = rotation.rotate_word_vectors(vectors)
+        vectors.matrix.close()
+        vectors = rotated
+    words, index = build_index(vectors, config.metric, config.partitioned, pq_config, write)
 
     def dump():                                                              # CommandUtils.writeIndex (:117-120)
         with open(config.output, "wb") as fh:
@@ -332,6 +394,7 @@ def run_recall(config: RecallConfig, write, load):
     """Test.run up to the result (Test.scala:47-51, CommandUtils.scala:153-164) -> {k: SummaryStats}.
     The vectors are read with normalize=False ALWAYS, for a cosine index too, as the reference does (Test.scala:48
     passes `false`): the index normalises the query itself, the recall distances are taken on the raw vectors.
+    config.rotation: the vectors are rotated on the device after they are read, the normalised reading too.
     An index form that cannot answer k = 1000 fails here with the library's message; k is never clamped.
     config.candidates: the recall of RefinedIndex(index, vectors, candidates) instead.  Its vectors are what the index
     prepares its queries for -- a NORMALISED reading of the same file for a cosine index -- while the queries and the
@@ -342,13 +405,15 @@ def run_recall(config: RecallConfig, write, load):
     from .word_vectors import read_word2vec_device
     vectors = log_task(write, "Reading word vectors", lambda: read_word2vec_device(config.vectors, normalize=False),
                        lambda v: f"Read {v.size} word vectors")
+    vectors = _rotated(config.rotation, vectors)
     index = load(config.index)
     raw = vectors.sorted()
     if config.fine is not None:
         index = index.fine_refined(load(config.fine), config.candidates)
     elif config.candidates is not None:
         cosine = index.metric == "cosine"
-        originals = read_word2vec_device(config.vectors, normalize=True).sorted() if cosine else raw
+        originals = _rotated(config.rotation, read_word2vec_device(config.vectors, normalize=True)).sorted() \
+            if cosine else raw
         index = index.refined(originals, config.candidates)
     tests = log_task(write, "Sampling test vectors and precomputing distances",
                      lambda: Tests.sample(raw, config.sample_size),
@@ -371,7 +436,11 @@ def run_inspect(config: InspectConfig, load, vectors):
     index = load(config.index)
     if config.vectors is None:
         return index.inspect()
-    return index.inspect(vectors(config.vectors, index.metric == "cosine"), config.worst)
+    originals = vectors(config.vectors, index.metric == "cosine")
+    if config.rotation is not None:
+        from .rotation import Rotation
+        originals = Rotation.load(config.rotation).rotate_word_vectors(originals)
+    return index.inspect(originals, config.worst)
 
 
 class UpdateError(Exception):
@@ -391,6 +460,7 @@ def run_update(config: UpdateConfig, write, load):
         add = log_task(write, "Reading word vectors",
                        lambda: read_word2vec_device(config.add, normalize=index.metric == "cosine"),
                        lambda v: f"Read {v.size} word vectors")
+        add = _rotated(config.rotation, add)
     if config.remove is not None:
         with open(config.remove, "rb") as fh:
             remove = read_lines(fh.read())
@@ -420,7 +490,8 @@ def run_build_fine(config: FineConfig, write, load):
     index = log_task(write, f"Reading index from {config.index}", lambda: load(config.index),
                      lambda i: f"Read index of {i.size} words")
     vectors = log_task(write, "Reading word vectors",
-                       lambda: read_word2vec_device(config.vectors, normalize=index.metric == "cosine").sorted(),
+                       lambda: _rotated(config.rotation, read_word2vec_device(
+                           config.vectors, normalize=index.metric == "cosine")).sorted(),
                        lambda v: f"Read {v.size} word vectors")
     fine = build_fine_index(index, vectors, Config(config.num_clusters, config.num_quantizers, config.max_iterations),
                             write)
@@ -435,6 +506,16 @@ def read_originals(path, normalize):
     """The -v vectors of the query commands: on the device, in word order (their key index resolves the index's words)."""
     from .word_vectors import read_word2vec_device
     return read_word2vec_device(path, normalize=normalize).sorted()
+
+
+def _loaded(args, load, rotation):
+    """The index file of the query commands as loaded, or with -R behind its rotation: wrapped before -v, -f, -r and -x
+    are applied, so each of them meets the rotated form."""
+    index = load(args.index)
+    if args.rotation is None:
+        return index
+    from .rotation import RotatedWordIndex, Rotation
+    return RotatedWordIndex(index, (rotation if rotation is not None else Rotation.load)(args.rotation))
 
 
 def _restricted(args, index):
@@ -459,7 +540,7 @@ def _refined(args, index, vectors, load):
 
 
 def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None, vectors=None, inspect=None,
-         update=None, fine=None):
+         update=None, fine=None, rotation=None):
     """Returns the exit code.  stdin / stdout: binary streams (default: the process's); load: path -> index with
     batch_query_by_words / batch_query (default WordIndex.load); build: (BuildConfig, write) -> None, the whole of
     build-index behind its argument handling (default run_build_index); recall: (RecallConfig, write, load) ->
@@ -468,7 +549,8 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
     (InspectConfig, load, vectors) -> IndexReport, the whole of inspect between its argument handling and its lines
     (default run_inspect); update: (UpdateConfig, write, load) -> the updated index with its four counters, the whole
     of update behind its argument handling (default run_update); fine: (FineConfig, write, load) -> None, the whole of
-    build-fine behind its argument handling (default run_build_fine).  The fine index behind -f is read with `load`."""
+    build-fine behind its argument handling (default run_build_fine).  The fine index behind -f is read with `load`.  rotation: path -> the rotation behind -R of the
+    query commands (default Rotation.load)."""
     parser = _parser()
     args = parser.parse_args(argv)
     if args.command == "update" and args.add is None and args.remove is None:
@@ -483,6 +565,10 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
             parser.error("--fine is not applicable with --vectors")
         if args.restrict is not None:
             parser.error("--fine is not applicable with --restrict")
+    if args.command == "inspect" and args.rotation is not None and args.vectors is None:
+        parser.error("--rotation is only applicable with --vectors")
+    if args.command == "update" and args.rotation is not None and args.add is None:
+        parser.error("--rotation is only applicable with --add")
     if args.command == "test" and args.fine is not None and args.candidates is None:
         parser.error("--fine needs --candidates")
     if args.command in ("query", "query-words") and args.restrict is not None:
@@ -507,17 +593,19 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
     if args.command == "build-index":
         (build if build is not None else run_build_index)(build_config(parser, args), log)
     elif args.command == "build-fine":
-        config = FineConfig(args.index, args.vectors, args.output, args.clusters, args.quantizers, args.max_iters)
+        config = FineConfig(args.index, args.vectors, args.output, args.clusters, args.quantizers, args.max_iters,
+                            args.rotation)
         (fine if fine is not None else run_build_fine)(config, log, load)
     elif args.command == "test":
-        config = RecallConfig(args.vectors, args.index, args.sample, args.error, args.candidates, args.fine)
+        config = RecallConfig(args.vectors, args.index, args.sample, args.error, args.candidates, args.fine,
+                              args.rotation)
         print_results((recall if recall is not None else run_recall)(config, log, load), write)
     elif args.command == "inspect":
-        config = InspectConfig(args.index, args.vectors, args.worst if args.worst is not None else 10)
+        config = InspectConfig(args.index, args.vectors, args.worst if args.worst is not None else 10, args.rotation)
         for line in (inspect if inspect is not None else run_inspect)(config, load, vectors).lines():
             write(line + "\n")
     elif args.command == "update":
-        config = UpdateConfig(args.index, args.output, args.add, args.remove)
+        config = UpdateConfig(args.index, args.output, args.add, args.remove, args.rotation)
         try:
             u = (update if update is not None else run_update)(config, log, load)
         except UpdateError as e:
@@ -526,7 +614,7 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
             return 1
         write(f"{u.added} added, {u.replaced} replaced, {u.removed} removed, {u.ignored} ignored\n")
     elif args.command == "query-words":
-        index = _refined(args, load(args.index), vectors, load)
+        index = _refined(args, _loaded(args, load, rotation), vectors, load)
         if args.file is None:
             data = stdin.read()
         else:
@@ -536,7 +624,7 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
     else:
         from .word_vectors import read_word2vec
         queries = read_word2vec(args.file)
-        index = _refined(args, load(args.index), vectors, load)
+        index = _refined(args, _loaded(args, load, rotation), vectors, load)
         query(index, args.neighbours, queries, write)
     stdout.flush()
     return 0

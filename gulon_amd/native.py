@@ -183,6 +183,10 @@ SIGNATURES = {
                                                      _i32p]),
     "gulon_grouped_index_refine_codes_topk_dev": (_i32, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp,
                                                          _vp]),
+    "gulon_dataset_rotate": (_i32, [_vp, _f32p, _i32, C.POINTER(_vp)]),
+    "gulon_rotate_rows": (_i32, [_f32p, _i32, _i32, _f32p, _i32, _f32p]),
+    "gulon_rotate_rows_dev": (_i32, [_vp, C.c_int64, _i32, _vp, _i32, _vp, _vp]),
+    "gulon_dataset_moment": (_i32, [_vp, _vp, _f64p]),
 }
 
 _lib = None

@@ -719,6 +719,29 @@ int32_t gulon_grouped_index_refine_codes_topk_dev(gulon_grouped_index *coarse, g
                                                   int32_t *d_out_idx, float *d_out_dist, int32_t *d_out_count,
                                                   void *stream);
 
+/* ---- Rotated indexes (rotate.hip; DESIGN.md "Rotated indexes") -------------------------------------------------------
+ * None of these is a Scala method: the reference has no rotation, so nothing here cites it.  An orthogonal d x d matrix R
+ * is applied once to the data and once to each query; the index over the rotated rows is an ordinary index.
+ *
+ * rotate: out[i][c] = sum_j x[i][j] * R[j][c] (transpose != 0: R[c][j] in its place), in the project's arithmetic --
+ * binary32, s = 0; for j ascending: s = s + (x[i][j] * R[j][c]); product and sum each rounded, nothing fused.  Non-finite
+ * inputs propagate as IEEE 754 says.  Any d >= 1 and n >= 0 (n = 0 succeeds and launches nothing); `rotation` is d * d
+ * row-major.  Otherwise GULON_ERR_INVALID_ARGUMENT.
+ *   gulon_dataset_rotate    rotation in host memory; *out = a new device dataset of ds's shape (gulon_dataset_destroy)
+ *   gulon_rotate_rows       x, rotation and out in host memory
+ *   gulon_rotate_rows_dev   every pointer a device pointer, d_out != d_x; enqueued on `stream` (hipStream_t) and not
+ *                           synchronised, nothing is allocated */
+int32_t gulon_dataset_rotate(const gulon_dataset *ds, const float *rotation, int32_t transpose, gulon_dataset **out);
+int32_t gulon_rotate_rows(const float *x, int32_t n, int32_t d, const float *rotation, int32_t transpose, float *out);
+int32_t gulon_rotate_rows_dev(const float *d_x, int64_t n, int32_t d, const float *d_rotation, int32_t transpose,
+                              float *d_out, void *stream);
+/* moment: out[p * b->d + q] = sum_r a[r][p] * b[r][q], accumulated in binary64 (host memory, a->d * b->d doubles); the
+ * two datasets must have the same number of rows.  The products are exact in binary64, only the additions round:
+ * |out - exact| <= gamma_(n-1) * sum_r |a[r][p] * b[r][q]|.  The order of the additions is fixed by the source (chunks of
+ * a constant number of rows, each summed r ascending, the chunks added in ascending order) and uses no atomics: the same
+ * bits on every call and every device.  Zero rows give zeros. */
+int32_t gulon_dataset_moment(const gulon_dataset *a, const gulon_dataset *b, double *out);
+
 #ifdef __cplusplus
 }
 #endif
