@@ -12,7 +12,7 @@
 // than 2E, the reference's scan takes exactly the same branches, draws no random bit, and
 // the MFMA argmin IS the reference's answer.  Rows with any comparison inside the 2E band
 // (including exact ties) are appended to a list and re-evaluated by the exact VALU kernel
-// (assign_exact + assign_resolve in kmeans.hip).  Output is therefore bit-identical to the
+// (assign_exact + assign_resolve in kmeans_assign.hip).  Output is therefore bit-identical to the
 // reference algorithm; the MFMA only decides which rows need the expensive path.
 //
 // Layout: centroid tiles are the MFMA M dimension, data rows the N dimension, the
@@ -860,6 +860,13 @@ void pack_slice(const float *dX, int n, int ld, int from, int s, int k, PackedSl
     hipLaunchKernelGGL(pack_slice_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, st, dX, n, ld, from, s, ps.T,
                        total, ps.xq.p);
   HIP_CHECK(hipGetLastError());
+}
+
+const PackedSlice *pack_slice_if_filtered(const float *dX, int n, int ld, int from, int s, int k, PackedSlice &ps,
+                                          hipStream_t st) {
+  if (!mfma_assign_supported(s, k)) return nullptr;
+  pack_slice(dX, n, ld, from, s, k, ps, st);
+  return &ps;
 }
 
 // Runs the filter.  d_assign receives the answer of every unflagged row; flagged rows are

@@ -1,8 +1,8 @@
 // KMeans.fromAssignment (KMeans.scala:198-226) without the regrouped copy of the data.
 //
 // The running mean  c <- c + (x - c) / n  is one sequential chain per (cluster, dimension), over the cluster's rows in
-// row order.  kmeans.hip feeds the chains by regrouping every sub-quantizer's slices by cluster (sort_place: 12 GB read,
-// 12.8 GB written in 160-byte runs at BASELINE config 3) and streaming the copy back (update_chains_pk: 12.8 GB): 37.6 GB
+// row order.  kmeans_update.hip feeds the chains by regrouping every sub-quantizer's slices by cluster (sort_place: 12 GB
+// read, 12.8 GB written in 160-byte runs at BASELINE config 3) and streaming the copy back (update_chains_pk: 12.8 GB): 37.6 GB
 // moved for 12 GB of data, 9.3-10.2 ms per full-PQ iteration.  Here the data is read ONCE, in row order:
 //
 //   * once per training, every sub-quantizer's slice is stored PAIR-MAJOR: xp[pair][row] = (x[row][2 pair],
@@ -19,8 +19,8 @@
 //     the reference's.
 //
 // Per step the arithmetic is update_chains_pk's: a = x - c, the correctly rounded quotient a / n as the corrected
-// product with y = RN(1 / n) (mean_quotient_fast, kmeans.hip) -- y is computed a group of four steps ahead (n is known
-// long before c is): v_rcp_f32 and one fma-corrected Newton step, which IS the correctly rounded reciprocal for every
+// product with y = RN(1 / n) (mean_quotient_fast, kmeans_update.hip) -- y is computed a group of four steps ahead (n is
+// known long before c is): v_rcp_f32 and one fma-corrected Newton step, which IS the correctly rounded reciprocal for every
 // integer n < 2^24 (checked exhaustively against 1.0f / n by gulon_selftest_mean_division) -- and the plain division
 // where the corrected form is not trusted: numerators below 2^-100 (found per chunk, which is then redone), values of
 // 2^99 and beyond / infinities / NaNs anywhere in the slice (found when it is packed), counts from 2^24.
@@ -350,6 +350,27 @@ void stream_pack_pairs(const float *xs, int n, int s, float *xp, int *wild, hipS
   HIP_CHECK(hipGetLastError());
 }
 
+void StreamSlice::prepare(const float *xs, int n, int s_, int k, hipStream_t st) {
+  s = s_;
+  ns = stream_padded_rows(n);
+  const size_t words = 2 * (size_t)ns * (size_t)((s + 1) / 2);
+  xp.alloc(words);
+  HIP_CHECK(hipMemsetAsync(xp.p, 0, sizeof(float) * words, st));   // the padding rows
+  wild.alloc(1);
+  HIP_CHECK(hipMemsetAsync(wild.p, 0, sizeof(int), st));
+  stream_pack_pairs(xs, n, s, xp.p, wild.p, st);
+  size_t coff_words = 0;
+  ord.alloc(stream_order_words(n, k, &coff_words));
+  coff.alloc(coff_words);
+}
+
+StreamDesc StreamSlice::desc(const int *assign, float *cout) const {
+  StreamDesc D{};
+  D.assign = assign; D.xp = xp.p; D.ord = ord.p; D.coff = coff.p; D.cout = cout; D.wild = wild.p;
+  D.s = s; D.ns = ns;
+  return D;
+}
+
 // the chunks' stable order of every problem's current assignment (descs[..].assign -> ord, coff)
 void kmeans_stream_order(const std::vector<StreamDesc> &descs, StreamDesc *d_descs, int n, int k, hipStream_t st) {
   const int np = (int)descs.size();
@@ -399,21 +420,14 @@ GULON_API int32_t gulon_selftest_stream_update(const float *x, int32_t n, int32_
     std::vector<float> slice((size_t)n * s);
     for (int r = 0; r < n; r++) memcpy(&slice[(size_t)r * s], x + (size_t)r * ld + from, sizeof(float) * s);
     DevBuf<float> xs((size_t)n * s), cout((size_t)k * s);
-    DevBuf<int> a(n), wild(1);
-    const size_t ns = (size_t)stream_padded_rows(n);
-    DevBuf<float> xp(2 * ns * (size_t)((s + 1) / 2));
-    size_t coff_words = 0;
-    DevBuf<unsigned short> ord(stream_order_words(n, k, &coff_words)), coff(coff_words);
+    DevBuf<int> a(n);
+    StreamSlice sl;
     DevBuf<StreamDesc> d_desc(1);
     HIP_CHECK(hipMemcpy(xs.p, slice.data(), sizeof(float) * slice.size(), hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(a.p, assign, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemset(wild.p, 0, sizeof(int)));
-    HIP_CHECK(hipMemset(xp.p, 0, sizeof(float) * 2 * ns * (size_t)((s + 1) / 2)));
     HIP_CHECK(hipMemset(cout.p, 0, sizeof(float) * (size_t)k * s));
-    stream_pack_pairs(xs.p, n, s, xp.p, wild.p, 0);
-    StreamDesc D;
-    D.assign = a.p; D.xp = xp.p; D.ord = ord.p; D.coff = coff.p; D.cout = cout.p; D.wild = wild.p;
-    D.s = s; D.pad = 0; D.ns = (long long)ns;
+    sl.prepare(xs.p, n, s, k, 0);
+    const StreamDesc D = sl.desc(a.p, cout.p);
     kmeans_stream_order({D}, d_desc.p, n, k, 0);
     kmeans_stream_chains({D}, d_desc.p, n, k, 0);
     HIP_CHECK(hipDeviceSynchronize());

@@ -1,5 +1,5 @@
 // Cycles per step of the running-mean recurrence p += RN((x - p) / n) in its three-operation quotient form
-// (kmeans.hip, update_chains*), ONE wave per SIMD, no memory traffic in the loop -- what a chain costs when nothing
+// (kmeans_update.hip, update_chains*), ONE wave per SIMD, no memory traffic in the loop -- what a chain costs when nothing
 // but its own dependent operations is in the way:
 //   mode 0: one chain per lane, scalar fp32 (5 dependent operations per step)
 //   mode 1: two chains per lane on the packed pipe (v_pk_add/mul/fma_f32)

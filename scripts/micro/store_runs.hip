@@ -1,4 +1,4 @@
-// What a scattered-run store stream costs (the k-means placement, kmeans.hip sort_place*): every workgroup writes
+// What a scattered-run store stream costs (the k-means placement, kmeans_update.hip sort_place*): every workgroup writes
 // 40 KiB as 256 runs of RUN bytes, run c of workgroup b at  base[c] + b * RUN  (neighbouring workgroups continue
 // each other's runs, as consecutive chunks do), from registers, nothing else in the kernel.
 //   mode 0: 8-byte stores (dwordx2), lanes walk the runs in order            (what sort_place does)

@@ -1,5 +1,5 @@
 // Test infrastructure (tests/test_markstein_exhaustive.py).  The k-means update computes (x - c) / n as the corrected
-// product  q0 = RN(a y), r = fma(-n, q0, a), q = fma(r, y, q0)  with y = RN(1 / n)  (gulon_amd/csrc/kmeans.hip,
+// product  q0 = RN(a y), r = fma(-n, q0, a), q = fma(r, y, q0)  with y = RN(1 / n)  (gulon_amd/csrc/kmeans_update.hip,
 // mean_quotient_fast; KMeans.scala:218 is a float division).  The proofs single out divisors whose significand is all
 // ones; for the integer counts nearest to that shape, n = 2^j - 1 (j = 24 IS that shape), this sweeps EVERY numerator
 // significand and sign of one binade -- the arithmetic is scale invariant away from under- and overflow, which the

@@ -1,10 +1,16 @@
 """GPU parity tests for the build path: KMeans init/assign/parAssign/fromAssignment/
 computeClusters/iterate and ProductQuantizer train/encode vs the CPU oracle.
 Everything is compared bit for bit (centroids as uint32 views, assignments and codes as ints)."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
 from conftest import bits
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 
@@ -297,3 +303,52 @@ def test_few_exact_ties_take_the_sparse_replay(oracle, g, n, d, m, k, iters, nba
     pq = g.ProductQuantizer.apply(g.DeviceMatrix.from_host(X), g.ProductQuantizerConfig(k, m, iters))
     cents, _, _ = oracle.pq_train(X, m, k, iters)
     assert np.array_equal(bits(pq.flat_centroids()), bits(cents))
+
+
+def _check_pq_against_oracle(oracle, X, m, k, cents_got, idx_got, iters):
+    cents, _, _ = oracle.pq_train(X, m, k, iters)
+    assert np.array_equal(bits(cents_got), bits(cents))
+    assert np.array_equal(idx_got, oracle.pq_encode(X, m, k, cents))
+
+
+@pytest.mark.parametrize("n,d,m,k,iters", [
+    (6000, 9, 2, 1100, 3),     # widths 5, 4: bucket strides 6 and 4 -> update_chains (mixed strides)
+    (6000, 7, 2, 1100, 3),     # widths 4, 3: one stride of 4 -> update_chains_pk<4>, a narrower problem and a padding column
+    (6000, 8, 2, 1100, 3),     # widths 4, 4 -> update_chains_pk<4>
+    (4000, 40, 2, 1100, 3),    # widths 20, 20: stride 20 > 16 -> update_chains
+])
+def test_pq_train_bucketed_update_batched(oracle, g, n, d, m, k, iters):
+    """More than 1024 clusters (the streamed update stops there; the radix path starts above 10240): training goes through
+    kmeans_update_batch with several problems per launch -- the unstaged sort_place, and each form of the chain kernels
+    that the one-stride decision picks.  Codebooks and codes equal the oracle's bit for bit."""
+    X = _clustered(n + d, n, d)
+    dm = g.DeviceMatrix.from_host(X)
+    pq = g.ProductQuantizer.apply(dm, g.ProductQuantizerConfig(k, m, iters))
+    _check_pq_against_oracle(oracle, X, m, k, pq.flat_centroids(), pq.encode(dm).indices(), iters)
+
+
+_STREAM_OFF_CHILD = """
+import sys
+sys.path.insert(0, sys.argv[1])
+import numpy as np
+import gulon_amd as g
+X = np.load(sys.argv[2])
+m, k, iters = (int(a) for a in sys.argv[3:6])
+dm = g.DeviceMatrix.from_host(X)
+pq = g.ProductQuantizer.apply(dm, g.ProductQuantizerConfig(k, m, iters))
+np.save(sys.argv[6], pq.flat_centroids())
+np.save(sys.argv[7], pq.encode(dm).indices())
+"""
+
+
+@pytest.mark.parametrize("n,d,m,k,iters", [(20000, 32, 4, 256, 4), (3000, 50, 7, 20, 6)])
+def test_pq_train_with_stream_update_off(oracle, g, tmp_path, n, d, m, k, iters):
+    """GULON_UPDATE_STREAM=0 (read once per process, hence the child): the same trainings through the bucketed update --
+    the staged sort_place and update_chains_pk<8> with several problems in one launch (widths 8; and 8 and 7)."""
+    X = _clustered(n, n, d)
+    xf, cf, kf = (str(tmp_path / f) for f in ("x.npy", "cents.npy", "codes.npy"))
+    np.save(xf, X)
+    r = subprocess.run([sys.executable, "-c", _STREAM_OFF_CHILD, ROOT, xf, str(m), str(k), str(iters), cf, kf],
+                       env={**os.environ, "GULON_UPDATE_STREAM": "0"}, timeout=120, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    _check_pq_against_oracle(oracle, X, m, k, np.load(cf), np.load(kf), iters)

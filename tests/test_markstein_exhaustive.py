@@ -1,4 +1,4 @@
-"""The corrected product the k-means update uses for (x - c) / n (gulon_amd/csrc/kmeans.hip, mean_quotient_fast;
+"""The corrected product the k-means update uses for (x - c) / n (gulon_amd/csrc/kmeans_update.hip, mean_quotient_fast;
 KMeans.scala:218) is THE correctly rounded quotient for the divisors 2^j - 1, for every numerator significand: the
 sweep the GPU self-test (gulon_selftest_mean_division) repeats with the device's own reciprocal."""
 import os
