@@ -671,6 +671,23 @@ bool replay_enabled() {
   return on;
 }
 
+int *tie_flags(gulon_index *ix, bool final_out, int *d_of, int B) {
+  if (!(final_out && replay_enabled() && d_of == nullptr)) return d_of;
+  ix->flags_scratch.ensure((size_t)B);
+  return ix->flags_scratch.p;
+}
+
+void finish_flat_query(gulon_index *ix, const float *dQ, int B, int K, int from, int until, bool final_out,
+                       const float *in_v, const int *in_i, int lists, long long stride_l, long long stride_q, int *d_oi,
+                       float *d_od, int *d_oc, int *d_of, float *d_pv, int *d_pi, hipStream_t st) {
+  int *flags = tie_flags(ix, final_out, d_of, B);
+  launch_merge(final_out, in_v, in_i, lists, stride_l, stride_q, B, K, d_oi, d_od, d_oc, flags, d_pv, d_pi, st);
+  // queries with exact distance ties: replay the reference heap's insertion history
+  if (final_out && replay_enabled()) run_tie_replay(ix, dQ, B, K, from, until, d_oi, d_od, d_oc, flags, st);
+  // queries whose distances can be NaN / +inf: the literal heap over all rows (TopKHeap.scala:69-79)
+  if (final_out && replay_enabled()) run_nonfinite_literal(ix, dQ, B, K, from, until, d_oi, d_od, d_oc, d_of, st);
+}
+
 }  // namespace gulon
 
 using namespace gulon;
@@ -894,17 +911,8 @@ void run_query(gulon_index *ix, const float *dQ, int B, int K, int from, int unt
     ix->events.emplace_back(e0, e1);
     ix->prof_rows += until - from;
   }
-  int *flags = d_of;
-  if (final_out && replay_enabled() && flags == nullptr) {   // the replay needs the tie flags even if the caller does not
-    ix->flags_scratch.ensure((size_t)B);
-    flags = ix->flags_scratch.p;
-  }
-  launch_merge(final_out, ix->part_v.p, ix->part_i.p, nchunks, (long long)keff, (long long)nchunks * keff, B, K, d_oi,
-               d_od, d_oc, flags, d_pv, d_pi, st);
-  // queries with exact distance ties: replay the reference heap's insertion history
-  if (final_out && replay_enabled()) run_tie_replay(ix, dQ, B, K, from, until, d_oi, d_od, d_oc, flags, st);
-  // queries whose distances can be NaN / +inf: the literal heap over all rows (TopKHeap.scala:69-79)
-  if (final_out && replay_enabled()) run_nonfinite_literal(ix, dQ, B, K, from, until, d_oi, d_od, d_oc, d_of, st);
+  finish_flat_query(ix, dQ, B, K, from, until, final_out, ix->part_v.p, ix->part_i.p, nchunks, (long long)keff,
+                    (long long)nchunks * keff, d_oi, d_od, d_oc, d_of, d_pv, d_pi, st);
 }
 
 }  // namespace

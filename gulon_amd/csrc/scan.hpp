@@ -89,7 +89,7 @@ struct gulon_index {
   // exact tie replay (replay.hip)
   DevBuf<int> rp_pack, rp_segcnt, rp_segi, rp_precnt, rp_l0i, rp_l0c;
   DevBuf<float> rp_q, rp_tables, rp_segtop, rp_prefix, rp_l0v;
-  DevBuf<int> rp_fb, rp_fini;           // level 2 of the replay through the quantized filter (filter.hip)
+  DevBuf<int> rp_fb, rp_fini;           // level 2 of the replay through the quantized filter (filter_query.hip)
   DevBuf<int> rp_done;                  // [3][F]: served by rp_shortcut / left to the segment scan / last row that can insert
   DevBuf<int> rp_order;                 // the long level's order of the flagged queries (rp_filter_order)
   DevBuf<float> rp_tau, rp_finv, rp_mins;
@@ -249,7 +249,45 @@ void launch_scan(gulon_index *ix, int ntiles, int nchunks, int rb_begin, int e_c
 // merge_lists<false> restricted to the queries of enabled tiles (fallback of the filter)
 void launch_merge_enabled(const float *in_v, const int *in_i, int lists, long long stride_l, long long stride_q, int B,
                           int K, float *out_pv, int *out_pi, const int *tile_enable, int qt, hipStream_t st);
-// filter.hip: level 2 of the tie replay (replay.hip) through the quantized filter.  For the flagged queries f < *count
+// ---- the quantized lower-bound filter of byte codes: kernels and one launcher per kernel in filter.hip, the query
+// driver, level 2 of the tie replay and the stage hook in filter_query.hip ----
+constexpr size_t FILTER_LDS_BUDGET = 144 * 1024;
+#ifndef GULON_FILTER_THREADS
+#define GULON_FILTER_THREADS 1024
+#endif
+constexpr int FILTER_THREADS = GULON_FILTER_THREADS;   // filter_kernel's workgroup
+constexpr int NSLOT = 16;   // survivor sub-queues per query (workgroups of different chunks use different ones)
+// the launch shape run_filter_query and replay_level2_filtered share
+struct FilterShape {
+  int qw, nqg;      // queries per quantized table entry, entry groups per workgroup
+  int nadd, qmax;   // table entries summed in 8 bits before widening, the top quantisation level
+  int cap;          // entries per survivor sub-queue
+  int slots;        // filter workgroups the chip holds at once
+};
+FilterShape filter_shape(const gulon_index *ix);
+int device_cus();   // compute units of the current device (cached per ordinal, lock-free)
+// the first block and the number of blocks a filter launch over rows [from, until) scans: whole ordering windows
+void filter_block_range(const gulon_index *ix, int qw, int nqg, int nadd, int from, int until, int &rb_begin,
+                        int &rb_total);
+int filter_sample_rows(const ScanTuning &t, int rb_total);   // rows of the sample scan over rb_total row blocks
+// per device: the event the main-stage launches take turns through; `fresh` = this call created it (nothing to wait for)
+hipEvent_t filter_lane_event(int dev, bool &fresh);
+// bound_tables, the batch's first kernel: counters, Index.prepareQuery into ix->tables / ix->qmins, and the sample
+// bounds of [from, until) into ix->tau0 (and bounds_out, where given), which also resets ix->fin_v / ix->fin_i
+void launch_bound_tables(gulon_index *ix, const float *dQ, int B, int Bp, int Bq, int ntiles, int keff, int from,
+                         int until, int rb_begin, int rb_total, float *bounds_out, hipStream_t st);
+void launch_shared_tau(gulon_index *ix, const float *all_bounds, int lists, int B, int keff, hipStream_t st);
+// qt_quantize: ix->qtab for Bq queries from `tables` (W-interleaved) and `mins` against min(tau0, a full list's last)
+void launch_qt_quantize(gulon_index *ix, const float *tables, int W, int Bp, int B, int Bq, const float *mins,
+                        const float *fin_v, const int *fin_i, const float *tau0, int keff, int qmax, int qw, int *fb,
+                        int qt, const int *slot, hipStream_t st);
+void launch_filter(gulon_index *ix, int qw, int nqg, int nadd, int ftiles, int nchunks, int rb_begin, int e_count,
+                   int e_per_chunk, RbMap mp, int from, int until, int cap, int stage, int B, hipStream_t st,
+                   int *fb = nullptr /* tile flags other than the index's own, one per `qt` queries */, int qt = 1,
+                   bool sorted = false /* read the key-sorted copy (the launch covers every row of the index) */);
+// survivors_kernel: the queued rows re-evaluated exactly and merged into ix->fin_v / ix->fin_i
+void launch_survivors(gulon_index *ix, int B, int Bq, int keff, int cap, int give_up, hipStream_t st);
+// filter_query.hip: level 2 of the tie replay (replay.hip) through the quantized filter.  For the flagged queries f < *count
 // (tables [f][m_pad][256] with their minima `mins`, bounds = the K-th of prefix_v[f][K] when prefix_c[f] >= K) every
 // row of blocks [rb_lo, rb_hi) with an exact distance BELOW the bound is appended to the query's candidate pool
 // (evv / evi / evcnt, `pool` entries per query).  only[f] is left 0 for the queries served here and 1 for those the
@@ -259,13 +297,14 @@ bool replay_level2_filtered(gulon_index *ix, int F, int K, int rb_lo, int rb_hi,
                             const float *tables, const float *mins, const float *prefix_v, const int *prefix_c,
                             const int *count, float *evv, int *evi, int *evcnt, int pool, int **only, hipStream_t st,
                             const int *done, const int *rlast, int *scanme);
-// filter.hip: sample scan -> quantized filter stages -> exact re-evaluation of the survivors.
+// filter.hip: does this index and range take the filter?
 bool filter_eligible(const gulon_index *ix, int K, int rb_total);
 // Bounds shared across row shards (sharded.py): phase 1 stops after the sample scan and writes the K+1
 // smallest sample distances per query ([B][K+1], ascending, +inf padded) to bounds_out; phase 2 resumes
 // with the `lists` gathered arrays ([lists][B][K+1]) -- the (K+1)-th smallest of their union bounds the
 // (K+1)-th distance of the WHOLE index, so every shard filters against the global bound.
 struct SharedBounds { int phase; float *bounds_out; const float *all_bounds; int lists; };
+// filter_query.hip: sample scan -> quantized filter stages -> exact re-evaluation of the survivors.
 void run_filter_query(gulon_index *ix, const float *dQ, int B, int K, int from, int until, bool final_out, int *d_oi,
                       float *d_od, int *d_oc, int *d_of, float *d_pv, int *d_pi, hipStream_t st,
                       const SharedBounds *sb = nullptr);
@@ -296,6 +335,14 @@ void run_nonfinite_literal(gulon_index *ix, const float *dQ, int B, int K, int f
 // reference's TopKHeap semantics (insertion history in row order) -- replay.hip
 void run_tie_replay(gulon_index *ix, const float *dQ, int B, int K, int from, int until, int *d_oi, float *d_od,
                     int *d_oc, int *d_of, hipStream_t st);
+// scan.hip: where a query path's merge writes its tie flags -- the caller's d_of, or (final outputs with the replay on: it
+// needs the flags even if the caller does not) the handle's scratch
+int *tie_flags(gulon_index *ix, bool final_out, int *d_of, int B);
+// scan.hip: the tail of the flat paths (run_query, run_filter_query) -- `lists` sorted lists per query merged into the
+// outputs, then the tie replay and the non-finite literal pass over the final ones
+void finish_flat_query(gulon_index *ix, const float *dQ, int B, int K, int from, int until, bool final_out,
+                       const float *in_v, const int *in_i, int lists, long long stride_l, long long stride_q, int *d_oi,
+                       float *d_od, int *d_oc, int *d_of, float *d_pv, int *d_pi, hipStream_t st);
 void launch_conflict_order(const uint8_t *src, uint8_t *dst, uint8_t *perm, long long nblk, int nq, int rounds,
                            hipStream_t st);
 bool conflict_order_windowed();   // the ordering spans windows of four blocks (default) or single blocks

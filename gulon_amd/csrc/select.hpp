@@ -1,6 +1,7 @@
 // What the query-path filters (filter.hip, wide_filter.hip, grouped_filter.hip, the selection kernels of grouped.hip)
 // share: ordered keys, the block radix select, the packed saturating subtract, the wave sum, the 64-lane bitonic
-// networks and the survivor sub-queues.  One copy of each; device code only.
+// networks and the survivor sub-queues.  One copy of each; device code only, but for the test hooks'
+// read-back of the sub-queues at the end.
 #pragma once
 
 #include "common.hpp"
@@ -202,5 +203,28 @@ __device__ __forceinline__ void enqueue_halves(uint32_t l, int q_lo, int slot, i
       else fb_word(q) = 1;
     }
 }
+
+#ifdef GULON_TEST_HOOKS
+// What the stage hooks (filter_query.hip, wide_filter.hip) hand back of the sub-queues a filter launch left on the device:
+// counts_out [B][nslot], the fill counters, unclamped; rows_out [B][nslot * cap], a query's queued rows (entries beyond a
+// full sub-queue are lost, as in production) plus row_base, ascending, padded with -1.  Host code; synchronous.
+inline void export_survivor_queues(const int *d_cnt, const int *d_queue, int nslot, int Bq, int B, int cap, int row_base,
+                                   int32_t *rows_out, int32_t *counts_out) {
+  std::vector<int> cnt((size_t)Bq * nslot), queue((size_t)Bq * nslot * cap);
+  HIP_CHECK(hipMemcpy(cnt.data(), d_cnt, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(queue.data(), d_queue, sizeof(int) * queue.size(), hipMemcpyDeviceToHost));
+  for (int q = 0; q < B; q++) {
+    int32_t *out = rows_out + (size_t)q * nslot * cap;
+    size_t fill = 0;
+    for (int sl = 0; sl < nslot; sl++) {
+      const int c = cnt[(size_t)q * nslot + sl];
+      counts_out[(size_t)q * nslot + sl] = c;
+      for (int e = 0; e < std::min(c, cap); e++) out[fill++] = queue[((size_t)q * nslot + sl) * cap + e] + row_base;
+    }
+    std::sort(out, out + fill);
+    for (size_t e = fill; e < (size_t)nslot * cap; e++) out[e] = -1;
+  }
+}
+#endif
 
 }  // namespace gulon

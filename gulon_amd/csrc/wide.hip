@@ -304,11 +304,7 @@ void run_wide_query(gulon_index *ix, const float *dQ, int B, int K, int from, in
     else launch_peel_export(ix->peel_v.p, ix->peel_i.p, B, cap, K + 1, d_pv, d_pi, st);   // a shard's K+1 smallest
     return;
   }
-  int *flags = d_of;
-  if (final_out && replay_enabled() && flags == nullptr) {   // the replay needs the tie flags even if the caller does not
-    ix->flags_scratch.ensure((size_t)B);
-    flags = ix->flags_scratch.p;
-  }
+  int *flags = tie_flags(ix, final_out, d_of, B);
   for (int q0 = 0; q0 < B; q0 += qb) {
     const int nq = std::min(qb, B - q0);
     launch_build_tables_wide(ix->cents.p, ix->from.p, ix->sdim.p, ix->d, m, k, dQ, q0, nq, ix->tables.p, st);

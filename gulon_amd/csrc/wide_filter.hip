@@ -333,6 +333,157 @@ int wf_slice(const gulon_index *ix) {   // quantizers per launch of wf_filter (m
   return (int)std::min<size_t>(fit, 8);   // (a slice's codes are held in registers while the previous block is looked up)
 }
 
+
+// what a batch starts with: its counters cleared and the fp32 tables of its queries ...
+void wf_reset_and_tables(gulon_index *ix, const float *dQ, int B, int Bq, hipStream_t st) {
+  hipLaunchKernelGGL(wf_reset, dim3(ceil_div(Bq * WF_NSLOT, 256)), dim3(256), 0, st, ix->fb_tile.p, Bq, ix->sv_cnt.p,
+                     Bq * WF_NSLOT);
+  launch_build_tables_wide(ix->cents.p, ix->from.p, ix->sdim.p, ix->d, ix->m, ix->k, dQ, 0, B, ix->tables.p, st);
+}
+// ... and, in front of the first stage, the tables' minima
+void wf_minima(gulon_index *ix, int B, hipStream_t st) {
+  hipLaunchKernelGGL(wf_table_mins, dim3(ix->m, B), dim3(256), 0, st, ix->tables.p, ix->m, ix->k, ix->qmins.p);
+  HIP_CHECK(hipGetLastError());
+}
+
+// One filter stage over row blocks [sb, sb + sc): the tables quantized against the running lists' last entries
+// (wf_quantize), then wf_filter -- the whole table, or in slices of wf_slice quantizers with the byte sums parked in
+// ix->wpark in between.  What run_wide_filter_query's stage loop and the stage hook both run; returns the chunks launched.
+int wf_filter_stage(gulon_index *ix, int B, int keff, int QW, int ngrp, size_t tstride, int cap, int from, int until,
+                    int sb, int sc, hipStream_t st) {
+  const int m = ix->m, k = ix->k;
+  const int jp = wf_slice(ix);                                       // quantizers per filter launch
+  const size_t lds_bytes = jp < m ? (size_t)jp * k * QW : tstride;
+  const int resident = std::max(1, (int)(160 * 1024 / lds_bytes));
+  auto quant = QW == 8 ? wf_quantize<8> : wf_quantize<4>;
+  hipLaunchKernelGGL(quant, dim3(ceil_div(k, 256), m, ngrp), dim3(256), 0, st, ix->tables.p, m, k, B, ix->qmins.p,
+                     ix->fin_v.p, ix->fin_i.p, keff, ix->qtab.p, tstride, ix->fb_tile.p);
+  HIP_CHECK(hipGetLastError());
+  // every workgroup stages its tables once, so few, long chunks
+  int nchunks = std::max(1, std::min(ceil_div(device_cus() * resident * 2, ngrp), sc / (4 * WF_NW)));
+  const int per = ceil_div(sc, nchunks);
+  nchunks = ceil_div(sc, per);
+  auto go = [&](auto kern, int j0, int j1, uint32_t *park) {
+    hipLaunchKernelGGL(kern, dim3(ngrp, nchunks), dim3(WF_THREADS), lds_bytes, st, ix->wcodes.p, m, k, ix->qtab.p, tstride,
+                       from, until, sb, sc, per, ix->sv_cnt.p, ix->sv_queue.p, cap, ix->fb_tile.p, B, j0, j1, park);
+  };
+  auto whole = [&](auto kern) {
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds_bytes));
+    go(kern, 0, 0, nullptr);
+  };
+  const int mq = ceil_div(m, 4);
+  if (jp < m) {   // the table in slices of jp quantizers, the byte sums parked in between
+    ix->wpark.ensure((size_t)ngrp * sc * 64);
+    auto kern = jp <= 4 ? wf_filter<4, 1, true> : wf_filter<4, 2, true>;
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds_bytes));
+    for (int j0 = 0; j0 < m; j0 += jp) go(kern, j0, std::min(m, j0 + jp), ix->wpark.p);
+  }
+  else if (QW == 8) { if (mq <= 2) whole(wf_filter<8, 2>); else if (mq <= 4) whole(wf_filter<8, 4>); else whole(wf_filter<8, 0>); }
+  else              { if (mq <= 2) whole(wf_filter<4, 2>); else if (mq <= 4) whole(wf_filter<4, 4>); else whole(wf_filter<4, 0>); }
+  HIP_CHECK(hipGetLastError());
+  return nchunks;
+}
+
+// One batch through the wide filter: what run_wide_filter_query works out once (plan) and the launches of its steps.
+struct WideFilterBatch {
+  gulon_index *ix;
+  const float *dQ;
+  int B, K, keff, from, until;
+  hipStream_t st;
+  // plan
+  int QW, ngrp, Bq, cap;                         // queries per 8-bit table entry, query groups, padded batch, sub-queue entries
+  size_t tstride;                                // bytes of one query group's 8-bit tables
+  int rb_begin, rb_total, sblocks, s_end;        // the range's row blocks; the sample: a prefix of them, its last row + 1
+  int stage_begin[2], stage_count[2];            // the filter's two stages over the rest
+  int nc_s, per_s, nc_all, per_all;              // scan_wide's chunks over the sample / over the whole range
+
+  void plan();
+  void workspace();
+  void sample_lists();
+  void filter_stages();
+  void fallback_scan();
+  void finish(bool final_out, int *d_oi, float *d_od, int *d_oc, int *d_of, float *d_pv, int *d_pi);
+};
+
+void WideFilterBatch::plan() {
+  const ScanTuning &t = tuning_of(ix);
+  QW = wf_qw(ix);
+  rb_begin = from / 64, rb_total = ceil_div(until, 64) - rb_begin;
+  ngrp = ceil_div(B, QW), Bq = ngrp * QW;
+  cap = std::max(64, t.filter_cap / WF_NSLOT);
+  tstride = ((size_t)ix->m * ix->k * QW + 15) & ~(size_t)15;
+  // the sample: a prefix of ~ 17 sqrt(rows) rows (as the byte-code filter sizes its sample), at least 16 K rows
+  const long long rows = (long long)rb_total * 64;
+  sblocks = (int)std::min<long long>(rb_total / 2, std::max<long long>(256, (long long)(17.0 * std::sqrt((double)rows)) / 64));
+  s_end = std::min(until, (rb_begin + sblocks) * 64);
+  // two filter stages over disjoint row ranges: a short one (~5 % of the rows) against the sample's bound, whose
+  // survivors tighten the running lists, then the rest against the lists' new last entries (the byte-code filter's
+  // stages, filter.hip: the first stage's survivor rate is ~8 times the second's)
+  const int f_begin = rb_begin + sblocks, f_count = rb_total - sblocks;      // the filter's row blocks
+  const int f_first = f_count >= 64 * WF_NW ? std::max(WF_NW, f_count / 20) : 0;      // blocks of the short stage
+  stage_begin[0] = f_begin, stage_begin[1] = f_begin + f_first;
+  stage_count[0] = f_first, stage_count[1] = f_count - f_first;
+  // scan_wide's launch shape (wide.hip): ~2048 workgroups, at least 2 row blocks per wave
+  auto chunks_of = [&](int blocks, int &nchunks, int &per) {
+    nchunks = std::max(1, std::min(ceil_div(2048, B), blocks / (2 * 8)));
+    per = ceil_div(blocks, nchunks);
+    nchunks = ceil_div(blocks, per);
+  };
+  chunks_of(sblocks, nc_s, per_s);
+  chunks_of(rb_total, nc_all, per_all);
+}
+
+void WideFilterBatch::workspace() {
+  const int m = ix->m, k = ix->k;
+  ix->tables.ensure((size_t)B * m * k);
+  ix->fin_v.ensure((size_t)Bq * keff);
+  ix->fin_i.ensure((size_t)Bq * keff);
+  ix->qmins.ensure((size_t)B * m);
+  ix->qtab.ensure((size_t)ngrp * tstride);
+  ix->sv_cnt.ensure((size_t)Bq * WF_NSLOT);
+  ix->sv_queue.ensure((size_t)Bq * WF_NSLOT * cap);
+  ix->fb_tile.ensure((size_t)Bq);
+  const int lists_max = std::max(nc_s, nc_all) * 8;
+  ix->part_v.ensure((size_t)B * lists_max * keff);
+  ix->part_i.ensure((size_t)B * lists_max * keff);
+}
+
+// 1. counters, fp32 tables, and running lists from the exact scan of the prefix
+void WideFilterBatch::sample_lists() {
+  wf_reset_and_tables(ix, dQ, B, Bq, st);
+  launch_scan_wide_range(ix, B, K, from, s_end, rb_begin, sblocks, per_s, nc_s, nullptr, st);
+  launch_merge(false, ix->part_v.p, ix->part_i.p, nc_s * 8, (long long)keff, (long long)nc_s * 8 * keff, B, K, nullptr,
+               nullptr, nullptr, nullptr, ix->fin_v.p, ix->fin_i.p, st);
+}
+
+// 2.-4. the table minima, then per stage: quantize -> filter -> the survivors, exactly
+void WideFilterBatch::filter_stages() {
+  wf_minima(ix, B, st);
+  for (int sidx = 0; sidx < 2; sidx++) {
+    if (stage_count[sidx] <= 0) continue;
+    wf_filter_stage(ix, B, keff, QW, ngrp, tstride, cap, from, until, stage_begin[sidx], stage_count[sidx], st);
+    // (the kernel empties the queues it has read)
+    hipLaunchKernelGGL(wf_survivors, dim3(B), dim3(64 * WF_SV_WAVES), 0, st, ix->wcodes.p, ix->m, ix->k, ix->tables.p,
+                       ix->row_base, ix->sv_cnt.p, ix->sv_queue.p, cap, B, keff, ix->fin_v.p, ix->fin_i.p, ix->fb_tile.p);
+    HIP_CHECK(hipGetLastError());
+  }
+}
+
+// 5. flagged queries: the exact scan over the whole range replaces their lists
+void WideFilterBatch::fallback_scan() {
+  launch_scan_wide_range(ix, B, K, from, until, rb_begin, rb_total, per_all, nc_all, ix->fb_tile.p, st);
+  launch_merge_enabled(ix->part_v.p, ix->part_i.p, nc_all * 8, (long long)keff, (long long)nc_all * 8 * keff, B, K,
+                       ix->fin_v.p, ix->fin_i.p, ix->fb_tile.p, 1, st);
+}
+
+void WideFilterBatch::finish(bool final_out, int *d_oi, float *d_od, int *d_oc, int *d_of, float *d_pv, int *d_pi) {
+  int *flags = tie_flags(ix, final_out, d_of, B);
+  launch_merge(final_out, ix->fin_v.p, ix->fin_i.p, 1, 0LL, (long long)keff, B, K, d_oi, d_od, d_oc, flags, d_pv, d_pi, st);
+  if (final_out && replay_enabled()) run_tie_replay(ix, dQ, B, K, from, until, d_oi, d_od, d_oc, flags, st);
+}
+
 }  // namespace
 
 // (K <= 63, one sub-batch of fp32 tables, the query's fp32 table in LDS for the sample scan, enough rows to pay)
@@ -347,110 +498,14 @@ bool wide_filter_eligible(const gulon_index *ix, int B, int K, int rb_total) {
 
 void run_wide_filter_query(gulon_index *ix, const float *dQ, int B, int K, int from, int until, bool final_out,
                            int *d_oi, float *d_od, int *d_oc, int *d_of, float *d_pv, int *d_pi, hipStream_t st) {
-  const ScanTuning &t = tuning_of(ix);
-  const int keff = K + 1, m = ix->m, k = ix->k;
-  const int QW = wf_qw(ix);
-  const int rb_begin = from / 64, rb_total = ceil_div(until, 64) - rb_begin;
-  const int ngrp = ceil_div(B, QW), Bq = ngrp * QW;
-  const int cap = std::max(64, t.filter_cap / WF_NSLOT);
-  // the sample: a prefix of ~ 17 sqrt(rows) rows (as the byte-code filter sizes its sample), at least 16 K rows
-  const long long rows = (long long)rb_total * 64;
-  int sblocks = (int)std::min<long long>(rb_total / 2, std::max<long long>(256, (long long)(17.0 * std::sqrt((double)rows)) / 64));
-  const int s_end = std::min(until, (rb_begin + sblocks) * 64);
-  const int f_begin = rb_begin + sblocks, f_count = rb_total - sblocks;      // the filter's row blocks
-  // scratch
-  ix->tables.ensure((size_t)B * m * k);
-  ix->fin_v.ensure((size_t)Bq * keff);
-  ix->fin_i.ensure((size_t)Bq * keff);
-  ix->qmins.ensure((size_t)B * m);
-  const size_t tstride = ((size_t)m * k * QW + 15) & ~(size_t)15;   // 8-bit tables of one query group
-  ix->qtab.ensure((size_t)ngrp * tstride);
-  ix->sv_cnt.ensure((size_t)Bq * WF_NSLOT);
-  ix->sv_queue.ensure((size_t)Bq * WF_NSLOT * cap);
-  ix->fb_tile.ensure((size_t)Bq);
+  WideFilterBatch wb{ix, dQ, B, K, K + 1, from, until, st};
+  wb.plan();
+  wb.workspace();
   ix->last_filter_tiles = B;
-  // scan_wide's launch shape (wide.hip): ~2048 workgroups, at least 2 row blocks per wave
-  auto chunks_of = [&](int blocks, int &nchunks, int &per) {
-    nchunks = std::max(1, std::min(ceil_div(2048, B), blocks / (2 * 8)));
-    per = ceil_div(blocks, nchunks);
-    nchunks = ceil_div(blocks, per);
-  };
-  int nc_s, per_s, nc_all, per_all;
-  chunks_of(sblocks, nc_s, per_s);
-  chunks_of(rb_total, nc_all, per_all);
-  const int lists_max = std::max(nc_s, nc_all) * 8;
-  ix->part_v.ensure((size_t)B * lists_max * keff);
-  ix->part_i.ensure((size_t)B * lists_max * keff);
-
-  hipLaunchKernelGGL(wf_reset, dim3(ceil_div(Bq * WF_NSLOT, 256)), dim3(256), 0, st, ix->fb_tile.p, Bq, ix->sv_cnt.p,
-                     Bq * WF_NSLOT);
-  launch_build_tables_wide(ix->cents.p, ix->from.p, ix->sdim.p, ix->d, m, k, dQ, 0, B, ix->tables.p, st);
-  // 1. running lists from the prefix
-  launch_scan_wide_range(ix, B, K, from, s_end, rb_begin, sblocks, per_s, nc_s, nullptr, st);
-  launch_merge(false, ix->part_v.p, ix->part_i.p, nc_s * 8, (long long)keff, (long long)nc_s * 8 * keff, B, K, nullptr,
-               nullptr, nullptr, nullptr, ix->fin_v.p, ix->fin_i.p, st);
-  // 2.-4. two filter stages over disjoint row ranges: a short one (~5 % of the rows) against the sample's bound, whose
-  // survivors tighten the running lists, then the rest against the lists' new last entries (the byte-code filter's
-  // stages, filter.hip: the first stage's survivor rate is ~8 times the second's)
-  hipLaunchKernelGGL(wf_table_mins, dim3(m, B), dim3(256), 0, st, ix->tables.p, m, k, ix->qmins.p);
-  HIP_CHECK(hipGetLastError());
-  const int jp = wf_slice(ix);                                       // quantizers per filter launch
-  const size_t lds_bytes = jp < m ? (size_t)jp * k * QW : tstride;
-  int cus = 256;
-  { int dev = 0; HIP_CHECK(hipGetDevice(&dev)); HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)); }
-  const int resident = std::max(1, (int)(160 * 1024 / lds_bytes));
-  const int f_first = f_count >= 64 * WF_NW ? std::max(WF_NW, f_count / 20) : 0;      // blocks of the short stage
-  const int stage_begin[2] = {f_begin, f_begin + f_first}, stage_count[2] = {f_first, f_count - f_first};
-  for (int sidx = 0; sidx < 2; sidx++) {
-    const int sb = stage_begin[sidx], sc = stage_count[sidx];
-    if (sc <= 0) continue;
-    if (QW == 8)
-      hipLaunchKernelGGL(wf_quantize<8>, dim3(ceil_div(k, 256), m, ngrp), dim3(256), 0, st, ix->tables.p, m, k, B, ix->qmins.p,
-                         ix->fin_v.p, ix->fin_i.p, keff, ix->qtab.p, tstride, ix->fb_tile.p);
-    else
-      hipLaunchKernelGGL(wf_quantize<4>, dim3(ceil_div(k, 256), m, ngrp), dim3(256), 0, st, ix->tables.p, m, k, B, ix->qmins.p,
-                         ix->fin_v.p, ix->fin_i.p, keff, ix->qtab.p, tstride, ix->fb_tile.p);
-    HIP_CHECK(hipGetLastError());
-    // every workgroup stages its tables once, so few, long chunks
-    int nchunks = std::max(1, std::min(ceil_div(cus * resident * 2, ngrp), sc / (4 * WF_NW)));
-    const int per = ceil_div(sc, nchunks);
-    nchunks = ceil_div(sc, per);
-    auto go = [&](auto kern) {
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds_bytes));
-      hipLaunchKernelGGL(kern, dim3(ngrp, nchunks), dim3(WF_THREADS), lds_bytes, st, ix->wcodes.p, m, k, ix->qtab.p, tstride,
-                         from, until, sb, sc, per, ix->sv_cnt.p, ix->sv_queue.p, cap, ix->fb_tile.p, B, 0, 0, (uint32_t *)nullptr);
-    };
-    const int mq = ceil_div(m, 4);
-    if (jp < m) {   // the table in slices of jp quantizers, the byte sums parked in between
-      ix->wpark.ensure((size_t)ngrp * sc * 64);
-      auto kern = jp <= 4 ? wf_filter<4, 1, true> : wf_filter<4, 2, true>;
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds_bytes));
-      for (int j0 = 0; j0 < m; j0 += jp)
-        hipLaunchKernelGGL(kern, dim3(ngrp, nchunks), dim3(WF_THREADS), lds_bytes, st, ix->wcodes.p, m, k, ix->qtab.p, tstride,
-                           from, until, sb, sc, per, ix->sv_cnt.p, ix->sv_queue.p, cap, ix->fb_tile.p, B, j0,
-                           std::min(m, j0 + jp), ix->wpark.p);
-    }
-    else if (QW == 8) { if (mq <= 2) go(wf_filter<8, 2>); else if (mq <= 4) go(wf_filter<8, 4>); else go(wf_filter<8, 0>); }
-    else              { if (mq <= 2) go(wf_filter<4, 2>); else if (mq <= 4) go(wf_filter<4, 4>); else go(wf_filter<4, 0>); }
-    HIP_CHECK(hipGetLastError());
-    // survivors, exactly (the kernel empties the queues it has read)
-    hipLaunchKernelGGL(wf_survivors, dim3(B), dim3(64 * WF_SV_WAVES), 0, st, ix->wcodes.p, m, k, ix->tables.p, ix->row_base,
-                       ix->sv_cnt.p, ix->sv_queue.p, cap, B, keff, ix->fin_v.p, ix->fin_i.p, ix->fb_tile.p);
-    HIP_CHECK(hipGetLastError());
-  }
-  // 5. flagged queries: the exact scan over the whole range replaces their lists
-  launch_scan_wide_range(ix, B, K, from, until, rb_begin, rb_total, per_all, nc_all, ix->fb_tile.p, st);
-  launch_merge_enabled(ix->part_v.p, ix->part_i.p, nc_all * 8, (long long)keff, (long long)nc_all * 8 * keff, B, K,
-                       ix->fin_v.p, ix->fin_i.p, ix->fb_tile.p, 1, st);
-  int *flags = d_of;
-  if (final_out && replay_enabled() && flags == nullptr) {
-    ix->flags_scratch.ensure((size_t)B);
-    flags = ix->flags_scratch.p;
-  }
-  launch_merge(final_out, ix->fin_v.p, ix->fin_i.p, 1, 0LL, (long long)keff, B, K, d_oi, d_od, d_oc, flags, d_pv, d_pi, st);
-  if (final_out && replay_enabled()) run_tie_replay(ix, dQ, B, K, from, until, d_oi, d_od, d_oc, flags, st);
+  wb.sample_lists();
+  wb.filter_stages();
+  wb.fallback_scan();
+  wb.finish(final_out, d_oi, d_od, d_oc, d_of, d_pv, d_pi);
 }
 
 }  // namespace gulon
@@ -458,10 +513,10 @@ void run_wide_filter_query(gulon_index *ix, const float *dQ, int B, int K, int f
 #ifdef GULON_TEST_HOOKS
 using namespace gulon;
 
-// The wide counterpart of gulon_selftest_filter_stage (filter.hip): ONE stage of run_wide_filter_query over every row
-// block of [from, until) -- the fp32 tables, wf_table_mins, wf_quantize, wf_filter (whole table or sliced, as wf_slice
-// decides) -- against the caller's bounds, which stand as the last entry of a full running list, where wf_quantize reads
-// them; no wf_survivors.  Outputs as the flat hook's (flagged_out: the query's own flag); info: QMAX, queries per table
+// The wide counterpart of gulon_selftest_filter_stage (filter_query.hip): ONE stage of run_wide_filter_query over every
+// row block of [from, until) -- the fp32 tables, wf_table_mins, then wf_filter_stage, the body of the driver's stage loop
+// (wf_quantize, wf_filter whole or sliced, as wf_slice decides) -- against the caller's bounds, which stand as the last
+// entry of a full running list, where wf_quantize reads them; no wf_survivors.  Outputs as the flat hook's (flagged_out: the query's own flag); info: QMAX, queries per table
 // entry, quantizers per launch, chunks launched.  Returns GULON_SELFTEST_WIDE_REFUSED (77) where wf_qw refuses the code
 // book (not even one quantizer's entries fit LDS).
 // (Declared here and bound by its test: the header's list of hooks is pinned by test_abi.)
@@ -501,70 +556,22 @@ GULON_API int32_t gulon_selftest_wide_filter_stage(const uint8_t *codes, int32_t
       HIP_CHECK(hipMemcpy(ix->fin_v.p, fv.data(), sizeof(float) * fv.size(), hipMemcpyHostToDevice));
       HIP_CHECK(hipMemcpy(ix->fin_i.p, fi.data(), sizeof(int) * fi.size(), hipMemcpyHostToDevice));
     }
-    hipLaunchKernelGGL(wf_reset, dim3(ceil_div(Bq * WF_NSLOT, 256)), dim3(256), 0, st, ix->fb_tile.p, Bq, ix->sv_cnt.p,
-                       Bq * WF_NSLOT);
-    launch_build_tables_wide(ix->cents.p, ix->from.p, ix->sdim.p, ix->d, m, k, dQ.p, 0, B, ix->tables.p, st);
-    hipLaunchKernelGGL(wf_table_mins, dim3(m, B), dim3(256), 0, st, ix->tables.p, m, k, ix->qmins.p);
-    HIP_CHECK(hipGetLastError());
-    // from here on: one turn of run_wide_filter_query's stage loop
-    const int jp = wf_slice(ix);
-    const size_t lds_bytes = jp < m ? (size_t)jp * k * QW : tstride;
-    int cus = 256;
-    { int dev = 0; HIP_CHECK(hipGetDevice(&dev)); HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)); }
-    const int resident = std::max(1, (int)(160 * 1024 / lds_bytes));
-    if (QW == 8)
-      hipLaunchKernelGGL(wf_quantize<8>, dim3(ceil_div(k, 256), m, ngrp), dim3(256), 0, st, ix->tables.p, m, k, B, ix->qmins.p,
-                         ix->fin_v.p, ix->fin_i.p, keff, ix->qtab.p, tstride, ix->fb_tile.p);
-    else
-      hipLaunchKernelGGL(wf_quantize<4>, dim3(ceil_div(k, 256), m, ngrp), dim3(256), 0, st, ix->tables.p, m, k, B, ix->qmins.p,
-                         ix->fin_v.p, ix->fin_i.p, keff, ix->qtab.p, tstride, ix->fb_tile.p);
-    HIP_CHECK(hipGetLastError());
-    int nchunks = std::max(1, std::min(ceil_div(cus * resident * 2, ngrp), sc / (4 * WF_NW)));
-    const int per = ceil_div(sc, nchunks);
-    nchunks = ceil_div(sc, per);
-    auto go = [&](auto kern) {
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds_bytes));
-      hipLaunchKernelGGL(kern, dim3(ngrp, nchunks), dim3(WF_THREADS), lds_bytes, st, ix->wcodes.p, m, k, ix->qtab.p, tstride,
-                         from, until, sb, sc, per, ix->sv_cnt.p, ix->sv_queue.p, cap, ix->fb_tile.p, B, 0, 0, (uint32_t *)nullptr);
-    };
-    const int mq = ceil_div(m, 4);
-    if (jp < m) {
-      ix->wpark.ensure((size_t)ngrp * sc * 64);
-      auto kern = jp <= 4 ? wf_filter<4, 1, true> : wf_filter<4, 2, true>;
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds_bytes));
-      for (int j0 = 0; j0 < m; j0 += jp)
-        hipLaunchKernelGGL(kern, dim3(ngrp, nchunks), dim3(WF_THREADS), lds_bytes, st, ix->wcodes.p, m, k, ix->qtab.p, tstride,
-                           from, until, sb, sc, per, ix->sv_cnt.p, ix->sv_queue.p, cap, ix->fb_tile.p, B, j0,
-                           std::min(m, j0 + jp), ix->wpark.p);
-    }
-    else if (QW == 8) { if (mq <= 2) go(wf_filter<8, 2>); else if (mq <= 4) go(wf_filter<8, 4>); else go(wf_filter<8, 0>); }
-    else              { if (mq <= 2) go(wf_filter<4, 2>); else if (mq <= 4) go(wf_filter<4, 4>); else go(wf_filter<4, 0>); }
-    HIP_CHECK(hipGetLastError());
+    wf_reset_and_tables(ix, dQ.p, B, Bq, st);
+    wf_minima(ix, B, st);
+    const int nchunks = wf_filter_stage(ix, B, keff, QW, ngrp, tstride, cap, from, until, sb, sc, st);
     HIP_CHECK(hipStreamSynchronize(st));
-    std::vector<int> cnt((size_t)Bq * WF_NSLOT), queue((size_t)Bq * WF_NSLOT * cap), fb((size_t)Bq);
+    export_survivor_queues(ix->sv_cnt.p, ix->sv_queue.p, WF_NSLOT, Bq, B, cap, ix->row_base, rows_out, counts_out);
+    std::vector<int> fb((size_t)Bq);
     std::vector<uint8_t> qt((size_t)ngrp * tstride);
-    HIP_CHECK(hipMemcpy(cnt.data(), ix->sv_cnt.p, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(queue.data(), ix->sv_queue.p, sizeof(int) * queue.size(), hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(fb.data(), ix->fb_tile.p, sizeof(int) * fb.size(), hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(qt.data(), ix->qtab.p, qt.size(), hipMemcpyDeviceToHost));
     for (int q = 0; q < B; q++) {
-      int32_t *out = rows_out + (size_t)q * WF_NSLOT * cap;
-      size_t fill = 0;
-      for (int sl = 0; sl < WF_NSLOT; sl++) {
-        const int c = cnt[(size_t)q * WF_NSLOT + sl];
-        counts_out[(size_t)q * WF_NSLOT + sl] = c;
-        for (int e = 0; e < std::min(c, (int)cap); e++) out[fill++] = queue[((size_t)q * WF_NSLOT + sl) * cap + e] + ix->row_base;
-      }
-      std::sort(out, out + fill);
-      for (size_t e = fill; e < (size_t)WF_NSLOT * cap; e++) out[e] = -1;
       flagged_out[q] = fb[q];
       for (int j = 0; j < m; j++)      // entry (j, c) of query q: byte q % QW of entry [j][c] of group q / QW (wf_quantize)
         for (int c = 0; c < k; c++)
           levels_out[((size_t)q * m + j) * k + c] = qt[(size_t)(q / QW) * tstride + ((size_t)j * k + c) * QW + q % QW];
     }
-    info[0] = WF_QMAX; info[1] = QW; info[2] = jp; info[3] = nchunks;
+    info[0] = WF_QMAX; info[1] = QW; info[2] = wf_slice(ix); info[3] = nchunks;
   });
   if (raw) (void)gulon_index_destroy(raw);
   return rc != GULON_OK ? rc : refused ? 77 : GULON_OK;

@@ -397,3 +397,37 @@ def test_conflict_ordered_copy_equals_plain_codes(oracle, g, tune, n, frm, until
     oi, od, oc = oracle.pq_batch_query(idx, d, k, cents, Q, K, frm, n if until is None else until)
     _check(oracle, ordered, oi, od, oc)
     ix.close()
+
+
+def _profile_record(ix):
+    import ctypes as C
+    from gulon_amd import native as N
+    ms, launches, rows = C.c_double(0), C.c_int32(0), C.c_int64(0)
+    N.check(N.lib().gulon_index_profile_read_ex(ix._h, C.byref(ms), C.byref(launches), C.byref(rows)))
+    return ms.value, launches.value, rows.value
+
+
+def test_profile_brackets_the_main_stage_of_every_batch(oracle, g, tune):
+    """gulon_index_profile (the roofline line of the benchmark) records one event pair per batch: around the main-stage
+    filter launch, counted with the rows that stage covers, or around the exact scan and the whole range with the filter
+    off.  51 200 rows are 800 row blocks = 100 periods of 8 and 200 whole 256-row windows, so on the plain, the
+    window-ordered and the key-sorted copy alike the main stage (5 of every 8 blocks) covers 500 blocks = 32 000 rows."""
+    from gulon_amd import native as N
+    n, d, m, k, B, K = 51200, 128, 16, 256, 37, 10
+    cents, idx, pq, enc = _make(oracle, g, n, d, m, k, seed=n + d)
+    Q = np.random.default_rng(7).standard_normal((B, d)).astype(np.float32)
+    oi, od, oc = oracle.pq_batch_query(idx, d, k, cents, Q, K, 0, n)
+    ix = g.PQIndex(pq, enc)
+    N.check(N.lib().gulon_index_profile(ix._h, 1))
+    for _ in range(3):
+        _check(oracle, ix.batch_query(K, Q), oi, od, oc)
+    ms, launches, rows = _profile_record(ix)
+    assert launches == 3 and rows == 96000 and ms > 0
+    tune(GULON_SCAN_FILTER=0)
+    N.check(N.lib().gulon_index_profile(ix._h, 1))      # enabling again clears the record
+    for _ in range(2):
+        _check(oracle, ix.batch_query(K, Q), oi, od, oc)
+    ms, launches, rows = _profile_record(ix)
+    assert launches == 2 and rows == 102400
+    N.check(N.lib().gulon_index_profile(ix._h, 0))
+    ix.close()

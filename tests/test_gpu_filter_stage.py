@@ -3,7 +3,7 @@
 Every other filter test compares final answers with the oracle, and two kinds of error leave those unchanged: a stage
 that drops a row between the true K-th distance and its (loose) production bound, and a stage that stopped filtering
 (levels too low, a wrapped byte sum, a byte lane of the wrong query) and only sends more work to the exact kernels.
-Here the test hooks gulon_selftest_filter_stage (filter.hip) and gulon_selftest_wide_filter_stage (wide_filter.hip)
+Here the test hooks gulon_selftest_filter_stage (filter_query.hip) and gulon_selftest_wide_filter_stage (wide_filter.hip)
 run the production kernels of ONE stage -- bound_tables / qt_quantize / filter_kernel, wf_table_mins / wf_quantize /
 wf_filter -- over every row block of a range against bounds the test chooses, and report the queued rows, the
 sub-queue counters, the flags and the 8-bit levels.  tests/filter_stage_ref.py holds the reference, the derivation of
