@@ -15,6 +15,7 @@ from .word_vectors import (DeviceWordVectors, GroupedWordVectors, KeyedIndex, Ke
 from .build import build_index
 from .word_index import WordIndex, WordResult
 from .refine import RefinedIndex, refine_topk
+from .exact import ExactIndex, ExactWordIndex
 from .fine import FineRefinedIndex, build_fine_index, refine_codes_topk, row_residuals
 from .inspect import IndexReport, reference_quality
 from .update import UpdatePlan, plan_update
@@ -28,4 +29,5 @@ __all__ = ["native", "GroupedIndex", "GroupedVectors", "LimitGroups", "LimitVect
            "WordVectors", "read_word2vec", "WordIndex", "WordResult", "DeviceWordVectors", "read_word2vec_device",
            "build_index", "RefinedIndex", "refine_topk", "Expression", "Term", "compose_reference", "parse_expression",
            "partition_by_operands", "IndexReport", "reference_quality", "UpdatePlan", "plan_update", "FineRefinedIndex", "build_fine_index",
-           "refine_codes_topk", "row_residuals", "Rotation", "RotatedWordIndex", "train_rotation", "rotate_reference"]
+           "refine_codes_topk", "row_residuals", "Rotation", "RotatedWordIndex", "train_rotation", "rotate_reference",
+           "ExactIndex", "ExactWordIndex"]

@@ -6,10 +6,10 @@
                                        parsed on the device (word_vectors.read_word2vec_device) and every later stage
                                        runs there too (build.build_index)
 
-  query-words -i INDEX [-k N] [-x] [-v VECTORS | -f FINE] [-c N] [FILE]
+  query-words -i INDEX [-k N] [-x] [-v VECTORS [--exact] | -f FINE] [-c N] [FILE]
                                        command/QueryWords.scala: one word per line of FILE (or stdin), printed as
                                        `word: w1,w2,...` or `word: not found`, in input order
-  query -i INDEX [-k N] [-v VECTORS | -f FINE] [-c N] FILE
+  query -i INDEX [-k N] [-v VECTORS [--exact] | -f FINE] [-c N] FILE
                                        command/Query.scala: a word2vec text file of query vectors, printed as
                                        `key: w1,w2,...`
   test -v VECTORS -i INDEX [-s SIZE] [-e ERROR] [[-f FINE] -c N]
@@ -50,6 +50,12 @@ re-ranked by their exact distance to the original vectors of that word2vec text 
 (refine.RefinedIndex).  test -c N reports the recall of that refined index.  The recall harness asks ONE query per
 sampled vector at the largest k it kept and scores prefixes of the answer, so every R@k line is a prefix of one refined
 result -- the max(N, largest k) candidates re-ranked, the largest k kept -- not a refined query at that k.
+
+--exact on the query commands (not in the reference; exact.py, csrc/exact.hip): with -v VECTORS, the TRUE neighbours among
+the original vectors instead of re-ranked candidates -- brute force over every word of the index on the device
+(WordIndex.exact).  The index file supplies the words, the metric and the row order; query-words asks with the word's
+original vector, so the word itself comes first.  The output lines are those of the plain command.  Not together with
+-c, -f, -r, -x or -R.
 
 -x/--expressions on query-words (not in the reference): every line is an expression `word (op word)*`, split on
 whitespace, op one of the stand-alone tokens + and - (weights +1 and -1; a word may itself contain + or -, which is why
@@ -272,6 +278,9 @@ def _parser():
         s.add_argument("-R", "--rotation", default=None, metavar="file",
                        help="rotation file the index was built with (build-index -R): query vectors, and the vectors of "
                             "--vectors, are rotated before they reach the index")
+        s.add_argument("--exact", action="store_true",
+                       help="with --vectors: the exact neighbours among the original vectors, by brute force on the "
+                            "device, instead of re-ranked candidates (not with -c, -f, -r, -x or -R)")
         if name == "query-words":
             s.add_argument("-x", "--expressions", action="store_true",
                            help="read every line as an expression `word (+|- word)*` (operators as stand-alone tokens): "
@@ -530,9 +539,12 @@ def _restricted(args, index):
 
 
 def _refined(args, index, vectors, load):
-    """The loaded index, or with -r its restriction, or with -v / -f its refined form; -c needs one of those."""
+    """The loaded index, or with -r its restriction, or with -v / -f its refined form; -c needs one of those.  With
+    --exact: the exact index over its words and the -v vectors."""
     if args.vectors is None and args.fine is None:
         return _restricted(args, index)
+    if args.exact:
+        return index.exact(vectors(args.vectors, index.metric == "cosine"))
     candidates = args.candidates if args.candidates is not None else 10 * args.neighbours
     if args.fine is not None:
         return index.fine_refined(load(args.fine), candidates)
@@ -557,6 +569,15 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
         parser.error("at least one of --add and --remove is required")
     if args.command == "inspect" and args.worst is not None and args.vectors is None:
         parser.error("--worst is only applicable with --vectors")
+    if args.command in ("query", "query-words") and args.exact:
+        if args.vectors is None:
+            parser.error("--exact needs -v/--vectors")
+        for given, option in ((args.candidates is not None, "-c/--candidates"), (args.fine is not None, "-f/--fine"),
+                              (args.restrict is not None, "-r/--restrict"),
+                              (getattr(args, "expressions", False), "-x/--expressions"),
+                              (args.rotation is not None, "-R/--rotation")):
+            if given:
+                parser.error(f"--exact is not applicable with {option}")
     if args.command in ("query", "query-words") and args.candidates is not None and args.vectors is None \
             and args.fine is None:
         parser.error("--candidates is only applicable with --vectors or --fine")

@@ -1,0 +1,637 @@
+// The exact index: Index.exactNearestNeighbours (Index.scala:209-229) with MathUtils.distanceSq (MathUtils.scala:85-95)
+// behind a handle, device-resident, and for k_nn > GULON_MAX_K in ONE pass over the rows instead of the peeled path's
+// ceil((k_nn + 1) / 64).
+//
+//   sample   exact_pass<true>   exact distances of S rows spread evenly over [from, until) -> [B][S]
+//   bound    exact_tau          tau_q = the (k_nn + 1)-th smallest of them: the distance of a real row, so an upper bound
+//                               of the true (k_nn + 1)-th distance
+//   main     exact_pass<false>  one read of [from, until), knn_kernel's tiling; every row with distance <= tau_q is
+//                               appended to the query's queue as (distance bits << 32) | row
+//   select   exact_select       per query: radix-select the (k_nn + 1)-th key, keep the keys up to it, sort, write
+//
+// The answer of a query whose distances are all finite is the (distance, row id) order of gulon_exact_knn, whatever the
+// order of its queue.  A query whose queue overflowed is answered by the peeled path (knn_kernel + launch_merge +
+// launch_peel_*, called, not copied) in a compacted sub-batch; a query that met a NaN / +inf distance by the same path in
+// a batch of one, which is what gulon_exact_knn gives it when asked alone.
+#include "exact.hpp"
+#include "select.hpp"
+
+#include <cstdlib>
+
+namespace gulon {
+namespace {
+
+constexpr int SEL_THREADS = 1024;                     // exact_select's workgroup
+constexpr size_t EXACT_SCRATCH_BYTES = size_t(1) << 30;   // sample distances + queues of one sub-batch of queries
+constexpr int EXACT_SAMPLE_MAX = 1 << 22;             // most sample rows chosen automatically
+
+// Slot j of a pass is row `from + j` (main) or the j-th of S rows spread evenly over the range (sample).
+template <bool SAMPLE>
+__device__ __forceinline__ int slot_row(int from, int range, int S, int j) {
+  return SAMPLE ? from + (int)((long long)j * range / S) : from + j;
+}
+
+// Distances of 16 queries to 256 slots per step, as knn_kernel computes them: rows staged in LDS 32 dims at a time,
+// lane = row, acc += (q_e - x_e) * (q_e - x_e) with e ascending, unfused.
+template <bool SAMPLE>
+__global__ __launch_bounds__(KNN_THREADS) void exact_pass(const float *__restrict__ X, int d, const float *__restrict__ Qt,
+                                                          int B, int from, int range, int S, int slots_per_chunk,
+                                                          float *__restrict__ sample_out,
+                                                          const float *__restrict__ tau, unsigned long long *__restrict__ queue,
+                                                          int cap, unsigned *__restrict__ cnt, int *__restrict__ overflow,
+                                                          int *__restrict__ nonfinite) {
+  __shared__ float xs[KNN_THREADS * (KNN_DT + 1)];
+  __shared__ int rowid[KNN_THREADS];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int tile = blockIdx.x, chunk = blockIdx.y;
+  const float *qt = Qt + (size_t)tile * d * KNN_QT;
+  const int total = SAMPLE ? S : range;
+  const int s0 = chunk * slots_per_chunk;
+  const int s1 = min(total, s0 + slots_per_chunk);
+
+  float tq[KNN_QT];
+  if (!SAMPLE) {
+#pragma unroll
+    for (int q = 0; q < KNN_QT; q++) tq[q] = tau[tile * KNN_QT + q];
+  }
+
+  for (int base = s0; base < s1; base += KNN_THREADS) {
+    float acc[KNN_QT];
+#pragma unroll
+    for (int q = 0; q < KNN_QT; q++) acc[q] = 0.f;
+    __syncthreads();   // the previous step's readers of rowid / xs are done
+    rowid[tid] = base + tid < s1 ? slot_row<SAMPLE>(from, range, S, base + tid) : -1;
+    for (int d0 = 0; d0 < d; d0 += KNN_DT) {
+      __syncthreads();
+      for (int e = tid; e < KNN_THREADS * KNN_DT; e += KNN_THREADS) {
+        const int r = e / KNN_DT, c = e % KNN_DT;
+        const int row = rowid[r], dim = d0 + c;
+        xs[r * (KNN_DT + 1) + c] = (row >= 0 && dim < d) ? X[(size_t)row * d + dim] : 0.f;
+      }
+      __syncthreads();
+      const int dl = min(KNN_DT, d - d0);
+      for (int c = 0; c < dl; c++) {
+        const float x = xs[tid * (KNN_DT + 1) + c];
+        const float *qv = qt + (size_t)(d0 + c) * KNN_QT;
+#pragma unroll
+        for (int q = 0; q < KNN_QT; q++) {
+          const float dx = qv[q] - x;   // dx = y(i) - x(i), y = query (MathUtils.scala:90)
+          acc[q] += dx * dx;
+        }
+      }
+    }
+    const int slot = base + tid;
+    const bool valid = slot < s1;
+    if (SAMPLE) {
+#pragma unroll
+      for (int q = 0; q < KNN_QT; q++) {
+        const int qg = tile * KNN_QT + q;
+        if (valid && qg < B) sample_out[(size_t)qg * S + slot] = acc[q];
+      }
+    } else {
+      const unsigned row = (unsigned)(from + slot);
+      const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+      for (int q = 0; q < KNN_QT; q++) {
+        const int qg = tile * KNN_QT + q;
+        const unsigned long long bad = __ballot(valid && !(acc[q] < INFINITY));   // NaN or +inf
+        if (bad && lane == 0) nonfinite[qg] = 1;
+        const bool keep = valid && acc[q] <= tq[q];
+        const unsigned long long mk = __ballot(keep);
+        if (mk) {
+          const int first = __ffsll((long long)mk) - 1, add = __popcll(mk);
+          unsigned pos = 0;
+          if (lane == first) pos = atomicAdd(&cnt[qg], (unsigned)add);
+          pos = (unsigned)readlane_i((int)pos, first);
+          if (pos + (unsigned)add <= (unsigned)cap) {
+            if (keep)
+              queue[(size_t)qg * cap + pos + __popcll(mk & below)] =
+                  ((unsigned long long)__float_as_uint(acc[q]) << 32) | row;
+          } else if (lane == first) {
+            overflow[qg] = 1;
+          }
+        }
+      }
+    }
+  }
+}
+
+// tau[q] = the want-th smallest of the query's S sample distances (q < B), -1 for the padding queries of the last tile
+// (nothing is at or below it).  NaN distances sort last (ordered_key); a query that has one is flagged by the main pass.
+__global__ __launch_bounds__(256) void exact_tau(const float *__restrict__ sample, int S, int want, int B,
+                                                 float *__restrict__ tau) {
+  __shared__ unsigned hsub[256 * 8], hist[256];
+  __shared__ RadixSelectState state;
+  const int q = blockIdx.x, tid = threadIdx.x;
+  if (q >= B) {   // (uniform per workgroup)
+    if (tid == 0) tau[q] = -1.f;
+    return;
+  }
+  const float *s = sample + (size_t)q * S;
+  const unsigned key = block_radix_select<256>(
+      [&](auto f) __attribute__((always_inline)) {
+        for (int e = tid; e < S; e += 256) f(ordered_key(s[e]));
+      },
+      (unsigned)want, hsub, hist, state);
+  if (tid == 0) tau[q] = ordered_float(key);
+}
+
+// no sample: every finite distance is queued
+__global__ void exact_tau_all(int B, int Bp, float *__restrict__ tau) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q < Bp) tau[q] = q < B ? INFINITY : -1.f;
+}
+
+// One workgroup per query over its queue of c keys: the want = min(K + 1, c) smallest, ascending, then rows, distances,
+// count and tie flags as launch_peel_finalize writes them.  Keys are distinct (one per row), so the want-th key is
+// found by two radix selects -- the distance word, then the row word among the keys that share it -- and exactly
+// `want` keys are at or below it.  Dynamic LDS only (a 16-byte aligned base): keys [P], then the select's scratch.
+__global__ __launch_bounds__(SEL_THREADS) void exact_select(const unsigned long long *__restrict__ queue, int cap,
+                                                            const unsigned *__restrict__ cnt,
+                                                            const int *__restrict__ overflow,
+                                                            const int *__restrict__ nonfinite, int K, int P,
+                                                            int *__restrict__ out_idx, float *__restrict__ out_dist,
+                                                            int *__restrict__ out_count, int *__restrict__ out_flags) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long sel_lds[];
+  unsigned long long *sk = sel_lds;                        // [P]
+  unsigned *hsub = reinterpret_cast<unsigned *>(sk + P);   // [256 * 8]
+  unsigned *hist = hsub + 256 * 8;                         // [256]
+  RadixSelectState &state = *reinterpret_cast<RadixSelectState *>(hist + 256);
+  unsigned *nkept = hist + 256 + 4, *tie = nkept + 1;
+  const int q = blockIdx.x, tid = threadIdx.x;
+  if (overflow[q] | nonfinite[q]) return;   // answered by the fallback (uniform per workgroup)
+  const unsigned c = cnt[q];
+  const unsigned long long *Q = queue + (size_t)q * cap;
+  const unsigned want = min((unsigned)K + 1u, c);
+  if (tid == 0) { *nkept = 0u; *tie = 0u; }
+  for (int e = tid; e < P; e += SEL_THREADS) sk[e] = ~0ull;
+  if (want > 0) {
+    const unsigned T = block_radix_select<SEL_THREADS>(
+        [&](auto f) __attribute__((always_inline)) {
+          for (unsigned e = tid; e < c; e += SEL_THREADS) f((unsigned)(Q[e] >> 32));
+        },
+        want, hsub, hist, state);
+    const unsigned rank = state.remaining;   // of the wanted key among those whose distance word is T
+    __syncthreads();                         // (the next select rewrites `state`)
+    const unsigned R = block_radix_select<SEL_THREADS>(
+        [&](auto f) __attribute__((always_inline)) {
+          for (unsigned e = tid; e < c; e += SEL_THREADS) {
+            const unsigned long long k = Q[e];
+            if ((unsigned)(k >> 32) == T) f((unsigned)k);
+          }
+        },
+        rank, hsub, hist, state);
+    const unsigned long long cut = ((unsigned long long)T << 32) | R;
+    for (unsigned e = tid; e < c; e += SEL_THREADS) {
+      const unsigned long long k = Q[e];
+      if (k <= cut) {
+        const unsigned pos = atomicAdd(nkept, 1u);
+        if (pos < (unsigned)P) sk[pos] = k;
+      }
+    }
+  }
+  __syncthreads();
+  for (int k = 2; k <= P; k <<= 1)
+    for (int j = k >> 1; j >= 1; j >>= 1) {
+      for (int t = tid; t < P / 2; t += SEL_THREADS) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+        const unsigned long long a = sk[i], b = sk[l];
+        const bool up = (i & k) == 0;
+        if ((a > b) == up) { sk[i] = b; sk[l] = a; }
+      }
+      __syncthreads();
+    }
+  unsigned flags = 0;
+  for (int e = tid; e < K; e += SEL_THREADS) {
+    const bool ok = (unsigned)e < want;
+    const unsigned long long k = ok ? sk[e] : 0ull;
+    out_idx[(size_t)q * K + e] = ok ? (int)(unsigned)k : -1;
+    out_dist[(size_t)q * K + e] = ok ? __uint_as_float((unsigned)(k >> 32)) : INFINITY;
+    if (ok && (unsigned)e + 1u < want && (unsigned)(sk[e + 1] >> 32) == (unsigned)(k >> 32))
+      flags |= (e == K - 1) ? GULON_FLAG_BOUNDARY_TIE : GULON_FLAG_INTERIOR_TIE;
+  }
+  if (flags) atomicOr(tie, flags);
+  __syncthreads();
+  if (tid == 0) {
+    if (out_count) out_count[q] = (int)min((unsigned)K, want);
+    if (out_flags) out_flags[q] = (int)*tie;
+  }
+}
+
+// small k_nn: can one of the query's distances to rows of magnitude <= absmax overflow, or is it NaN?  Conservative:
+// d * (absmax + max |q_e|)^2 below 3e38 keeps every partial sum finite.
+__global__ void exact_screen(const float *__restrict__ Q, int B, int d, float absmax, int *__restrict__ nonfinite) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= B) return;
+  float m = 0.f;
+  bool bad = !(absmax < INFINITY);
+  for (int e = 0; e < d; e++) {
+    const float a = fabsf(Q[(size_t)q * d + e]);
+    bad = bad || !(a < INFINITY);
+    m = fmaxf(m, a);
+  }
+  const double s = (double)absmax + (double)m;
+  nonfinite[q] = (bad || !((double)d * s * s < 3.0e38)) ? 1 : 0;
+}
+
+__global__ void exact_fill_empty(long long bk, int B, int *__restrict__ out_idx, float *__restrict__ out_dist,
+                                 int *__restrict__ out_count, int *__restrict__ out_flags) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < bk) { out_idx[t] = -1; out_dist[t] = INFINITY; }
+  if (t < B) {
+    if (out_count) out_count[t] = 0;
+    if (out_flags) out_flags[t] = 0;
+  }
+}
+
+// out[t] = X[rows[t]] (a row outside [0, n): NaN, which the non-finite path then answers)
+__global__ void exact_gather_rows(const float *__restrict__ X, int n, int d, const int *__restrict__ rows, int b,
+                                  float *__restrict__ out) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long long)b * d) return;
+  const int r = rows[t / d];
+  out[t] = (r >= 0 && r < n) ? X[(size_t)r * d + t % d] : NAN;
+}
+
+// the fallback's sub-batch: out[f] = Q[ids[f]], and its answers back to the rows of the batch
+__global__ void exact_gather_queries(const float *__restrict__ Q, int d, const int *__restrict__ ids, int F,
+                                     float *__restrict__ out) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long long)F * d) return;
+  out[t] = Q[(size_t)ids[t / d] * d + t % d];
+}
+__global__ void exact_scatter_answers(const int *__restrict__ ids, int F, int K, const int *__restrict__ ci,
+                                      const float *__restrict__ cd, const int *__restrict__ cc,
+                                      const int *__restrict__ cf, int *__restrict__ out_idx,
+                                      float *__restrict__ out_dist, int *__restrict__ out_count,
+                                      int *__restrict__ out_flags) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long long)F * K) return;
+  const int f = (int)(t / K), e = (int)(t % K), q = ids[f];
+  out_idx[(size_t)q * K + e] = ci[t];
+  out_dist[(size_t)q * K + e] = cd[t];
+  if (e == 0) {
+    if (out_count) out_count[q] = cc[f];
+    if (out_flags) out_flags[q] = cf[f];
+  }
+}
+
+}  // namespace
+}  // namespace gulon
+
+using namespace gulon;
+
+struct gulon_exact_index {
+  const gulon_dataset *ds = nullptr;   // not owned: the dataset outlives the handle
+  int from = 0, until = 0;
+  float absmax = 0.f;                  // max |x| over the range, +inf if any value is NaN / inf
+  int knob_sample = 0;                 // GULON_EXACT_SAMPLE: sample rows S (0: by k_nn, the range and the capacity)
+  int knob_cap = 32768;                // GULON_EXACT_QUEUE_CAP: queue entries per query
+  int64_t stats[6] = {0, 0, 0, 0, 0, 0};
+  // scratch, grown on demand under `mu`
+  DevBuf<float> qt, sample, tau;
+  DevBuf<unsigned long long> queue;
+  DevBuf<unsigned> cnt;
+  DevBuf<int> overflow, nonfinite, ids, count_tmp, flags_tmp;
+  DevBuf<float> fq, fd;
+  DevBuf<int> fi, fc, ff;
+  // the single-pass / peeled path of knn.hip
+  DevBuf<float> l_qt, l_pv, l_accv, l_tv, l_lbv;
+  DevBuf<int> l_pi, l_acci, l_ti, l_lbi;
+  // the host-pointer forms
+  DevBuf<float> stage_q, stage_od;
+  DevBuf<int> stage_rows, stage_oi, stage_oc, stage_of;
+  std::vector<int> h_cnt, h_ovf, h_nf, h_ids;
+  hipEvent_t order_ev = nullptr;
+  hipStream_t order_st = nullptr;
+  bool order_set = false;
+  std::mutex mu;
+  ~gulon_exact_index() {
+    if (order_ev) (void)hipEventDestroy(order_ev);
+  }
+};
+
+namespace {
+
+bool set_knob(gulon_exact_index *h, const char *key, int v) {
+  if (!strcmp(key, "GULON_EXACT_SAMPLE")) { h->knob_sample = v < 0 ? 0 : v; return true; }
+  if (!strcmp(key, "GULON_EXACT_QUEUE_CAP")) { h->knob_cap = v < 16 ? 16 : v > (1 << 22) ? (1 << 22) : v; return true; }
+  return false;
+}
+
+// gulon_exact_knn's device work for b queries at d_q, on `st`, with its launch geometry: k_nn <= GULON_MAX_K in one
+// knn_kernel pass and launch_merge, larger k_nn peeled 64 entries per pass.  Outputs are device pointers, none null.
+void legacy_dev(gulon_exact_index *h, const float *d_q, int b, int K, int *oi, float *od, int *oc, int *of,
+                hipStream_t st) {
+  const gulon_dataset *ds = h->ds;
+  const int from = h->from, until = h->until, d = ds->d;
+  const bool peeled = K > GULON_MAX_K;
+  const int keff = peeled ? 64 : K + 1;
+  const int ntiles = ceil_div(b, KNN_QT);
+  const int rbeg = (from / KNN_THREADS) * KNN_THREADS;
+  const int groups = ceil_div(until - rbeg, KNN_THREADS);
+  int want = ceil_div(2048, ntiles);
+  int nchunks = want < groups ? want : groups;
+  int groups_per_chunk = ceil_div(groups, nchunks);
+  nchunks = ceil_div(groups, groups_per_chunk);
+  const int rows_per_chunk = groups_per_chunk * KNN_THREADS;
+  const int Bp = ntiles * KNN_QT;
+  h->l_qt.ensure((size_t)ntiles * d * KNN_QT);
+  h->l_pv.ensure((size_t)Bp * nchunks * keff);
+  h->l_pi.ensure((size_t)Bp * nchunks * keff);
+  const long long tq = (long long)ntiles * d * KNN_QT;
+  hipLaunchKernelGGL(transpose_queries, dim3(ceil_div(tq, 256)), dim3(256), 0, st, d_q, b, d, ntiles, h->l_qt.p);
+  if (peeled) {
+    const int rounds = ceil_div(K + 1, 64), cap = rounds * 64;
+    h->l_accv.ensure((size_t)b * cap); h->l_acci.ensure((size_t)b * cap);
+    h->l_tv.ensure((size_t)b * 64); h->l_ti.ensure((size_t)b * 64);
+    h->l_lbv.ensure(Bp); h->l_lbi.ensure(Bp);
+    HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)h->l_lbv.p, 0xBF800000 /* -1.0f */, (size_t)Bp, st));
+    HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)h->l_lbi.p, 0xFFFFFFFF, (size_t)Bp, st));
+    for (int r = 0; r < rounds; r++) {
+      hipLaunchKernelGGL(knn_kernel, dim3(ntiles, nchunks), dim3(KNN_THREADS), 0, st, ds->x.p, ds->n, d, h->l_qt.p, from,
+                         until, rows_per_chunk, nchunks, 64, h->l_pv.p, h->l_pi.p, h->l_lbv.p, h->l_lbi.p);
+      HIP_CHECK(hipGetLastError());
+      launch_merge(false, h->l_pv.p, h->l_pi.p, nchunks, 64LL, (long long)nchunks * 64, b, 63, nullptr, nullptr, nullptr,
+                   nullptr, h->l_tv.p, h->l_ti.p, st);
+      launch_peel_update(h->l_tv.p, h->l_ti.p, b, r, cap, h->l_accv.p, h->l_acci.p, h->l_lbv.p, h->l_lbi.p, st);
+    }
+    launch_peel_finalize(h->l_accv.p, h->l_acci.p, b, cap, K, oi, od, oc, of, st);
+  } else {
+    hipLaunchKernelGGL(knn_kernel, dim3(ntiles, nchunks), dim3(KNN_THREADS), 0, st, ds->x.p, ds->n, d, h->l_qt.p, from,
+                       until, rows_per_chunk, nchunks, keff, h->l_pv.p, h->l_pi.p, (const float *)nullptr,
+                       (const int *)nullptr);
+    HIP_CHECK(hipGetLastError());
+    launch_merge(true, h->l_pv.p, h->l_pi.p, nchunks, (long long)keff, (long long)nchunks * keff, b, K, oi, od, oc, of,
+                 nullptr, nullptr, st);
+  }
+}
+
+// k_nn <= GULON_MAX_K: knn_kernel's single pass.  It has no test for non-finite distances, so exact_screen flags the
+// queries that may meet one; those go one at a time, the others in the runs between them.
+void small_k_dev(gulon_exact_index *h, const float *dQ, int B, int K, int *oi, float *od, int *oc, int *of,
+                 hipStream_t st) {
+  const int d = h->ds->d;
+  h->nonfinite.ensure(B);
+  hipLaunchKernelGGL(exact_screen, dim3(ceil_div(B, 256)), dim3(256), 0, st, dQ, B, d, h->absmax, h->nonfinite.p);
+  HIP_CHECK(hipGetLastError());
+  h->h_nf.resize(B);
+  h->nonfinite.download(h->h_nf.data(), B, st);
+  HIP_CHECK(hipStreamSynchronize(st));
+  int q = 0;
+  while (q < B) {
+    int e = q + 1;
+    if (!h->h_nf[q]) while (e < B && !h->h_nf[e]) e++;
+    legacy_dev(h, dQ + (size_t)q * d, e - q, K, oi + (size_t)q * K, od + (size_t)q * K, oc + q, of + q, st);
+    if (h->h_nf[q]) h->stats[2]++; else h->stats[0] += e - q;
+    q = e;
+  }
+}
+
+void large_k_dev(gulon_exact_index *h, const float *dQ, int B, int K, int *oi, float *od, int *oc, int *of,
+                 hipStream_t st) {
+  const gulon_dataset *ds = h->ds;
+  const int d = ds->d, from = h->from, range = h->until - h->from, cap = h->knob_cap;
+  // the sample: none for a range the queue holds; else S rows, by default twice as many as make the expected fill
+  // (k_nn + 1) * range / S equal to the capacity
+  const bool sampled = range > cap;
+  int S = 0;
+  if (sampled) {
+    long long s = h->knob_sample > 0 ? h->knob_sample
+                                     : std::min<long long>(ceil_div(2LL * (K + 1) * range, cap), EXACT_SAMPLE_MAX);
+    s = std::max<long long>(s, K + 1);
+    S = (int)std::min<long long>(s, range);
+  }
+  const int want_tau = std::min(K + 1, S);
+  int P = 2;
+  while (P < std::min(K + 1, std::min(range, cap))) P <<= 1;
+  const size_t sel_lds = (size_t)P * 8 + (256 * 8 + 256 + 8) * sizeof(unsigned);
+  static std::mutex attr_mu;
+  static size_t attr_set[16] = {0};
+  {
+    int dev = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> g(attr_mu);
+    if (dev < 0 || dev >= 16 || attr_set[dev] < sel_lds) {
+      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(exact_select),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_lds));
+      if (dev >= 0 && dev < 16) attr_set[dev] = sel_lds;
+    }
+  }
+  // queries per sub-batch: whole tiles whose sample distances and queues fit the scratch budget
+  const size_t per_query = (size_t)S * 4 + (size_t)cap * 8;
+  int sub = (int)std::min<size_t>(EXACT_SCRATCH_BYTES / per_query, (size_t)1 << 20) / KNN_QT * KNN_QT;
+  sub = std::max(sub, KNN_QT);
+  sub = std::min(sub, ceil_div(B, KNN_QT) * KNN_QT);
+  const int Bp = ceil_div(B, KNN_QT) * KNN_QT;
+  h->qt.ensure((size_t)sub * d);
+  h->sample.ensure((size_t)sub * S);
+  h->queue.ensure((size_t)sub * cap);
+  h->tau.ensure(sub);
+  h->cnt.ensure(Bp); h->overflow.ensure(Bp); h->nonfinite.ensure(Bp);
+  HIP_CHECK(hipMemsetAsync(h->cnt.p, 0, sizeof(unsigned) * Bp, st));
+  HIP_CHECK(hipMemsetAsync(h->overflow.p, 0, sizeof(int) * Bp, st));
+  HIP_CHECK(hipMemsetAsync(h->nonfinite.p, 0, sizeof(int) * Bp, st));
+  const int cus = device_cus();
+  for (int q0 = 0; q0 < B; q0 += sub) {
+    const int b = std::min(sub, B - q0), ntiles = ceil_div(b, KNN_QT), bp = ntiles * KNN_QT;
+    const float *dq = dQ + (size_t)q0 * d;
+    const long long tq = (long long)ntiles * d * KNN_QT;
+    hipLaunchKernelGGL(transpose_queries, dim3(ceil_div(tq, 256)), dim3(256), 0, st, dq, b, d, ntiles, h->qt.p);
+    auto shape = [&](int total, int &per_chunk, int &nchunks) {   // about 64 workgroups per compute unit
+      const int groups = ceil_div(total, KNN_THREADS);
+      const int want = std::max(1, ceil_div((long long)cus * 64, ntiles));
+      const int gpc = ceil_div(groups, std::min(want, groups));
+      per_chunk = gpc * KNN_THREADS;
+      nchunks = ceil_div(groups, gpc);
+    };
+    int per_chunk = 0, nchunks = 0;
+    if (sampled) {
+      shape(S, per_chunk, nchunks);
+      hipLaunchKernelGGL(exact_pass<true>, dim3(ntiles, nchunks), dim3(KNN_THREADS), 0, st, ds->x.p, d, h->qt.p, b, from,
+                         range, S, per_chunk, h->sample.p, (const float *)nullptr, (unsigned long long *)nullptr, 0,
+                         (unsigned *)nullptr, (int *)nullptr, (int *)nullptr);
+      hipLaunchKernelGGL(exact_tau, dim3(bp), dim3(256), 0, st, h->sample.p, S, want_tau, b, h->tau.p);
+    } else {
+      hipLaunchKernelGGL(exact_tau_all, dim3(ceil_div(bp, 256)), dim3(256), 0, st, b, bp, h->tau.p);
+    }
+    shape(range, per_chunk, nchunks);
+    hipLaunchKernelGGL(exact_pass<false>, dim3(ntiles, nchunks), dim3(KNN_THREADS), 0, st, ds->x.p, d, h->qt.p, b, from,
+                       range, 0, per_chunk, (float *)nullptr, h->tau.p, h->queue.p, cap, h->cnt.p + q0, h->overflow.p + q0,
+                       h->nonfinite.p + q0);
+    hipLaunchKernelGGL(exact_select, dim3(b), dim3(SEL_THREADS), sel_lds, st, h->queue.p, cap, h->cnt.p + q0,
+                       h->overflow.p + q0, h->nonfinite.p + q0, K, P, oi + (size_t)q0 * K, od + (size_t)q0 * K, oc + q0,
+                       of + q0);
+    HIP_CHECK(hipGetLastError());
+  }
+  // what the device flagged decides the rest of the batch: one small read
+  h->h_cnt.resize(B); h->h_ovf.resize(B); h->h_nf.resize(B);
+  h->cnt.download((unsigned *)h->h_cnt.data(), B, st);
+  h->overflow.download(h->h_ovf.data(), B, st);
+  h->nonfinite.download(h->h_nf.data(), B, st);
+  HIP_CHECK(hipStreamSynchronize(st));
+  h->h_ids.clear();
+  int64_t fill = 0;
+  for (int q = 0; q < B; q++) {
+    fill = std::max<int64_t>(fill, (unsigned)h->h_cnt[q]);
+    if (h->h_nf[q]) h->stats[2]++;
+    else if (h->h_ovf[q]) h->h_ids.push_back(q);
+    else h->stats[0]++;
+  }
+  h->stats[1] = (int64_t)h->h_ids.size();
+  h->stats[3] = S; h->stats[4] = cap; h->stats[5] = fill;
+  const int F = (int)h->h_ids.size();
+  if (F > 0) {   // overflowed queues: the peeled path over the compacted sub-batch
+    h->ids.upload(h->h_ids.data(), F, st);
+    h->fq.ensure((size_t)F * d);
+    h->fi.ensure((size_t)F * K); h->fd.ensure((size_t)F * K); h->fc.ensure(F); h->ff.ensure(F);
+    hipLaunchKernelGGL(exact_gather_queries, dim3(ceil_div((long long)F * d, 256)), dim3(256), 0, st, dQ, d, h->ids.p, F,
+                       h->fq.p);
+    legacy_dev(h, h->fq.p, F, K, h->fi.p, h->fd.p, h->fc.p, h->ff.p, st);
+    hipLaunchKernelGGL(exact_scatter_answers, dim3(ceil_div((long long)F * K, 256)), dim3(256), 0, st, h->ids.p, F, K,
+                       h->fi.p, h->fd.p, h->fc.p, h->ff.p, oi, od, oc, of);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(st));   // (h_ids is read by the upload)
+  }
+  for (int q = 0; q < B; q++)   // a NaN / +inf distance: the answer of a batch of one
+    if (h->h_nf[q]) legacy_dev(h, dQ + (size_t)q * d, 1, K, oi + (size_t)q * K, od + (size_t)q * K, oc + q, of + q, st);
+}
+
+// the body of every query form: device pointers, outputs [B][K] / [B] (count and flags may be null)
+void exact_query_dev(gulon_exact_index *h, const float *dQ, int B, int K, int *oi, float *od, int *oc, int *of,
+                     hipStream_t st) {
+  GULON_REQUIRE(B >= 0 && K >= 0, "bad arguments");
+  GULON_UNSUPPORTED(K > GULON_MAX_K_PEELED, "k_nn = %d > %d", K, GULON_MAX_K_PEELED);
+  for (auto &s : h->stats) s = 0;
+  h->stats[4] = h->knob_cap;
+  if (B == 0) return;
+  if (!h->order_ev) HIP_CHECK(hipEventCreateWithFlags(&h->order_ev, hipEventDisableTiming));
+  if (h->order_set && h->order_st != st) HIP_CHECK(hipStreamWaitEvent(st, h->order_ev, 0));
+  if (!oc) { h->count_tmp.ensure(B); oc = h->count_tmp.p; }
+  if (!of) { h->flags_tmp.ensure(B); of = h->flags_tmp.p; }
+  const long long bk = (long long)B * K;
+  if (K == 0 || h->from == h->until) {
+    hipLaunchKernelGGL(exact_fill_empty, dim3(ceil_div(std::max<long long>(bk, B), 256)), dim3(256), 0, st, bk, B, oi, od,
+                       oc, of);
+    HIP_CHECK(hipGetLastError());
+    h->stats[0] = B;
+  } else if (K <= GULON_MAX_K) {
+    small_k_dev(h, dQ, B, K, oi, od, oc, of, st);
+  } else {
+    large_k_dev(h, dQ, B, K, oi, od, oc, of, st);
+  }
+  HIP_CHECK(hipEventRecord(h->order_ev, st));
+  h->order_st = st;
+  h->order_set = true;
+}
+
+void exact_query_host(gulon_exact_index *h, const float *dQ, int b, int K, int32_t *out_idx, float *out_dist,
+                      int32_t *out_count, int32_t *out_flags) {
+  const size_t bk = (size_t)b * K;
+  h->stage_oi.ensure(std::max<size_t>(bk, 1)); h->stage_od.ensure(std::max<size_t>(bk, 1));
+  h->stage_oc.ensure(b); h->stage_of.ensure(b);
+  exact_query_dev(h, dQ, b, K, h->stage_oi.p, h->stage_od.p, h->stage_oc.p, h->stage_of.p, nullptr);
+  h->stage_oi.download(out_idx, bk); h->stage_od.download(out_dist, bk);
+  if (out_count) h->stage_oc.download(out_count, b);
+  if (out_flags) h->stage_of.download(out_flags, b);
+  HIP_CHECK(hipDeviceSynchronize());
+}
+
+void gather_rows(gulon_exact_index *h, const int *d_rows, int b, hipStream_t st) {
+  const int d = h->ds->d;
+  h->stage_q.ensure((size_t)b * d);
+  hipLaunchKernelGGL(exact_gather_rows, dim3(ceil_div((long long)b * d, 256)), dim3(256), 0, st, h->ds->x.p, h->ds->n, d,
+                     d_rows, b, h->stage_q.p);
+  HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace
+
+GULON_API int32_t gulon_exact_index_create(const gulon_dataset *ds, int32_t from, int32_t until, gulon_exact_index **out) {
+  return guarded([&] {
+    GULON_REQUIRE(ds != nullptr && out != nullptr, "dataset or out is null");
+    GULON_REQUIRE(from <= until, "invalid range: expected from=%d <= until=%d", from, until);
+    GULON_REQUIRE(until <= ds->n, "invalid range: expected until=%d <= vectors.length=%d", until, ds->n);
+    GULON_REQUIRE(from >= 0, "invalid range: from=%d < 0", from);
+    auto h = std::make_unique<gulon_exact_index>();
+    h->ds = ds; h->from = from; h->until = until;
+    if (const char *e = getenv("GULON_EXACT_SAMPLE")) set_knob(h.get(), "GULON_EXACT_SAMPLE", atoi(e));
+    if (const char *e = getenv("GULON_EXACT_QUEUE_CAP")) set_knob(h.get(), "GULON_EXACT_QUEUE_CAP", atoi(e));
+    h->absmax = centroid_absmax(ds->x.p + (size_t)from * ds->d, (long long)(until - from) * ds->d);
+    *out = h.release();
+  });
+}
+
+GULON_API int32_t gulon_exact_index_destroy(gulon_exact_index *idx) {
+  return guarded([&] {
+    if (idx) (void)hipDeviceSynchronize();
+    delete idx;
+  });
+}
+
+GULON_API int32_t gulon_exact_index_batch_query_dev(gulon_exact_index *idx, const float *d_queries, int32_t b,
+                                                    int32_t k_nn, int32_t *d_out_idx, float *d_out_dist,
+                                                    int32_t *d_out_count, int32_t *d_out_flags, void *stream) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr, "index is null");
+    std::lock_guard<std::mutex> g(idx->mu);
+    exact_query_dev(idx, d_queries, b, k_nn, d_out_idx, d_out_dist, d_out_count, d_out_flags, (hipStream_t)stream);
+  });
+}
+
+GULON_API int32_t gulon_exact_index_batch_query(gulon_exact_index *idx, const float *queries, int32_t b, int32_t k_nn,
+                                                int32_t *out_idx, float *out_dist, int32_t *out_count,
+                                                int32_t *out_flags) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr, "index is null");
+    GULON_REQUIRE(b >= 0 && k_nn >= 0, "bad arguments");
+    std::lock_guard<std::mutex> g(idx->mu);
+    if (b == 0) { for (auto &s : idx->stats) s = 0; return; }
+    idx->stage_q.upload(queries, (size_t)b * idx->ds->d);
+    exact_query_host(idx, idx->stage_q.p, b, k_nn, out_idx, out_dist, out_count, out_flags);
+  });
+}
+
+GULON_API int32_t gulon_exact_index_query_rows_dev(gulon_exact_index *idx, const int32_t *d_rows, int32_t b,
+                                                   int32_t k_nn, int32_t *d_out_idx, float *d_out_dist,
+                                                   int32_t *d_out_count, int32_t *d_out_flags, void *stream) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr, "index is null");
+    GULON_REQUIRE(b >= 0 && k_nn >= 0, "bad arguments");
+    std::lock_guard<std::mutex> g(idx->mu);
+    if (b > 0) gather_rows(idx, d_rows, b, (hipStream_t)stream);
+    exact_query_dev(idx, idx->stage_q.p, b, k_nn, d_out_idx, d_out_dist, d_out_count, d_out_flags, (hipStream_t)stream);
+  });
+}
+
+GULON_API int32_t gulon_exact_index_query_rows(gulon_exact_index *idx, const int32_t *rows, int32_t b, int32_t k_nn,
+                                               int32_t *out_idx, float *out_dist, int32_t *out_count,
+                                               int32_t *out_flags) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr, "index is null");
+    GULON_REQUIRE(b >= 0 && k_nn >= 0, "bad arguments");
+    for (int r = 0; r < b; r++)
+      GULON_REQUIRE(rows[r] >= 0 && rows[r] < idx->ds->n, "row %d = %d outside [0, %d)", r, rows[r], idx->ds->n);
+    std::lock_guard<std::mutex> g(idx->mu);
+    if (b == 0) { for (auto &s : idx->stats) s = 0; return; }
+    idx->stage_rows.upload(rows, b);
+    gather_rows(idx, idx->stage_rows.p, b, nullptr);
+    exact_query_host(idx, idx->stage_q.p, b, k_nn, out_idx, out_dist, out_count, out_flags);
+  });
+}
+
+GULON_API int32_t gulon_exact_index_tuning(gulon_exact_index *idx, const char *key, int32_t value) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr && key != nullptr, "index or key is null");
+    std::lock_guard<std::mutex> g(idx->mu);
+    GULON_REQUIRE(set_knob(idx, key, value), "unknown tuning key %s", key);
+  });
+}
+
+GULON_API int32_t gulon_exact_index_stats(gulon_exact_index *idx, int64_t *out) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr && out != nullptr, "index or out is null");
+    std::lock_guard<std::mutex> g(idx->mu);
+    for (int i = 0; i < 6; i++) out[i] = idx->stats[i];
+  });
+}

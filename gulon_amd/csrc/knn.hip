@@ -2,15 +2,10 @@
 // (MathUtils.scala:85-95): brute-force squared L2, sequential unfused fp32, then the
 // same wavefront top-k as the ADC scan.  Used for BASELINE config 1 and for the
 // recall ground truth (Tests.scala:89-97).
-#include "scan.hpp"
+#include "exact.hpp"   // the tile shape (KNN_QT, KNN_DT, KNN_THREADS) and the two kernels' declarations
 
 namespace gulon {
 
-constexpr int KNN_QT = 16;       // queries per workgroup
-constexpr int KNN_DT = 32;       // dims staged per step
-constexpr int KNN_THREADS = 256; // 4 waves, lane = row
-
-// Qt[tile][t][KNN_QT]: queries transposed so one uniform (scalar) load serves a wave
 __global__ void transpose_queries(const float *__restrict__ Q, int B, int d, int ntiles, float *__restrict__ Qt) {
   long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long total = (long long)ntiles * d * KNN_QT;

@@ -1,0 +1,207 @@
+"""The exact index: brute-force neighbours over the original vectors, with the query surface of the other indexes
+(csrc/exact.hip).
+
+ExactIndex answers what `exact_nearest_neighbours` answers -- Index.exactNearestNeighbours (Index.scala:209-229) with
+MathUtils.distanceSq, entries ascending in (distance, row id), tie flags -- from a handle that keeps its scratch, takes
+device pointers as well as arrays, and above 63 neighbours reads the rows once instead of once per 64 entries.
+ExactWordIndex puts words on it; WordIndex.exact(vectors) builds one over an index's words in the index's row order, so
+its answers compare entry by entry with the index's own."""
+import ctypes as C
+from typing import List, Optional
+
+import numpy as np
+
+from . import native as N
+from .index import Result, normalize
+from .matrix import as_device
+from .word_index import BATCH, WordResult
+
+KNOBS = ("GULON_EXACT_SAMPLE", "GULON_EXACT_QUEUE_CAP")
+STATS = ("one_pass", "fallback", "nonfinite", "sample", "capacity", "max_fill")
+
+
+class ExactIndex:
+    """Exact neighbours of rows [frm, until) of `matrix` (a DeviceMatrix, a Matrix or an array; the index does not own a
+    DeviceMatrix it is given, which must outlive it).  metric "cosine": the queries are normalised as
+    SortedIndex._prepare normalises them and the matrix is expected to hold normalised vectors already -- the
+    normalised reading that build-index feeds."""
+
+    def __init__(self, matrix, metric="l2", frm=0, until=None):
+        if metric not in ("l2", "cosine"):
+            raise ValueError(f"unknown metric {metric!r}")
+        self.matrix, self.metric = as_device(matrix), metric
+        self.frm, self.until = int(frm), self.matrix.rows if until is None else int(until)
+        self._h = C.c_void_p()
+        N.check(N.lib().gulon_exact_index_create(self.matrix._h, self.frm, self.until, C.byref(self._h)))
+
+    @property
+    def dimension(self):
+        return self.matrix.cols
+
+    @property
+    def size(self):
+        return self.until - self.frm
+
+    def _prepare(self, q):
+        q = N.f32(q).reshape(-1, self.dimension)
+        if self.metric == "cosine" and len(q):
+            q = np.stack([normalize(r) for r in q])
+        return q
+
+    @staticmethod
+    def _outputs(b, k):
+        return (np.zeros((b, max(k, 1)), np.int32), np.zeros((b, max(k, 1)), np.float32), np.zeros(max(b, 1), np.int32),
+                np.zeros(max(b, 1), np.int32))
+
+    def batch_query_raw(self, k, vectors):
+        """(rows [B][k] with -1 after a query's last entry, distances [B][k] with +inf there, counts [B], flags [B])."""
+        q = self._prepare(vectors)
+        b = len(q)
+        oi, od, oc, of = self._outputs(b, k)
+        N.check(N.lib().gulon_exact_index_batch_query(self._h, q.reshape(-1) if q.size else np.zeros(1, np.float32), b, k,
+                                                      oi.reshape(-1), od.reshape(-1), oc, of))
+        return oi[:, :k], od[:, :k], oc[:b], of[:b]
+
+    def batch_query_rows_raw(self, k, rows):
+        """batch_query_raw with rows of the matrix as the queries, gathered on the device (they are taken as stored: a
+        cosine index holds normalised rows)."""
+        rows = N.i32(rows).reshape(-1)
+        b = len(rows)
+        oi, od, oc, of = self._outputs(b, k)
+        N.check(N.lib().gulon_exact_index_query_rows(self._h, rows if b else np.zeros(1, np.int32), b, k, oi.reshape(-1),
+                                                     od.reshape(-1), oc, of))
+        return oi[:, :k], od[:, :k], oc[:b], of[:b]
+
+    @staticmethod
+    def _results(oi, od, oc, of):
+        return [Result(oi[i, :oc[i]].copy(), od[i, :oc[i]].copy(), int(of[i])) for i in range(len(oc))]
+
+    def batch_query(self, k, vectors) -> List[Result]:
+        return self._results(*self.batch_query_raw(k, vectors))
+
+    def query(self, k, vector) -> Result:
+        return self.batch_query(k, N.f32(vector).reshape(1, -1))[0]
+
+    def batch_query_rows(self, k, rows) -> List[Result]:
+        return self._results(*self.batch_query_rows_raw(k, rows))
+
+    def batch_query_dev(self, k, d_queries, b, d_rows, d_dist, d_counts=None, d_flags=None, stream=None):
+        """The device form: every argument but k and b a device address (int), the queries taken as they are."""
+        N.check(N.lib().gulon_exact_index_batch_query_dev(self._h, d_queries, b, k, d_rows, d_dist, d_counts, d_flags,
+                                                          stream))
+
+    def batch_query_rows_dev(self, k, d_query_rows, b, d_rows, d_dist, d_counts=None, d_flags=None, stream=None):
+        N.check(N.lib().gulon_exact_index_query_rows_dev(self._h, d_query_rows, b, k, d_rows, d_dist, d_counts, d_flags,
+                                                         stream))
+
+    def lookup_rows(self, rows):
+        """The rows themselves: [len(rows)][dimension]."""
+        return self.matrix.get_rows(rows)
+
+    def stats(self):
+        """Of the last batch: queries answered in one pass, by the peeled fallback and one at a time as non-finite; the
+        sample rows S (0: no sample pass), the queue capacity, the largest number of rows at or below a bound."""
+        out = np.zeros(6, np.int64)
+        N.check(N.lib().gulon_exact_index_stats(self._h, out))
+        return dict(zip(STATS, out.tolist()))
+
+    def tune(self, **knobs):
+        """GULON_EXACT_SAMPLE=..., GULON_EXACT_QUEUE_CAP=... on this handle; results never depend on them."""
+        for key, value in knobs.items():
+            N.check(N.lib().gulon_exact_index_tuning(self._h, key.encode(), int(value)))
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            N.lib().gulon_exact_index_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ExactWordIndex:
+    """Words over an ExactIndex whose row i holds the vector of words[i]: the query surface of WordIndex.  `key_index`
+    maps a word to its row (default: a dictionary over `words`)."""
+
+    def __init__(self, words, index, key_index=None):
+        self.words, self.index = list(words), index
+        if len(self.words) != index.size or index.frm != 0:
+            raise ValueError(f"{len(self.words)} words for an exact index of rows [{index.frm}, {index.until})")
+        self._rows = None if key_index is not None else {w: i for i, w in enumerate(self.words)}
+        self.key_index = key_index
+
+    @property
+    def size(self):
+        return len(self.words)
+
+    @property
+    def dimension(self):
+        return self.index.dimension
+
+    @property
+    def metric(self):
+        return self.index.metric
+
+    def row_of(self, word) -> Optional[int]:
+        return self.key_index.lookup(word) if self.key_index is not None else self._rows.get(word)
+
+    def lookup(self, word) -> Optional[np.ndarray]:
+        """The word's original vector, None if it is absent."""
+        row = self.row_of(word)
+        return None if row is None else self.index.lookup_rows([row])[0]
+
+    def _result(self, r) -> WordResult:
+        return WordResult([self.words[i] for i in r.rows.tolist()], r.distances, r.rows, r.flags)
+
+    def batch_query(self, k, vectors) -> List[WordResult]:
+        q = np.ascontiguousarray(vectors, np.float32).reshape(-1, self.dimension)
+        out = []
+        for s in range(0, len(q), BATCH):
+            out.extend(self._result(r) for r in self.index.batch_query(k, q[s:s + BATCH]))
+        return out
+
+    def query(self, k, vector) -> WordResult:
+        return self.batch_query(k, np.asarray(vector, np.float32).reshape(1, -1))[0]
+
+    def batch_query_by_words(self, k, words) -> List[Optional[WordResult]]:
+        """Index.queryByWord (Index.scala:43-45) with the word's ORIGINAL vector as the query, so the word itself comes
+        first at distance 0; None for a word the index lacks."""
+        words = list(words)
+        rows = [self.row_of(w) for w in words]
+        present = [i for i, r in enumerate(rows) if r is not None]
+        out: List[Optional[WordResult]] = [None] * len(words)
+        for s in range(0, len(present), BATCH):
+            part = present[s:s + BATCH]
+            results = self.index.batch_query_rows(k, np.asarray([rows[i] for i in part], np.int32))
+            for i, r in zip(part, results):
+                out[i] = self._result(r)
+        return out
+
+    def query_by_word(self, k, word) -> Optional[WordResult]:
+        return self.batch_query_by_words(k, [word])[0]
+
+    def close(self):
+        """Frees the handle and the gathered matrix this index was built over, when it owns one."""
+        self.index.close()
+        owned = getattr(self, "_owned_matrix", None)
+        if owned is not None:
+            owned.close()
+            self._owned_matrix = None
+
+
+def exact_word_index(word_index, vectors):
+    """WordIndex.exact: the ExactWordIndex over `word_index`'s words in its row order, the vectors matched by
+    refine.word_row_map (LookupError for a word they lack) and gathered once on the device."""
+    from .matrix import DeviceMatrix
+    from .refine import word_row_map
+    row_map = word_row_map(word_index, vectors)[:word_index.size]
+    h = C.c_void_p()
+    N.check(N.lib().gulon_dataset_gather(vectors.matrix._h, row_map if row_map.size else np.zeros(1, np.int32),
+                                         row_map.size, C.byref(h)))
+    matrix = DeviceMatrix(h, row_map.size, vectors.matrix.cols)
+    out = ExactWordIndex(word_index.words, ExactIndex(matrix, word_index.metric), word_index.key_index)
+    out._owned_matrix = matrix
+    return out

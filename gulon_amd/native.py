@@ -187,6 +187,14 @@ SIGNATURES = {
     "gulon_rotate_rows": (_i32, [_f32p, _i32, _i32, _f32p, _i32, _f32p]),
     "gulon_rotate_rows_dev": (_i32, [_vp, C.c_int64, _i32, _vp, _i32, _vp, _vp]),
     "gulon_dataset_moment": (_i32, [_vp, _vp, _f64p]),
+    "gulon_exact_index_create": (_i32, [_vp, _i32, _i32, C.POINTER(_vp)]),
+    "gulon_exact_index_destroy": (_i32, [_vp]),
+    "gulon_exact_index_batch_query": (_i32, [_vp, _f32p, _i32, _i32, _i32p, _f32p, _i32p, _i32p]),
+    "gulon_exact_index_batch_query_dev": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "gulon_exact_index_query_rows": (_i32, [_vp, _i32p, _i32, _i32, _i32p, _f32p, _i32p, _i32p]),
+    "gulon_exact_index_query_rows_dev": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "gulon_exact_index_tuning": (_i32, [_vp, C.c_char_p, _i32]),
+    "gulon_exact_index_stats": (_i32, [_vp, _i64p]),
 }
 
 _lib = None

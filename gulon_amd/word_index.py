@@ -76,6 +76,14 @@ class WordIndex:
         from .fine import FineRefinedIndex
         return FineRefinedIndex(self, fine, candidates)
 
+    def exact(self, vectors):
+        """The exact index over this index's words (exact.ExactWordIndex): brute-force neighbours among the original
+        `vectors` (DeviceWordVectors with a key index; the normalised reading for a cosine index), matched to the
+        index's words as `refined` matches them and gathered once on the device in this index's row order -- its row ids
+        are this index's row ids, sorted or grouped.  A word the vectors lack: LookupError."""
+        from .exact import exact_word_index
+        return exact_word_index(self, vectors)
+
     def inspect(self, vectors=None, worst=10):
         """The diagnostics of this index (inspect.IndexReport): its shape and how its code books are used; with
         `vectors` (DeviceWordVectors with a key index; the normalised reading for a cosine index), matched to the
@@ -247,6 +255,9 @@ class RestrictedWordIndex(WordIndex):
 
     def fine_refined(self, fine, candidates):
         raise NotImplementedError("fine_refined is not supported by a restricted index")
+
+    def exact(self, vectors):
+        raise NotImplementedError("exact is not supported by a restricted index")
 
     def inspect(self, vectors=None, worst=10):
         raise NotImplementedError("inspect is not supported by a restricted index")

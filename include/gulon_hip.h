@@ -742,6 +742,46 @@ int32_t gulon_rotate_rows_dev(const float *d_x, int64_t n, int32_t d, const floa
  * bits on every call and every device.  Zero rows give zeros. */
 int32_t gulon_dataset_moment(const gulon_dataset *a, const gulon_dataset *b, double *out);
 
+/* ---- The exact index (exact.hip; DESIGN.md "Exact index") ------------------------------------------------------------
+ * Brute-force neighbours of rows [from, until) of a dataset behind a handle: what gulon_exact_knn answers -- squared L2
+ * summed e ascending in unfused binary32, entries ascending in (distance, row id), count = min(k_nn, until - from) with
+ * -1 / +inf after the last entry, GULON_FLAG_BOUNDARY_TIE / GULON_FLAG_INTERIOR_TIE -- the same rows, distance bits,
+ * counts and flags for every query whose distances are all finite, 0 <= k_nn <= GULON_MAX_K_PEELED.  A query that meets
+ * a NaN / +inf distance gets what gulon_exact_knn returns for it when asked alone.  k_nn <= GULON_MAX_K takes
+ * gulon_exact_knn's single pass; a larger k_nn reads the rows ONCE (a sample pass bounds the (k_nn + 1)-th distance,
+ * the main pass queues the rows at or below the bound, a selection sorts each queue) where gulon_exact_knn reads them
+ * ceil((k_nn + 1) / 64) times; a query whose queue overflows is answered by that peeled path.
+ *   create      the handle holds scratch, knobs and counters; it does NOT own the dataset, which must outlive it.
+ *   batch_query host pointers; outputs as gulon_exact_knn (out_count / out_flags may be NULL).
+ *   *_dev       device pointers, enqueued on `stream` (hipStream_t).  The outputs are complete only after the stream;
+ *               the call itself waits for the stream once per batch, to read the per-query counters that decide
+ *               whether fallback launches are needed, and may grow the handle's scratch.
+ *   query_rows  the queries are rows of the DATASET (0 <= row < its rows, whatever [from, until) is), gathered on the
+ *               device.  The host form checks every row before anything is launched (GULON_ERR_INVALID_ARGUMENT names
+ *               the first bad one); in the device form such a row is a NaN query.
+ *   tuning      keys "GULON_EXACT_SAMPLE" (sample rows S; 0 = chosen from k_nn, the range and the capacity) and
+ *               "GULON_EXACT_QUEUE_CAP" (queue entries per query, default 32768); a handle reads the environment
+ *               variables of the same names when it is created.  Results never depend on them.
+ *   stats       of the last batch on the handle: out[0] queries answered in one pass, out[1] by the peeled fallback,
+ *               out[2] one at a time as non-finite, out[3] S (0: no sample pass ran), out[4] the capacity, out[5] the
+ *               largest number of rows at or below a query's bound (above out[4]: that queue overflowed).
+ * One batch at a time per handle (calls are serialised); batches on different streams are ordered on the device. */
+typedef struct gulon_exact_index gulon_exact_index;
+int32_t gulon_exact_index_create(const gulon_dataset *ds, int32_t from, int32_t until, gulon_exact_index **out);
+int32_t gulon_exact_index_destroy(gulon_exact_index *idx);
+int32_t gulon_exact_index_batch_query(gulon_exact_index *idx, const float *queries, int32_t b, int32_t k_nn,
+                                      int32_t *out_idx, float *out_dist, int32_t *out_count, int32_t *out_flags);
+int32_t gulon_exact_index_batch_query_dev(gulon_exact_index *idx, const float *d_queries, int32_t b, int32_t k_nn,
+                                          int32_t *d_out_idx, float *d_out_dist, int32_t *d_out_count,
+                                          int32_t *d_out_flags, void *stream);
+int32_t gulon_exact_index_query_rows(gulon_exact_index *idx, const int32_t *rows, int32_t b, int32_t k_nn,
+                                     int32_t *out_idx, float *out_dist, int32_t *out_count, int32_t *out_flags);
+int32_t gulon_exact_index_query_rows_dev(gulon_exact_index *idx, const int32_t *d_rows, int32_t b, int32_t k_nn,
+                                         int32_t *d_out_idx, float *d_out_dist, int32_t *d_out_count,
+                                         int32_t *d_out_flags, void *stream);
+int32_t gulon_exact_index_tuning(gulon_exact_index *idx, const char *key, int32_t value);
+int32_t gulon_exact_index_stats(gulon_exact_index *idx, int64_t *out);
+
 #ifdef __cplusplus
 }
 #endif
