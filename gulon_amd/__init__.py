@@ -21,6 +21,7 @@ from .inspect import IndexReport, reference_quality
 from .update import UpdatePlan, plan_update
 from .expressions import Expression, Term, compose_reference, parse_expression, partition_by_operands
 from .rotation import RotatedWordIndex, Rotation, rotate_reference, train_rotation
+from .analogies import AnalogyReport, evaluate_analogies, read_questions
 
 __all__ = ["native", "GroupedIndex", "GroupedVectors", "LimitGroups", "LimitVectors", "group", "Coder", "width_for_clusters", "Index", "PQIndex", "PQIndexView", "DevicePQIndex", "Result", "SortedIndex",
            "exact_nearest_neighbours", "prepare_query", "tune_live", "KMeans", "KMeansConfig", "DeviceMatrix", "Matrix",
@@ -30,4 +31,4 @@ __all__ = ["native", "GroupedIndex", "GroupedVectors", "LimitGroups", "LimitVect
            "build_index", "RefinedIndex", "refine_topk", "Expression", "Term", "compose_reference", "parse_expression",
            "partition_by_operands", "IndexReport", "reference_quality", "UpdatePlan", "plan_update", "FineRefinedIndex", "build_fine_index",
            "refine_codes_topk", "row_residuals", "Rotation", "RotatedWordIndex", "train_rotation", "rotate_reference",
-           "ExactIndex", "ExactWordIndex"]
+           "ExactIndex", "ExactWordIndex", "AnalogyReport", "evaluate_analogies", "read_questions"]

@@ -1,4 +1,5 @@
-"""`python -m gulon_amd`: the reference's four commands (command/Main.scala:7-11), `inspect`, `update` and `build-fine`.
+"""`python -m gulon_amd`: the reference's four commands (command/Main.scala:7-11), `inspect`, `update`, `build-fine` and
+`analogies`.
 
   build-index -d l2|cosine -o INDEX [-k N] [-m N] [-n N] [-p [--partitions N] [-l N]] [-R ROTATION [--rotation-rounds N]]
               FILE
@@ -39,6 +40,21 @@
                                        second quantizer over the residuals the index leaves against the word2vec text
                                        file VECTORS it was built from (read normalised for a cosine index), written as an
                                        ordinary sorted l2 index file.  -k / -m / -n as for build-index
+
+  analogies -i INDEX [-k 1,5,10] [--lowercase] [-v VECTORS [--exact | -c N]] FILE
+                                       (not in the reference) the analogy accuracy of an index file (analogies.py,
+                                       csrc/analogy.hip) on FILE, questions in the questions-words.txt format: `: name`
+                                       opens a section, every other line is `a b c d`.  A question is right at k when d
+                                       is among the first k neighbours of b - a + c that are none of a, b, c.  One line
+                                       per section, `name: @1 0.7312 @5 0.8103 @10 0.8521 (n = 506, skipped 12)` -- n
+                                       the questions asked, skipped those with a word the index lacks -- and a `total:`
+                                       line.  The target is the index alone; with -v its form refined against that
+                                       word2vec text file (-c N candidates, default 10 * the largest k); with -v --exact
+                                       the true vectors of the index's words (WordIndex.exact).  Composed, queried and
+                                       scored on the device.  -f, -r and -R are not offered: a rotated index needs no
+                                       rotation file when it is evaluated alone or with --exact (the stored rows are
+                                       composed where they live, and --exact reads the index for its words only);
+                                       -v -c on a rotated index is outside this command
 
 -f FINE on the query commands and on test (not in the reference): as -v / -c, but the candidates are re-ranked by their
 distance to the index's row plus the fine index's row of the same word (fine.FineRefinedIndex) -- no original vectors in
@@ -182,7 +198,28 @@ class UpdateConfig:
     rotation: Optional[str] = None        # -R: the index was built over vectors rotated by this file
 
 
-def _sample_size(s):                                         # Test.scala:24-28
+@dataclass(frozen=True)
+class AnalogiesConfig:
+    index: str
+    questions: str
+    ks: tuple = (1, 5, 10)                # -k: the depths reported, ascending
+    lowercase: bool = False               # --lowercase: lower the questions' words
+    vectors: Optional[str] = None         # -v: refine against (or, exact, ask) the vectors the index was built from
+    exact: bool = False                   # --exact: the true vectors of the index's words are the target
+    candidates: Optional[int] = None      # -c: candidates of the refined form (default 10 * the largest k)
+
+
+def _depths(s):
+    try:
+        ks = tuple(int(t) for t in s.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"invalid list of integers: {s!r}")
+    if not ks or len(ks) > 16 or ks[0] < 1 or any(b <= a for a, b in zip(ks, ks[1:])):
+        raise argparse.ArgumentTypeError("must be 1 to 16 ascending integers from 1 up, separated by commas")
+    return ks
+
+
+def _sample_size(s):                                     # Test.scala:24-28
     if _integer(s) <= 0:
         raise argparse.ArgumentTypeError("must be greater than 0")
     return _integer(s)
@@ -311,6 +348,22 @@ def _parser():
     i.add_argument("-w", "--worst", type=_positive, default=None, metavar="num",
                    help="words with the largest error to list (needs --vectors; default 10)")
     i.add_argument("-R", "--rotation", default=None, metavar="file", help=_ROTATED_VECTORS + " (needs --vectors)")
+    a = sub.add_parser("analogies", help="report the analogy accuracy of an index",
+                       description="report the a:b :: c:d accuracy of an index on a questions-words.txt file: one line "
+                                   "per section and a total")
+    a.add_argument("-i", "--index", required=True, metavar="file", help="path to ANN index")
+    a.add_argument("-k", "--depths", type=_depths, default=(1, 5, 10), metavar="k1,k2,...",
+                   help="a question counts at k when its answer is among the first k neighbours (default 1,5,10)")
+    a.add_argument("--lowercase", action="store_true", help="lower the words of the questions")
+    a.add_argument("-v", "--vectors", default=None, metavar="file",
+                   help="word2vec word vectors the index was built from: evaluate the index refined against these")
+    a.add_argument("--exact", action="store_true",
+                   help="with --vectors: evaluate the original vectors themselves, by brute force on the device")
+    a.add_argument("-c", "--candidates", type=_positive, default=None, metavar="num",
+                   help="candidates taken from the index per question before re-ranking (needs --vectors, not with "
+                        "--exact; default 10 * the largest depth).  Not for a rotated index: this command takes no "
+                        "rotation file")
+    a.add_argument("file", metavar="file", help="questions: `: section` lines and lines of `a b c d`")
     u = sub.add_parser("update", help="add, replace and remove words of an index without retraining",
                        description="add, replace and remove words of an index without retraining")
     u.add_argument("-i", "--index", required=True, metavar="file", help="path to ANN index")
@@ -511,6 +564,36 @@ def run_build_fine(config: FineConfig, write, load):
     log_task(write, f"Writing index to {config.output}", dump, f"Wrote index to {config.output}")
 
 
+class AnalogiesError(Exception):
+    """What `analogies` reports and exits on: an unreadable or malformed questions file, vectors that lack a word of the
+    index, a depth the index form cannot answer."""
+
+
+def run_analogies(config: AnalogiesConfig, load, vectors):
+    """analogies between its argument handling and its lines -> analogies.AnalogyReport.  For a cosine index the vectors
+    are read normalised, as the query commands read them."""
+    from .analogies import evaluate_analogies, read_questions
+    try:
+        with open(config.questions, "rb") as fh:
+            sections = read_questions(read_lines(fh.read()), config.lowercase)
+    except OSError as e:
+        raise AnalogiesError(f"{config.questions}: {e.strerror or e}")
+    except ValueError as e:
+        raise AnalogiesError(f"{config.questions}: {e}")
+    index = load(config.index)
+    try:
+        if config.vectors is not None:
+            originals = vectors(config.vectors, index.metric == "cosine")
+            if config.exact:
+                index = index.exact(originals)
+            else:
+                index = index.refined(originals, config.candidates if config.candidates is not None
+                                      else 10 * config.ks[-1])
+        return evaluate_analogies(index, sections, config.ks)
+    except (LookupError, NotImplementedError, ValueError) as e:
+        raise AnalogiesError(str(e))
+
+
 def read_originals(path, normalize):
     """The -v vectors of the query commands: on the device, in word order (their key index resolves the index's words)."""
     from .word_vectors import read_word2vec_device
@@ -552,7 +635,7 @@ def _refined(args, index, vectors, load):
 
 
 def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None, vectors=None, inspect=None,
-         update=None, fine=None, rotation=None):
+         update=None, fine=None, rotation=None, analogies=None):
     """Returns the exit code.  stdin / stdout: binary streams (default: the process's); load: path -> index with
     batch_query_by_words / batch_query (default WordIndex.load); build: (BuildConfig, write) -> None, the whole of
     build-index behind its argument handling (default run_build_index); recall: (RecallConfig, write, load) ->
@@ -562,9 +645,17 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
     (default run_inspect); update: (UpdateConfig, write, load) -> the updated index with its four counters, the whole
     of update behind its argument handling (default run_update); fine: (FineConfig, write, load) -> None, the whole of
     build-fine behind its argument handling (default run_build_fine).  The fine index behind -f is read with `load`.  rotation: path -> the rotation behind -R of the
-    query commands (default Rotation.load)."""
+    query commands (default Rotation.load).  analogies: (AnalogiesConfig, load, vectors) -> AnalogyReport, the whole of
+    analogies between its argument handling and its lines (default run_analogies)."""
     parser = _parser()
     args = parser.parse_args(argv)
+    if args.command == "analogies":
+        if args.exact and args.vectors is None:
+            parser.error("--exact needs -v/--vectors")
+        if args.candidates is not None and args.vectors is None:
+            parser.error("--candidates is only applicable with --vectors")
+        if args.candidates is not None and args.exact:
+            parser.error("--candidates is not applicable with --exact")
     if args.command == "update" and args.add is None and args.remove is None:
         parser.error("at least one of --add and --remove is required")
     if args.command == "inspect" and args.worst is not None and args.vectors is None:
@@ -624,6 +715,17 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
     elif args.command == "inspect":
         config = InspectConfig(args.index, args.vectors, args.worst if args.worst is not None else 10, args.rotation)
         for line in (inspect if inspect is not None else run_inspect)(config, load, vectors).lines():
+            write(line + "\n")
+    elif args.command == "analogies":
+        config = AnalogiesConfig(args.index, args.file, args.depths, args.lowercase, args.vectors, args.exact,
+                                 args.candidates)
+        try:
+            report = (analogies if analogies is not None else run_analogies)(config, load, vectors)
+        except AnalogiesError as e:
+            stdout.flush()
+            print(f"error: {e}", file=sys.stderr)
+            return 1
+        for line in report.lines():
             write(line + "\n")
     elif args.command == "update":
         config = UpdateConfig(args.index, args.output, args.add, args.remove, args.rotation)

@@ -10,89 +10,10 @@
 //                         query's term rows, in their order, padded as gulon_index_batch_query pads.
 // Between the two runs the handle's own *_dev batch query, on the same stream: tie flags, the peeled order above 63
 // neighbours and the limits of the index form are inherited.
-#include "normalize.hpp"
+#include "compose.hpp"
 #include "row_decode.hpp"
 
 namespace gulon {
-namespace {
-
-constexpr int CR_THREADS = 256;
-
-// One workgroup per expression; thread t owns coordinates t, t + 256, ... (CPT of them: d <= 256 * CPT) and keeps their
-// running sums in registers.  A term is staged in LDS only where it is normalised: xs[d] the decoded row, ys[d] its
-// normalised form (normalize_staged_row reads all of xs in every thread, so it cannot write in place).  The composed
-// vector goes through xs for the final normalisation.  An expression without terms, or with a term row outside
-// [0, n), gives an all-NaN vector and sets *err (nothing is read for it).
-template <int CPT>
-__global__ __launch_bounds__(CR_THREADS) void compose_rows_kernel(
-    CodeSrc src, const float *__restrict__ cents, int n, int d, int k, const int *__restrict__ term_offsets,
-    const int *__restrict__ term_rows, const float *__restrict__ term_weights, const float *__restrict__ gcent,
-    const int *__restrict__ offsets, int n_offsets, int normalize_terms, int normalize_query, float *__restrict__ out,
-    int *__restrict__ err) {
-  extern __shared__ float xs[];   // [d], and [d] more when terms are normalised
-  float *ys = xs + d;
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int t0 = term_offsets[b], t1 = term_offsets[b + 1];
-  float *o = out + (size_t)b * d;
-  bool bad = t1 <= t0;
-  for (int t = t0; t < t1; t++) {
-    const int row = term_rows[t];
-    bad = bad || row < 0 || row >= n;
-  }
-  if (bad) {   // (uniform over the workgroup: no barrier is skipped by a part of it)
-    for (int e = tid; e < d; e += CR_THREADS) o[e] = __int_as_float(0x7FC00000);
-    if (tid == 0 && err) *err = 1;
-    return;
-  }
-  const SubvectorMap sv(d, src.m);
-  float acc[CPT];
-  for (int t = t0; t < t1; t++) {
-    const int row = term_rows[t];
-    const float w = term_weights[t];
-    const float *base = gcent ? lookup_base(gcent, offsets, n_offsets, row, d) : nullptr;
-    float v[CPT];
-#pragma unroll
-    for (int i = 0; i < CPT; i++) {
-      const int e = tid + i * CR_THREADS;
-      v[i] = e < d ? decoded_coordinate(src, sv, cents, k, row, e, base) : 0.f;
-    }
-    if (normalize_terms) {
-#pragma unroll
-      for (int i = 0; i < CPT; i++) {
-        const int e = tid + i * CR_THREADS;
-        if (e < d) xs[e] = v[i];
-      }
-      __syncthreads();
-      normalize_staged_row(xs, d, tid, CR_THREADS, ys);
-#pragma unroll
-      for (int i = 0; i < CPT; i++) {   // (its own writes: ys[tid], ys[tid + 256], ...)
-        const int e = tid + i * CR_THREADS;
-        if (e < d) v[i] = ys[e];
-      }
-      __syncthreads();   // every thread has summed xs before the next term overwrites it
-    }
-#pragma unroll
-    for (int i = 0; i < CPT; i++) {
-      const float p = __fmul_rn(w, v[i]);
-      acc[i] = t == t0 ? p : __fadd_rn(acc[i], p);
-    }
-  }
-  if (!normalize_query) {
-#pragma unroll
-    for (int i = 0; i < CPT; i++) {
-      const int e = tid + i * CR_THREADS;
-      if (e < d) o[e] = acc[i];
-    }
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < CPT; i++) {
-    const int e = tid + i * CR_THREADS;
-    if (e < d) xs[e] = acc[i];
-  }
-  __syncthreads();
-  normalize_staged_row(xs, d, tid, CR_THREADS, o);
-}
 
 // One wavefront per query.  in_*: [b][kin] lists with in_count[q] live entries (row ids carry the index's row_base, the
 // term rows do not).  The live entries are walked 64 at a time; an entry is kept unless its row is one of the query's
@@ -128,6 +49,52 @@ __global__ __launch_bounds__(64) void drop_rows_kernel(const int *__restrict__ i
   if (lane == 0 && out_count) out_count[q] = kept;
 }
 
+void launch_drop(const int *in_idx, const float *in_dist, const int *in_count, int b, int kin, int k_nn,
+                 const int *d_off, const int *d_rows, int row_base, int *out_idx, float *out_dist, int *out_count,
+                 hipStream_t st) {
+  if (b == 0) return;
+  hipLaunchKernelGGL(drop_rows_kernel, dim3(b), dim3(64), 0, st, in_idx, in_dist, in_count, kin, k_nn, d_off, d_rows,
+                     row_base, out_idx, out_dist, out_count);
+  HIP_CHECK(hipGetLastError());
+}
+
+int check_terms_host(const int32_t *off, const int32_t *rows, const float *w, int b, int n) {
+  GULON_REQUIRE(b >= 0, "batch size must be non-negative");
+  if (b == 0) return 0;
+  GULON_REQUIRE(off != nullptr && rows != nullptr && w != nullptr, "null argument");
+  GULON_REQUIRE(off[0] == 0, "term_offsets[0] = %d, expected 0", off[0]);
+  for (int q = 0; q < b; q++)
+    GULON_REQUIRE(off[q + 1] > off[q], "expression %d is empty (term offsets must ascend strictly)", q);
+  for (int t = 0; t < off[b]; t++)
+    GULON_REQUIRE(rows[t] >= 0 && rows[t] < n, "term %d: row %d outside [0, %d)", t, rows[t], n);
+  return off[b];
+}
+
+namespace {
+
+// One workgroup per expression (compose.hpp's compose_terms), a term row read as Index.lookup reads it.  An expression
+// without terms, or with a term row outside [0, n), gives an all-NaN vector and sets *err (nothing is read for it).
+template <int CPT>
+__global__ __launch_bounds__(CR_THREADS) void compose_rows_kernel(
+    CodeSrc src, const float *__restrict__ cents, int n, int d, int k, const int *__restrict__ term_offsets,
+    const int *__restrict__ term_rows, const float *__restrict__ term_weights, const float *__restrict__ gcent,
+    const int *__restrict__ offsets, int n_offsets, int normalize_terms, int normalize_query, float *__restrict__ out,
+    int *__restrict__ err) {
+  extern __shared__ float xs[];   // [d], and [d] more when terms are normalised
+  const int b = blockIdx.x;
+  const int t0 = term_offsets[b], t1 = term_offsets[b + 1];
+  float *o = out + (size_t)b * d;
+  if (terms_unusable(term_rows, t0, t1, n)) {   // (uniform over the workgroup: no barrier is skipped by a part of it)
+    write_nan_vector(o, d, threadIdx.x, err);
+    return;
+  }
+  const SubvectorMap sv(d, src.m);
+  compose_terms<CPT>(t0, t1, term_rows, term_weights, d, normalize_terms, normalize_query, xs, o, [&](int row) {
+    const float *base = gcent ? lookup_base(gcent, offsets, n_offsets, row, d) : nullptr;
+    return [&, row, base](int e) { return decoded_coordinate(src, sv, cents, k, row, e, base); };
+  });
+}
+
 void launch_compose(const gulon_index *ix, const int *d_off, const int *d_rows, const float *d_w, int b,
                     const float *gcent, const int *offsets, int n_offsets, bool norm_terms, bool norm_query,
                     float *d_out, int *d_err, hipStream_t st) {
@@ -135,7 +102,7 @@ void launch_compose(const gulon_index *ix, const int *d_off, const int *d_rows, 
   GULON_UNSUPPORTED((size_t)ix->d * sizeof(float) > 64 * 1024, "d = %d: a decoded row does not fit in LDS", ix->d);
   if (b == 0) return;
   GULON_REQUIRE(d_off != nullptr && d_rows != nullptr && d_w != nullptr && d_out != nullptr, "null argument");
-  const size_t lds = (size_t)ix->d * sizeof(float) * (norm_terms ? 2 : norm_query ? 1 : 0);
+  const size_t lds = compose_lds_bytes(ix->d, norm_terms, norm_query);
 #define CR(CPT) hipLaunchKernelGGL(compose_rows_kernel<CPT>, dim3(b), dim3(CR_THREADS), lds, st, code_src(ix), \
                                    ix->cents.p, ix->n, ix->d, ix->k, d_off, d_rows, d_w, gcent, offsets, n_offsets, \
                                    norm_terms ? 1 : 0, norm_query ? 1 : 0, d_out, d_err)
@@ -150,28 +117,6 @@ void launch_compose(const gulon_index *ix, const int *d_off, const int *d_rows, 
   }
 #undef CR
   HIP_CHECK(hipGetLastError());
-}
-
-void launch_drop(const int *in_idx, const float *in_dist, const int *in_count, int b, int kin, int k_nn,
-                 const int *d_off, const int *d_rows, int row_base, int *out_idx, float *out_dist, int *out_count,
-                 hipStream_t st) {
-  if (b == 0) return;
-  hipLaunchKernelGGL(drop_rows_kernel, dim3(b), dim3(64), 0, st, in_idx, in_dist, in_count, kin, k_nn, d_off, d_rows,
-                     row_base, out_idx, out_dist, out_count);
-  HIP_CHECK(hipGetLastError());
-}
-
-// The host-pointer forms check everything before anything is launched; returns the number of terms.
-int check_terms_host(const int32_t *off, const int32_t *rows, const float *w, int b, int n) {
-  GULON_REQUIRE(b >= 0, "batch size must be non-negative");
-  if (b == 0) return 0;
-  GULON_REQUIRE(off != nullptr && rows != nullptr && w != nullptr, "null argument");
-  GULON_REQUIRE(off[0] == 0, "term_offsets[0] = %d, expected 0", off[0]);
-  for (int q = 0; q < b; q++)
-    GULON_REQUIRE(off[q + 1] > off[q], "expression %d is empty (term offsets must ascend strictly)", q);
-  for (int t = 0; t < off[b]; t++)
-    GULON_REQUIRE(rows[t] >= 0 && rows[t] < n, "term %d: row %d outside [0, %d)", t, rows[t], n);
-  return off[b];
 }
 
 void upload_terms(ExprWork &x, const int32_t *off, const int32_t *rows, const float *w, int b, int terms,

@@ -13,6 +13,10 @@
 // order of its queue.  A query whose queue overflowed is answered by the peeled path (knn_kernel + launch_merge +
 // launch_peel_*, called, not copied) in a compacted sub-batch; a query that met a NaN / +inf distance by the same path in
 // a batch of one, which is what gulon_exact_knn gives it when asked alone.
+//
+// Expression queries: dataset_compose.hip composes the term rows of the dataset, the handle answers the
+// composed vectors at k_nn + extra by the path above, compose.hip's drop_rows_kernel removes the term rows.
+#include "compose.hpp"
 #include "exact.hpp"
 #include "select.hpp"
 
@@ -301,6 +305,7 @@ struct gulon_exact_index {
   // the host-pointer forms
   DevBuf<float> stage_q, stage_od;
   DevBuf<int> stage_rows, stage_oi, stage_oc, stage_of;
+  ExprWork expr;                       // the expression queries' term lists, composed vectors and answers at k_nn + extra
   std::vector<int> h_cnt, h_ovf, h_nf, h_ids;
   hipEvent_t order_ev = nullptr;
   hipStream_t order_st = nullptr;
@@ -317,6 +322,17 @@ bool set_knob(gulon_exact_index *h, const char *key, int v) {
   if (!strcmp(key, "GULON_EXACT_SAMPLE")) { h->knob_sample = v < 0 ? 0 : v; return true; }
   if (!strcmp(key, "GULON_EXACT_QUEUE_CAP")) { h->knob_cap = v < 16 ? 16 : v > (1 << 22) ? (1 << 22) : v; return true; }
   return false;
+}
+
+// Batches on different streams are ordered on the device: a batch waits for the event the last one recorded.
+void order_wait(gulon_exact_index *h, hipStream_t st) {
+  if (h->order_set && h->order_st != st) HIP_CHECK(hipStreamWaitEvent(st, h->order_ev, 0));
+}
+void order_record(gulon_exact_index *h, hipStream_t st) {
+  if (!h->order_ev) HIP_CHECK(hipEventCreateWithFlags(&h->order_ev, hipEventDisableTiming));
+  HIP_CHECK(hipEventRecord(h->order_ev, st));
+  h->order_st = st;
+  h->order_set = true;
 }
 
 // gulon_exact_knn's device work for b queries at d_q, on `st`, with its launch geometry: k_nn <= GULON_MAX_K in one
@@ -505,8 +521,7 @@ void exact_query_dev(gulon_exact_index *h, const float *dQ, int B, int K, int *o
   for (auto &s : h->stats) s = 0;
   h->stats[4] = h->knob_cap;
   if (B == 0) return;
-  if (!h->order_ev) HIP_CHECK(hipEventCreateWithFlags(&h->order_ev, hipEventDisableTiming));
-  if (h->order_set && h->order_st != st) HIP_CHECK(hipStreamWaitEvent(st, h->order_ev, 0));
+  order_wait(h, st);
   if (!oc) { h->count_tmp.ensure(B); oc = h->count_tmp.p; }
   if (!of) { h->flags_tmp.ensure(B); of = h->flags_tmp.p; }
   const long long bk = (long long)B * K;
@@ -520,9 +535,28 @@ void exact_query_dev(gulon_exact_index *h, const float *dQ, int B, int K, int *o
   } else {
     large_k_dev(h, dQ, B, K, oi, od, oc, of, st);
   }
-  HIP_CHECK(hipEventRecord(h->order_ev, st));
-  h->order_st = st;
-  h->order_set = true;
+  order_record(h, st);
+}
+
+// Expression queries: compose over the dataset's rows -> the handle's own answer at k_nn + extra -> the
+// term rows dropped, all on `st`.  The ids the handle returns are dataset rows, as the term rows are: row_base 0.
+void exact_terms_dev(gulon_exact_index *h, const int *d_off, const int *d_rows, const float *d_w, int b, int k_nn,
+                     int extra, bool nt, bool nq, int *oi, float *od, int *oc, int *of, hipStream_t st) {
+  GULON_REQUIRE(b >= 0 && k_nn >= 0 && extra >= 0, "k, extra and batch size must be non-negative");
+  GULON_UNSUPPORTED((long long)k_nn + extra > GULON_MAX_K_PEELED, "k_nn + extra = %lld > %d", (long long)k_nn + extra,
+                    GULON_MAX_K_PEELED);
+  if (b == 0) { for (auto &s : h->stats) s = 0; return; }
+  ExprWork &x = h->expr;
+  const int kin = k_nn + extra;
+  x.q.ensure((size_t)b * h->ds->d);
+  x.oi.ensure((size_t)b * kin + 1);
+  x.od.ensure((size_t)b * kin + 1);
+  x.oc.ensure((size_t)b);
+  order_wait(h, st);   // the workspace may still be read by the last batch, on another stream
+  launch_dataset_compose(h->ds, d_off, d_rows, d_w, b, nt, nq, x.q.p, nullptr, st);
+  exact_query_dev(h, x.q.p, b, kin, x.oi.p, x.od.p, x.oc.p, of, st);
+  launch_drop(x.oi.p, x.od.p, x.oc.p, b, kin, k_nn, d_off, d_rows, 0, oi, od, oc, st);
+  order_record(h, st);
 }
 
 void exact_query_host(gulon_exact_index *h, const float *dQ, int b, int K, int32_t *out_idx, float *out_dist,
@@ -617,6 +651,47 @@ GULON_API int32_t gulon_exact_index_query_rows(gulon_exact_index *idx, const int
     idx->stage_rows.upload(rows, b);
     gather_rows(idx, idx->stage_rows.p, b, nullptr);
     exact_query_host(idx, idx->stage_q.p, b, k_nn, out_idx, out_dist, out_count, out_flags);
+  });
+}
+
+GULON_API int32_t gulon_exact_index_query_terms_dev(gulon_exact_index *idx, const int32_t *d_term_offsets,
+                                                    const int32_t *d_term_rows, const float *d_term_weights, int32_t b,
+                                                    int32_t k_nn, int32_t extra, int32_t normalize_terms,
+                                                    int32_t normalize_query, int32_t *d_out_idx, float *d_out_dist,
+                                                    int32_t *d_out_count, int32_t *d_out_flags, void *stream) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr, "index is null");
+    std::lock_guard<std::mutex> g(idx->mu);
+    exact_terms_dev(idx, d_term_offsets, d_term_rows, d_term_weights, b, k_nn, extra, normalize_terms != 0,
+                    normalize_query != 0, d_out_idx, d_out_dist, d_out_count, d_out_flags, (hipStream_t)stream);
+  });
+}
+
+GULON_API int32_t gulon_exact_index_query_terms(gulon_exact_index *idx, const int32_t *term_offsets,
+                                                const int32_t *term_rows, const float *term_weights, int32_t b,
+                                                int32_t k_nn, int32_t extra, int32_t normalize_terms,
+                                                int32_t normalize_query, int32_t *out_idx, float *out_dist,
+                                                int32_t *out_count, int32_t *out_flags) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr, "index is null");
+    GULON_REQUIRE(b >= 0 && k_nn >= 0 && extra >= 0, "k, extra and batch size must be non-negative");
+    const int terms = check_terms_host(term_offsets, term_rows, term_weights, b, idx->ds->n);
+    std::lock_guard<std::mutex> g(idx->mu);
+    ExprWork &x = idx->expr;
+    const hipStream_t st = nullptr;
+    const size_t bk = (size_t)b * (size_t)k_nn;
+    if (b > 0) {
+      x.off.upload(term_offsets, (size_t)b + 1, st);
+      x.rows.upload(term_rows, (size_t)terms, st);
+      x.w.upload(term_weights, (size_t)terms, st);
+    }
+    x.fi.ensure(bk + 1); x.fd.ensure(bk + 1); x.fc.ensure((size_t)b + 1); x.ff.ensure((size_t)b + 1);
+    exact_terms_dev(idx, x.off.p, x.rows.p, x.w.p, b, k_nn, extra, normalize_terms != 0, normalize_query != 0, x.fi.p,
+                    x.fd.p, x.fc.p, x.ff.p, st);
+    if (bk) { x.fi.download(out_idx, bk, st); x.fd.download(out_dist, bk, st); }
+    if (b > 0 && out_count) x.fc.download(out_count, (size_t)b, st);
+    if (b > 0 && out_flags) x.ff.download(out_flags, (size_t)b, st);
+    HIP_CHECK(hipStreamSynchronize(st));
   });
 }
 

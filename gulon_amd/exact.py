@@ -98,6 +98,44 @@ class ExactIndex:
         """The rows themselves: [len(rows)][dimension]."""
         return self.matrix.get_rows(rows)
 
+    # ---- expression queries (expressions.py; DESIGN.md 9u): the terms are rows of the MATRIX
+    def compose_rows(self, expressions):
+        """The query vector of every expression over row ids as this index prepares it -- terms and sum normalised for a
+        cosine index -- composed on the device from the original rows (gulon_dataset_compose_rows).  -> [b][d] float32."""
+        from .expressions import to_csr
+        off, rows, w = to_csr(expressions)
+        b = len(off) - 1
+        cosine = int(self.metric == "cosine")
+        out = np.zeros((b, self.dimension), np.float32)
+        one_i, one_f = np.zeros(1, np.int32), np.zeros(1, np.float32)
+        N.check(N.lib().gulon_dataset_compose_rows(self.matrix._h, off, rows if b else one_i, w if b else one_f, b,
+                                                   cosine, cosine, out.reshape(-1) if out.size else one_f))
+        return out
+
+    def batch_query_terms_raw(self, k, expressions, extra):
+        """gulon_exact_index_query_terms as it is: the answer at k + extra with every expression's term rows removed,
+        the first k kept.  -> (rows [b][k], distances [b][k], counts [b], flags [b])."""
+        from .expressions import to_csr
+        off, rows, w = to_csr(expressions)
+        b = len(off) - 1
+        cosine = int(self.metric == "cosine")
+        oi, od, oc, of = self._outputs(b, k)
+        one_i, one_f = np.zeros(1, np.int32), np.zeros(1, np.float32)
+        N.check(N.lib().gulon_exact_index_query_terms(self._h, off, rows if b else one_i, w if b else one_f, b, k, extra,
+                                                      cosine, cosine, oi.reshape(-1), od.reshape(-1), oc, of))
+        return oi[:, :k], od[:, :k], oc[:b], of[:b]
+
+    def batch_query_expressions_raw(self, k, expressions):
+        """batch_query_terms_raw per partition of the batch by its number E of distinct term rows, extra = E, in input
+        order: (rows [b][k] with -1 after a query's last entry, distances [b][k] with +inf there, counts [b], flags [b])."""
+        from .expressions import query_partitioned
+        return query_partitioned(expressions, lambda part, extra: self.batch_query_terms_raw(k, part, extra),
+                                 (((k,), np.int32, -1), ((k,), np.float32, np.inf), ((), np.int32, 0), ((), np.int32, 0)))
+
+    def batch_query_expressions(self, k, expressions) -> List[Result]:
+        """Per expression over row ids the k nearest rows of its composed vector that are none of its operands."""
+        return self._results(*self.batch_query_expressions_raw(k, expressions))
+
     def stats(self):
         """Of the last batch: queries answered in one pass, by the peeled fallback and one at a time as non-finite; the
         sample rows S (0: no sample pass), the queue capacity, the largest number of rows at or below a bound."""
@@ -182,6 +220,27 @@ class ExactWordIndex:
 
     def query_by_word(self, k, word) -> Optional[WordResult]:
         return self.batch_query_by_words(k, [word])[0]
+
+    def resolve_expressions(self, expressions):
+        """As WordIndex.resolve_expressions: expressions over words -> the same over row ids, None where a word is
+        absent."""
+        from .expressions import resolve_expressions
+        return resolve_expressions(self.row_of, expressions)
+
+    def batch_query_expressions(self, k, expressions) -> List[Optional[WordResult]]:
+        """As WordIndex.batch_query_expressions, over the ORIGINAL vectors of the words: per expression the k nearest
+        words of its composed vector that are none of its operands; None where a word is absent."""
+        resolved = self.resolve_expressions(expressions)
+        present = [i for i, e in enumerate(resolved) if e is not None]
+        out: List[Optional[WordResult]] = [None] * len(resolved)
+        for s in range(0, len(present), BATCH):
+            part = present[s:s + BATCH]
+            for i, r in zip(part, self.index.batch_query_expressions(k, [resolved[i] for i in part])):
+                out[i] = self._result(r)
+        return out
+
+    def query_expression(self, k, expression) -> Optional[WordResult]:
+        return self.batch_query_expressions(k, [expression])[0]
 
     def close(self):
         """Frees the handle and the gathered matrix this index was built over, when it owns one."""

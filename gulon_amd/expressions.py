@@ -70,6 +70,18 @@ def parse_expression(line: str) -> Expression:
     return Expression(tuple(terms))
 
 
+def resolve_expressions(row_of, expressions):
+    """Expressions over words (Expression objects, sequences of Term / (word, weight), or text for parse_expression)
+    -> the same over row ids by `row_of` (word -> row or None); None where a word is absent."""
+    out = []
+    for e in expressions:
+        e = parse_expression(e) if isinstance(e, str) else as_expression(e)
+        rows = [row_of(t.key) for t in e]
+        out.append(None if any(r is None for r in rows) else
+                   Expression(tuple(Term(r, t.weight) for r, t in zip(rows, e))))
+    return out
+
+
 def compose_reference(vectors, weights, normalize_terms=False, normalize_query=False) -> np.ndarray:
     """The composed vector of one expression: vectors [T][d] = Index.lookup of its term rows, weights [T]."""
     from .index import normalize

@@ -195,6 +195,14 @@ SIGNATURES = {
     "gulon_exact_index_query_rows_dev": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gulon_exact_index_tuning": (_i32, [_vp, C.c_char_p, _i32]),
     "gulon_exact_index_stats": (_i32, [_vp, _i64p]),
+    "gulon_dataset_compose_rows": (_i32, [_vp, _i32p, _i32p, _f32p, _i32, _i32, _i32, _f32p]),
+    "gulon_dataset_compose_rows_dev": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "gulon_exact_index_query_terms": (_i32, [_vp, _i32p, _i32p, _f32p, _i32, _i32, _i32, _i32, _i32, _i32p, _f32p, _i32p,
+                                             _i32p]),
+    "gulon_exact_index_query_terms_dev": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
+                                                 _vp]),
+    "gulon_analogy_counts": (_i32, [_i32p, _i32p, _i32, _i32, _i32p, _i32p, _i32p, _i32, _i32, _i32p, _i32p, _vp]),
+    "gulon_analogy_counts_dev": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -151,14 +151,8 @@ class WordIndex:
     def resolve_expressions(self, expressions):
         """Expressions over words (Expression objects, sequences of Term / (word, weight), or text for
         parse_expression) -> the same over row ids, None where a word is absent."""
-        from .expressions import Expression, Term, as_expression, parse_expression
-        out = []
-        for e in expressions:
-            e = parse_expression(e) if isinstance(e, str) else as_expression(e)
-            rows = [self.row_of(t.key) for t in e]
-            out.append(None if any(r is None for r in rows) else
-                       Expression(tuple(Term(r, t.weight) for r, t in zip(rows, e))))
-        return out
+        from .expressions import resolve_expressions
+        return resolve_expressions(self.row_of, expressions)
 
     def batch_query_expressions(self, k, expressions) -> List[Optional[WordResult]]:
         """Per expression over words (`king - man + woman`) the k nearest words of its composed vector that are none of

@@ -782,6 +782,61 @@ int32_t gulon_exact_index_query_rows_dev(gulon_exact_index *idx, const int32_t *
 int32_t gulon_exact_index_tuning(gulon_exact_index *idx, const char *key, int32_t value);
 int32_t gulon_exact_index_stats(gulon_exact_index *idx, int64_t *out);
 
+/* ---- Expressions over the true vectors (dataset_compose.hip, exact.hip) ---------------------------------
+ * gulon_dataset_compose_rows: the composed vectors of b expressions, out [b][d] -- the CSR input and the arithmetic of
+ * gulon_index_compose_rows (above) with v_t = row row_t of the DATASET in the place of Index.lookup: optionally
+ * MathUtils.normalize per term; per coordinate acc = w_0 * v_0[e], acc = acc + (w_t * v_t[e]) in list order, every product
+ * and every sum its own binary32 operation; optionally MathUtils.normalize of the sum.  d * 4 <= 64 KiB.  The host form
+ * checks b, the offsets and every row before anything is launched (GULON_ERR_INVALID_ARGUMENT names the first bad row).
+ * The _dev form takes device pointers and a stream, does not synchronise and cannot check: an expression without terms,
+ * or with a row outside [0, n), comes back as an all-NaN vector and sets *d_err = 1 (d_err may be NULL; the caller zeroes
+ * it). */
+int32_t gulon_dataset_compose_rows(const gulon_dataset *ds, const int32_t *term_offsets, const int32_t *term_rows,
+                                   const float *term_weights, int32_t b, int32_t normalize_terms,
+                                   int32_t normalize_query, float *out);
+int32_t gulon_dataset_compose_rows_dev(const gulon_dataset *ds, const int32_t *d_term_offsets,
+                                       const int32_t *d_term_rows, const float *d_term_weights, int32_t b,
+                                       int32_t normalize_terms, int32_t normalize_query, float *d_out, int32_t *d_err,
+                                       void *stream);
+/* gulon_exact_index_query_terms: gulon_index_query_terms on the exact index.  Term rows are rows of the DATASET, as in
+ * gulon_exact_index_query_rows and as the ids the index returns (from + slot).  Per expression (extra >= 0):
+ *   1. the handle's own answer to the composed vector (gulon_dataset_compose_rows) at depth k_nn + extra: what
+ *      gulon_exact_index_batch_query_dev returns for it -- flags, the one-pass path above GULON_MAX_K, its fallbacks and
+ *      the non-finite rule included; k_nn + extra > GULON_MAX_K_PEELED is GULON_ERR_UNSUPPORTED;
+ *   2. every entry whose row is one of the expression's term rows is removed (a term row outside [from, until) removes
+ *      nothing), the others keep their order;
+ *   3. the first k_nn are kept, -1 / +inf after the last; out_count per query; out_flags those of step 1 (both nullable).
+ * Everything runs on one stream; the call waits for it once per batch, as gulon_exact_index_batch_query_dev does.  The
+ * host form checks the term lists first; in the _dev form a bad expression is a NaN query.  gulon_exact_index_stats then
+ * tells of step 1. */
+int32_t gulon_exact_index_query_terms(gulon_exact_index *idx, const int32_t *term_offsets, const int32_t *term_rows,
+                                      const float *term_weights, int32_t b, int32_t k_nn, int32_t extra,
+                                      int32_t normalize_terms, int32_t normalize_query, int32_t *out_idx,
+                                      float *out_dist, int32_t *out_count, int32_t *out_flags);
+int32_t gulon_exact_index_query_terms_dev(gulon_exact_index *idx, const int32_t *d_term_offsets,
+                                          const int32_t *d_term_rows, const float *d_term_weights, int32_t b,
+                                          int32_t k_nn, int32_t extra, int32_t normalize_terms, int32_t normalize_query,
+                                          int32_t *d_out_idx, float *d_out_dist, int32_t *d_out_count,
+                                          int32_t *d_out_flags, void *stream);
+
+/* ---- Analogy accuracy (analogy.hip) --------------------------------------------------------------------
+ * Scores b answer lists against one expected row each.  idx_lists [b][kin] with counts[q] live entries (what a
+ * *_query_terms call returns); expected[q] >= 0; section[q] in [0, nsections).
+ *   rank(q) = the position of expected[q] among the first counts[q] entries of idx_lists[q], or -1;
+ *   hits[section[q]][j] += 1 for every j < nks with 0 <= rank(q) < ks[j];   asked[section[q]] += 1.
+ * hits [nsections][nks] and asked [nsections] are int32 and ACCUMULATE over calls: the caller zeroes them.  ks ascends
+ * within [1, kin], nks <= 16, as for gulon_recall_counts.  out_rank [b]: NULL, or the ranks.  Integer atomics only: the
+ * counters are the same whatever the order of the questions.  The host form checks ks, section and expected
+ * (GULON_ERR_INVALID_ARGUMENT) and copies the counters up and down; the _dev form takes device pointers (ks too) and a
+ * stream, does not synchronise, and counts a question with a section outside [0, nsections) nowhere. */
+int32_t gulon_analogy_counts(const int32_t *idx_lists, const int32_t *counts, int32_t b, int32_t kin,
+                             const int32_t *expected, const int32_t *section, const int32_t *ks, int32_t nks,
+                             int32_t nsections, int32_t *hits, int32_t *asked, int32_t *out_rank);
+int32_t gulon_analogy_counts_dev(const int32_t *d_idx_lists, const int32_t *d_counts, int32_t b, int32_t kin,
+                                 const int32_t *d_expected, const int32_t *d_section, const int32_t *d_ks, int32_t nks,
+                                 int32_t nsections, int32_t *d_hits, int32_t *d_asked, int32_t *d_out_rank,
+                                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif
