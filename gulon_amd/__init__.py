@@ -19,7 +19,8 @@ from .exact import ExactIndex, ExactWordIndex
 from .fine import FineRefinedIndex, build_fine_index, refine_codes_topk, row_residuals
 from .inspect import IndexReport, reference_quality
 from .update import UpdatePlan, plan_update
-from .expressions import Expression, Term, compose_reference, parse_expression, partition_by_operands
+from .expressions import (COSMUL_EPS, Expression, Term, compose_reference, cosmul_reference, parse_expression,
+                          partition_by_operands)
 from .rotation import RotatedWordIndex, Rotation, rotate_reference, train_rotation
 from .analogies import AnalogyReport, evaluate_analogies, read_questions
 
@@ -31,4 +32,5 @@ __all__ = ["native", "GroupedIndex", "GroupedVectors", "LimitGroups", "LimitVect
            "build_index", "RefinedIndex", "refine_topk", "Expression", "Term", "compose_reference", "parse_expression",
            "partition_by_operands", "IndexReport", "reference_quality", "UpdatePlan", "plan_update", "FineRefinedIndex", "build_fine_index",
            "refine_codes_topk", "row_residuals", "Rotation", "RotatedWordIndex", "train_rotation", "rotate_reference",
-           "ExactIndex", "ExactWordIndex", "AnalogyReport", "evaluate_analogies", "read_questions"]
+           "ExactIndex", "ExactWordIndex", "AnalogyReport", "evaluate_analogies", "read_questions",
+           "COSMUL_EPS", "cosmul_reference"]

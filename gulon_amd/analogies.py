@@ -11,7 +11,12 @@ Two routes give the same report:
            *_query_terms_dev and gulon_analogy_counts_dev on one stream; the answer lists never reach the host, the two
            counter arrays are read once, at the end;
   generic  any other target with `row_of` and `batch_query_expressions` (a RefinedIndex, ...): its result lists are
-           scored by the host form gulon_analogy_counts."""
+           scored by the host form gulon_analogy_counts.
+
+method "mul" asks the same questions by the multiplicative objective 3CosMul (csrc/cosmul.hip): the rows
+are ranked by cos'(d, b) * cos'(d, c) / (cos'(d, a) + eps) instead of by their distance to b - a + c.  Its device route
+(a flat WordIndex, an ExactWordIndex) is *_query_cosmul_dev in the place of *_query_terms_dev; its generic route asks
+the target's `batch_query_cosmul`."""
 from dataclasses import dataclass, field
 from typing import Dict, List, Tuple
 
@@ -143,8 +148,26 @@ def _device_query(target):
         pq._h, off, rows, w, b, k, extra, cosine, cosine, 0, pq.length, oi, od, oc, of, None))
 
 
-def _count_on_device(query, asked, ks, nsections):
-    """The device route: -> (hits [nsections][len(ks)], asked [nsections])."""
+def _device_cosmul(target):
+    """_device_query for method "mul": the *_query_cosmul_dev call of a flat WordIndex or an ExactWordIndex, with the
+    arguments of _device_query's (extra and d_of are not used: the answer has no depth to choose and no tie flags)."""
+    from .exact import ExactWordIndex
+    from .word_index import WordIndex
+    L = N.lib()
+    if isinstance(target, ExactWordIndex):
+        h = target.index._h
+        return lambda off, rows, w, b, k, extra, oi, od, oc, of: N.check(L.gulon_exact_index_query_cosmul_dev(
+            h, off, rows, w, b, k, 1, oi, od, oc, None, None))
+    if type(target) is not WordIndex or target._grouped:
+        return None
+    pq = target.index.vector_index
+    return lambda off, rows, w, b, k, extra, oi, od, oc, of: N.check(L.gulon_index_query_cosmul_dev(
+        pq._h, off, rows, w, b, k, 1, 0, pq.length, oi, od, oc, None))
+
+
+def _count_on_device(query, asked, ks, nsections, by_operands=True):
+    """The device route: -> (hits [nsections][len(ks)], asked [nsections]).  by_operands: the questions are asked in
+    parts by their number of distinct operands, which is the `extra` of each part."""
     from .refine import _DeviceArray
     kmax, nks = ks[-1], len(ks)
     hits, count = np.zeros((nsections, nks), np.int32), np.zeros(nsections, np.int32)
@@ -156,7 +179,7 @@ def _count_on_device(query, asked, ks, nsections):
         dev["asked"].upload(count)
         parts: Dict[int, list] = {}
         for item in asked:                                  # by the number of distinct operands: extra = that number
-            parts.setdefault(len(set(item[1])), []).append(item)
+            parts.setdefault(len(set(item[1])) if by_operands else 0, []).append(item)
         for extra in sorted(parts):
             part = parts[extra]
             for s in range(0, len(part), BATCH):
@@ -199,15 +222,17 @@ def count_lists(lists, counts, expected, section, ks, nsections, hits=None, aske
     return (hits, asked, rank[:b]) if ranks else (hits, asked)
 
 
-def _count_generic(target, sections, ks, nsections):
-    """The generic route: the target's own batch_query_expressions over words, its lists scored by the host form."""
+def _count_generic(target, sections, ks, nsections, method="add"):
+    """The generic route: the target's own batch_query_expressions (method "mul": batch_query_cosmul) over words, its
+    lists scored by the host form."""
     kmax = ks[-1]
     hits, count = np.zeros((nsections, len(ks)), np.int32), np.zeros(nsections, np.int32)
     items = [(s, q) for s, (_, questions) in enumerate(sections) for q in questions
              if all(target.row_of(w) is not None for w in q)]
     for s0 in range(0, len(items), BATCH):
         batch = items[s0:s0 + BATCH]
-        results = target.batch_query_expressions(kmax, [question_expression(a, b, c) for _, (a, b, c, _) in batch])
+        ask = target.batch_query_cosmul if method == "mul" else target.batch_query_expressions
+        results = ask(kmax, [question_expression(a, b, c) for _, (a, b, c, _) in batch])
         lists, counts = np.full((len(batch), kmax), -1, np.int32), np.zeros(len(batch), np.int32)
         for i, r in enumerate(results):
             counts[i] = len(r.rows)
@@ -217,22 +242,31 @@ def _count_generic(target, sections, ks, nsections):
     return hits, count
 
 
-def evaluate_analogies(target, sections, ks=(1, 5, 10), route=None) -> AnalogyReport:
+def evaluate_analogies(target, sections, ks=(1, 5, 10), route=None, method="add") -> AnalogyReport:
     """The accuracy of `target` on `sections` (read_questions) at every k of `ks` (ascending, at most 16).  route: None
     takes the device route where the target has one; "generic" forces the other, which every target with `row_of` and
-    `batch_query_expressions` has.  The report does not depend on the route."""
+    `batch_query_expressions` has.  The report does not depend on the route.  method: "add", the neighbours of
+    b - a + c (3CosAdd), or "mul", the multiplicative objective 3CosMul: a cosine target (ValueError otherwise) with
+    `batch_query_cosmul` (NotImplementedError otherwise)."""
     ks = _check_ks(ks)
     if route not in (None, "generic"):
         raise ValueError(f"unknown route {route!r}")
+    if method not in ("add", "mul"):
+        raise ValueError(f"unknown method {method!r}")
+    if method == "mul":
+        if not hasattr(target, "batch_query_cosmul"):
+            raise NotImplementedError(f"{type(target).__name__} has no cosmul queries: --method mul is not supported")
+        if getattr(target, "metric", "cosine") != "cosine":
+            raise ValueError("requirement failed: cosmul queries need a cosine index")
     sections = [(name, list(questions)) for name, questions in sections]
     nsections = len(sections)
     skipped, asked = _resolve(target, sections)
-    query = _device_query(target) if route is None else None
+    query = None if route is not None else _device_cosmul(target) if method == "mul" else _device_query(target)
     if not asked:
         hits, count = np.zeros((nsections, len(ks)), np.int32), np.zeros(nsections, np.int32)
     elif query is not None:
-        hits, count = _count_on_device(query, asked, ks, nsections)
+        hits, count = _count_on_device(query, asked, ks, nsections, by_operands=method == "add")
     else:
-        hits, count = _count_generic(target, sections, ks, nsections)
+        hits, count = _count_generic(target, sections, ks, nsections, method)
     return AnalogyReport(ks, [SectionScore(name, int(count[s]), skipped[s], {k: int(hits[s, j]) for j, k in enumerate(ks)})
                               for s, (name, _) in enumerate(sections)])

@@ -7,7 +7,7 @@
                                        parsed on the device (word_vectors.read_word2vec_device) and every later stage
                                        runs there too (build.build_index)
 
-  query-words -i INDEX [-k N] [-x] [-v VECTORS [--exact] | -f FINE] [-c N] [FILE]
+  query-words -i INDEX [-k N] [-x [--method add|mul]] [-v VECTORS [--exact] | -f FINE] [-c N] [FILE]
                                        command/QueryWords.scala: one word per line of FILE (or stdin), printed as
                                        `word: w1,w2,...` or `word: not found`, in input order
   query -i INDEX [-k N] [-v VECTORS [--exact] | -f FINE] [-c N] FILE
@@ -41,7 +41,7 @@
                                        file VECTORS it was built from (read normalised for a cosine index), written as an
                                        ordinary sorted l2 index file.  -k / -m / -n as for build-index
 
-  analogies -i INDEX [-k 1,5,10] [--lowercase] [-v VECTORS [--exact | -c N]] FILE
+  analogies -i INDEX [-k 1,5,10] [--lowercase] [--method add|mul] [-v VECTORS [--exact | -c N]] FILE
                                        (not in the reference) the analogy accuracy of an index file (analogies.py,
                                        csrc/analogy.hip) on FILE, questions in the questions-words.txt format: `: name`
                                        opens a section, every other line is `a b c d`.  A question is right at k when d
@@ -54,7 +54,10 @@
                                        scored on the device.  -f, -r and -R are not offered: a rotated index needs no
                                        rotation file when it is evaluated alone or with --exact (the stored rows are
                                        composed where they live, and --exact reads the index for its words only);
-                                       -v -c on a rotated index is outside this command
+                                       -v -c on a rotated index is outside this command.  --method mul ranks the
+                                       rows by 3CosMul instead (csrc/cosmul.hip): s(d, b) * s(d, c) / (s(d, a) + 0.001)
+                                       with s = (1 + cos) / 2, for a flat cosine index alone or with -v --exact.
+                                       query-words -x --method mul answers expressions the same way
 
 -f FINE on the query commands and on test (not in the reference): as -v / -c, but the candidates are re-ranked by their
 distance to the index's row plus the fine index's row of the same word (fine.FineRefinedIndex) -- no original vectors in
@@ -207,6 +210,7 @@ class AnalogiesConfig:
     vectors: Optional[str] = None         # -v: refine against (or, exact, ask) the vectors the index was built from
     exact: bool = False                   # --exact: the true vectors of the index's words are the target
     candidates: Optional[int] = None      # -c: candidates of the refined form (default 10 * the largest k)
+    method: str = "add"                   # --method: add (3CosAdd, the neighbours of b - a + c) or mul (3CosMul)
 
 
 def _depths(s):
@@ -323,6 +327,10 @@ def _parser():
                            help="read every line as an expression `word (+|- word)*` (operators as stand-alone tokens): "
                                 "query with the sum of the words' vectors and leave the words themselves out of the "
                                 "answer")
+            s.add_argument("--method", choices=("add", "mul"), default="add",
+                           help="with -x: add ranks by the distance to the sum of the words' vectors (3CosAdd), mul by "
+                                "the multiplicative objective 3CosMul, the similarities to the + words over those to "
+                                "the - words (a cosine index; not with -v, -f, -r or -R)")
         s.add_argument("file", nargs=None if need_file else "?", metavar="file")
     t = sub.add_parser("test", help="calculate recall of index", description="calculate recall of index")
     t.add_argument("-v", "--vectors", required=True, metavar="file", help="word2vec word vectors")
@@ -363,6 +371,10 @@ def _parser():
                    help="candidates taken from the index per question before re-ranking (needs --vectors, not with "
                         "--exact; default 10 * the largest depth).  Not for a rotated index: this command takes no "
                         "rotation file")
+    a.add_argument("--method", choices=("add", "mul"), default="add",
+                   help="add asks for the neighbours of b - a + c (3CosAdd); mul ranks by the multiplicative objective "
+                        "3CosMul, cos(d, b) * cos(d, c) / (cos(d, a) + 0.001) with the cosines shifted into [0, 1] (a "
+                        "cosine index; with --vectors only together with --exact)")
     a.add_argument("file", metavar="file", help="questions: `: section` lines and lines of `a b c d`")
     u = sub.add_parser("update", help="add, replace and remove words of an index without retraining",
                        description="add, replace and remove words of an index without retraining")
@@ -387,8 +399,9 @@ def query_words(index, k, lines, write):
             write(_line(word, result) + "\n")
 
 
-def query_expressions(index, k, lines, write):
-    """query-words -x: every line an expression; invalid lines are answered without reaching the index."""
+def query_expressions(index, k, lines, write, method="add"):
+    """query-words -x: every line an expression; invalid lines are answered without reaching the index.  method "mul":
+    the index's batch_query_cosmul answers in the place of batch_query_expressions."""
     from .expressions import parse_expression
     for s in range(0, len(lines), CHUNK):
         part = lines[s:s + CHUNK]
@@ -398,7 +411,8 @@ def query_expressions(index, k, lines, write):
                 parsed.append(parse_expression(line))
             except ValueError:
                 parsed.append(None)
-        results = iter(index.batch_query_expressions(k, [e for e in parsed if e is not None]))
+        ask = index.batch_query_cosmul if method == "mul" else index.batch_query_expressions
+        results = iter(ask(k, [e for e in parsed if e is not None]))
         for line, e in zip(part, parsed):
             write((f"{line}: invalid expression" if e is None else _line(line, next(results))) + "\n")
 
@@ -589,7 +603,9 @@ def run_analogies(config: AnalogiesConfig, load, vectors):
             else:
                 index = index.refined(originals, config.candidates if config.candidates is not None
                                       else 10 * config.ks[-1])
-        return evaluate_analogies(index, sections, config.ks)
+        if config.method == "add":
+            return evaluate_analogies(index, sections, config.ks)
+        return evaluate_analogies(index, sections, config.ks, method=config.method)
     except (LookupError, NotImplementedError, ValueError) as e:
         raise AnalogiesError(str(e))
 
@@ -656,6 +672,15 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
             parser.error("--candidates is only applicable with --vectors")
         if args.candidates is not None and args.exact:
             parser.error("--candidates is not applicable with --exact")
+        if args.method == "mul" and args.vectors is not None and not args.exact:
+            parser.error("--method mul is only applicable with --vectors together with --exact")
+    if args.command == "query-words" and args.method == "mul":
+        if not args.expressions:
+            parser.error("--method mul needs -x/--expressions")
+        for given, option in ((args.vectors is not None, "-v/--vectors"), (args.fine is not None, "-f/--fine"),
+                              (args.restrict is not None, "-r/--restrict"), (args.rotation is not None, "-R/--rotation")):
+            if given:
+                parser.error(f"--method mul is not applicable with {option}")
     if args.command == "update" and args.add is None and args.remove is None:
         parser.error("at least one of --add and --remove is required")
     if args.command == "inspect" and args.worst is not None and args.vectors is None:
@@ -718,7 +743,7 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
             write(line + "\n")
     elif args.command == "analogies":
         config = AnalogiesConfig(args.index, args.file, args.depths, args.lowercase, args.vectors, args.exact,
-                                 args.candidates)
+                                 args.candidates, args.method)
         try:
             report = (analogies if analogies is not None else run_analogies)(config, load, vectors)
         except AnalogiesError as e:
@@ -743,7 +768,15 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
         else:
             with open(args.file, "rb") as fh:
                 data = fh.read()
-        (query_expressions if args.expressions else query_words)(index, args.neighbours, read_lines(data), write)
+        if args.expressions and args.method == "mul":
+            try:
+                query_expressions(index, args.neighbours, read_lines(data), write, method="mul")
+            except (NotImplementedError, ValueError) as e:
+                stdout.flush()
+                print(f"error: {e}", file=sys.stderr)
+                return 1
+        else:
+            (query_expressions if args.expressions else query_words)(index, args.neighbours, read_lines(data), write)
     else:
         from .word_vectors import read_word2vec
         queries = read_word2vec(args.file)

@@ -16,7 +16,11 @@
 //
 // Expression queries: dataset_compose.hip composes the term rows of the dataset, the handle answers the
 // composed vectors at k_nn + extra by the path above, compose.hip's drop_rows_kernel removes the term rows.
+//
+// Multiplicative analogy queries: gulon_exact_index_query_cosmul[_dev] hand the handle's range and its
+// CosmulWork to cosmul.hip, under the handle's mutex and stream order.
 #include "compose.hpp"
+#include "cosmul.hpp"
 #include "exact.hpp"
 #include "select.hpp"
 
@@ -306,6 +310,7 @@ struct gulon_exact_index {
   DevBuf<float> stage_q, stage_od;
   DevBuf<int> stage_rows, stage_oi, stage_oc, stage_of;
   ExprWork expr;                       // the expression queries' term lists, composed vectors and answers at k_nn + extra
+  CosmulWork cosmul;                   // the multiplicative analogy queries (cosmul.hip)
   std::vector<int> h_cnt, h_ovf, h_nf, h_ids;
   hipEvent_t order_ev = nullptr;
   hipStream_t order_st = nullptr;
@@ -691,6 +696,50 @@ GULON_API int32_t gulon_exact_index_query_terms(gulon_exact_index *idx, const in
     if (bk) { x.fi.download(out_idx, bk, st); x.fd.download(out_dist, bk, st); }
     if (b > 0 && out_count) x.fc.download(out_count, (size_t)b, st);
     if (b > 0 && out_flags) x.ff.download(out_flags, (size_t)b, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+  });
+}
+
+// Multiplicative analogy queries: cosmul.hip scores rows [from, until) of the dataset against the term
+// rows, which are dataset rows as the returned ids are.
+GULON_API int32_t gulon_exact_index_query_cosmul_dev(gulon_exact_index *idx, const int32_t *d_term_offsets,
+                                                     const int32_t *d_term_rows, const float *d_term_weights, int32_t b,
+                                                     int32_t k_nn, int32_t normalize, int32_t *d_out_idx,
+                                                     float *d_out_score, int32_t *d_out_count, int32_t *d_err,
+                                                     void *stream) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr, "index is null");
+    std::lock_guard<std::mutex> g(idx->mu);
+    const hipStream_t st = (hipStream_t)stream;
+    order_wait(idx, st);
+    launch_cosmul_exact(idx->ds, idx->from, idx->until, idx->cosmul, d_term_offsets, d_term_rows, d_term_weights, b,
+                        k_nn, normalize != 0, d_out_idx, d_out_score, d_out_count, d_err, st);
+    if (b > 0) order_record(idx, st);
+  });
+}
+
+GULON_API int32_t gulon_exact_index_query_cosmul(gulon_exact_index *idx, const int32_t *term_offsets,
+                                                 const int32_t *term_rows, const float *term_weights, int32_t b,
+                                                 int32_t k_nn, int32_t normalize, int32_t *out_idx, float *out_score,
+                                                 int32_t *out_count) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr, "index is null");
+    const int terms = check_cosmul_host(term_offsets, term_rows, term_weights, b, idx->ds->n, k_nn, nullptr);
+    if (b == 0) return;
+    std::lock_guard<std::mutex> g(idx->mu);
+    CosmulWork &x = idx->cosmul;
+    const hipStream_t st = nullptr;
+    const size_t bk = (size_t)b * (size_t)k_nn;
+    x.off.upload(term_offsets, (size_t)b + 1, st);
+    x.rows.upload(term_rows, (size_t)terms, st);
+    x.w.upload(term_weights, (size_t)terms, st);
+    x.fi.ensure(bk + 1); x.fd.ensure(bk + 1); x.fc.ensure((size_t)b);
+    order_wait(idx, st);
+    launch_cosmul_exact(idx->ds, idx->from, idx->until, x, x.off.p, x.rows.p, x.w.p, b, k_nn, normalize != 0,
+                        x.fi.p, x.fd.p, x.fc.p, nullptr, st);
+    order_record(idx, st);
+    if (bk) { x.fi.download(out_idx, bk, st); x.fd.download(out_score, bk, st); }
+    if (out_count) x.fc.download(out_count, (size_t)b, st);
     HIP_CHECK(hipStreamSynchronize(st));
   });
 }

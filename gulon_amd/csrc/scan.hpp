@@ -40,6 +40,20 @@ struct ExprWork {
   DevBuf<float> fd;
   std::mutex mu;
 };
+// Workspace of the cosmul calls of one handle.  The exact index uses it under its own mutex; the flat index holds `mu`
+// for a whole call and takes the handle's mutex inside it, as ExprWork does.
+struct CosmulWork {
+  DevBuf<int> plan, bad;        // [3]: slots per question E' (1, 2, 4, 8), live term slots, first term; [b]: unusable
+  DevBuf<int> uoff, urows;      // the terms as one-term expressions: offsets [tcap + 1], rows [tcap]
+  DevBuf<float> ones;           // their weights [tcap]
+  DevBuf<float> q, qt;          // the term vectors q_t [tcap][d]; exact: transposed per workgroup [tile][d][16]
+  DevBuf<float> tables;         // flat: Index.prepareQuery of every q_t [tcap][m_pad][256]
+  DevBuf<float> pv, od;         // per-chunk lists of keys; the merged answer at depth kin
+  DevBuf<int> pi, oi, oc;
+  DevBuf<int> off, rows, fi, fc;   // the host-pointer forms: term lists and final lists
+  DevBuf<float> w, fd;
+  std::mutex mu;
+};
 }
 // PQIndex on the device (opaque to C callers)
 using gulon::DevBuf;
@@ -82,6 +96,7 @@ struct gulon_index {
   DevBuf<int> stage_rows;  // row ids of the host-pointer decode / query-by-row calls (decode.hip)
   DevBuf<int> row_err;     // set by the row decode when a *_dev call asked for a row outside [0, n)
   gulon::ExprWork expr;    // expression queries (compose.hip)
+  gulon::CosmulWork cosmul;   // multiplicative analogy queries (cosmul.hip)
   DevBuf<unsigned long long> dbg;   // GULON_REPLAY_STATS stamps (replay.hip)
   // large-K peeling rounds
   DevBuf<float> peel_v, peel_tv, peel_lbv;

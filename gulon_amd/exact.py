@@ -136,6 +136,25 @@ class ExactIndex:
         """Per expression over row ids the k nearest rows of its composed vector that are none of its operands."""
         return self._results(*self.batch_query_expressions_raw(k, expressions))
 
+    def batch_query_cosmul_raw(self, k, expressions):
+        """gulon_exact_index_query_cosmul: per expression over rows of the matrix the k rows of [frm, until) with the
+        largest 3CosMul score that are none of its term rows (expressions.cosmul_reference); the term
+        vectors are normalised for a cosine index.  -> (rows [b][k] with -1 after an expression's last entry, SCORES
+        [b][k] in descending order with -inf there, counts [b])."""
+        from .expressions import to_csr
+        off, rows, w = to_csr(expressions)
+        b = len(off) - 1
+        oi, od, oc, _ = self._outputs(b, k)
+        one_i, one_f = np.zeros(1, np.int32), np.zeros(1, np.float32)
+        N.check(N.lib().gulon_exact_index_query_cosmul(self._h, off, rows if b else one_i, w if b else one_f, b, k,
+                                                       int(self.metric == "cosine"), oi.reshape(-1), od.reshape(-1), oc))
+        return oi[:, :k], od[:, :k], oc[:b]
+
+    def batch_query_cosmul(self, k, expressions) -> List[Result]:
+        """batch_query_cosmul_raw as Results: `distances` holds the SCORES, in descending order; flags is 0."""
+        oi, od, oc = self.batch_query_cosmul_raw(k, expressions)
+        return [Result(oi[i, :oc[i]].copy(), od[i, :oc[i]].copy(), 0) for i in range(len(oc))]
+
     def stats(self):
         """Of the last batch: queries answered in one pass, by the peeled fallback and one at a time as non-finite; the
         sample rows S (0: no sample pass), the queue capacity, the largest number of rows at or below a bound."""
@@ -241,6 +260,24 @@ class ExactWordIndex:
 
     def query_expression(self, k, expression) -> Optional[WordResult]:
         return self.batch_query_expressions(k, [expression])[0]
+
+    def batch_query_cosmul(self, k, expressions) -> List[Optional[WordResult]]:
+        """As WordIndex.batch_query_cosmul, over the ORIGINAL vectors of the words: per expression the k words with the
+        largest 3CosMul score that are none of its operands, `distances` holding the SCORES in descending order; None
+        where a word is absent.  ValueError on an l2 index."""
+        if self.metric != "cosine":
+            raise ValueError("requirement failed: cosmul queries need a cosine index")
+        resolved = self.resolve_expressions(expressions)
+        present = [i for i, e in enumerate(resolved) if e is not None]
+        out: List[Optional[WordResult]] = [None] * len(resolved)
+        for s in range(0, len(present), BATCH):
+            part = present[s:s + BATCH]
+            for i, r in zip(part, self.index.batch_query_cosmul(k, [resolved[i] for i in part])):
+                out[i] = self._result(r)
+        return out
+
+    def query_cosmul(self, k, expression) -> Optional[WordResult]:
+        return self.batch_query_cosmul(k, [expression])[0]
 
     def close(self):
         """Frees the handle and the gathered matrix this index was built over, when it owns one."""

@@ -98,6 +98,31 @@ def compose_reference(vectors, weights, normalize_terms=False, normalize_query=F
         return normalize(acc) if normalize_query else acc
 
 
+COSMUL_EPS = np.float32(0.001)
+
+
+def cosmul_reference(distances, weights) -> np.ndarray:
+    """The 3CosMul scores of n rows against one expression (csrc/cosmul.hip): distances [E][n], the
+    distance of every row to each term's vector as the index's ordinary query returns it; weights [E], a weight > 0 a
+    positive term, any other a negative one.  s_t = max(1 - 0.25 * d_t, 0) with a NaN taken as 0; P and N the products of
+    the positive and of the negative terms' s_t in list order, the first factor starting each, N = 1 without a negative
+    term; score = P / (N + COSMUL_EPS).  Every operation is rounded to float32 on its own.  -> [n] float32."""
+    d = np.ascontiguousarray(distances, np.float32)
+    w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+    if d.ndim != 2 or len(d) != len(w) or len(w) == 0 or not (w > 0).any():
+        raise ValueError("requirement failed: one weight per row of distances, at least one of them positive")
+    quarter, one, zero = np.float32(0.25), np.float32(1), np.float32(0)
+    prod = {True: None, False: None}
+    with np.errstate(invalid="ignore", over="ignore"):
+        for t in range(len(w)):
+            s = (one - (quarter * d[t]).astype(np.float32)).astype(np.float32)
+            s = np.where(s > zero, s, zero).astype(np.float32)      # fmaxf(s, 0): a NaN goes to 0
+            sign = bool(w[t] > 0)
+            prod[sign] = s if prod[sign] is None else (prod[sign] * s).astype(np.float32)
+        neg = np.ones(d.shape[1], np.float32) if prod[False] is None else prod[False]
+        return (prod[True] / (neg + COSMUL_EPS).astype(np.float32)).astype(np.float32)
+
+
 def distinct_operands(expression) -> int:
     return len({t.key for t in as_expression(expression)})
 

@@ -232,6 +232,28 @@ class PQIndex:
         oi, od, oc, of = self.batch_query_terms_partitioned(k, expressions, frm, until, normalize_terms, normalize_query)
         return [Result(oi[i, :oc[i]].copy(), od[i, :oc[i]].copy(), int(of[i])) for i in range(len(oc))]
 
+    def batch_query_cosmul_raw(self, k, expressions, frm=0, until=None, normalize=False):
+        """gulon_index_query_cosmul: per expression over row ids the k rows of [frm, until) with the largest 3CosMul
+        score that are none of its term rows (expressions.cosmul_reference).  -> (rows [b][k] with -1
+        after an expression's last entry, SCORES [b][k] in descending order with -inf there, counts [b])."""
+        from .expressions import to_csr
+        off, rows, w = to_csr(expressions)
+        b = len(off) - 1
+        until = self.length if until is None else until
+        oi = np.zeros((b, max(k, 1)), np.int32)
+        od = np.zeros((b, max(k, 1)), np.float32)
+        oc = np.zeros(max(b, 1), np.int32)
+        one_i, one_f = np.zeros(1, np.int32), np.zeros(1, np.float32)
+        N.check(N.lib().gulon_index_query_cosmul(self._h, off, rows if b else one_i, w if b else one_f, b, k,
+                                                 int(bool(normalize)), frm, until, oi.reshape(-1), od.reshape(-1), oc))
+        return oi[:, :k], od[:, :k], oc[:b]
+
+    def batch_query_cosmul(self, k, expressions, frm=0, until=None, normalize=False):
+        """batch_query_cosmul_raw as Results: `distances` holds the SCORES, in descending order; flags is 0 (the order
+        (score descending, row ascending) is total)."""
+        oi, od, oc = self.batch_query_cosmul_raw(k, expressions, frm, until, normalize)
+        return [Result(oi[i, :oc[i]].copy(), od[i, :oc[i]].copy(), 0) for i in range(len(oc))]
+
     def select(self, rows=None, mask=None):
         """The view of this index over a subset of its rows (gulon_index_select_*): an index of its own, gathered on
         the device, that answers in THIS index's row ids.  Exactly one of `rows` (strictly ascending row numbers) and
@@ -525,6 +547,17 @@ class SortedIndex:
         """Per expression over row ids the k nearest rows of its composed vector that are none of its operands."""
         cosine = self.metric == "cosine"
         return self.vector_index.batch_query_terms(k, expressions, normalize_terms=cosine, normalize_query=cosine)
+
+
+    def batch_query_cosmul_raw(self, k, expressions):
+        """PQIndex.batch_query_cosmul_raw over all rows, the term vectors normalised for a cosine index: (rows,
+        SCORES in descending order, counts)."""
+        return self.vector_index.batch_query_cosmul_raw(k, expressions, normalize=self.metric == "cosine")
+
+    def batch_query_cosmul(self, k, expressions):
+        """Per expression over row ids the k rows with the largest 3CosMul score that are none of its operands;
+        `distances` of a Result holds the SCORES, in descending order."""
+        return self.vector_index.batch_query_cosmul(k, expressions, normalize=self.metric == "cosine")
 
 
 class Index:

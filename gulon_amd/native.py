@@ -203,6 +203,10 @@ SIGNATURES = {
                                                  _vp]),
     "gulon_analogy_counts": (_i32, [_i32p, _i32p, _i32, _i32, _i32p, _i32p, _i32p, _i32, _i32, _i32p, _i32p, _vp]),
     "gulon_analogy_counts_dev": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "gulon_exact_index_query_cosmul": (_i32, [_vp, _i32p, _i32p, _f32p, _i32, _i32, _i32, _i32p, _f32p, _i32p]),
+    "gulon_exact_index_query_cosmul_dev": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "gulon_index_query_cosmul": (_i32, [_vp, _i32p, _i32p, _f32p, _i32, _i32, _i32, _i32, _i32, _i32p, _f32p, _i32p]),
+    "gulon_index_query_cosmul_dev": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

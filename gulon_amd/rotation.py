@@ -272,6 +272,12 @@ class RotatedWordIndex:
         v = self.inner.lookup(word)
         return None if v is None else self.rotation.apply_transposed(v)
 
+    def batch_query_cosmul(self, k, expressions):
+        raise NotImplementedError("cosmul queries are not supported by a rotated index")
+
+    def query_cosmul(self, k, expression):
+        raise NotImplementedError("cosmul queries are not supported by a rotated index")
+
     # ---- forms of the index that take word vectors or give an index back
     def refined(self, vectors, candidates):
         return RotatedWordIndex(self.inner.refined(self._vectors(vectors), candidates), self.rotation)

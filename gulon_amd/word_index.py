@@ -170,6 +170,28 @@ class WordIndex:
     def query_expression(self, k, expression) -> Optional[WordResult]:
         return self.batch_query_expressions(k, [expression])[0]
 
+    def batch_query_cosmul(self, k, expressions) -> List[Optional[WordResult]]:
+        """Per expression over words the k words with the largest 3CosMul score (Levy & Goldberg's multiplicative
+        objective; expressions.cosmul_reference) that are none of its operands, in input order; None for
+        an expression that names a word the index lacks.  `distances` of a result holds the SCORES, in descending
+        order.  Scored on the device, up to BATCH expressions per batch.  ValueError on an l2 index;
+        NotImplementedError for a grouped index (and, from the library, for codes wider than a byte)."""
+        if self.metric != "cosine":
+            raise ValueError("requirement failed: cosmul queries need a cosine index")
+        if self._grouped:
+            raise NotImplementedError("cosmul queries are not supported by the grouped index")
+        resolved = self.resolve_expressions(expressions)
+        present = [i for i, e in enumerate(resolved) if e is not None]
+        out: List[Optional[WordResult]] = [None] * len(resolved)
+        for s in range(0, len(present), BATCH):
+            part = present[s:s + BATCH]
+            for i, r in zip(part, self.index.batch_query_cosmul(k, [resolved[i] for i in part])):
+                out[i] = self._result(r)
+        return out
+
+    def query_cosmul(self, k, expression) -> Optional[WordResult]:
+        return self.batch_query_cosmul(k, [expression])[0]
+
     def batch_query(self, k, vectors) -> List[WordResult]:
         """Index.batchQuery (Index.scala:25-32) with the results' words."""
         q = np.ascontiguousarray(vectors, np.float32).reshape(-1, self.dimension)
@@ -261,6 +283,9 @@ class RestrictedWordIndex(WordIndex):
 
     def batch_query_expressions(self, k, expressions):
         raise NotImplementedError("expressions are not supported by a restricted index")
+
+    def batch_query_cosmul(self, k, expressions):
+        raise NotImplementedError("cosmul queries are not supported by a restricted index")
 
     def close(self):
         self.index.vector_index.close()

@@ -837,6 +837,42 @@ int32_t gulon_analogy_counts_dev(const int32_t *d_idx_lists, const int32_t *d_co
                                  int32_t nsections, int32_t *d_hits, int32_t *d_asked, int32_t *d_out_rank,
                                  void *stream);
 
+/* ---- Multiplicative analogy queries, 3CosMul (cosmul.hip) ------------------------------------------------
+ * Levy & Goldberg's objective on the exact index and on a flat byte-code index.  Expressions are CSR term lists as in
+ * gulon_index_query_terms; a term with weight > 0 is positive, any other negative.  Per expression with E terms and per
+ * row r of the handle's range (the index: of [from, until)):
+ *   q_t   = what the handle's *_compose_rows returns for [(row_t, 1.0)] with normalize_terms = normalize_query = normalize
+ *           (the dataset row; the decoded row);
+ *   d_t   = the bits the handle's ordinary query returns as the distance between q_t and r;
+ *   s_t   = fmaxf(1 - 0.25 * d_t, 0): (1 + cos) / 2 on unit vectors, 0 for a NaN distance;
+ *   P, N  = the products of the positive and of the negative terms' s_t in list order, the first factor starting each,
+ *           N = 1 without a negative term;   score = P / (N + 0.001);   every operation rounded to binary32 on its own.
+ * The answer: the rows that are no term rows by (score descending, row id ascending), the first k_nn.  out_idx [b][k_nn]
+ * padded with -1, out_score [b][k_nn] padded with -inf, out_count [b] (nullable).  The order is total: no tie flags.  A
+ * term row outside the range removes nothing but still scores.
+ * Limits: 1 <= E <= 8, else GULON_ERR_UNSUPPORTED; k_nn + (largest E of the batch) <= GULON_MAX_K, else
+ * GULON_ERR_UNSUPPORTED; the index: byte codes only (wide codes and views are GULON_ERR_UNSUPPORTED), and the tables of
+ * one question, E * m_pad KiB, must fit in 144 KiB of LDS, else GULON_ERR_UNSUPPORTED naming m and E.
+ * The host forms check b, the offsets, every row, |w_t| == 1, a positive term per expression
+ * (GULON_ERR_INVALID_ARGUMENT) and the limits before anything is launched.  The _dev forms take device pointers and a
+ * stream and do not synchronise: there an expression with no term, no positive term, a row outside the handle or
+ * beyond a limit comes back with count 0 and nothing but padding, and sets *d_err (nullable) / the index's row-error
+ * word (gulon_index_row_error). */
+int32_t gulon_exact_index_query_cosmul(gulon_exact_index *idx, const int32_t *term_offsets, const int32_t *term_rows,
+                                       const float *term_weights, int32_t b, int32_t k_nn, int32_t normalize,
+                                       int32_t *out_idx, float *out_score, int32_t *out_count);
+int32_t gulon_exact_index_query_cosmul_dev(gulon_exact_index *idx, const int32_t *d_term_offsets,
+                                           const int32_t *d_term_rows, const float *d_term_weights, int32_t b,
+                                           int32_t k_nn, int32_t normalize, int32_t *d_out_idx, float *d_out_score,
+                                           int32_t *d_out_count, int32_t *d_err, void *stream);
+int32_t gulon_index_query_cosmul(gulon_index *idx, const int32_t *term_offsets, const int32_t *term_rows,
+                                 const float *term_weights, int32_t b, int32_t k_nn, int32_t normalize, int32_t from,
+                                 int32_t until, int32_t *out_idx, float *out_score, int32_t *out_count);
+int32_t gulon_index_query_cosmul_dev(gulon_index *idx, const int32_t *d_term_offsets, const int32_t *d_term_rows,
+                                     const float *d_term_weights, int32_t b, int32_t k_nn, int32_t normalize,
+                                     int32_t from, int32_t until, int32_t *d_out_idx, float *d_out_score,
+                                     int32_t *d_out_count, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
