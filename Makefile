@@ -14,7 +14,7 @@ HDRS = $(CSRC)/common.hpp $(CSRC)/scan.hpp $(CSRC)/kmeans.hpp include/gulon_hip.
 # The product library carries no test code.  The self-tests of the kernels (gulon_selftest_*) live in a second library
 # that only tests/ loads: the same objects, with the files that have hooks compiled again under -DGULON_TEST_HOOKS.
 HOOKLIB = gulon_amd/lib/libgulon_hip_testhooks.so
-HOOKED = kmeans_update kmeans_stream kmeans_mfma conflict_order grouped grouped_filter filter_query wide_filter
+HOOKED = kmeans_update kmeans_stream kmeans_mfma conflict_order grouped grouped_filter filter_query wide_filter cosmul exact
 HOOKOBJS = $(patsubst %,$(OBJDIR)/%.hooks.o,$(HOOKED)) $(filter-out $(patsubst %,$(OBJDIR)/%.o,$(HOOKED)),$(OBJS))
 
 all: $(LIB) $(HOOKLIB) oracle build/test_host_api

@@ -416,6 +416,28 @@ int check_cosmul_host(const int32_t *off, const int32_t *rows, const float *w, i
   return terms;
 }
 
+CosmulShape cosmul_exact_shape(int from, int until, int b) {
+  const int nb = std::min(EXACT_SUB_BATCH, b);
+  const int rbeg = (from / KNN_THREADS) * KNN_THREADS;
+  const int groups = std::max(1, ceil_div(until - rbeg, KNN_THREADS));
+  // the row chunks: about 2048 workgroups at four questions each, whatever E' turns out to be
+  const int want = std::max(1, ceil_div(2048, ceil_div(nb, 4)));
+  const int groups_per_chunk = ceil_div(groups, std::min(want, groups));
+  return {EXACT_SUB_BATCH, ceil_div(groups, groups_per_chunk), groups_per_chunk};
+}
+
+CosmulShape cosmul_flat_shape(const gulon_index *ix, int from, int until, int b) {
+  constexpr int NW = CF_THREADS / 64;
+  const size_t tab = (size_t)ix->m_pad * 256;
+  const int sub = (int)std::max<size_t>(1, FLAT_TABLE_BYTES / ((size_t)COSMUL_MAX_TERMS * tab * sizeof(float)));
+  const int nb = std::min(sub, b);
+  const int rb_total = ceil_div(until, 64) - from / 64;
+  const int want = std::max(1, ceil_div(2048, nb));
+  const int nchunks_max = std::max(1, rb_total / (2 * NW));
+  const int rb_per_chunk = std::max(1, ceil_div(rb_total, std::min(want, nchunks_max)));
+  return {sub, std::max(1, ceil_div(rb_total, rb_per_chunk)), rb_per_chunk};
+}
+
 void launch_cosmul_exact(const gulon_dataset *ds, int from, int until, CosmulWork &x, const int *d_off, const int *d_rows,
                          const float *d_w, int b, int k_nn, bool normalize, int *out_idx, float *out_score,
                          int *out_count, int *d_err, hipStream_t st) {
@@ -423,16 +445,12 @@ void launch_cosmul_exact(const gulon_dataset *ds, int from, int until, CosmulWor
   if (b == 0) return;
   const int d = ds->d;
   const int kin = std::min(k_nn + COSMUL_MAX_TERMS, GULON_MAX_K), keff = kin + 1;
-  const int rbeg = (from / KNN_THREADS) * KNN_THREADS;
-  const int groups = std::max(1, ceil_div(until - rbeg, KNN_THREADS));
   for (int q0 = 0; q0 < b; q0 += EXACT_SUB_BATCH) {
     const int nb = std::min(EXACT_SUB_BATCH, b - q0), tcap = nb * COSMUL_MAX_TERMS;
     const int *off = d_off + q0;
-    // the row chunks: about 2048 workgroups at four questions each, whatever E' turns out to be
-    const int want = std::max(1, ceil_div(2048, ceil_div(nb, 4)));
-    const int groups_per_chunk = ceil_div(groups, std::min(want, groups));
-    const int nchunks = ceil_div(groups, groups_per_chunk);
-    const int rows_per_chunk = groups_per_chunk * KNN_THREADS;
+    const CosmulShape shape = cosmul_exact_shape(from, until, nb);
+    const int nchunks = shape.nchunks;
+    const int rows_per_chunk = shape.per_chunk * KNN_THREADS;
     const int bp = ceil_div(nb, KNN_QT) * KNN_QT;                 // questions the lists are kept for, at any E'
     const size_t qt_len = (size_t)ceil_div(nb, 2) * d * KNN_QT;   // E' = 8: two questions per tile
     x.plan.ensure(3); x.bad.ensure(nb);
@@ -474,19 +492,16 @@ void launch_cosmul_flat(gulon_index *ix, CosmulWork &x, const int *d_off, const 
                     ix->m_pad, (int)(COSMUL_LDS_BUDGET / 1024));
   if (b == 0) return;
   lds_terms = std::min(std::max(lds_terms, 1), max_terms);
-  constexpr int NW = CF_THREADS / 64;
   const int kin = std::min(k_nn + COSMUL_MAX_TERMS, GULON_MAX_K), keff = kin + 1;
   const int tab = ix->m_pad * 256;
   const size_t lds_bytes = (size_t)lds_terms * tab * sizeof(float);
-  const int rb_begin = from / 64, rb_end = ceil_div(until, 64), rb_total = rb_end - rb_begin;
-  const int sub = (int)std::max<size_t>(1, FLAT_TABLE_BYTES / ((size_t)COSMUL_MAX_TERMS * tab * sizeof(float)));
+  const int rb_begin = from / 64, rb_end = ceil_div(until, 64);
+  const int sub = cosmul_flat_shape(ix, from, until, b).per_pass;
   for (int q0 = 0; q0 < b; q0 += sub) {
     const int nb = std::min(sub, b - q0), tcap = nb * COSMUL_MAX_TERMS;
     const int *off = d_off + q0;
-    const int want = std::max(1, ceil_div(2048, nb));
-    const int nchunks_max = std::max(1, rb_total / (2 * NW));
-    const int rb_per_chunk = std::max(1, ceil_div(rb_total, std::min(want, nchunks_max)));
-    const int nchunks = std::max(1, ceil_div(rb_total, rb_per_chunk));
+    const CosmulShape shape = cosmul_flat_shape(ix, from, until, nb);
+    const int rb_per_chunk = shape.per_chunk, nchunks = shape.nchunks;
     {
       std::lock_guard<std::mutex> lock(ix->mu);
       ix->pend_b = -1;
@@ -579,3 +594,19 @@ GULON_API int32_t gulon_index_query_cosmul(gulon_index *idx, const int32_t *term
     HIP_CHECK(hipStreamSynchronize(st));
   });
 }
+
+#ifdef GULON_TEST_HOOKS
+// Which launch geometry gulon_index_query_cosmul[_dev] takes for b questions over rows [from, until) of `idx`
+// (tests/test_gpu_cosmul_paths.py): out = {questions per pass, row chunks of the first pass, 64-row code blocks per
+// chunk}, by the launcher's own cosmul_flat_shape.  Host code: nothing is launched.
+GULON_API int32_t gulon_selftest_cosmul_flat_shape(const gulon_index *idx, int32_t b, int32_t from, int32_t until,
+                                                   int32_t out[3]) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr && out != nullptr && b >= 1, "bad arguments");
+    GULON_UNSUPPORTED(idx->wide, "cosmul queries take byte codes: k = %d > 256 is not supported", idx->k);
+    GULON_REQUIRE(from >= 0 && from <= until && until <= idx->n, "expected: 0 <= from <= until <= length");
+    const CosmulShape s = cosmul_flat_shape(idx, from, until, b);
+    out[0] = s.per_pass; out[1] = s.nchunks; out[2] = s.per_chunk;
+  });
+}
+#endif

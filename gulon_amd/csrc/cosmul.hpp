@@ -28,4 +28,11 @@ void launch_cosmul_flat(gulon_index *ix, CosmulWork &x, const int *d_off, const 
                         int *out_count, bool dev_rows, hipStream_t st);
 int cosmul_flat_max_terms(const gulon_index *ix);   // the E whose tables fit COSMUL_LDS_BUDGET, at most COSMUL_MAX_TERMS
 
+// The launch geometry of the two launchers, which take it from here: the questions of one pass, and for a pass whose
+// first question has b questions from it on (a pass takes the first per_pass of them) the row chunks and what one chunk
+// holds -- 256-row groups on the exact index, 64-row code blocks on the flat one.  b >= 1.
+struct CosmulShape { int per_pass, nchunks, per_chunk; };
+CosmulShape cosmul_exact_shape(int from, int until, int b);
+CosmulShape cosmul_flat_shape(const gulon_index *ix, int from, int until, int b);
+
 }  // namespace gulon

@@ -744,6 +744,19 @@ GULON_API int32_t gulon_exact_index_query_cosmul(gulon_exact_index *idx, const i
   });
 }
 
+#ifdef GULON_TEST_HOOKS
+// Which launch geometry gulon_exact_index_query_cosmul[_dev] takes for b questions on this handle's range
+// (tests/test_gpu_cosmul_paths.py): out = {questions per pass, row chunks of the first pass, 256-row groups per chunk}, by
+// the launcher's own cosmul_exact_shape.  Here because the handle's range is: host code, nothing is launched.
+GULON_API int32_t gulon_selftest_cosmul_exact_shape(const gulon_exact_index *idx, int32_t b, int32_t out[3]) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr && out != nullptr && b >= 1, "bad arguments");
+    const CosmulShape s = cosmul_exact_shape(idx->from, idx->until, b);
+    out[0] = s.per_pass; out[1] = s.nchunks; out[2] = s.per_chunk;
+  });
+}
+#endif
+
 GULON_API int32_t gulon_exact_index_tuning(gulon_exact_index *idx, const char *key, int32_t value) {
   return guarded([&] {
     GULON_REQUIRE(idx != nullptr && key != nullptr, "index or key is null");

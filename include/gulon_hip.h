@@ -872,6 +872,14 @@ int32_t gulon_index_query_cosmul_dev(gulon_index *idx, const int32_t *d_term_off
                                      const float *d_term_weights, int32_t b, int32_t k_nn, int32_t normalize,
                                      int32_t from, int32_t until, int32_t *d_out_idx, float *d_out_score,
                                      int32_t *d_out_count, void *stream);
+#ifdef GULON_TEST_HOOKS   /* libgulon_hip_testhooks.so only */
+/* The launch geometry of the 3CosMul scans (cosmul.hip), by the arithmetic their launchers run; host code, nothing is
+ * launched.  b >= 1 questions.  Flat index, rows [from, until): out = {questions per pass, row chunks of the first
+ * pass, 64-row code blocks per chunk}.  Exact index, the handle's range: out = {questions per pass, row chunks of the
+ * first pass, 256-row groups per chunk}. */
+int32_t gulon_selftest_cosmul_flat_shape(const gulon_index *idx, int32_t b, int32_t from, int32_t until, int32_t out[3]);
+int32_t gulon_selftest_cosmul_exact_shape(const gulon_exact_index *idx, int32_t b, int32_t out[3]);
+#endif
 
 #ifdef __cplusplus
 }

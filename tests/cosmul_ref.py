@@ -78,3 +78,57 @@ def same(got, want):
     assert np.array_equal(got[2], want[2]), (got[2], want[2])
     assert np.array_equal(got[0], want[0])
     assert np.array_equal(bits(got[1]), bits(want[1]))
+
+
+def zero_factors(D):
+    """[E][n] bool: where a term's factor s_t is 0 (a distance of 4 or more, or a NaN).  A one-term expression scores
+    s_t / 1.001, so cosmul_reference itself says it."""
+    from gulon_amd.expressions import cosmul_reference
+    return np.stack([cosmul_reference(D[t:t + 1], [1.0]) == 0 for t in range(len(D))])
+
+
+def equal_neighbours(lists):
+    """Per answer list of (rows, scores, counts): the (row, next row) pairs of adjacent entries with equal scores."""
+    ri, rs, rc = lists
+    return [[(int(ri[q, e]), int(ri[q, e + 1])) for e in range(rc[q] - 1) if rs[q, e] == rs[q, e + 1]]
+            for q in range(len(rc))]
+
+
+def native_index(g, pq, idx, row_base=0):
+    """The flat index gulon_index_create makes of the planted codes idx [m][n]: no training."""
+    coder = pq.coder_factory(idx.shape[1])
+    return g.PQIndex(pq, g.EncodedMatrix(coder, [coder.build_code(idx[j]) for j in range(idx.shape[0])]), row_base)
+
+
+def flat_term_distances(oracle, vi, codes, cents, exprs, normalize):
+    """[T][n] over the PQIndex `vi` with codes [n][m]: every term's vector by the handle's own compose_rows, the oracle's
+    Index.prepareQuery tables of it, adc_distances."""
+    d, m = vi.dimension, codes.shape[1]
+    Q = vi.compose_rows([[(r, 1.0)] for e in exprs for r, _ in e], normalize, normalize)
+    return adc_distances(oracle.prepare_query(cents, d, m, vi.product_quantizer.num_clusters, Q), codes)
+
+
+def run_dev(g, call, exprs, k, with_err):
+    """A *_query_cosmul_dev call on device copies of the term lists: call(off, rows, w, b, oi, os, oc, err) with device
+    addresses (err: a zeroed word, None unless with_err) -> (rows [b][k], scores [b][k], counts [b]), *err or None."""
+    from gulon_amd.expressions import to_csr
+    from gulon_amd.refine import _DeviceArray
+    off, rows, w = to_csr(exprs)
+    b = len(exprs)
+    dev = {name: _DeviceArray() for name in ("off", "rows", "w", "oi", "os", "oc", "err")}
+    try:
+        dev["off"].upload(off), dev["rows"].upload(rows), dev["w"].upload(w)
+        dev["err"].upload(np.zeros(1, np.int32))
+        for name, nbytes in (("oi", b * k * 4), ("os", b * k * 4), ("oc", b * 4)):
+            dev[name].ensure(nbytes)
+        g.native.check(call(dev["off"].ptr, dev["rows"].ptr, dev["w"].ptr, b, dev["oi"].ptr, dev["os"].ptr,
+                            dev["oc"].ptr, dev["err"].ptr if with_err else None))
+        g.native.check(g.native.lib().gulon_device_synchronize())
+        oi = dev["oi"].download(np.zeros((b, k), np.int32))
+        os_ = dev["os"].download(np.zeros((b, k), np.float32))
+        oc = dev["oc"].download(np.zeros(b, np.int32))
+        err = int(dev["err"].download(np.zeros(1, np.int32))[0]) if with_err else None
+    finally:
+        for a in dev.values():
+            a.free()
+    return (oi, os_, oc), err

@@ -31,6 +31,27 @@ def test_symbols_are_declared_bound_and_exported():
     assert L.gulon_abi_version() == 3
 
 
+def test_shape_hooks_are_in_the_hooks_library_only():
+    """gulon_selftest_cosmul_{flat,exact}_shape: declared under GULON_TEST_HOOKS, bound with the header's argument
+    counts, exported by libgulon_hip_testhooks.so and not by the product; cosmul.hip is compiled with hooks."""
+    from gulon_amd import native
+    header = open(os.path.join(ROOT, "include", "gulon_hip.h")).read()
+    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    guarded = "".join(re.findall(r"#ifdef GULON_TEST_HOOKS(.*?)#endif", header, flags=re.S))
+    plain = re.sub(r"#ifdef GULON_TEST_HOOKS.*?#endif", "", header, flags=re.S)
+    def exported(path):
+        out = subprocess.check_output(["nm", "-D", "--defined-only", path], text=True)
+        return {l.split()[-1] for l in out.splitlines() if " T " in l}
+    prod, hooks = exported(native.LIB_PATH), exported(native.HOOKS_LIB_PATH)
+    for name in ("gulon_selftest_cosmul_flat_shape", "gulon_selftest_cosmul_exact_shape"):
+        args = re.search(r"\bint32_t\s+" + name + r"\s*\(([^)]*)\)", guarded).group(1)
+        assert len(args.split(",")) == len(native.TEST_HOOK_SIGNATURES[name][1]), name
+        assert name not in plain and name not in native.SIGNATURES
+        assert name in hooks and name not in prod
+    make = open(os.path.join(ROOT, "Makefile")).read()
+    assert "cosmul" in re.search(r"^HOOKED = (.*)$", make, flags=re.M).group(1).split()
+
+
 def test_source_is_in_the_makefile():
     make = open(os.path.join(ROOT, "Makefile")).read()
     srcs = re.search(r"^SRCS = (.*)$", make, flags=re.M).group(1).split()
