@@ -205,6 +205,60 @@ struct WaveList {
     tau_i = readlane_i(i, keff - 1);
   }
 };
+
+// The 64 keys of one wave's step offered to a list: lane l holds `key` of row row0 + l, `valid` says whether the row
+// counts, vmask = __ballot(valid).  Until the list has seen keff rows (cnt) every valid row is inserted; after that only
+// the lanes below tau are visited and accepts() settles ties.  Rows arrive in ascending order within a wave, so a key
+// equal to the list's last loses to it.  eligible(cv, cr), wave-uniform, is asked before a row is counted or inserted:
+// the peel rounds' lower bound; AnyRow compiles it out.
+struct AnyRow {
+  __device__ bool operator()(float, int) const { return true; }
+};
+template <class Eligible = AnyRow>
+__device__ __forceinline__ void wave_offer(WaveList &wl, int &cnt, float key, bool valid, unsigned long long vmask,
+                                           int row0, int keff, int lane, Eligible eligible = Eligible()) {
+  unsigned long long mk = __ballot(valid && key < wl.tau);
+  if (cnt < keff) mk = vmask;
+  while (mk) {
+    const int l = __ffsll((long long)mk) - 1;
+    mk &= mk - 1;
+    const float cv = readlane_f(key, l);
+    const int cr = row0 + l;
+    if (!eligible(cv, cr)) continue;
+    if (cnt < keff || wl.accepts(cv, cr)) {
+      wl.insert(cv, cr, keff, lane);
+      if (cnt < keff) cnt++;
+    }
+  }
+}
+
+// The tail of a workgroup of NW waves that kept NQ lists per wave: list q of wave w goes to sv / si[(q * NW + w) * 64 +
+// lane] (caller-provided LDS, NQ * NW * 64 entries each, free to be written when the call is made), then wave q % NW
+// re-inserts the NW lists of query q, each up to its INT_MAX padding, and hands the merged list to out(q, list).  All
+// waves call; it holds one barrier.
+template <int NQ, int NW, class Out>
+__device__ __forceinline__ void merge_wave_lists(const WaveList *wl, float *sv, int *si, int keff, int lane, int wave,
+                                                 Out out) {
+#pragma unroll
+  for (int q = 0; q < NQ; q++) {
+    sv[(q * NW + wave) * 64 + lane] = wl[q].v;
+    si[(q * NW + wave) * 64 + lane] = wl[q].i;
+  }
+  __syncthreads();
+  for (int q = wave; q < NQ; q += NW) {
+    WaveList m;
+    m.init();
+    for (int w2 = 0; w2 < NW; w2++) {
+      for (int e = 0; e < keff; e++) {
+        const float cv = sv[(q * NW + w2) * 64 + e];
+        const int cr = si[(q * NW + w2) * 64 + e];
+        if (cr == INT_MAX) break;  // sorted: the rest of this list is padding
+        if (m.accepts(cv, cr)) m.insert(cv, cr, keff, lane);
+      }
+    }
+    out(q, m);
+  }
+}
 #endif
 
 }  // namespace gulon

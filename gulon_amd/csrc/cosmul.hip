@@ -12,14 +12,14 @@
 //   cosmul_plan        one workgroup: which expressions are unusable, the slots per question E' = the largest E rounded
 //                      up to 1, 2, 4 or 8, and the terms as one-term expressions for the compose launchers
 //   (compose)          q_t for every term slot: launch_dataset_compose / gulon_index_compose_rows_dev
-//   exact index        cosmul_transpose: q_t of the 16 / E' questions of a workgroup -> [dim][16], one uniform load per
-//                      wave and dim; cosmul_exact_scan: knn_kernel's tiling -- rows staged in LDS, lane = row, 16
-//                      accumulators = the term slots of 16 / E' questions
+//   exact index        cosmul_transpose: q_t of the 16 / E' questions of a workgroup -> Qt; cosmul_exact_scan: the d_t by
+//                      exact_tile (exact.hpp), its 16 accumulators = the term slots of 16 / E' questions
 //   flat index         launch_build_tables: Index.prepareQuery of every q_t; cosmul_flat_scan: a workgroup is (question,
 //                      row chunk), the question's E tables in LDS, lanes the rows of the 64-row code blocks, one running
 //                      sum per term in the order of scan.hip's exact scan
-//   both               after the sums the score, and the key -score into the question's WaveList, which orders by (key
-//                      ascending, row ascending); launch_merge: the row chunks' lists -> one list of depth
+//   both               after the sums the score, and the key -score into the question's WaveList (wave_offer), which
+//                      orders by (key ascending, row ascending); the workgroup's lists merged (merge_wave_lists) into
+//                      the chunk's; launch_merge: the row chunks' lists -> one list of depth
 //                      kin = min(k_nn + 8, 63); launch_drop (compose.hip's kernel): the term rows removed, the first
 //                      k_nn kept; cosmul_negate: key -> score (the +inf padding becomes -inf)
 // E' is known on the device only (the *_dev forms do not synchronise), so the exact scan is launched once per E' and the
@@ -112,27 +112,10 @@ __device__ __forceinline__ void question_terms(const int *__restrict__ bad, cons
   t0 = __builtin_amdgcn_readfirstlane(t0);
 }
 
-// The rows of one wave's step offered to a question's list: knn_kernel's insertion.  Rows arrive in ascending order
-// within a wave, so a key equal to the list's last loses to it.
-__device__ __forceinline__ void offer_rows(WaveList &wl, int &cnt, float key, bool valid, unsigned long long vmask,
-                                           int row0, int keff, int lane) {
-  unsigned long long mk = __ballot(valid && key < wl.tau);
-  if (cnt < keff) mk = vmask;
-  while (mk) {
-    const int l = __ffsll((long long)mk) - 1;
-    mk &= mk - 1;
-    const float cv = readlane_f(key, l);
-    const int cr = row0 + l;
-    if (cnt < keff || wl.accepts(cv, cr)) {
-      wl.insert(cv, cr, keff, lane);
-      if (cnt < keff) cnt++;
-    }
-  }
-}
-
 // ---- exact index ------------------------------------------------------------------------------------------------------
 
-// Qt[tile][dim][16]: slot u of a tile is term u % E' of its question u / E'; a slot without a term holds zeros.
+// Qt (exact.hpp) of the term vectors: slot u of a tile is term u % E' of its question u / E'; a slot without a term
+// holds zeros.
 __global__ void cosmul_transpose(const float *__restrict__ Q1, const int *__restrict__ off, const int *__restrict__ bad,
                                  const int *__restrict__ plan, int b, int d, float *__restrict__ Qt) {
   const int EP = plan[0], QW = KNN_QT / EP, base = plan[2];
@@ -186,27 +169,7 @@ __global__ __launch_bounds__(KNN_THREADS) void cosmul_exact_scan(const float *__
   const int r1 = min(row_until, r0 + rows_per_chunk);
   for (int base = r0; base < r1; base += KNN_THREADS) {
     float acc[KNN_QT];
-#pragma unroll
-    for (int s = 0; s < KNN_QT; s++) acc[s] = 0.f;
-    for (int d0 = 0; d0 < d; d0 += KNN_DT) {
-      __syncthreads();
-      for (int e = tid; e < KNN_THREADS * KNN_DT; e += KNN_THREADS) {
-        const int r = e / KNN_DT, c = e % KNN_DT;
-        const int row = base + r, dim = d0 + c;
-        xs[r * (KNN_DT + 1) + c] = (row < n && dim < d) ? X[(size_t)row * d + dim] : 0.f;
-      }
-      __syncthreads();
-      const int dl = min(KNN_DT, d - d0);
-      for (int c = 0; c < dl; c++) {
-        const float x = xs[tid * (KNN_DT + 1) + c];
-        const float *qv = qt + (size_t)(d0 + c) * KNN_QT;
-#pragma unroll
-        for (int s = 0; s < KNN_QT; s++) {
-          const float dx = qv[s] - x;   // as knn_kernel: query minus row, unfused
-          acc[s] += dx * dx;
-        }
-      }
-    }
+    exact_tile(X, n, d, qt, xs, tid, [&](int r) { return base + r; }, acc);
     const int row = base + tid;
     const bool valid = row >= row_from && row < row_until;
     const unsigned long long vmask = __ballot(valid);
@@ -214,33 +177,17 @@ __global__ __launch_bounds__(KNN_THREADS) void cosmul_exact_scan(const float *__
     for (int u = 0; u < QW; u++) {
       if (ne[u] == 0) continue;   // (wave-uniform)
       const float key = cosmul_key<EP>([&](int t) { return acc[u * EP + t]; }, ne[u], pos[u]);
-      offer_rows(wl[u], cnt[u], key, valid, vmask, base + wave * 64, keff, lane);
+      wave_offer(wl[u], cnt[u], key, valid, vmask, base + wave * 64, keff, lane);
     }
   }
   __syncthreads();
-#pragma unroll
-  for (int u = 0; u < QW; u++) {
-    sv[(u * NW + wave) * 64 + lane] = wl[u].v;
-    si[(u * NW + wave) * 64 + lane] = wl[u].i;
-  }
-  __syncthreads();
-  for (int u = wave; u < QW; u += NW) {
-    WaveList out;
-    out.init();
-    for (int w2 = 0; w2 < NW; w2++) {
-      for (int e = 0; e < keff; e++) {
-        const float cv = sv[(u * NW + w2) * 64 + e];
-        const int cr = si[(u * NW + w2) * 64 + e];
-        if (cr == INT_MAX) break;
-        if (out.accepts(cv, cr)) out.insert(cv, cr, keff, lane);
-      }
-    }
+  merge_wave_lists<QW, NW>(wl, sv, si, keff, lane, wave, [&](int u, const WaveList &out) {
     if (lane < keff) {   // (every question slot of the tile has its lists: part_* hold ceil(b / 16) * 16 questions)
       const size_t o = ((size_t)(tile * QW + u) * nchunks + chunk) * keff + lane;
       part_v[o] = out.v;
       part_i[o] = out.i;
     }
-  }
+  });
 }
 
 __global__ void cosmul_negate(float *__restrict__ v, long long n) {
@@ -320,7 +267,7 @@ __device__ __forceinline__ void flat_rows(const uint8_t *__restrict__ codes, int
     const int row = rb * 64 + lane;
     const bool valid = row >= row_from && row < row_until;
     const float key = cosmul_key<E>([&](int t) { return acc[t]; }, E, pos);
-    offer_rows(wl, cnt, key, valid, __ballot(valid), rb * 64 + row_base, keff, lane);
+    wave_offer(wl, cnt, key, valid, __ballot(valid), rb * 64 + row_base, keff, lane);
   }
 }
 
@@ -368,25 +315,13 @@ __global__ __launch_bounds__(CF_THREADS) void cosmul_flat_scan(const uint8_t *__
     }
 #undef CF_ROWS
   }
-  sv[wave * 64 + lane] = wl.v;
-  si[wave * 64 + lane] = wl.i;
-  __syncthreads();
-  if (wave != 0) return;
-  WaveList out;
-  out.init();
-  for (int w2 = 0; w2 < NW; w2++) {
-    for (int e = 0; e < keff; e++) {
-      const float cv = sv[w2 * 64 + e];
-      const int cr = si[w2 * 64 + e];
-      if (cr == INT_MAX) break;
-      if (out.accepts(cv, cr)) out.insert(cv, cr, keff, lane);
+  merge_wave_lists<1, NW>(&wl, sv, si, keff, lane, wave, [&](int, const WaveList &out) {
+    if (lane < keff) {
+      const size_t o = ((size_t)q * nchunks + chunk) * keff + lane;
+      part_v[o] = out.v;
+      part_i[o] = out.i;
     }
-  }
-  if (lane < keff) {
-    const size_t o = ((size_t)q * nchunks + chunk) * keff + lane;
-    part_v[o] = out.v;
-    part_i[o] = out.i;
-  }
+  });
 }
 
 void rethrow(int32_t rc) {   // a nested entry point has recorded its message
@@ -418,12 +353,9 @@ int check_cosmul_host(const int32_t *off, const int32_t *rows, const float *w, i
 
 CosmulShape cosmul_exact_shape(int from, int until, int b) {
   const int nb = std::min(EXACT_SUB_BATCH, b);
-  const int rbeg = (from / KNN_THREADS) * KNN_THREADS;
-  const int groups = std::max(1, ceil_div(until - rbeg, KNN_THREADS));
-  // the row chunks: about 2048 workgroups at four questions each, whatever E' turns out to be
-  const int want = std::max(1, ceil_div(2048, ceil_div(nb, 4)));
-  const int groups_per_chunk = ceil_div(groups, std::min(want, groups));
-  return {EXACT_SUB_BATCH, ceil_div(groups, groups_per_chunk), groups_per_chunk};
+  // about 2048 workgroups at four questions each, whatever E' turns out to be
+  const RowChunks c = knn_row_chunks(from, until, ceil_div(nb, 4));
+  return {EXACT_SUB_BATCH, c.nchunks, c.groups_per_chunk};
 }
 
 CosmulShape cosmul_flat_shape(const gulon_index *ix, int from, int until, int b) {

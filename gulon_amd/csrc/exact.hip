@@ -5,13 +5,13 @@
 //   sample   exact_pass<true>   exact distances of S rows spread evenly over [from, until) -> [B][S]
 //   bound    exact_tau          tau_q = the (k_nn + 1)-th smallest of them: the distance of a real row, so an upper bound
 //                               of the true (k_nn + 1)-th distance
-//   main     exact_pass<false>  one read of [from, until), knn_kernel's tiling; every row with distance <= tau_q is
+//   main     exact_pass<false>  one read of [from, until), distances by exact_tile; every row with distance <= tau_q is
 //                               appended to the query's queue as (distance bits << 32) | row
 //   select   exact_select       per query: radix-select the (k_nn + 1)-th key, keep the keys up to it, sort, write
 //
 // The answer of a query whose distances are all finite is the (distance, row id) order of gulon_exact_knn, whatever the
-// order of its queue.  A query whose queue overflowed is answered by the peeled path (knn_kernel + launch_merge +
-// launch_peel_*, called, not copied) in a compacted sub-batch; a query that met a NaN / +inf distance by the same path in
+// order of its queue.  A query whose queue overflowed is answered by the peeled path (knn.hip's exact_knn_dev) in a
+// compacted sub-batch; a query that met a NaN / +inf distance by the same path in
 // a batch of one, which is what gulon_exact_knn gives it when asked alone.
 //
 // Expression queries: dataset_compose.hip composes the term rows of the dataset, the handle answers the
@@ -39,8 +39,7 @@ __device__ __forceinline__ int slot_row(int from, int range, int S, int j) {
   return SAMPLE ? from + (int)((long long)j * range / S) : from + j;
 }
 
-// Distances of 16 queries to 256 slots per step, as knn_kernel computes them: rows staged in LDS 32 dims at a time,
-// lane = row, acc += (q_e - x_e) * (q_e - x_e) with e ascending, unfused.
+// Distances of 16 queries to 256 slots per step (exact_tile), written out (sample) or queued when at or below tau.
 template <bool SAMPLE>
 __global__ __launch_bounds__(KNN_THREADS) void exact_pass(const float *__restrict__ X, int d, const float *__restrict__ Qt,
                                                           int B, int from, int range, int S, int slots_per_chunk,
@@ -65,29 +64,9 @@ __global__ __launch_bounds__(KNN_THREADS) void exact_pass(const float *__restric
 
   for (int base = s0; base < s1; base += KNN_THREADS) {
     float acc[KNN_QT];
-#pragma unroll
-    for (int q = 0; q < KNN_QT; q++) acc[q] = 0.f;
-    __syncthreads();   // the previous step's readers of rowid / xs are done
+    __syncthreads();   // the previous step's readers of rowid are done
     rowid[tid] = base + tid < s1 ? slot_row<SAMPLE>(from, range, S, base + tid) : -1;
-    for (int d0 = 0; d0 < d; d0 += KNN_DT) {
-      __syncthreads();
-      for (int e = tid; e < KNN_THREADS * KNN_DT; e += KNN_THREADS) {
-        const int r = e / KNN_DT, c = e % KNN_DT;
-        const int row = rowid[r], dim = d0 + c;
-        xs[r * (KNN_DT + 1) + c] = (row >= 0 && dim < d) ? X[(size_t)row * d + dim] : 0.f;
-      }
-      __syncthreads();
-      const int dl = min(KNN_DT, d - d0);
-      for (int c = 0; c < dl; c++) {
-        const float x = xs[tid * (KNN_DT + 1) + c];
-        const float *qv = qt + (size_t)(d0 + c) * KNN_QT;
-#pragma unroll
-        for (int q = 0; q < KNN_QT; q++) {
-          const float dx = qv[q] - x;   // dx = y(i) - x(i), y = query (MathUtils.scala:90)
-          acc[q] += dx * dx;
-        }
-      }
-    }
+    exact_tile(X, from + range, d, qt, xs, tid, [&](int r) { return rowid[r]; }, acc);
     const int slot = base + tid;
     const bool valid = slot < s1;
     if (SAMPLE) {
@@ -303,9 +282,7 @@ struct gulon_exact_index {
   DevBuf<int> overflow, nonfinite, ids, count_tmp, flags_tmp;
   DevBuf<float> fq, fd;
   DevBuf<int> fi, fc, ff;
-  // the single-pass / peeled path of knn.hip
-  DevBuf<float> l_qt, l_pv, l_accv, l_tv, l_lbv;
-  DevBuf<int> l_pi, l_acci, l_ti, l_lbi;
+  KnnScratch knn;                      // the single-pass / peeled path of knn.hip
   // the host-pointer forms
   DevBuf<float> stage_q, stage_od;
   DevBuf<int> stage_rows, stage_oi, stage_oc, stage_of;
@@ -340,52 +317,10 @@ void order_record(gulon_exact_index *h, hipStream_t st) {
   h->order_set = true;
 }
 
-// gulon_exact_knn's device work for b queries at d_q, on `st`, with its launch geometry: k_nn <= GULON_MAX_K in one
-// knn_kernel pass and launch_merge, larger k_nn peeled 64 entries per pass.  Outputs are device pointers, none null.
+// gulon_exact_knn's answer for b queries at d_q: the single-pass / peeled driver of knn.hip on the handle's range
 void legacy_dev(gulon_exact_index *h, const float *d_q, int b, int K, int *oi, float *od, int *oc, int *of,
                 hipStream_t st) {
-  const gulon_dataset *ds = h->ds;
-  const int from = h->from, until = h->until, d = ds->d;
-  const bool peeled = K > GULON_MAX_K;
-  const int keff = peeled ? 64 : K + 1;
-  const int ntiles = ceil_div(b, KNN_QT);
-  const int rbeg = (from / KNN_THREADS) * KNN_THREADS;
-  const int groups = ceil_div(until - rbeg, KNN_THREADS);
-  int want = ceil_div(2048, ntiles);
-  int nchunks = want < groups ? want : groups;
-  int groups_per_chunk = ceil_div(groups, nchunks);
-  nchunks = ceil_div(groups, groups_per_chunk);
-  const int rows_per_chunk = groups_per_chunk * KNN_THREADS;
-  const int Bp = ntiles * KNN_QT;
-  h->l_qt.ensure((size_t)ntiles * d * KNN_QT);
-  h->l_pv.ensure((size_t)Bp * nchunks * keff);
-  h->l_pi.ensure((size_t)Bp * nchunks * keff);
-  const long long tq = (long long)ntiles * d * KNN_QT;
-  hipLaunchKernelGGL(transpose_queries, dim3(ceil_div(tq, 256)), dim3(256), 0, st, d_q, b, d, ntiles, h->l_qt.p);
-  if (peeled) {
-    const int rounds = ceil_div(K + 1, 64), cap = rounds * 64;
-    h->l_accv.ensure((size_t)b * cap); h->l_acci.ensure((size_t)b * cap);
-    h->l_tv.ensure((size_t)b * 64); h->l_ti.ensure((size_t)b * 64);
-    h->l_lbv.ensure(Bp); h->l_lbi.ensure(Bp);
-    HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)h->l_lbv.p, 0xBF800000 /* -1.0f */, (size_t)Bp, st));
-    HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)h->l_lbi.p, 0xFFFFFFFF, (size_t)Bp, st));
-    for (int r = 0; r < rounds; r++) {
-      hipLaunchKernelGGL(knn_kernel, dim3(ntiles, nchunks), dim3(KNN_THREADS), 0, st, ds->x.p, ds->n, d, h->l_qt.p, from,
-                         until, rows_per_chunk, nchunks, 64, h->l_pv.p, h->l_pi.p, h->l_lbv.p, h->l_lbi.p);
-      HIP_CHECK(hipGetLastError());
-      launch_merge(false, h->l_pv.p, h->l_pi.p, nchunks, 64LL, (long long)nchunks * 64, b, 63, nullptr, nullptr, nullptr,
-                   nullptr, h->l_tv.p, h->l_ti.p, st);
-      launch_peel_update(h->l_tv.p, h->l_ti.p, b, r, cap, h->l_accv.p, h->l_acci.p, h->l_lbv.p, h->l_lbi.p, st);
-    }
-    launch_peel_finalize(h->l_accv.p, h->l_acci.p, b, cap, K, oi, od, oc, of, st);
-  } else {
-    hipLaunchKernelGGL(knn_kernel, dim3(ntiles, nchunks), dim3(KNN_THREADS), 0, st, ds->x.p, ds->n, d, h->l_qt.p, from,
-                       until, rows_per_chunk, nchunks, keff, h->l_pv.p, h->l_pi.p, (const float *)nullptr,
-                       (const int *)nullptr);
-    HIP_CHECK(hipGetLastError());
-    launch_merge(true, h->l_pv.p, h->l_pi.p, nchunks, (long long)keff, (long long)nchunks * keff, b, K, oi, od, oc, of,
-                 nullptr, nullptr, st);
-  }
+  exact_knn_dev(h->ds, h->from, h->until, d_q, b, K, h->knn, oi, od, oc, of, st);
 }
 
 // k_nn <= GULON_MAX_K: knn_kernel's single pass.  It has no test for non-finite distances, so exact_screen flags the
@@ -460,11 +395,9 @@ void large_k_dev(gulon_exact_index *h, const float *dQ, int B, int K, int *oi, f
     const long long tq = (long long)ntiles * d * KNN_QT;
     hipLaunchKernelGGL(transpose_queries, dim3(ceil_div(tq, 256)), dim3(256), 0, st, dq, b, d, ntiles, h->qt.p);
     auto shape = [&](int total, int &per_chunk, int &nchunks) {   // about 64 workgroups per compute unit
-      const int groups = ceil_div(total, KNN_THREADS);
-      const int want = std::max(1, ceil_div((long long)cus * 64, ntiles));
-      const int gpc = ceil_div(groups, std::min(want, groups));
-      per_chunk = gpc * KNN_THREADS;
-      nchunks = ceil_div(groups, gpc);
+      const RowChunks c = split_groups(row_groups(0, total), ceil_div((long long)cus * 64, ntiles));
+      per_chunk = c.groups_per_chunk * KNN_THREADS;
+      nchunks = c.nchunks;
     };
     int per_chunk = 0, nchunks = 0;
     if (sampled) {

@@ -323,23 +323,7 @@ __device__ __forceinline__ void scan_body(
   __syncthreads();
   float *sv = reinterpret_cast<float *>(lds_raw);
   int *si = reinterpret_cast<int *>(sv + QT * NW * 64);
-#pragma unroll
-  for (int q = 0; q < QT; q++) {
-    sv[(q * NW + wave) * 64 + lane] = wl[q].v;
-    si[(q * NW + wave) * 64 + lane] = wl[q].i;
-  }
-  __syncthreads();
-  for (int q = wave; q < QT; q += NW) {
-    WaveList out;
-    out.init();
-    for (int w2 = 0; w2 < NW; w2++) {
-      for (int e = 0; e < keff; e++) {
-        float cv = sv[(q * NW + w2) * 64 + e];
-        int cr = si[(q * NW + w2) * 64 + e];
-        if (cr == INT_MAX) break;  // sorted: the rest of this list is padding
-        if (out.accepts(cv, cr)) out.insert(cv, cr, keff, lane);
-      }
-    }
+  merge_wave_lists<QT, NW>(wl, sv, si, keff, lane, wave, [&](int q, const WaveList &out) {
     if (lane < keff) {
       size_t o = ((size_t)(tile * QT + q) * nchunks + chunk) * keff + lane;
       part_v[o] = out.v;
@@ -348,7 +332,7 @@ __device__ __forceinline__ void scan_body(
     if (lane == 0 && out.tau < INFINITY)
       __hip_atomic_fetch_min(&gtau[tile * QT + q], __float_as_uint(out.tau), __ATOMIC_RELAXED,
                              __HIP_MEMORY_SCOPE_AGENT);
-  }
+  });
 }
 
 #define GULON_SCAN_PARAMS                                                                                          \

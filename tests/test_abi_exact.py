@@ -33,15 +33,14 @@ def test_exact_is_in_the_makefile():
     assert "$(CSRC)/exact.hip" in open(os.path.join(ROOT, "Makefile")).read()
 
 
-def test_exact_kernels_use_no_scratch():
-    """The distance tile with its sixteen accumulators and the per-wave append, the two radix selects and the LDS sort
-    keep everything in registers."""
+def kernel_scratch(source):
+    """{mangled kernel name: scratch bytes per lane} of one file of csrc, compiled for the device only."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
     cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
            "-fvisibility=hidden", "-I" + os.path.join(ROOT, "include"), "--cuda-device-only", "-c",
-           os.path.join(ROOT, "gulon_amd", "csrc", "exact.hip"), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
+           os.path.join(ROOT, "gulon_amd", "csrc", source), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
     out = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
     name, scratch = None, {}
     for line in out.splitlines():
@@ -51,7 +50,28 @@ def test_exact_kernels_use_no_scratch():
         m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
         if m and name:
             scratch[name] = int(m.group(1))
+    return scratch
+
+
+def test_exact_kernels_use_no_scratch():
+    """The distance tile with its sixteen accumulators and the per-wave append, the two radix selects and the LDS sort
+    keep everything in registers."""
+    scratch = kernel_scratch("exact.hip")
     assert len(scratch) == len(KERNELS), scratch
     for k in KERNELS:
         assert sum(k in name for name in scratch) == 1, (k, sorted(scratch))
     assert set(scratch.values()) == {0}, scratch
+
+
+@pytest.mark.parametrize("source,kernels", [
+    ("knn.hip", ("knn_kernelE",)),
+    ("cosmul.hip", ("cosmul_exact_scanILi1E", "cosmul_exact_scanILi2E", "cosmul_exact_scanILi4E",
+                    "cosmul_exact_scanILi8E", "cosmul_flat_scanILi4E", "cosmul_flat_scanILi16E"))])
+def test_tile_and_list_users_use_no_scratch(source, kernels):
+    """The other callers of the distance tile (exact.hpp) and of the WaveList helpers (common.hpp): sixteen accumulators
+    beside up to sixteen lists, at 124 and 127 of the 128 registers that two waves per SIMD allow, spill nothing."""
+    scratch = kernel_scratch(source)
+    for k in kernels:
+        hits = [name for name in scratch if k in name]
+        assert len(hits) == 1, (k, sorted(scratch))
+        assert scratch[hits[0]] == 0, (hits[0], scratch)
