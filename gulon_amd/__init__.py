@@ -23,6 +23,8 @@ from .expressions import (COSMUL_EPS, Expression, Term, compose_reference, cosmu
                           partition_by_operands)
 from .rotation import RotatedWordIndex, Rotation, rotate_reference, train_rotation
 from .analogies import AnalogyReport, evaluate_analogies, read_questions
+from .similarity import (SimilarityReport, evaluate_pairs, pair_distance_reference, rank_sums, rank_sums_reference,
+                         read_pairs, spearman)
 
 __all__ = ["native", "GroupedIndex", "GroupedVectors", "LimitGroups", "LimitVectors", "group", "Coder", "width_for_clusters", "Index", "PQIndex", "PQIndexView", "DevicePQIndex", "Result", "SortedIndex",
            "exact_nearest_neighbours", "prepare_query", "tune_live", "KMeans", "KMeansConfig", "DeviceMatrix", "Matrix",
@@ -33,4 +35,5 @@ __all__ = ["native", "GroupedIndex", "GroupedVectors", "LimitGroups", "LimitVect
            "partition_by_operands", "IndexReport", "reference_quality", "UpdatePlan", "plan_update", "FineRefinedIndex", "build_fine_index",
            "refine_codes_topk", "row_residuals", "Rotation", "RotatedWordIndex", "train_rotation", "rotate_reference",
            "ExactIndex", "ExactWordIndex", "AnalogyReport", "evaluate_analogies", "read_questions",
-           "COSMUL_EPS", "cosmul_reference"]
+           "COSMUL_EPS", "cosmul_reference", "SimilarityReport", "evaluate_pairs", "read_pairs",
+           "pair_distance_reference", "rank_sums", "rank_sums_reference", "spearman"]

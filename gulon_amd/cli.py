@@ -1,5 +1,5 @@
-"""`python -m gulon_amd`: the reference's four commands (command/Main.scala:7-11), `inspect`, `update`, `build-fine` and
-`analogies`.
+"""`python -m gulon_amd`: the reference's four commands (command/Main.scala:7-11), `inspect`, `update`, `build-fine`,
+`analogies` and `similarity`.
 
   build-index -d l2|cosine -o INDEX [-k N] [-m N] [-n N] [-p [--partitions N] [-l N]] [-R ROTATION [--rotation-rounds N]]
               FILE
@@ -58,6 +58,20 @@
                                        rows by 3CosMul instead (csrc/cosmul.hip): s(d, b) * s(d, c) / (s(d, a) + 0.001)
                                        with s = (1 + cos) / 2, for a flat cosine index alone or with -v --exact.
                                        query-words -x --method mul answers expressions the same way
+
+  similarity -i INDEX [--lowercase] [-v VECTORS --exact] FILE
+                                       (not in the reference) Spearman's rank correlation between the human scores of a
+                                       word-pair similarity file (WordSim-353, SimLex-999, MEN, RW ...) and the distances
+                                       the index puts between the words of every pair (similarity.py, csrc/pairs.hip).
+                                       FILE: lines of `word1 word2 score`; blank lines and lines starting with # are
+                                       skipped; `: name` opens a section, so several benchmarks fit in one file.  One line
+                                       per section, `name: rho 0.6532 (n = 353, skipped 12, dropped 0)` -- n the pairs
+                                       ranked, skipped those with a word the index lacks, dropped those whose distance is
+                                       NaN -- and a `total:` line over the pooled pairs.  rho is that of the scores
+                                       against the similarity, i.e. the negated rho of the distances.  The target is the
+                                       index alone; with -v --exact the true vectors of the index's words.  Distances
+                                       and ranks are computed on the device.  -R is not offered: distances between stored
+                                       rows need no rotation
 
 -f FINE on the query commands and on test (not in the reference): as -v / -c, but the candidates are re-ranked by their
 distance to the index's row plus the fine index's row of the same word (fine.FineRefinedIndex) -- no original vectors in
@@ -211,6 +225,15 @@ class AnalogiesConfig:
     exact: bool = False                   # --exact: the true vectors of the index's words are the target
     candidates: Optional[int] = None      # -c: candidates of the refined form (default 10 * the largest k)
     method: str = "add"                   # --method: add (3CosAdd, the neighbours of b - a + c) or mul (3CosMul)
+
+
+@dataclass(frozen=True)
+class SimilarityConfig:
+    index: str
+    pairs: str
+    lowercase: bool = False               # --lowercase: lower the pairs' words
+    vectors: Optional[str] = None         # -v: the vectors the index was built from (with --exact)
+    exact: bool = False                   # --exact: the true vectors of the index's words are the target
 
 
 def _depths(s):
@@ -376,6 +399,16 @@ def _parser():
                         "3CosMul, cos(d, b) * cos(d, c) / (cos(d, a) + 0.001) with the cosines shifted into [0, 1] (a "
                         "cosine index; with --vectors only together with --exact)")
     a.add_argument("file", metavar="file", help="questions: `: section` lines and lines of `a b c d`")
+    s = sub.add_parser("similarity", help="report the word-pair rank correlation of an index",
+                       description="report Spearman's rank correlation between the human scores of a word-pair "
+                                   "similarity file and the index's distances: one line per section and a total")
+    s.add_argument("-i", "--index", required=True, metavar="file", help="path to ANN index")
+    s.add_argument("--lowercase", action="store_true", help="lower the words of the pairs")
+    s.add_argument("-v", "--vectors", default=None, metavar="file",
+                   help="word2vec word vectors the index was built from (needs --exact)")
+    s.add_argument("--exact", action="store_true",
+                   help="with --vectors: evaluate the original vectors of the index's words instead of its rows")
+    s.add_argument("file", metavar="file", help="pairs: `: section` lines and lines of `word1 word2 score`")
     u = sub.add_parser("update", help="add, replace and remove words of an index without retraining",
                        description="add, replace and remove words of an index without retraining")
     u.add_argument("-i", "--index", required=True, metavar="file", help="path to ANN index")
@@ -610,6 +643,31 @@ def run_analogies(config: AnalogiesConfig, load, vectors):
         raise AnalogiesError(str(e))
 
 
+class SimilarityError(Exception):
+    """What `similarity` reports and exits on: an unreadable or malformed pairs file, vectors that lack a word of the
+    index, more pairs than can be ranked."""
+
+
+def run_similarity(config: SimilarityConfig, load, vectors):
+    """similarity between its argument handling and its lines -> similarity.SimilarityReport.  For a cosine index the
+    vectors are read normalised, as the query commands read them."""
+    from .similarity import evaluate_pairs, read_pairs
+    try:
+        with open(config.pairs, "rb") as fh:
+            sections = read_pairs(read_lines(fh.read()), config.lowercase)
+    except OSError as e:
+        raise SimilarityError(f"{config.pairs}: {e.strerror or e}")
+    except ValueError as e:
+        raise SimilarityError(f"{config.pairs}: {e}")
+    index = load(config.index)
+    try:
+        if config.exact:
+            index = index.exact(vectors(config.vectors, index.metric == "cosine"))
+        return evaluate_pairs(index, sections)
+    except (LookupError, NotImplementedError, ValueError) as e:
+        raise SimilarityError(str(e))
+
+
 def read_originals(path, normalize):
     """The -v vectors of the query commands: on the device, in word order (their key index resolves the index's words)."""
     from .word_vectors import read_word2vec_device
@@ -651,7 +709,7 @@ def _refined(args, index, vectors, load):
 
 
 def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None, vectors=None, inspect=None,
-         update=None, fine=None, rotation=None, analogies=None):
+         update=None, fine=None, rotation=None, analogies=None, similarity=None):
     """Returns the exit code.  stdin / stdout: binary streams (default: the process's); load: path -> index with
     batch_query_by_words / batch_query (default WordIndex.load); build: (BuildConfig, write) -> None, the whole of
     build-index behind its argument handling (default run_build_index); recall: (RecallConfig, write, load) ->
@@ -662,9 +720,15 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
     of update behind its argument handling (default run_update); fine: (FineConfig, write, load) -> None, the whole of
     build-fine behind its argument handling (default run_build_fine).  The fine index behind -f is read with `load`.  rotation: path -> the rotation behind -R of the
     query commands (default Rotation.load).  analogies: (AnalogiesConfig, load, vectors) -> AnalogyReport, the whole of
-    analogies between its argument handling and its lines (default run_analogies)."""
+    analogies between its argument handling and its lines (default run_analogies).  similarity: (SimilarityConfig, load,
+    vectors) -> SimilarityReport, the same for similarity (default run_similarity)."""
     parser = _parser()
     args = parser.parse_args(argv)
+    if args.command == "similarity":
+        if args.exact and args.vectors is None:
+            parser.error("--exact needs -v/--vectors")
+        if args.vectors is not None and not args.exact:
+            parser.error("--vectors is only applicable with --exact")
     if args.command == "analogies":
         if args.exact and args.vectors is None:
             parser.error("--exact needs -v/--vectors")
@@ -747,6 +811,16 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
         try:
             report = (analogies if analogies is not None else run_analogies)(config, load, vectors)
         except AnalogiesError as e:
+            stdout.flush()
+            print(f"error: {e}", file=sys.stderr)
+            return 1
+        for line in report.lines():
+            write(line + "\n")
+    elif args.command == "similarity":
+        config = SimilarityConfig(args.index, args.file, args.lowercase, args.vectors, args.exact)
+        try:
+            report = (similarity if similarity is not None else run_similarity)(config, load, vectors)
+        except SimilarityError as e:
             stdout.flush()
             print(f"error: {e}", file=sys.stderr)
             return 1

@@ -98,6 +98,16 @@ class ExactIndex:
         """The rows themselves: [len(rows)][dimension]."""
         return self.matrix.get_rows(rows)
 
+    def pair_distances(self, rows_a, rows_b):
+        """MathUtils.distanceSq between rows rows_a[i] and rows_b[i] of the MATRIX -- the ids the queries return -- for
+        every i, on the device (gulon_dataset_pair_distances).  -> [n] float32."""
+        from .similarity import pair_distances_raw
+        return pair_distances_raw(N.lib().gulon_dataset_pair_distances, self.matrix._h, rows_a, rows_b)
+
+    def pair_distances_dev(self, d_rows_a, d_rows_b, n, d_dist, stream=None):
+        """The device form: the rows and the distances device addresses; `stream` is waited for."""
+        N.check(N.lib().gulon_dataset_pair_distances_dev(self.matrix._h, d_rows_a, d_rows_b, n, d_dist, stream))
+
     # ---- expression queries (expressions.py; DESIGN.md 9u): the terms are rows of the MATRIX
     def compose_rows(self, expressions):
         """The query vector of every expression over row ids as this index prepares it -- terms and sum normalised for a
@@ -209,6 +219,12 @@ class ExactWordIndex:
         """The word's original vector, None if it is absent."""
         row = self.row_of(word)
         return None if row is None else self.index.lookup_rows([row])[0]
+
+    def distances(self, pairs):
+        """Per (word1, word2) the distance between the two words' original vectors, on the device; None where a word is
+        absent."""
+        from .similarity import word_distances
+        return word_distances(self, pairs)
 
     def _result(self, r) -> WordResult:
         return WordResult([self.words[i] for i in r.rows.tolist()], r.distances, r.rows, r.flags)

@@ -150,6 +150,17 @@ class GroupedIndex:
     def lookup_row(self, row):
         return self.lookup_rows([row])[0]
 
+    def pair_distances(self, rows_a, rows_b):
+        """MathUtils.distanceSq(lookup_rows(rows_a)[i], lookup_rows(rows_b)[i]) for every i, on the device
+        (gulon_grouped_index_pair_distances): between the vectors lookup_rows hands out, so with ITS partition rule, not
+        with the row's own group as row_errors.  -> [n] float32."""
+        from .similarity import pair_distances_raw
+        return pair_distances_raw(N.lib().gulon_grouped_index_pair_distances, self._h, rows_a, rows_b)
+
+    def pair_distances_dev(self, d_rows_a, d_rows_b, n, d_dist, stream=None):
+        """The device form: the rows and the distances device addresses; `stream` is waited for."""
+        N.check(N.lib().gulon_grouped_index_pair_distances_dev(self._h, d_rows_a, d_rows_b, n, d_dist, stream))
+
     def code_histogram(self, from_=0, until=None):
         """H[j][c] = the number of rows in [from_, until) whose residual code at quantizer j is c, counted on the
         device (gulon_grouped_index_code_histogram).  -> int64 [m][k]."""

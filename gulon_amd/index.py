@@ -167,6 +167,16 @@ class PQIndex:
         return row_errors_raw(N.lib().gulon_index_row_errors, self._h, len(self.product_quantizer.quantizers),
                               self.length, matrix, row_map, from_, until, norms)
 
+    def pair_distances(self, rows_a, rows_b):
+        """MathUtils.distanceSq(decode(rows_a[i]), decode(rows_b[i])) for every i, on the device
+        (gulon_index_pair_distances; similarity.pair_distance_reference).  -> [n] float32."""
+        from .similarity import pair_distances_raw
+        return pair_distances_raw(N.lib().gulon_index_pair_distances, self._h, rows_a, rows_b)
+
+    def pair_distances_dev(self, d_rows_a, d_rows_b, n, d_dist, stream=None):
+        """The device form: the rows and the distances device addresses; `stream` is waited for."""
+        N.check(N.lib().gulon_index_pair_distances_dev(self._h, d_rows_a, d_rows_b, n, d_dist, stream))
+
     def batch_query_rows_raw(self, k, rows, frm=0, until=None, normalize=False):
         r = N.i32(rows).reshape(-1)
         until = self.length if until is None else until
@@ -509,6 +519,13 @@ class SortedIndex:
         """Index.queryByWord (Index.scala:38-45) on row ids: query(k, lookup(row)) for every row, decoded (and for a
         cosine index normalised, Index.scala:324-331) on the device."""
         return self.vector_index.batch_query_rows(k, rows, normalize=self.metric == "cosine")
+
+    def pair_distances(self, rows_a, rows_b):
+        """The distance between lookup_rows(rows_a)[i] and lookup_rows(rows_b)[i] for every i, on the device."""
+        return self.vector_index.pair_distances(rows_a, rows_b)
+
+    def pair_distances_dev(self, d_rows_a, d_rows_b, n, d_dist, stream=None):
+        self.vector_index.pair_distances_dev(d_rows_a, d_rows_b, n, d_dist, stream)
 
     def code_histogram(self, from_=0, until=None):
         return self.vector_index.code_histogram(from_, until)

@@ -207,6 +207,14 @@ SIGNATURES = {
     "gulon_exact_index_query_cosmul_dev": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gulon_index_query_cosmul": (_i32, [_vp, _i32p, _i32p, _f32p, _i32, _i32, _i32, _i32, _i32, _i32p, _f32p, _i32p]),
     "gulon_index_query_cosmul_dev": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "gulon_index_pair_distances": (_i32, [_vp, _i32p, _i32p, _i32, _f32p]),
+    "gulon_index_pair_distances_dev": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp]),
+    "gulon_grouped_index_pair_distances": (_i32, [_vp, _i32p, _i32p, _i32, _f32p]),
+    "gulon_grouped_index_pair_distances_dev": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp]),
+    "gulon_dataset_pair_distances": (_i32, [_vp, _i32p, _i32p, _i32, _f32p]),
+    "gulon_dataset_pair_distances_dev": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp]),
+    "gulon_rank_sums": (_i32, [_f32p, _f32p, _vp, _i32, _i32, _i64p]),
+    "gulon_rank_sums_dev": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),
 }
 
 _lib = None

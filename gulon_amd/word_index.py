@@ -128,6 +128,12 @@ class WordIndex:
         row = self.row_of(word)
         return None if row is None else self.index.lookup_rows([row])[0]
 
+    def distances(self, pairs):
+        """Per (word1, word2) the distance between lookup(word1) and lookup(word2) -- MathUtils.distanceSq, on the
+        device (csrc/pairs.hip) -- None where a word is absent."""
+        from .similarity import word_distances
+        return word_distances(self, pairs)
+
     def _result(self, r) -> WordResult:
         return WordResult([self.words[i] for i in r.rows.tolist()], r.distances, r.rows, r.flags)
 
@@ -240,6 +246,9 @@ class RestrictedWordIndex(WordIndex):
 
     def lookup(self, word):
         return self.parent.lookup(word)
+
+    def distances(self, pairs):
+        return self.parent.distances(pairs)
 
     def batch_query_by_words(self, k, words) -> List[Optional[WordResult]]:
         """queryByWord with the word's vector decoded from the PARENT and the neighbours taken from the restriction."""

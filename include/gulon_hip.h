@@ -872,6 +872,45 @@ int32_t gulon_index_query_cosmul_dev(gulon_index *idx, const int32_t *d_term_off
                                      const float *d_term_weights, int32_t b, int32_t k_nn, int32_t normalize,
                                      int32_t from, int32_t until, int32_t *d_out_idx, float *d_out_score,
                                      int32_t *d_out_count, void *stream);
+
+/* ---- Word-pair similarity (pairs.hip) -------------------------------------------------------------------
+ * gulon_*_pair_distances: for n pairs of row ids, out_dist[i] = MathUtils.distanceSq(y_a[i], y_b[i])
+ * (MathUtils.scala:85-95): binary32, t = y_a[e] - y_b[e]; sum += t * t, unfused, e ascending, one running sum from 0 --
+ * the arithmetic of gulon_index_row_errors.  y_r is the vector `lookup` returns for row r:
+ *   gulon_index           ProductQuantizer.decode of the row (gulon_index_decode_rows); a view's rows are its positions;
+ *   gulon_grouped_index   centroid + decode with the partition of GroupedIndex.lookup (gulon_grouped_index_lookup_rows),
+ *                         NOT the row's own group that gulon_grouped_index_row_errors uses;
+ *   gulon_dataset         the stored row as it is.
+ * A row id outside [0, rows of the handle) is GULON_ERR_INVALID_ARGUMENT: the host form checks before anything is launched
+ * and names the pair; the _dev form (device pointers, the work enqueued on `stream`, a hipStream_t, NULL allowed) finds
+ * it on the device -- nothing is read for that pair, its distance is NaN -- and reports it when the call returns: the
+ * _dev forms synchronise `stream` once.  n == 0 returns without touching the device.  The calls leave no scratch on a
+ * handle. */
+int32_t gulon_index_pair_distances(gulon_index *idx, const int32_t *rows_a, const int32_t *rows_b, int32_t n,
+                                   float *out_dist);
+int32_t gulon_index_pair_distances_dev(gulon_index *idx, const int32_t *d_rows_a, const int32_t *d_rows_b, int32_t n,
+                                       float *d_out_dist, void *stream);
+int32_t gulon_grouped_index_pair_distances(gulon_grouped_index *idx, const int32_t *rows_a, const int32_t *rows_b,
+                                           int32_t n, float *out_dist);
+int32_t gulon_grouped_index_pair_distances_dev(gulon_grouped_index *idx, const int32_t *d_rows_a,
+                                               const int32_t *d_rows_b, int32_t n, float *d_out_dist, void *stream);
+int32_t gulon_dataset_pair_distances(const gulon_dataset *ds, const int32_t *rows_a, const int32_t *rows_b, int32_t n,
+                                     float *out_dist);
+int32_t gulon_dataset_pair_distances_dev(const gulon_dataset *ds, const int32_t *d_rows_a, const int32_t *d_rows_b,
+                                         int32_t n, float *d_out_dist, void *stream);
+/* gulon_rank_sums: the integer sums of Spearman's rank correlation between x [n] and y [n], per section.  section [n]
+ * holds ids, in any order; NULL: one section, and nsections must be 1.  A pair is LIVE if neither x[i] nor y[i] is NaN
+ * and its section lies in [0, nsections).  For a live pair i, over the live pairs j of its section:
+ *   less_x = #{j : x[j] < x[i]},  eq_x = #{j : x[j] == x[i]}  (IEEE comparisons: -0 == +0, an infinity ties with itself, i
+ *   counts in eq),  cx = 2 * less_x + eq_x - n_s -- twice the centred average rank -- and cy likewise from y.
+ * out [nsections][5] = {n_s, sum cx * cy, sum cx * cx, sum cy * cy, dropped}: n_s the section's live pairs, dropped its
+ * pairs with a NaN.  out is overwritten.  Integer work only: exact, whatever the order.  0 <= n <= 2^20 (then every sum
+ * stays below 2^60) and nsections >= 1, checked before any device call.  An all-pairs count, O(n^2).  The _dev form takes
+ * device pointers (out too) and a stream and does not synchronise. */
+int32_t gulon_rank_sums(const float *x, const float *y, const int32_t *section, int32_t n, int32_t nsections,
+                        int64_t *out);
+int32_t gulon_rank_sums_dev(const float *d_x, const float *d_y, const int32_t *d_section, int32_t n, int32_t nsections,
+                            int64_t *d_out, void *stream);
 #ifdef GULON_TEST_HOOKS   /* libgulon_hip_testhooks.so only */
 /* The launch geometry of the 3CosMul scans (cosmul.hip), by the arithmetic their launchers run; host code, nothing is
  * launched.  b >= 1 questions.  Flat index, rows [from, until): out = {questions per pass, row chunks of the first
