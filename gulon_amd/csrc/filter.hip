@@ -380,7 +380,8 @@ template <> struct QEntry<4> { using type = uint32_t; };
 
 template <int QW, int NQG, int VEC, int NADD, int MAIN,
           int NG1 /* 1: a single code word per row (ng == 1); 2: and `codes` is the conflict-ordered copy, `perm` its row order;
-                     3: and `codes` is the key-sorted copy, `perm` its 32-bit row ids (conflict_order.hip) */>
+                     3: and `codes` is the key-sorted copy, `perm` its 32-bit row ids (conflict_order.hip) */,
+          int PFX = 0 /* key-sorted main stage: quantizers tested per row before the others are looked up (0: all at once) */>
 __global__ __launch_bounds__(FILTER_THREADS) void filter_kernel(
     const uint8_t *__restrict__ codes, const uint8_t *__restrict__ perm, int ng, int m_pad, const uint8_t *__restrict__ qtab, int row_from, int row_until,
     int rb_begin, int e_count, int e_per_chunk, RbMap mp, int *__restrict__ cnt, int *__restrict__ queue, int cap /* entries per sub-queue */,
@@ -477,25 +478,125 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_kernel(
     if (lane == 0) grab_v = atomicAdd(run_ctr, 1);
     w_first = cw[((size_t)block_of(mp_p, mp_r) * ng) * 64 + lane];
   }
-  while (run < nruns) {
-    const int rb = block_of(mp_p, mp_r);
-    // the block after this one
-    int e_n = e + 1, p_n = mp_p, r_n = mp_r + 1, run_n = run, end_n = e_run_end;
-    if (r_n == mp.width) { r_n = 0; p_n++; }
-    if (e_n == e_run_end) {
-      run_n = __builtin_amdgcn_readfirstlane(grab_v);
-      if (run_n < nruns) {
-        e_n = e0 + run_n * RUN;
-        end_n = min(e1, e_n + RUN);
-        locate(e_n, p_n, r_n);
-        if (lane == 0) grab_v = atomicAdd(run_ctr, 1);
+  // PFX: a row block is first tested on PFX of its sixteen quantizers only -- the two sorted ones (15, 14: half-price
+  // L1 look-ups, see above) and PFX - 2 from LDS.  Partial sums are <= full sums, so every (query, row) pair the full
+  // test keeps has a row that passes for some query of the tile; at the bench's bounds a few percent of the rows do.
+  // Such a lane appends its place in the sorted copy to the wave's ring in LDS (ballot + mbcnt, one ds_write_b32, the
+  // fill level uniform; nothing leaves the wave), and whenever the ring holds 64 places every lane takes one, gathers
+  // that row's code word (L2) and the wave runs the full sixteen look-ups, test and queueing below on them -- the
+  // same code, `pos` instead of rb * 64 + lane; what is left at the end of the wave's last run goes through with the
+  // idle lanes dead.  The stage's survivor set is the full test's, pair for pair.
+  constexpr int RING = 128;      // places per wave: < 64 waiting + <= 64 appended
+  int *ring = reinterpret_cast<int *>(qlds_raw + NQG * tab * QW / 16 + 1) + wave * RING;
+  int fill = 0, head = 0;        // (uniform; places appended / taken so far)
+  // Where the bounds separate little (rows without a tail of near ones: iid data) most rows pass, and the prefix test is
+  // work on top of the full one: by the vector instructions alone (per block: 110 full test, 78 prefix test, 114 full
+  // test of a ring) it pays while fewer than (110 - 78) / 114 = 0.28 of the rows pass.  A wave that has seen more than
+  // a quarter of its rows pass, over eight blocks or more, empties its ring and takes its remaining blocks whole, as
+  // without PFX.  (Per batch on the iid bench data: 2.63 ms without PFX, 4.13 with no switch, 2.92-2.95 with the switch
+  // at a quarter or at an eighth -- what is left is every wave's eight probe blocks and this kernel's whole-block turns
+  // against the kernel without PFX.  At an eighth waves of small ranges, whose bounds are looser, switch for nothing:
+  // 1.25 M rows 0.396 ms against 0.38 at a quarter, 1 M rows 0.356 against 0.34.)
+  int seen = 0;                  // blocks this wave has put through the prefix test
+  bool direct = false;
+  while (PFX ? (run < nruns || fill != head) : run < nruns) {
+    int rb = 0, pos = 0;
+    bool live = true;
+    Word w{};
+    const bool whole = PFX > 0 && direct && fill == head;    // this turn: one block, every lane its row (run < nruns here)
+    bool more = PFX > 0 ? whole || (!direct && run < nruns && fill - head < 64) : true;
+    while (more) {   // (without PFX, or `whole`: once)
+      rb = block_of(mp_p, mp_r);
+      // the block after this one
+      int e_n = e + 1, p_n = mp_p, r_n = mp_r + 1, run_n = run, end_n = e_run_end;
+      if (r_n == mp.width) { r_n = 0; p_n++; }
+      if (e_n == e_run_end) {
+        run_n = __builtin_amdgcn_readfirstlane(grab_v);
+        if (run_n < nruns) {
+          e_n = e0 + run_n * RUN;
+          end_n = min(e1, e_n + RUN);
+          locate(e_n, p_n, r_n);
+          if (lane == 0) grab_v = atomicAdd(run_ctr, 1);
+        }
       }
+      w = w_first;
+      // (unconditional: the last iteration re-reads its own block -- a conditional load costs a copy of the word back)
+      w_first = cw[((size_t)(run_n < nruns ? block_of(p_n, r_n) : rb) * ng) * 64 + lane];
+      run = run_n; e = e_n; e_run_end = end_n; mp_p = p_n; mp_r = r_n;
+      pos = rb * 64 + lane;
+      if constexpr (PFX > 0) if (!whole) {
+        constexpr int PL1 = 2;                 // look-ups through the vector L1: the sorted quantizers 15 and 14
+        static_assert(PFX == 0 || (SORTED && MAIN == 1 && GLB >= PL1 && PFX > PL1 && PFX - PL1 <= VEC - GLB && DW == 4 && NQG == 1),
+                      "the prefix test is the key-sorted main stage's");
+        constexpr int NL = PFX - PL1;          // look-ups from LDS: quantizers 0 .. NL - 1
+        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        const uint8_t *tj_glb = qtab + (size_t)tile * tab * sizeof(QE);
+        QE gl[PL1];
+#pragma unroll
+        for (int a = 0; a < PL1; a++)
+          gl[a] = *reinterpret_cast<const QE *>(tj_glb + (size_t)(VEC - 1 - a) * 256 * sizeof(QE) +
+                                                code_byte<VEC>(w, VEC - 1 - a) * (uint32_t)sizeof(QE));
+        uint32_t pa[2 * DW];
+#pragma unroll
+        for (int x = 0; x < 2 * DW; x++) pa[x] = 0;
+        // the PFX entries in NGRP byte-sum groups of even size (10: 3 + 3 + 4, not 4 + 4 + 2 -- a sum of three is one
+        // three-operand add, and the widening is paid per group either way)
+        constexpr int NGRP = (PFX + NADD - 1) / NADD;
+#pragma unroll
+        for (int gi = 0; gi < NGRP; gi++) {
+          const int b = gi * PFX / NGRP, b_end = (gi + 1) * PFX / NGRP;
+          uint32_t xs[DW];
+#pragma unroll
+          for (int dd = 0; dd < DW; dd++) xs[dd] = 0;
+#pragma unroll
+          for (int a = 0; a < NADD; a++) {     // bytes cannot carry: at most NADD entries, NADD * QMAX <= 255
+            const int en = b + a;
+            if (en >= b_end) continue;
+            if (en < NL) {
+              const u32x4 y = reinterpret_cast<const __attribute__((address_space(3))) u32x4 *>(0)[en * 256 + code_byte<VEC>(w, en)];
+#pragma unroll
+              for (int dd = 0; dd < DW; dd++) xs[dd] += y[dd];
+            } else {
+#pragma unroll
+              for (int dd = 0; dd < DW; dd++) xs[dd] += reinterpret_cast<const uint32_t *>(&gl[en - NL])[dd];
+            }
+          }
+#pragma unroll
+          for (int dd = 0; dd < DW; dd++) {
+            pa[2 * dd] += xs[dd];                                                // (unmasked: see `acc` below)
+            pa[2 * dd + 1] += __builtin_amdgcn_perm(0u, xs[dd], 0x0C030C01u);   // bytes 1 and 3
+          }
+        }
+        uint32_t near = 0;
+#pragma unroll
+        for (int dd = 0; dd < DW; dd++) {
+          pa[2 * dd] -= pa[2 * dd + 1] << 8;
+          near |= pk_sub_sat_u16(QMAXP, pa[2 * dd]) | pk_sub_sat_u16(QMAXP, pa[2 * dd + 1]);
+        }
+        const unsigned long long mask = __ballot(near != 0);
+        if (mask != 0ull) {
+          const int before = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+          if (near != 0) ring[(fill + before) & (RING - 1)] = pos;
+          fill += __popcll(mask);
+        }
+        seen++;
+        direct = seen >= 8 && fill * 4 > seen * 64;
+      }
+      more = PFX > 0 && !whole && !direct && run < nruns && fill - head < 64;
+    }
+    if constexpr (PFX > 0) if (!whole) {
+      // (one wave: its LDS accesses execute in order, the places written above are read back below)
+      __builtin_amdgcn_wave_barrier();
+      const int take = min(64, fill - head);
+      if (take == 0) continue;              // an empty ring: the last run has ended, or the wave goes on block by block
+      live = lane < take;
+      pos = ring[(head + lane) & (RING - 1)];
+      if (!live) pos = rb * 64 + lane;      // (an idle lane: any word of the copy)
+      head += take;
+      __builtin_amdgcn_wave_barrier();
+      w = cw[pos];
     }
     const Word *p = cw + ((size_t)rb * ng) * 64 + lane;
-    Word w = w_first;
-    // (unconditional: the last iteration re-reads its own block -- a conditional load costs a copy of the word back)
-    w_first = cw[((size_t)(run_n < nruns ? block_of(p_n, r_n) : rb) * ng) * 64 + lane];
-    run = run_n; e = e_n; e_run_end = end_n; mp_p = p_n; mp_r = r_n;
 
     // acc[s][2*dd+1] : 16-bit sums of queries 4dd+1 (low half) and 4dd+3 (high half) of group s
     // acc[s][2*dd]   : queries 4dd and 4dd+2 -- after the words.  While the words are walked it is the plain 32-bit sum W
@@ -620,7 +721,7 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_kernel(
     // conflict-ordered copy: which row a lane holds is only looked up (one byte) when a lane has something to report
     constexpr bool PERM = NG1 >= 2;
     int row = rb * 64 + lane;
-    bool valid = PERM || (row >= row_from && row < row_until);
+    bool valid = PERM ? live : (row >= row_from && row < row_until);
     uint32_t any = 0;
     uint32_t left[NQG][2 * DW];
 #pragma unroll
@@ -641,9 +742,9 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_kernel(
         const uint8_t *perm_l = perm;
         int pwin_l = pwin;
         asm volatile("" : "+s"(perm_l), "+s"(pwin_l));
-        if constexpr (SORTED) row = reinterpret_cast<const int *>(perm_l)[(size_t)rb * 64 + lane];   // (-1: padding)
+        if constexpr (SORTED) row = reinterpret_cast<const int *>(perm_l)[PFX > 0 ? (size_t)pos : (size_t)rb * 64 + lane];   // (-1: padding)
         else row = (rb & ~pwin_l) * 64 + perm_l[(size_t)rb * 64 + lane];
-        valid = row >= row_from && row < row_until;
+        valid = live && row >= row_from && row < row_until;
       }
 #pragma unroll
       for (int s = 0; s < NQG; s++)
@@ -770,9 +871,10 @@ __global__ __launch_bounds__(64 * SV_WAVES * 4) void survivors_kernel(
 
 template <int QW, int NQG, int VEC, int NADD>
 void launch_filter_t(gulon_index *ix, int ftiles, int nchunks, int rb_begin, int e_count, int e_per_chunk, RbMap mp,
-                     int from, int until, int cap, int stage, int B, hipStream_t st, int *fb, int qt, bool sorted) {
+                     int from, int until, int cap, int stage, int B, hipStream_t st, int *fb, int qt, bool sorted,
+                     int prefix) {
   const int W_fp32 = ix->w;
-  const size_t lds_bytes = (size_t)NQG * ix->m_pad * 256 * QW + 16;   // tables + the run counter
+  size_t lds_bytes = (size_t)NQG * ix->m_pad * 256 * QW + 16;   // tables + the run counter
   // (the single-word form only for the instantiation the headline index runs on: m = 16, two workgroups per CU)
   constexpr bool one_word_form = QW == 16 && NQG == 1 && VEC == 16 && NADD == 4;
   // stage: 0 a short stage, 1 the main stage (a tag of its own for the profilers), 2 the tie replay's long level
@@ -815,6 +917,33 @@ void launch_filter_t(gulon_index *ix, int ftiles, int nchunks, int rb_begin, int
       kern = stage == 1 ? filter_kernel<QW, NQG, VEC, NADD, 1, 3> : filter_kernel<QW, NQG, VEC, NADD, 0, 3>;
       codes = ix->scodes.p;
       perm = reinterpret_cast<const uint8_t *>(ix->sids.p);
+      if (stage == 1 && prefix > 0) {
+        // the main stage with the prefix test: a ring of 128 places per wave behind the run counter.  Taken where two
+        // such workgroups fit a CU, as without the rings (2 x 72 KiB of 160; asked once per device) and the kernel has
+        // no static LDS (tables at offset 0); elsewhere the launch stays the form without the prefix
+        const auto pkern = filter_kernel<QW, NQG, VEC, NADD, 1, 3, FILTER_PREFIX_P>;
+        const size_t plds = lds_bytes + (size_t)(FILTER_THREADS / 64) * 128 * sizeof(int);
+        constexpr int MAX_DEV = 64;
+        static std::atomic<int> fits[MAX_DEV];   // per device -- 0: not asked yet, 1: two resident, -1: not
+        int dev = 0;
+        HIP_CHECK(hipGetDevice(&dev));
+        GULON_REQUIRE(dev >= 0 && dev < MAX_DEV, "device ordinal %d out of range", dev);
+        int f = fits[dev].load(std::memory_order_relaxed);
+        if (f == 0) {
+          const void *k = reinterpret_cast<const void *>(pkern);
+          int nb = 0;
+          hipFuncAttributes fa;
+          HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds));
+          HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, FILTER_THREADS, plds));
+          HIP_CHECK(hipFuncGetAttributes(&fa, k));
+          f = fa.sharedSizeBytes == 0 && nb >= 2 ? 1 : -1;
+          fits[dev].store(f, std::memory_order_relaxed);
+        }
+        if (f > 0) {
+          kern = pkern;
+          lds_bytes = plds;
+        }
+      }
     }
   }
   HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -866,6 +995,7 @@ int filter_nqg(const gulon_index *ix) {
 }  // namespace
 
 hipEvent_t filter_lane_event(int dev, bool &fresh) { return filter_lane().of(dev, fresh); }
+
 
 int device_cus() {
   static std::atomic<int> cus[FilterLane::MAX_DEVICES];
@@ -968,9 +1098,9 @@ void launch_qt_quantize(gulon_index *ix, const float *tables, int W, int Bp, int
 
 void launch_filter(gulon_index *ix, int qw, int nqg, int nadd, int ftiles, int nchunks, int rb_begin, int e_count,
                    int e_per_chunk, RbMap mp, int from, int until, int cap, int stage, int B, hipStream_t st, int *fb,
-                   int qt, bool sorted) {
+                   int qt, bool sorted, int prefix) {
 #define GO(W_, Q, V, A) \
-  launch_filter_t<W_, Q, V, A>(ix, ftiles, nchunks, rb_begin, e_count, e_per_chunk, mp, from, until, cap, stage, B, st, fb, qt, sorted)
+  launch_filter_t<W_, Q, V, A>(ix, ftiles, nchunks, rb_begin, e_count, e_per_chunk, mp, from, until, cap, stage, B, st, fb, qt, sorted, prefix)
 #define GO_QV(W_, Q, V) do { if (nadd == 4) GO(W_, Q, V, 4); else GO(W_, Q, V, 2); } while (0)
 #define GO_W(W_) do {                                                  \
     if (ix->vec == 16) { if (nqg == 2) GO_QV(W_, 2, 16); else GO_QV(W_, 1, 16); } \

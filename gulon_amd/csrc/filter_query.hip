@@ -253,7 +253,7 @@ void FilterBatch::quantize() {   // the tables against the current bounds: the s
 
 void FilterBatch::filter(RbMap mp, int en, int nchunks, int per, bool main_stage) {
   launch_filter(ix, fs.qw, fs.nqg, fs.nadd, ftiles, nchunks, frb_begin, en, per, mp, from, until, cap, main_stage ? 1 : 0,
-                B, st, nullptr, 1, sorted);
+                B, st, nullptr, 1, sorted, sorted ? t.filter_prefix : 0);
 }
 
 // one stage: quantize -> filter (the main stage in its turn on the device, and timed where the handle profiles) ->

@@ -620,7 +620,8 @@ ScanTuning::ScanTuning() {
   static const char *keys[] = {"GULON_SCAN_BLOCKS", "GULON_SCAN_PRUNE", "GULON_SCAN_PRUNE_FROM", "GULON_SCAN_FILTER",
                                "GULON_FILTER_MIN_RB", "GULON_FILTER_PERIOD", "GULON_FILTER_STAGE1", "GULON_FILTER_CAP",
                                "GULON_FILTER_NADD", "GULON_FILTER_SAMPLE", "GULON_FILTER_STAGE0", "GULON_FILTER_BLOCKS",
-                               "GULON_FILTER_SHARED_STAGE1", "GULON_FILTER_ORDER", "GULON_FILTER_SORT"};
+                               "GULON_FILTER_SHARED_STAGE1", "GULON_FILTER_ORDER", "GULON_FILTER_SORT",
+                               "GULON_FILTER_PREFIX"};
   for (const char *k : keys)
     if (const char *e = getenv(k)) set(k, atoi(e));
 }
@@ -642,6 +643,7 @@ bool ScanTuning::set(const char *key, int v) {
   else if (k == "GULON_FILTER_SHARED_STAGE1") { if (v >= -1 && v <= 1) filter_shared_stage1 = v; }
   else if (k == "GULON_FILTER_ORDER") { if (v >= 0 && v <= 8) filter_order = v; }
   else if (k == "GULON_FILTER_SORT") filter_sort = v != 0;
+  else if (k == "GULON_FILTER_PREFIX") { if (v == 0 || v == FILTER_PREFIX_P) filter_prefix = v; }
   else return false;
   return true;
 }

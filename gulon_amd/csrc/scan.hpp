@@ -219,6 +219,11 @@ constexpr int FILTER_LDS_QUANTIZERS = 16 - GULON_FILTER_GLB;
 #endif
 constexpr int FILTER_SORT_LDS_QUANTIZERS = 16 - GULON_FILTER_SORT_GLB;
 
+// filter.hip: the main stage on the key-sorted copy tests a row on this many of its sixteen quantizers (the two sorted
+// ones through the vector L1, the others from LDS) before it looks up the rest.  Measured at 10 M rows, five alternating
+// runs each: 9 -> 1.814 ms per batch, 10 -> 1.797, 11 -> 1.810 (without: 2.268); profiles/r05/configs.md
+constexpr int FILTER_PREFIX_P = 10;
+
 struct ScanTuning {
   int threads = 1024;        // workgroup size (16 waves hide the pruning checkpoints' LDS drain)
   int target_blocks = 4096;  // workgroups per launch aimed for
@@ -237,6 +242,7 @@ struct ScanTuning {
   int filter_shared_stage1 = -1;    // bounds shared across shards: run the short first stage? (-1: by sample size)
   int filter_order = 1;             // conflict-ordered code copy: built at index creation (the environment's value) / used (per handle)
   int filter_sort = 1;              // key-sorted code copy: built at index creation (the environment's value) / used (per handle)
+  int filter_prefix = FILTER_PREFIX_P;   // main stage on the key-sorted copy: quantizers tested before a row's other look-ups (0: off)
   ScanTuning();
   bool set(const char *key, int v);
 };
@@ -299,7 +305,8 @@ void launch_qt_quantize(gulon_index *ix, const float *tables, int W, int Bp, int
 void launch_filter(gulon_index *ix, int qw, int nqg, int nadd, int ftiles, int nchunks, int rb_begin, int e_count,
                    int e_per_chunk, RbMap mp, int from, int until, int cap, int stage, int B, hipStream_t st,
                    int *fb = nullptr /* tile flags other than the index's own, one per `qt` queries */, int qt = 1,
-                   bool sorted = false /* read the key-sorted copy (the launch covers every row of the index) */);
+                   bool sorted = false /* read the key-sorted copy (the launch covers every row of the index) */,
+                   int prefix = 0 /* sorted main stage: quantizers of the prefix test (filter.hip), 0: none */);
 // survivors_kernel: the queued rows re-evaluated exactly and merged into ix->fin_v / ix->fin_i
 void launch_survivors(gulon_index *ix, int B, int Bq, int keff, int cap, int give_up, hipStream_t st);
 // filter_query.hip: level 2 of the tie replay (replay.hip) through the quantized filter.  For the flagged queries f < *count

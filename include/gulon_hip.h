@@ -568,7 +568,9 @@ int32_t gulon_index_filter_stats(gulon_index *idx, int32_t *query_tiles, int32_t
  * rounds of the ordering); per handle 0 makes the filter read the plain copy again.
  * "GULON_FILTER_SORT" (default 1): such an index also keeps a copy of its codes sorted by the last two quantizers'
  * codes with a 32-bit row id per row (+ 20 bytes per row), which the filter reads for queries over the index's whole
- * row range; per handle 0 makes those queries read the other copies again. */
+ * row range; per handle 0 makes those queries read the other copies again.
+ * "GULON_FILTER_PREFIX" (default 10): the filter's main stage on that copy tests a row on 10 of its 16 quantizers first
+ * and looks up the other six only for rows some query of the tile may still keep; 0: all sixteen at once. */
 int32_t gulon_index_tuning(gulon_index *idx, const char *key, int32_t value);
 /* TopKHeap.merge semantics (TopKHeap.scala:44-53, used at Index.scala:279) under
  * the deterministic (distance, row id) order: merges `lists` partial lists per
