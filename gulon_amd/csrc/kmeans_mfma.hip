@@ -56,10 +56,14 @@ __global__ void pack_centroids_kernel(const float *__restrict__ C, const float *
   }
   if (t0 < nkb * 32) {
     // padding centroids (last block): a huge FINITE offset -- never the minimum, and its key stays a
-    // number (+inf with an index in the mantissa would be a NaN and flag every row through the band)
+    // number (+inf with an index in the mantissa would be a signalling NaN: see below)
     float o = t0 < k ? off[t0] : 1.0e38f;
     offp[t0] = o;
-    if (t0 < k && o == o && o < INFINITY) atomicMax(cmax2_bits, __float_as_uint(o));
+    // An offset that is not finite (a centroid coordinate that is Inf or NaN, or squares that overflow) makes cmax2 Inf or
+    // NaN -- as unsigned bits both lie above every finite offset -- and with it every row's band: the whole slice goes to
+    // the exact kernel.  (Leaving such a centroid out of cmax2 is not sound: its key, +Inf with an index in the mantissa,
+    // is a signalling NaN, v_min_f32 returns it quieted, and the running minimum before it is lost without a flag.)
+    if (t0 < k) atomicMax(cmax2_bits, __float_as_uint(o));
   }
 }
 
@@ -531,7 +535,7 @@ __global__ void pack_centroids_split(const float *__restrict__ C, const float *_
   if (t0 < nkb * 32) {
     float o = t0 < k ? off[t0] : 1.0e38f;
     offp[t0] = o;
-    if (t0 < k && o == o && o < INFINITY) atomicMax(cmax2_bits, __float_as_uint(o));
+    if (t0 < k) atomicMax(cmax2_bits, __float_as_uint(o));   // a non-finite offset: every row flagged (pack_centroids_kernel)
   }
 }
 
@@ -1013,6 +1017,46 @@ GULON_API int32_t gulon_selftest_assign_band(int32_t s, uint64_t seed, float sca
   return gulon::guarded([&] {
     GULON_REQUIRE(max_error_over_band != nullptr && s >= 1 && s <= 16, "bad arguments");
     *max_error_over_band = gulon::selftest_assign_band(s, seed, scale);
+  });
+}
+// The filter stage of one assign as the product runs it (pack_slice_if_filtered + assign_stage1), stopped before the exact
+// re-check: what the filter wrote, which rows it handed on, and which kernel form the dispatch chose
+// (tests/test_gpu_assign_filter.py)
+GULON_API int32_t gulon_selftest_assign_filter(const float *x, int32_t n, int32_t ld, int32_t from, int32_t s,
+                                               const float *centroids, int32_t k, int32_t *assign_inout,
+                                               int32_t *flagged_rows_out, int32_t *n_flagged, int32_t form_out[2]) {
+  using namespace gulon;
+  return guarded([&] {
+    GULON_REQUIRE(x && centroids && assign_inout && flagged_rows_out && n_flagged && form_out && n >= 1 && k >= 1 && s >= 1 &&
+                  from >= 0 && from + s <= ld, "bad arguments");
+    *n_flagged = 0;
+    form_out[0] = form_out[1] = 0;
+    if (mfma_assign_supported(s, k)) {
+      if (mfma_split(s, k)) {
+        const int words = split_compact_words(s);
+        form_out[0] = words ? 3 : 4;
+        form_out[1] = words ? words : 3;
+      } else {
+        form_out[0] = mfma_streams(s, k) ? 2 : 1;
+        form_out[1] = mfma_kernel_T(s, k);
+      }
+    }
+    DevBuf<float> dX, dC;
+    DevBuf<int> da;
+    dX.upload(x, (size_t)n * ld);
+    dC.upload(centroids, (size_t)k * s);
+    da.upload(assign_inout, (size_t)n);
+    KmeansWorkspace ws;
+    PackedSlice ps;
+    AssignJob j(ws, dX.p, n, ld, from, s, dC.p, k, 0, da.p, nullptr, pack_slice_if_filtered(dX.p, n, ld, from, s, k, ps, nullptr));
+    if (!j.ps) return;             // no filter for this shape: every row would take the exact scan
+    assign_stage1(j);
+    HIP_CHECK(hipStreamSynchronize(nullptr));
+    GULON_REQUIRE(j.filtered && ws.host->flagged <= (unsigned)n, "the filter stage did not run");
+    *n_flagged = (int32_t)ws.host->flagged;
+    da.download(assign_inout, (size_t)n);
+    ws.flag_rows.download(flagged_rows_out, (size_t)ws.host->flagged);
+    HIP_CHECK(hipStreamSynchronize(nullptr));
   });
 }
 #endif

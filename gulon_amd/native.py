@@ -228,6 +228,7 @@ TEST_HOOK_SIGNATURES = {
     "gulon_selftest_stream_update": (_i32, [C.c_void_p, _i32, _i32, _i32, _i32, _i32, C.c_void_p, C.c_void_p]),
     "gulon_selftest_conflict_order": (_i32, [C.c_void_p, C.c_int64, _i32, C.c_void_p, C.c_void_p]),
     "gulon_selftest_assign_band": (_i32, [_i32, C.c_uint64, C.c_float, C.POINTER(C.c_double)]),
+    "gulon_selftest_assign_filter": (_i32, [_f32p, _i32, _i32, _i32, _i32, _f32p, _i32, _i32p, _i32p, C.POINTER(_i32), _i32p]),
     "gulon_selftest_cosmul_flat_shape": (_i32, [_vp, _i32, _i32, _i32, _i32p]),
     "gulon_selftest_cosmul_exact_shape": (_i32, [_vp, _i32, _i32p]),
 }

@@ -197,6 +197,16 @@ int32_t gulon_selftest_conflict_order(const uint8_t *codes, int64_t n_blocks, in
  * outliers), d' = the matrix cores' value, d = the reference's unfused fp32 chain (KMeans.scala:42-47).  The filter
  * is sound while the result stays below 0.5 (the band is twice the error bound). */
 int32_t gulon_selftest_assign_band(int32_t s, uint64_t seed, float scale, double *max_error_over_band);
+/* The MFMA filter stage of KMeans.assign (KMeans.scala:24-98) alone, as the library runs it in front of the exact
+ * kernels: the slice [from, from + s) of the host matrix x (n rows, leading dimension ld) is packed and filtered against
+ * centroids (k x s).  assign_inout (n, pre-filled by the caller) comes back as the filter left it: the answer of every
+ * row it decided, untouched where it did not.  flagged_rows_out (n) receives the rows it handed to the exact kernel, in
+ * no particular order, *n_flagged their number.  form_out = {kind, width} of the kernel the dispatch chose:
+ * kind 0 no filter for this (s, k) (nothing runs), 1 assign_mfma<T>, 2 assign_mfma_stream<T>, 3 assign_bf16 with compact
+ * operand words, 4 assign_bf16 with three pieces; width = T, or the operand words per lane. */
+int32_t gulon_selftest_assign_filter(const float *x, int32_t n, int32_t ld, int32_t from, int32_t s,
+                                     const float *centroids, int32_t k, int32_t *assign_inout,
+                                     int32_t *flagged_rows_out, int32_t *n_flagged, int32_t form_out[2]);
 #endif
 /* Stage times of the training loop for bench.py's k-means record (BASELINE config 3): while enabled, every
  * stage of KMeans.computeClusters / ProductQuantizer.apply is closed by a device synchronisation and its wall
