@@ -25,6 +25,9 @@ from .rotation import RotatedWordIndex, Rotation, rotate_reference, train_rotati
 from .analogies import AnalogyReport, evaluate_analogies, read_questions
 from .similarity import (SimilarityReport, evaluate_pairs, pair_distance_reference, rank_sums, rank_sums_reference,
                          read_pairs, spearman)
+from .csls import (DeviceOffsets, TranslationReport, csls_offsets, evaluate_dictionary, mean_similarity,
+                   mean_similarity_reference, offset_query_reference, read_dictionary, translate_words,
+                   translation_scores)
 
 __all__ = ["native", "GroupedIndex", "GroupedVectors", "LimitGroups", "LimitVectors", "group", "Coder", "width_for_clusters", "Index", "PQIndex", "PQIndexView", "DevicePQIndex", "Result", "SortedIndex",
            "exact_nearest_neighbours", "prepare_query", "tune_live", "KMeans", "KMeansConfig", "DeviceMatrix", "Matrix",
@@ -36,4 +39,6 @@ __all__ = ["native", "GroupedIndex", "GroupedVectors", "LimitGroups", "LimitVect
            "refine_codes_topk", "row_residuals", "Rotation", "RotatedWordIndex", "train_rotation", "rotate_reference",
            "ExactIndex", "ExactWordIndex", "AnalogyReport", "evaluate_analogies", "read_questions",
            "COSMUL_EPS", "cosmul_reference", "SimilarityReport", "evaluate_pairs", "read_pairs",
-           "pair_distance_reference", "rank_sums", "rank_sums_reference", "spearman"]
+           "pair_distance_reference", "rank_sums", "rank_sums_reference", "spearman", "DeviceOffsets",
+           "TranslationReport", "csls_offsets", "evaluate_dictionary", "mean_similarity", "mean_similarity_reference",
+           "offset_query_reference", "read_dictionary", "translate_words", "translation_scores"]

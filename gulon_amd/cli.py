@@ -1,5 +1,5 @@
 """`python -m gulon_amd`: the reference's four commands (command/Main.scala:7-11), `inspect`, `update`, `build-fine`,
-`analogies` and `similarity`.
+`analogies`, `similarity` and `translate`.
 
   build-index -d l2|cosine -o INDEX [-k N] [-m N] [-n N] [-p [--partitions N] [-l N]] [-R ROTATION [--rotation-rounds N]]
               FILE
@@ -72,6 +72,24 @@
                                        index alone; with -v --exact the true vectors of the index's words.  Distances
                                        and ranks are computed on the device.  -R is not offered: distances between stored
                                        rows need no rotation
+
+  translate -i TARGET -s SOURCE [--method nn|csls] [-n 10] [-k 10] [-v VECTORS --exact] [-R ROTATION] [--lowercase]
+            (WORDS | -e DICTIONARY)
+                                       (not in the reference) word translation between two aligned embedding spaces
+                                       (csls.py, csrc/offset.hip).  TARGET is an index file over the target language's
+                                       vectors, SOURCE a word2vec text file of the source language's, already mapped
+                                       into the target's space (read normalised for a cosine index).  Every line of
+                                       WORDS is a source word, printed as `word: t1,t2,...` with its -k (default 10)
+                                       nearest target words, or `word: not found`.  --method nn ranks by the index's
+                                       distance; csls (a flat cosine index, or -v --exact) by CSLS: the distance plus the
+                                       mean similarity of the target word to its -n (default 10) nearest source words,
+                                       which demotes the hubs that are near everything.  -e DICTIONARY replaces WORDS:
+                                       lines of `source target` (MUSE's format, a source word may have several lines),
+                                       and one line is printed, `csls: @1 0.6120 @5 0.8010 @10 0.8522 (n = 1500,
+                                       skipped 12)` -- the precision at -k 1,5,10, n the source words asked, skipped the
+                                       pairs with a word either side lacks.  -v VECTORS --exact: the target is the true
+                                       vectors of the index's words.  -R ROTATION: the index was built with build-index
+                                       -R, and the source vectors are rotated after they are read (not with --exact)
 
 -f FINE on the query commands and on test (not in the reference): as -v / -c, but the candidates are re-ranked by their
 distance to the index's row plus the fine index's row of the same word (fine.FineRefinedIndex) -- no original vectors in
@@ -234,6 +252,22 @@ class SimilarityConfig:
     lowercase: bool = False               # --lowercase: lower the pairs' words
     vectors: Optional[str] = None         # -v: the vectors the index was built from (with --exact)
     exact: bool = False                   # --exact: the true vectors of the index's words are the target
+
+
+@dataclass(frozen=True)
+class TranslateConfig:
+    index: str
+    source: str                           # -s: word2vec text of the source language, aligned with the target
+    words: Optional[str] = None           # the file of source words to translate ...
+    dictionary: Optional[str] = None      # ... or -e: the dictionary to evaluate
+    method: str = "nn"                    # --method: nn (the index's distance) or csls
+    neighbours: int = 10                  # -n: the K of CSLS's mean similarities
+    k: int = 10                           # -k: translations printed per word
+    ks: tuple = (1, 5, 10)                # -k with -e: the depths reported, ascending
+    lowercase: bool = False               # --lowercase: lower the words of WORDS / the dictionary
+    vectors: Optional[str] = None         # -v: the vectors the index was built from (with --exact)
+    exact: bool = False                   # --exact: the true vectors of the index's words are the target
+    rotation: Optional[str] = None        # -R: the index was built over vectors rotated by this file
 
 
 def _depths(s):
@@ -409,6 +443,32 @@ def _parser():
     s.add_argument("--exact", action="store_true",
                    help="with --vectors: evaluate the original vectors of the index's words instead of its rows")
     s.add_argument("file", metavar="file", help="pairs: `: section` lines and lines of `word1 word2 score`")
+    tr = sub.add_parser("translate", help="translate words between two aligned embedding spaces",
+                        description="translate the words of a source embedding file into the words of a target index, "
+                                    "by nearest neighbours or by CSLS; with --evaluate, report the precision of a "
+                                    "bilingual dictionary")
+    tr.add_argument("-i", "--index", required=True, metavar="file", help="path to the ANN index of the target language")
+    tr.add_argument("-s", "--source", required=True, metavar="file",
+                    help="word2vec word vectors of the source language, mapped into the target's space")
+    tr.add_argument("--method", choices=("nn", "csls"), default="nn",
+                    help="nn ranks by the index's distance; csls adds the mean similarity of every target word to its "
+                         "nearest source words (a cosine index)")
+    tr.add_argument("-n", "--csls-neighbours", type=_positive, default=10, metavar="num",
+                    help="neighbours behind the mean similarities of csls (default 10)")
+    tr.add_argument("-k", "--neighbours", default=None, metavar="num",
+                    help="translations printed per word (default 10); with --evaluate the depths reported, ascending and "
+                         "separated by commas (default 1,5,10)")
+    tr.add_argument("-e", "--evaluate", default=None, metavar="file",
+                    help="a dictionary, lines of `source target`: print its precision instead of translations")
+    tr.add_argument("-v", "--vectors", default=None, metavar="file",
+                    help="word2vec word vectors the index was built from (needs --exact)")
+    tr.add_argument("--exact", action="store_true",
+                    help="with --vectors: translate into the original vectors of the index's words instead of its rows")
+    tr.add_argument("-R", "--rotation", default=None, metavar="file",
+                    help="rotation file the index was built with (build-index -R): the source vectors are rotated after "
+                         "they are read (not with --exact)")
+    tr.add_argument("--lowercase", action="store_true", help="lower the words to translate")
+    tr.add_argument("file", nargs="?", metavar="file", help="source words, one per line")
     u = sub.add_parser("update", help="add, replace and remove words of an index without retraining",
                        description="add, replace and remove words of an index without retraining")
     u.add_argument("-i", "--index", required=True, metavar="file", help="path to ANN index")
@@ -668,6 +728,54 @@ def run_similarity(config: SimilarityConfig, load, vectors):
         raise SimilarityError(str(e))
 
 
+class TranslateError(Exception):
+    """What `translate` reports and exits on: an unreadable or malformed file, vectors of another dimension, csls on an
+    index that cannot answer it."""
+
+
+def run_translate(config: TranslateConfig, write, load, vectors):
+    """translate between its argument handling and the end of its output: the translations are written as they come;
+    with a dictionary -> csls.TranslationReport, else None.  The source vectors are read as the index's own were: in
+    word order, normalised for a cosine index."""
+    from .csls import evaluate_dictionary, read_dictionary, translate_words
+    from .exact import ExactIndex, ExactWordIndex
+    path = config.dictionary if config.dictionary is not None else config.words
+    try:
+        with open(path, "rb") as fh:
+            lines = read_lines(fh.read())
+        pairs = read_dictionary(lines, config.lowercase) if config.dictionary is not None else None
+    except OSError as e:
+        raise TranslateError(f"{path}: {e.strerror or e}")
+    except ValueError as e:
+        raise TranslateError(f"{path}: {e}")
+    index = load(config.index)
+    try:
+        cosine = index.metric == "cosine"
+        if config.exact:
+            index = index.exact(vectors(config.vectors, cosine))
+        originals = _rotated(config.rotation, vectors(config.source, cosine))
+        source = ExactWordIndex(originals.words, ExactIndex(originals.matrix, index.metric), originals.key_index)
+        if pairs is not None:
+            return evaluate_dictionary(index, source, pairs, config.ks, config.method, config.neighbours)
+        words = [w.lower() for w in lines] if config.lowercase else lines
+        offsets = None
+        if config.method == "csls" and words:                    # r_S once, for every chunk of words
+            from .csls import csls_offsets
+            offsets = csls_offsets(index, source, config.neighbours)
+        try:
+            for s in range(0, len(words), CHUNK):
+                part = words[s:s + CHUNK]
+                results = translate_words(index, source, part, config.k, config.method, config.neighbours, offsets)
+                for word, result in zip(lines[s:s + CHUNK], results):
+                    write(_line(word, result) + "\n")
+        finally:
+            if offsets is not None:
+                offsets.free()
+        return None
+    except (LookupError, NotImplementedError, ValueError) as e:
+        raise TranslateError(str(e))
+
+
 def read_originals(path, normalize):
     """The -v vectors of the query commands: on the device, in word order (their key index resolves the index's words)."""
     from .word_vectors import read_word2vec_device
@@ -709,7 +817,7 @@ def _refined(args, index, vectors, load):
 
 
 def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None, vectors=None, inspect=None,
-         update=None, fine=None, rotation=None, analogies=None, similarity=None):
+         update=None, fine=None, rotation=None, analogies=None, similarity=None, translate=None):
     """Returns the exit code.  stdin / stdout: binary streams (default: the process's); load: path -> index with
     batch_query_by_words / batch_query (default WordIndex.load); build: (BuildConfig, write) -> None, the whole of
     build-index behind its argument handling (default run_build_index); recall: (RecallConfig, write, load) ->
@@ -721,7 +829,9 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
     build-fine behind its argument handling (default run_build_fine).  The fine index behind -f is read with `load`.  rotation: path -> the rotation behind -R of the
     query commands (default Rotation.load).  analogies: (AnalogiesConfig, load, vectors) -> AnalogyReport, the whole of
     analogies between its argument handling and its lines (default run_analogies).  similarity: (SimilarityConfig, load,
-    vectors) -> SimilarityReport, the same for similarity (default run_similarity)."""
+    vectors) -> SimilarityReport, the same for similarity (default run_similarity).  translate: (TranslateConfig, write,
+    load, vectors) -> TranslationReport or None, the whole of translate behind its argument handling (default
+    run_translate)."""
     parser = _parser()
     args = parser.parse_args(argv)
     if args.command == "similarity":
@@ -729,6 +839,20 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
             parser.error("--exact needs -v/--vectors")
         if args.vectors is not None and not args.exact:
             parser.error("--vectors is only applicable with --exact")
+    if args.command == "translate":
+        if (args.file is None) == (args.evaluate is None):
+            parser.error("exactly one of a file of words and -e/--evaluate is required")
+        if args.exact and args.vectors is None:
+            parser.error("--exact needs -v/--vectors")
+        if args.vectors is not None and not args.exact:
+            parser.error("--vectors is only applicable with --exact")
+        if args.exact and args.rotation is not None:
+            parser.error("--exact is not applicable with -R/--rotation")
+        try:
+            depth = _depths(args.neighbours or "1,5,10") if args.evaluate is not None \
+                else _positive(args.neighbours or "10")
+        except argparse.ArgumentTypeError as e:
+            parser.error(f"argument -k/--neighbours: {e}")
     if args.command == "analogies":
         if args.exact and args.vectors is None:
             parser.error("--exact needs -v/--vectors")
@@ -826,6 +950,19 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
             return 1
         for line in report.lines():
             write(line + "\n")
+    elif args.command == "translate":
+        k, ks = (10, depth) if args.evaluate is not None else (depth, (1, 5, 10))      # -k means depths with -e
+        config = TranslateConfig(args.index, args.source, args.file, args.evaluate, args.method, args.csls_neighbours,
+                                 k, ks, args.lowercase, args.vectors, args.exact, args.rotation)
+        try:
+            report = (translate if translate is not None else run_translate)(config, write, load, vectors)
+        except TranslateError as e:
+            stdout.flush()
+            print(f"error: {e}", file=sys.stderr)
+            return 1
+        if report is not None:
+            for line in report.lines():
+                write(line + "\n")
     elif args.command == "update":
         config = UpdateConfig(args.index, args.output, args.add, args.remove, args.rotation)
         try:

@@ -226,16 +226,6 @@ void check_dev_shape(int b, int k_nn, const int *d_off, const int *d_rows, const
 
 // ---- flat index -------------------------------------------------------------------------------------------------------
 
-// 32-bit word `seg` of a code word (seg need not be a constant: no register array is indexed)
-template <int VEC>
-__device__ __forceinline__ uint32_t code_word32(const typename CodeWord<VEC>::type &w, int seg);
-template <>
-__device__ __forceinline__ uint32_t code_word32<4>(const uint32_t &w, int) { return w; }
-template <>
-__device__ __forceinline__ uint32_t code_word32<16>(const uint4 &w, int seg) {
-  return seg == 0 ? w.x : seg == 1 ? w.y : seg == 2 ? w.z : w.w;
-}
-
 // The row blocks of one chunk against one question with E terms: tables [E][m_pad][256] in LDS, the wave's lanes the rows
 // of a block, acc[t] += T_t[j][code_j] with j ascending from 0.f, as scan.hip's exact scan adds them.
 template <int E, int VEC>

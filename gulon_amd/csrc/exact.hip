@@ -19,9 +19,13 @@
 //
 // Multiplicative analogy queries: gulon_exact_index_query_cosmul[_dev] hand the handle's range and its
 // CosmulWork to cosmul.hip, under the handle's mutex and stream order.
+//
+// Offset queries: gulon_exact_index_query_offset[_dev] hand the range and the handle's OffsetWork to
+// offset.hip in the same way.
 #include "compose.hpp"
 #include "cosmul.hpp"
 #include "exact.hpp"
+#include "offset.hpp"
 #include "select.hpp"
 
 #include <cstdlib>
@@ -288,6 +292,7 @@ struct gulon_exact_index {
   DevBuf<int> stage_rows, stage_oi, stage_oc, stage_of;
   ExprWork expr;                       // the expression queries' term lists, composed vectors and answers at k_nn + extra
   CosmulWork cosmul;                   // the multiplicative analogy queries (cosmul.hip)
+  OffsetWork offset;                   // the offset queries (offset.hip)
   std::vector<int> h_cnt, h_ovf, h_nf, h_ids;
   hipEvent_t order_ev = nullptr;
   hipStream_t order_st = nullptr;
@@ -672,6 +677,50 @@ GULON_API int32_t gulon_exact_index_query_cosmul(gulon_exact_index *idx, const i
                         x.fi.p, x.fd.p, x.fc.p, nullptr, st);
     order_record(idx, st);
     if (bk) { x.fi.download(out_idx, bk, st); x.fd.download(out_score, bk, st); }
+    if (out_count) x.fc.download(out_count, (size_t)b, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+  });
+}
+
+// Offset queries: offset.hip ranks rows [from, until) of the dataset by distance + row_offsets[row]; the
+// offsets and the excluded rows are indexed by dataset row, as the returned ids are.
+GULON_API int32_t gulon_exact_index_query_offset_dev(gulon_exact_index *idx, const float *d_queries, int32_t b,
+                                                     int32_t k_nn, const float *d_row_offsets, const int32_t *d_exclude,
+                                                     int32_t *d_out_idx, float *d_out_key, int32_t *d_out_count,
+                                                     void *stream) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr, "index is null");
+    std::lock_guard<std::mutex> g(idx->mu);
+    const hipStream_t st = (hipStream_t)stream;
+    order_wait(idx, st);
+    launch_offset_exact(idx->ds, idx->from, idx->until, idx->offset, d_queries, b, k_nn, d_row_offsets, d_exclude,
+                        d_out_idx, d_out_key, d_out_count, st);
+    if (b > 0) order_record(idx, st);
+  });
+}
+
+GULON_API int32_t gulon_exact_index_query_offset(gulon_exact_index *idx, const float *queries, int32_t b, int32_t k_nn,
+                                                 const float *row_offsets, const int32_t *exclude, int32_t *out_idx,
+                                                 float *out_key, int32_t *out_count) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr, "index is null");
+    check_offset_host(row_offsets, idx->ds->n, exclude, b, k_nn, 0);
+    if (b == 0) return;
+    GULON_REQUIRE(queries != nullptr && out_idx != nullptr && out_key != nullptr, "null argument");
+    std::lock_guard<std::mutex> g(idx->mu);
+    OffsetWork &x = idx->offset;
+    const hipStream_t st = nullptr;
+    const size_t bk = (size_t)b * (size_t)k_nn;
+    order_wait(idx, st);   // the workspace may still be read by the last batch, on another stream
+    x.q.upload(queries, (size_t)b * idx->ds->d, st);
+    x.off.upload(row_offsets, (size_t)idx->ds->n, st);
+    x.off.ensure(1);
+    if (exclude) x.ex.upload(exclude, (size_t)b, st);
+    x.fi.ensure(bk); x.fd.ensure(bk); x.fc.ensure((size_t)b);
+    launch_offset_exact(idx->ds, idx->from, idx->until, x, x.q.p, b, k_nn, x.off.p, exclude ? x.ex.p : nullptr, x.fi.p,
+                        x.fd.p, x.fc.p, st);
+    order_record(idx, st);
+    x.fi.download(out_idx, bk, st); x.fd.download(out_key, bk, st);
     if (out_count) x.fc.download(out_count, (size_t)b, st);
     HIP_CHECK(hipStreamSynchronize(st));
   });

@@ -54,6 +54,16 @@ struct CosmulWork {
   DevBuf<float> w, fd;
   std::mutex mu;
 };
+// Workspace of the offset queries of one handle (offset.hip), under the same two rules.
+struct OffsetWork {
+  DevBuf<float> qt;             // exact: the queries transposed per workgroup [tile][d][16]
+  DevBuf<float> tables;         // flat: Index.prepareQuery of every query [b][m_pad][256]
+  DevBuf<float> pv;             // per-chunk lists of keys
+  DevBuf<int> pi;
+  DevBuf<float> q, off, fd;     // the host-pointer forms: queries, row offsets, final keys
+  DevBuf<int> ex, fi, fc;       // ... the excluded rows, final rows and counts
+  std::mutex mu;
+};
 }
 // PQIndex on the device (opaque to C callers)
 using gulon::DevBuf;
@@ -97,6 +107,7 @@ struct gulon_index {
   DevBuf<int> row_err;     // set by the row decode when a *_dev call asked for a row outside [0, n)
   gulon::ExprWork expr;    // expression queries (compose.hip)
   gulon::CosmulWork cosmul;   // multiplicative analogy queries (cosmul.hip)
+  gulon::OffsetWork offset;   // offset queries (offset.hip)
   DevBuf<unsigned long long> dbg;   // GULON_REPLAY_STATS stamps (replay.hip)
   // large-K peeling rounds
   DevBuf<float> peel_v, peel_tv, peel_lbv;
@@ -343,6 +354,15 @@ template <>
 __device__ inline uint32_t code_byte<16>(const uint4 &w, int b) {
   uint32_t x = (b < 4) ? w.x : (b < 8) ? w.y : (b < 12) ? w.z : w.w;
   return (x >> (8 * (b & 3))) & 0xFFu;
+}
+// 32-bit word `seg` of a code word (seg need not be a constant: no register array is indexed)
+template <int VEC>
+__device__ __forceinline__ uint32_t code_word32(const typename CodeWord<VEC>::type &w, int seg);
+template <>
+__device__ __forceinline__ uint32_t code_word32<4>(const uint32_t &w, int) { return w; }
+template <>
+__device__ __forceinline__ uint32_t code_word32<16>(const uint4 &w, int seg) {
+  return seg == 0 ? w.x : seg == 1 ? w.y : seg == 2 ? w.z : w.w;
 }
 #endif
 

@@ -165,6 +165,23 @@ class ExactIndex:
         oi, od, oc = self.batch_query_cosmul_raw(k, expressions)
         return [Result(oi[i, :oc[i]].copy(), od[i, :oc[i]].copy(), 0) for i in range(len(oc))]
 
+    # ---- offset queries (csls.py): the offsets are indexed by rows of the MATRIX
+    def batch_query_offset_raw(self, k, vectors, offsets, exclude=None):
+        """gulon_exact_index_query_offset: per query the k rows of [frm, until) with the smallest t = distance +
+        offsets[row] among those whose t is finite and that are not exclude[q] (a row of the matrix, or -1), ties by
+        row id (csls.offset_query_reference).  The queries are normalised for a cosine index.  offsets: one float32 per
+        row of the matrix, an array or the device array csls.csls_offsets returned.  1 <= k <= 63.
+        -> (rows [b][k] with -1 after a query's last entry, keys t [b][k] with +inf there, counts [b])."""
+        from .csls import offset_query_raw
+        L = N.lib()
+        return offset_query_raw(L.gulon_exact_index_query_offset, L.gulon_exact_index_query_offset_dev, self._h, (),
+                                self.dimension, self.matrix.rows, k, self._prepare(vectors), offsets, exclude)
+
+    def batch_query_offset(self, k, vectors, offsets, exclude=None) -> List[Result]:
+        """batch_query_offset_raw as Results: `distances` holds the keys t, ascending; flags is 0."""
+        from .csls import as_results
+        return as_results(*self.batch_query_offset_raw(k, vectors, offsets, exclude))
+
     def stats(self):
         """Of the last batch: queries answered in one pass, by the peeled fallback and one at a time as non-finite; the
         sample rows S (0: no sample pass), the queue capacity, the largest number of rows at or below a bound."""
@@ -294,6 +311,17 @@ class ExactWordIndex:
 
     def query_cosmul(self, k, expression) -> Optional[WordResult]:
         return self.batch_query_cosmul(k, [expression])[0]
+
+    def batch_query_offset_raw(self, k, vectors, offsets, exclude=None):
+        """ExactIndex.batch_query_offset_raw, up to BATCH queries per device batch."""
+        from .csls import batched_offset_query
+        return batched_offset_query(self.index, self.dimension, k, vectors, offsets, exclude)
+
+    def batch_query_offset(self, k, vectors, offsets, exclude=None) -> List[WordResult]:
+        """Per query vector the k words with the smallest distance + offsets[row] (csls.py); `distances` of a result
+        holds those keys."""
+        from .csls import as_results
+        return [self._result(r) for r in as_results(*self.batch_query_offset_raw(k, vectors, offsets, exclude))]
 
     def close(self):
         """Frees the handle and the gathered matrix this index was built over, when it owns one."""

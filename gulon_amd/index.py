@@ -264,6 +264,24 @@ class PQIndex:
         oi, od, oc = self.batch_query_cosmul_raw(k, expressions, frm, until, normalize)
         return [Result(oi[i, :oc[i]].copy(), od[i, :oc[i]].copy(), 0) for i in range(len(oc))]
 
+    def batch_query_offset_raw(self, k, vectors, offsets, exclude=None, frm=0, until=None):
+        """gulon_index_query_offset: per query (taken as given) the k rows of [frm, until) with the smallest
+        t = distance + offsets[row] among those whose t is finite and that are not exclude[q] (a row id as returned, or
+        -1), ties by row id (csls.offset_query_reference).  offsets: one float32 per row of the index, an
+        array or the device array csls.csls_offsets returned.  1 <= k <= 63, byte codes, no view.
+        -> (rows [b][k] with -1 after a query's last entry, keys t [b][k] with +inf there, counts [b])."""
+        from .csls import offset_query_raw
+        L = N.lib()
+        until = self.length if until is None else until
+        return offset_query_raw(L.gulon_index_query_offset, L.gulon_index_query_offset_dev, self._h, (frm, until),
+                                self.dimension, self.length, k, vectors, offsets, exclude)
+
+    def batch_query_offset(self, k, vectors, offsets, exclude=None, frm=0, until=None):
+        """batch_query_offset_raw as Results: `distances` holds the keys t, ascending; flags is 0 (the order (t, row) is
+        total)."""
+        from .csls import as_results
+        return as_results(*self.batch_query_offset_raw(k, vectors, offsets, exclude, frm, until))
+
     def select(self, rows=None, mask=None):
         """The view of this index over a subset of its rows (gulon_index_select_*): an index of its own, gathered on
         the device, that answers in THIS index's row ids.  Exactly one of `rows` (strictly ascending row numbers) and
@@ -575,6 +593,16 @@ class SortedIndex:
         """Per expression over row ids the k rows with the largest 3CosMul score that are none of its operands;
         `distances` of a Result holds the SCORES, in descending order."""
         return self.vector_index.batch_query_cosmul(k, expressions, normalize=self.metric == "cosine")
+
+    def batch_query_offset_raw(self, k, vectors, offsets, exclude=None):
+        """PQIndex.batch_query_offset_raw over all rows, the queries normalised for a cosine index: (rows, keys
+        distance + offsets[row] in ascending order, counts)."""
+        return self.vector_index.batch_query_offset_raw(k, self._prepare(vectors), offsets, exclude)
+
+    def batch_query_offset(self, k, vectors, offsets, exclude=None):
+        """Per query the k rows with the smallest distance + offsets[row] among the rows whose sum is finite and that
+        are not exclude[q]; `distances` of a Result holds those keys."""
+        return self.vector_index.batch_query_offset(k, self._prepare(vectors), offsets, exclude)
 
 
 class Index:

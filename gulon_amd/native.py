@@ -215,6 +215,12 @@ SIGNATURES = {
     "gulon_dataset_pair_distances_dev": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp]),
     "gulon_rank_sums": (_i32, [_f32p, _f32p, _vp, _i32, _i32, _i64p]),
     "gulon_rank_sums_dev": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "gulon_exact_index_query_offset": (_i32, [_vp, _f32p, _i32, _i32, _f32p, _vp, _i32p, _f32p, _i32p]),
+    "gulon_exact_index_query_offset_dev": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gulon_index_query_offset": (_i32, [_vp, _f32p, _i32, _i32, _i32, _i32, _f32p, _vp, _i32p, _f32p, _i32p]),
+    "gulon_index_query_offset_dev": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gulon_mean_similarity": (_i32, [_f32p, _vp, _i32, _i32, _i32, _f32p]),
+    "gulon_mean_similarity_dev": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
 }
 
 _lib = None

@@ -198,6 +198,22 @@ class WordIndex:
     def query_cosmul(self, k, expression) -> Optional[WordResult]:
         return self.batch_query_cosmul(k, [expression])[0]
 
+    def batch_query_offset_raw(self, k, vectors, offsets, exclude=None):
+        """SortedIndex.batch_query_offset_raw (csls.py), up to BATCH queries per device batch: (rows
+        [b][k] with -1 after a query's last entry, keys [b][k] with +inf there, counts [b]).  NotImplementedError for a
+        grouped index (and, from the library, for codes wider than a byte)."""
+        if self._grouped:
+            raise NotImplementedError("offset queries are not supported by the grouped index")
+        from .csls import batched_offset_query
+        return batched_offset_query(self.index, self.dimension, k, vectors, offsets, exclude)
+
+    def batch_query_offset(self, k, vectors, offsets, exclude=None) -> List[WordResult]:
+        """Per query vector the k words with the smallest distance + offsets[row] among the rows whose sum is finite
+        and that are not exclude[q]; `distances` of a result holds those keys.  offsets: one float32 per row, an array
+        or what csls.csls_offsets returned."""
+        from .csls import as_results
+        return [self._result(r) for r in as_results(*self.batch_query_offset_raw(k, vectors, offsets, exclude))]
+
     def batch_query(self, k, vectors) -> List[WordResult]:
         """Index.batchQuery (Index.scala:25-32) with the results' words."""
         q = np.ascontiguousarray(vectors, np.float32).reshape(-1, self.dimension)
@@ -295,6 +311,9 @@ class RestrictedWordIndex(WordIndex):
 
     def batch_query_cosmul(self, k, expressions):
         raise NotImplementedError("cosmul queries are not supported by a restricted index")
+
+    def batch_query_offset_raw(self, k, vectors, offsets, exclude=None):
+        raise NotImplementedError("offset queries are not supported by a restricted index")
 
     def close(self):
         self.index.vector_index.close()

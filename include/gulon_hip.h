@@ -923,6 +923,50 @@ int32_t gulon_rank_sums(const float *x, const float *y, const int32_t *section, 
                         int64_t *out);
 int32_t gulon_rank_sums_dev(const float *d_x, const float *d_y, const int32_t *d_section, int32_t n, int32_t nsections,
                             int64_t *d_out, void *stream);
+
+/* ---- Offset queries and CSLS (offset.hip) ----------------------------------------------------------------
+ * Neighbours by distance plus one number per row, on the exact index and on a flat byte-code index.  Per query q and per
+ * row r of the handle's range (the index: of [from, until)):
+ *   d = the bits the handle's ordinary query returns as the distance between q and r (the exact index: the sum of
+ *       MathUtils.distanceSq; the index: the running sum over the quantizers' Index.prepareQuery tables, quantizer 0
+ *       first, from 0);
+ *   t = d + row_offsets[r], one binary32 addition.
+ * row_offsets is indexed by the row: the exact index returns dataset rows and the array has the dataset's rows; the
+ * index returns row_base + r for its row r and the array has the index's length, entry r for that row.  exclude
+ * (nullable) holds per query one row id as the handle returns it, or -1.
+ * A row is a candidate if and only if t is finite and its id is not exclude[q].  The answer: the candidates by
+ * (t ascending, row id ascending; -0 equals +0), the first k_nn.  out_idx [b][k_nn] padded with -1, out_key [b][k_nn] = t
+ * padded with +inf, out_count [b] (nullable).  The order is total: no tie flags.  An offset of +inf masks its row; the
+ * same array serves a per-row prior, and CSLS retrieval (Conneau et al. 2018): on unit vectors CSLS(x, y) = 2 - d(x, y)
+ * - r_T(x) - r_S(y), so ranking by d + r_S ascending is ranking by CSLS descending, r_S from gulon_mean_similarity.
+ * Queries are taken as given (no normalisation).
+ * Limits: 1 <= k_nn <= GULON_MAX_K, else GULON_ERR_UNSUPPORTED.  The index: byte codes only (wide codes and views are
+ * GULON_ERR_UNSUPPORTED), and the tables of one query, m_pad KiB, must fit in 144 KiB of LDS, else GULON_ERR_UNSUPPORTED
+ * naming m.
+ * The host forms check b, k_nn, from / until, NaN or -inf in row_offsets and exclude outside -1 or the handle's row ids
+ * (GULON_ERR_INVALID_ARGUMENT) before anything is launched.  The _dev forms take device pointers and a stream and neither
+ * check the arrays nor synchronise: there a NaN or -inf offset makes t non-finite and so masks its row. */
+int32_t gulon_exact_index_query_offset(gulon_exact_index *idx, const float *queries, int32_t b, int32_t k_nn,
+                                       const float *row_offsets, const int32_t *exclude, int32_t *out_idx,
+                                       float *out_key, int32_t *out_count);
+int32_t gulon_exact_index_query_offset_dev(gulon_exact_index *idx, const float *d_queries, int32_t b, int32_t k_nn,
+                                           const float *d_row_offsets, const int32_t *d_exclude, int32_t *d_out_idx,
+                                           float *d_out_key, int32_t *d_out_count, void *stream);
+int32_t gulon_index_query_offset(gulon_index *idx, const float *queries, int32_t b, int32_t k_nn, int32_t from,
+                                 int32_t until, const float *row_offsets, const int32_t *exclude, int32_t *out_idx,
+                                 float *out_key, int32_t *out_count);
+int32_t gulon_index_query_offset_dev(gulon_index *idx, const float *d_queries, int32_t b, int32_t k_nn, int32_t from,
+                                     int32_t until, const float *d_row_offsets, const int32_t *d_exclude,
+                                     int32_t *d_out_idx, float *d_out_key, int32_t *d_out_count, void *stream);
+/* gulon_mean_similarity: the mean cosine similarity of each of b lists of squared distances between unit vectors,
+ * dist_lists [b][kin] as a query returns them.  c = min(counts[q], K), or min(kin, K) when counts is NULL; out[q] = 0
+ * when c == 0; else s_j = 1 - 0.5 * d_j, sum = s_0, sum = sum + s_j for j = 1 .. c - 1, out[q] = sum / (float)c, every
+ * operation rounded to binary32 on its own.  b >= 0, kin >= 1, K >= 1 (GULON_ERR_INVALID_ARGUMENT).  The _dev form takes
+ * device pointers and a stream and does not synchronise. */
+int32_t gulon_mean_similarity(const float *dist_lists, const int32_t *counts, int32_t b, int32_t kin, int32_t K,
+                              float *out);
+int32_t gulon_mean_similarity_dev(const float *d_dist_lists, const int32_t *d_counts, int32_t b, int32_t kin, int32_t K,
+                                  float *d_out, void *stream);
 #ifdef GULON_TEST_HOOKS   /* libgulon_hip_testhooks.so only */
 /* The launch geometry of the 3CosMul scans (cosmul.hip), by the arithmetic their launchers run; host code, nothing is
  * launched.  b >= 1 questions.  Flat index, rows [from, until): out = {questions per pass, row chunks of the first
