@@ -268,7 +268,11 @@ class PQIndex:
         """gulon_index_query_offset: per query (taken as given) the k rows of [frm, until) with the smallest
         t = distance + offsets[row] among those whose t is finite and that are not exclude[q] (a row id as returned, or
         -1), ties by row id (csls.offset_query_reference).  offsets: one float32 per row of the index, an
-        array or the device array csls.csls_offsets returned.  1 <= k <= 63, byte codes, no view.
+        array or the device array csls.csls_offsets returned.  1 <= k <= 63, byte codes, no view.  Offsets may be
+        negative; NaN and -inf are refused (ValueError).  A query none of whose t is finite -- a NaN or infinite
+        component, distances that overflow -- is answered with no row.  With a row_base, offsets stay indexed by the
+        index's own rows, exclude and the answer carry the base.  Every byte-code index there is has a table of at most
+        144 KiB (PQIndex refuses a larger m with NotImplementedError), which is what one query slot of the scan needs.
         -> (rows [b][k] with -1 after a query's last entry, keys t [b][k] with +inf there, counts [b])."""
         from .csls import offset_query_raw
         L = N.lib()

@@ -4,7 +4,8 @@ against csls.offset_query_reference over the handle's own distances -- its ordin
 Shapes: 700 rows are three 256-row groups (several row chunks are merged), 33 dimensions cross the 32-wide staging step
 by one, the handle covers [37, 695), 17 queries leave one in the second query tile.  Offsets come from eight values and
 twenty rows are copies of others with the same offset, so equal keys occur and the row id decides; a tenth of the
-offsets are +inf; every other query excludes the row it was made from."""
+offsets are +inf; every other query excludes the row it was made from.  Negative keys, tie groups larger than a list
+and non-finite queries: test_gpu_offset_paths.py."""
 import numpy as np
 import pytest
 

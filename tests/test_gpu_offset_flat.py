@@ -6,7 +6,8 @@ Shapes: 256 centroids, m = 3 (one 4-byte code word) and m = 16 (one 16-byte word
 [5, n - 3), so neither end is on a 64-row code block; batches of 5 (eight query slots to a workgroup, three idle), 3, 2
 and 1 (four, two and one slot).  A second world of 70 code blocks is cut into two row chunks.  Twenty rows are copies of
 others with the same offset, so equal keys occur; a tenth of the offsets are +inf; every other query excludes the row it
-was made from."""
+was made from.  Rows of several code words, E bound by the LDS, two passes, three row chunks, tie groups larger than a
+list, negative and non-finite keys and a row base: test_gpu_offset_paths.py."""
 import numpy as np
 import pytest
 
