@@ -28,6 +28,8 @@ from .similarity import (SimilarityReport, evaluate_pairs, pair_distance_referen
 from .csls import (DeviceOffsets, TranslationReport, csls_offsets, evaluate_dictionary, mean_similarity,
                    mean_similarity_reference, offset_query_reference, read_dictionary, translate_words,
                    translation_scores)
+from .alignment import (induce_matches, mutual_rows, mutual_rows_reference, pair_moment, pair_moment_reference,
+                        seed_alignment, train_alignment)
 
 __all__ = ["native", "GroupedIndex", "GroupedVectors", "LimitGroups", "LimitVectors", "group", "Coder", "width_for_clusters", "Index", "PQIndex", "PQIndexView", "DevicePQIndex", "Result", "SortedIndex",
            "exact_nearest_neighbours", "prepare_query", "tune_live", "KMeans", "KMeansConfig", "DeviceMatrix", "Matrix",
@@ -41,4 +43,6 @@ __all__ = ["native", "GroupedIndex", "GroupedVectors", "LimitGroups", "LimitVect
            "COSMUL_EPS", "cosmul_reference", "SimilarityReport", "evaluate_pairs", "read_pairs",
            "pair_distance_reference", "rank_sums", "rank_sums_reference", "spearman", "DeviceOffsets",
            "TranslationReport", "csls_offsets", "evaluate_dictionary", "mean_similarity", "mean_similarity_reference",
-           "offset_query_reference", "read_dictionary", "translate_words", "translation_scores"]
+           "offset_query_reference", "read_dictionary", "translate_words", "translation_scores",
+           "induce_matches", "mutual_rows", "mutual_rows_reference", "pair_moment", "pair_moment_reference",
+           "seed_alignment", "train_alignment"]

@@ -1,5 +1,5 @@
 """`python -m gulon_amd`: the reference's four commands (command/Main.scala:7-11), `inspect`, `update`, `build-fine`,
-`analogies`, `similarity` and `translate`.
+`analogies`, `similarity`, `translate` and `align`.
 
   build-index -d l2|cosine -o INDEX [-k N] [-m N] [-n N] [-p [--partitions N] [-l N]] [-R ROTATION [--rotation-rounds N]]
               FILE
@@ -73,8 +73,8 @@
                                        and ranks are computed on the device.  -R is not offered: distances between stored
                                        rows need no rotation
 
-  translate -i TARGET -s SOURCE [--method nn|csls] [-n 10] [-k 10] [-v VECTORS --exact] [-R ROTATION] [--lowercase]
-            (WORDS | -e DICTIONARY)
+  translate -i TARGET -s SOURCE [--method nn|csls] [-n 10] [-k 10] [-v VECTORS --exact] [-R ROTATION] [-a MAP]
+            [--lowercase] (WORDS | -e DICTIONARY)
                                        (not in the reference) word translation between two aligned embedding spaces
                                        (csls.py, csrc/offset.hip).  TARGET is an index file over the target language's
                                        vectors, SOURCE a word2vec text file of the source language's, already mapped
@@ -89,7 +89,23 @@
                                        skipped 12)` -- the precision at -k 1,5,10, n the source words asked, skipped the
                                        pairs with a word either side lacks.  -v VECTORS --exact: the target is the true
                                        vectors of the index's words.  -R ROTATION: the index was built with build-index
-                                       -R, and the source vectors are rotated after they are read (not with --exact)
+                                       -R, and the source vectors are rotated after they are read (not with --exact).
+                                       -a MAP: SOURCE is NOT mapped yet; the map `align` wrote is applied to its vectors
+                                       on the device after they are read, before -R's rotation
+
+  align -s SOURCE -t TARGET (-d DICTIONARY | --identical) -o MAP [--rounds 5] [--max-rank 15000] [-n 10] [--lowercase]
+                                       (not in the reference) learn the orthogonal map that takes the vectors of SOURCE
+                                       into the space of TARGET (alignment.py, csrc/alignment.hip): MUSE's supervised
+                                       recipe.  Both are word2vec text files in frequency order, read normalised and NOT
+                                       sorted.  The seed is DICTIONARY, lines of `source target`, or with --identical the
+                                       words spelt the same on both sides; an orthogonal Procrustes solve on it, then
+                                       --rounds refinements, each solving again on the pairs among the first --max-rank
+                                       words of either side that are each other's CSLS best match (-n neighbours behind
+                                       the mean similarities).  Printed: `seed: 4821 pairs, skipped 179`, per round
+                                       `round 2: mutual 9312 of 15000, criterion 0.612345` -- the criterion the mean
+                                       cosine of the 10 000 most frequent source words with their best match -- and
+                                       `chosen: round 3`, the round whose map is written to MAP (a rotation file, as
+                                       build-index -R writes them) for translate -a
 
 -f FINE on the query commands and on test (not in the reference): as -v / -c, but the candidates are re-ranked by their
 distance to the index's row plus the fine index's row of the same word (fine.FineRefinedIndex) -- no original vectors in
@@ -268,6 +284,20 @@ class TranslateConfig:
     vectors: Optional[str] = None         # -v: the vectors the index was built from (with --exact)
     exact: bool = False                   # --exact: the true vectors of the index's words are the target
     rotation: Optional[str] = None        # -R: the index was built over vectors rotated by this file
+    alignment: Optional[str] = None       # -a: the map of the source vectors into the target's space (align)
+
+
+@dataclass(frozen=True)
+class AlignConfig:
+    source: str                           # -s: word2vec text of the source language, in frequency order
+    target: str                           # -t: the same of the target language
+    output: str                           # -o: the map, a rotation file
+    dictionary: Optional[str] = None      # -d: the seed dictionary ...
+    identical: bool = False               # ... or --identical: the words spelt the same on both sides
+    rounds: int = 5                       # --rounds: refinement rounds after the seed
+    max_rank: int = 15000                 # --max-rank: the most frequent words of either side that take part
+    neighbours: int = 10                  # -n: the K of CSLS's mean similarities
+    lowercase: bool = False               # --lowercase: lower the dictionary's words
 
 
 def _depths(s):
@@ -313,10 +343,27 @@ def _rotated(path, vectors):
     if path is None:
         return vectors
     from .rotation import Rotation
-    rotated = Rotation.load(path).rotate_word_vectors(vectors)
+    return _rotated_by(Rotation.load(path), vectors)
+
+
+def _rotated_by(rotation, vectors):
+    rotated = rotation.rotate_word_vectors(vectors)
     if vectors.matrix is not None:
         vectors.matrix.close()
     return rotated
+
+
+def _aligned(path, vectors):
+    """The source vectors as read, or with -a mapped on the device by that file (the unmapped matrix is freed).
+    ValueError: a map of another dimension."""
+    if path is None:
+        return vectors
+    from .rotation import Rotation
+    rotation = Rotation.load(path)
+    if rotation.dimension != vectors.dimension:
+        raise ValueError(f"{path}: a map of dimension {rotation.dimension} for source vectors of dimension "
+                         f"{vectors.dimension}")
+    return _rotated_by(rotation, vectors)
 
 
 def _parser():
@@ -467,8 +514,30 @@ def _parser():
     tr.add_argument("-R", "--rotation", default=None, metavar="file",
                     help="rotation file the index was built with (build-index -R): the source vectors are rotated after "
                          "they are read (not with --exact)")
+    tr.add_argument("-a", "--alignment", default=None, metavar="file",
+                    help="map written by align: the source vectors are not mapped yet, and are mapped on the device "
+                         "after they are read (before --rotation applies)")
     tr.add_argument("--lowercase", action="store_true", help="lower the words to translate")
     tr.add_argument("file", nargs="?", metavar="file", help="source words, one per line")
+    al = sub.add_parser("align", help="learn the map between two embedding spaces",
+                        description="learn the orthogonal map that takes the source language's word vectors into the "
+                                    "target's space: a Procrustes solve on a seed dictionary, refined on CSLS mutual "
+                                    "nearest neighbours")
+    al.add_argument("-s", "--source", required=True, metavar="file",
+                    help="word2vec word vectors of the source language, most frequent word first")
+    al.add_argument("-t", "--target", required=True, metavar="file",
+                    help="word2vec word vectors of the target language, most frequent word first")
+    al.add_argument("-d", "--dictionary", default=None, metavar="file",
+                    help="the seed dictionary, lines of `source target`")
+    al.add_argument("--identical", action="store_true",
+                    help="seed from the words spelt the same on both sides instead of a dictionary")
+    al.add_argument("-o", "--output", required=True, metavar="file", help="map output file")
+    al.add_argument("--rounds", type=_rounds, default=5, metavar="num", help="refinement rounds (default 5)")
+    al.add_argument("--max-rank", type=_positive, default=15000, metavar="num",
+                    help="most frequent words of either side that take part in the refinement (default 15000)")
+    al.add_argument("-n", "--csls-neighbours", type=_positive, default=10, metavar="num",
+                    help="neighbours behind the mean similarities of csls (default 10)")
+    al.add_argument("--lowercase", action="store_true", help="lower the words of the dictionary")
     u = sub.add_parser("update", help="add, replace and remove words of an index without retraining",
                        description="add, replace and remove words of an index without retraining")
     u.add_argument("-i", "--index", required=True, metavar="file", help="path to ANN index")
@@ -753,7 +822,11 @@ def run_translate(config: TranslateConfig, write, load, vectors):
         cosine = index.metric == "cosine"
         if config.exact:
             index = index.exact(vectors(config.vectors, cosine))
-        originals = _rotated(config.rotation, vectors(config.source, cosine))
+        try:
+            originals = _aligned(config.alignment, vectors(config.source, cosine))
+        except OSError as e:
+            raise TranslateError(f"{config.alignment}: {e.strerror or e}")
+        originals = _rotated(config.rotation, originals)
         source = ExactWordIndex(originals.words, ExactIndex(originals.matrix, index.metric), originals.key_index)
         if pairs is not None:
             return evaluate_dictionary(index, source, pairs, config.ks, config.method, config.neighbours)
@@ -774,6 +847,55 @@ def run_translate(config: TranslateConfig, write, load, vectors):
         return None
     except (LookupError, NotImplementedError, ValueError) as e:
         raise TranslateError(str(e))
+
+
+class AlignError(Exception):
+    """What `align` reports and exits on: an unreadable or malformed file, vectors of different dimensions, a seed
+    without a usable pair."""
+
+
+def read_ranked(path):
+    """The vectors of align: on the device, normalised, in FILE order -- the row is the frequency rank."""
+    from .word_vectors import read_word2vec_device
+    return read_word2vec_device(path, normalize=True)
+
+
+def run_align(config: AlignConfig, write, vectors=None):
+    """align between its argument handling and the end of its output: the seed, the rounds and the choice are written
+    as lines, the map to config.output.  vectors: path -> DeviceWordVectors in file order (default read_ranked).
+    -> (Rotation, history) of alignment.train_alignment."""
+    from .alignment import identical_pairs, train_alignment
+    from .csls import read_dictionary
+    path = config.dictionary
+    try:
+        pairs = None
+        if path is not None:
+            with open(path, "rb") as fh:
+                pairs = read_dictionary(read_lines(fh.read()), config.lowercase)
+        read = vectors if vectors is not None else read_ranked
+        path = config.source
+        source = read(path)
+        path = config.target
+        target = read(path)
+    except OSError as e:
+        raise AlignError(f"{path}: {e.strerror or e}")
+    except ValueError as e:
+        raise AlignError(f"{path}: {e}")
+    try:
+        if pairs is None:
+            pairs = identical_pairs(source, target)
+        rotation, history = train_alignment(source, target, pairs, config.rounds, config.max_rank, config.neighbours)
+    except ValueError as e:
+        raise AlignError(str(e))
+    write(f"seed: {history['seed']['used']} pairs, skipped {history['seed']['skipped']}\n")
+    for t, r in enumerate(history["rounds"]):
+        write(f"round {t}: mutual {r['mutual']} of {r['asked']}, criterion {r['criterion']:.6f}\n")
+    write(f"chosen: round {history['chosen']}\n")
+    try:
+        rotation.save(config.output)
+    except OSError as e:
+        raise AlignError(f"{config.output}: {e.strerror or e}")
+    return rotation, history
 
 
 def read_originals(path, normalize):
@@ -817,7 +939,7 @@ def _refined(args, index, vectors, load):
 
 
 def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None, vectors=None, inspect=None,
-         update=None, fine=None, rotation=None, analogies=None, similarity=None, translate=None):
+         update=None, fine=None, rotation=None, analogies=None, similarity=None, translate=None, align=None):
     """Returns the exit code.  stdin / stdout: binary streams (default: the process's); load: path -> index with
     batch_query_by_words / batch_query (default WordIndex.load); build: (BuildConfig, write) -> None, the whole of
     build-index behind its argument handling (default run_build_index); recall: (RecallConfig, write, load) ->
@@ -831,7 +953,8 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
     analogies between its argument handling and its lines (default run_analogies).  similarity: (SimilarityConfig, load,
     vectors) -> SimilarityReport, the same for similarity (default run_similarity).  translate: (TranslateConfig, write,
     load, vectors) -> TranslationReport or None, the whole of translate behind its argument handling (default
-    run_translate)."""
+    run_translate).  align: (AlignConfig, write) -> anything, the whole of align behind its argument handling
+    (default run_align)."""
     parser = _parser()
     args = parser.parse_args(argv)
     if args.command == "similarity":
@@ -853,6 +976,8 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
                 else _positive(args.neighbours or "10")
         except argparse.ArgumentTypeError as e:
             parser.error(f"argument -k/--neighbours: {e}")
+    if args.command == "align" and (args.dictionary is None) != args.identical:
+        parser.error("exactly one of -d/--dictionary and --identical is required")
     if args.command == "analogies":
         if args.exact and args.vectors is None:
             parser.error("--exact needs -v/--vectors")
@@ -953,7 +1078,7 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
     elif args.command == "translate":
         k, ks = (10, depth) if args.evaluate is not None else (depth, (1, 5, 10))      # -k means depths with -e
         config = TranslateConfig(args.index, args.source, args.file, args.evaluate, args.method, args.csls_neighbours,
-                                 k, ks, args.lowercase, args.vectors, args.exact, args.rotation)
+                                 k, ks, args.lowercase, args.vectors, args.exact, args.rotation, args.alignment)
         try:
             report = (translate if translate is not None else run_translate)(config, write, load, vectors)
         except TranslateError as e:
@@ -963,6 +1088,15 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
         if report is not None:
             for line in report.lines():
                 write(line + "\n")
+    elif args.command == "align":
+        config = AlignConfig(args.source, args.target, args.output, args.dictionary, args.identical, args.rounds,
+                             args.max_rank, args.csls_neighbours, args.lowercase)
+        try:
+            (align if align is not None else run_align)(config, write)
+        except AlignError as e:
+            stdout.flush()
+            print(f"error: {e}", file=sys.stderr)
+            return 1
     elif args.command == "update":
         config = UpdateConfig(args.index, args.output, args.add, args.remove, args.rotation)
         try:

@@ -8,8 +8,10 @@
 //            function of the device -- each chunk summed r ascending by one workgroup into a slab of partial sums, the
 //            slabs added in ascending chunk order by a second kernel.  No floating-point atomics: the result is the same
 //            bits on every run and every device                         -- moment_partial_kernel, moment_sum_kernel
+//            The rows may come through a row map, r then a position in two lists of rows (moment_rows, moment.hpp;
+//            alignment.hip's pair moment): the same kernels and the same chunk driver.
 // Both use scratch of their own and touch no index handle.
-#include "common.hpp"
+#include "moment.hpp"
 
 namespace gulon {
 namespace {
@@ -103,18 +105,32 @@ constexpr long long ROT_MAX_ROWS = (long long)INT_MAX * ROT_ROWS;   // the row t
 // cover one 256-byte row).  Fused or not is the same number: the product is exact.  Staged zeros outside the matrices
 // add +0 and only ever meet a non-finite value in a tile entry that is not stored.
 constexpr int MOMENT_ROWS = 4096;
+constexpr long long MOMENT_MAX_ROWS = (long long)INT_MAX * MOMENT_ROWS;   // the chunk number is an int
 constexpr int MOM_THREADS = 256, MOM_TILE = 64, MOM_SLAB = 16;
 constexpr size_t MOM_SCRATCH_BYTES = (size_t)256 << 20;   // partial slabs held at a time; more chunks go in batches
+constexpr int MOM_STEPS = MOM_SLAB / (MOM_THREADS / 64);   // rows of a slab one wave stages
+static_assert(MOM_TILE == 64, "a wave stages one row segment: the row of a staged element is wave-uniform");
 
+// The rows are those of a row map: position i of the chunk reads a[ra(i)] and b[rb(i)].  MAPPED false: ra(i) = rb(i) = i,
+// the full-matrix moment.  MAPPED true: ra(i) = rows_a[i], rb(i) = rows_b[i], a negative row on either side stages zeros
+// for both (the pair adds +0).  A wave stages one 256-byte segment of one row of a and of b per step, so the map is read
+// once per wave and row (a uniform address: a scalar load).  A slab is staged in three passes over the wave's MOM_STEPS
+// rows -- the map entries (read at a position clamped into the chunk, so none of the loads is conditional), the row
+// segments into registers, the registers into LDS -- so that the 2 * MOM_STEPS gathered segments are in flight together
+// instead of each waiting for the one before it.
+template <bool MAPPED>
 __global__ __launch_bounds__(MOM_THREADS) void moment_partial_kernel(const float *__restrict__ a, int da,
-                                                                     const float *__restrict__ b, int db, int n,
+                                                                     const float *__restrict__ b, int db,
+                                                                     const int *__restrict__ rows_a,
+                                                                     const int *__restrict__ rows_b, long long n,
                                                                      int chunk0, double *__restrict__ partial) {
   __shared__ __attribute__((aligned(16))) float s_a[MOM_SLAB * MOM_TILE];
   __shared__ __attribute__((aligned(16))) float s_b[MOM_SLAB * MOM_TILE];
   const int tid = threadIdx.x, tp = tid >> 4, tq = tid & 15;
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int p0 = blockIdx.y * MOM_TILE, q0 = blockIdx.z * MOM_TILE;
   const long long begin = (long long)(chunk0 + (int)blockIdx.x) * MOMENT_ROWS;
-  const long long end = min((long long)n, begin + MOMENT_ROWS);
+  const long long end = min(n, begin + MOMENT_ROWS);
   double acc[4][4];
 #pragma unroll
   for (int i = 0; i < 4; i++)
@@ -122,11 +138,31 @@ __global__ __launch_bounds__(MOM_THREADS) void moment_partial_kernel(const float
     for (int j = 0; j < 4; j++) acc[i][j] = 0.0;
   for (long long r0 = begin; r0 < end; r0 += MOM_SLAB) {
     __syncthreads();
-    for (int e = tid; e < MOM_SLAB * MOM_TILE; e += MOM_THREADS) {
-      const long long r = r0 + e / MOM_TILE;
-      const int cc = e % MOM_TILE;
-      s_a[e] = (r < end && p0 + cc < da) ? a[(size_t)r * da + p0 + cc] : 0.0f;
-      s_b[e] = (r < end && q0 + cc < db) ? b[(size_t)r * db + q0 + cc] : 0.0f;
+    long long ra[MOM_STEPS], rb[MOM_STEPS];   // -1: zeros
+#pragma unroll
+    for (int t = 0; t < MOM_STEPS; t++) {
+      const long long i = r0 + wave + t * (MOM_THREADS / 64);
+      if (MAPPED) {
+        const long long ic = min(i, end - 1);   // r0 < end: a position of this chunk
+        const int xa = rows_a[ic], xb = rows_b[ic];
+        const bool live = i < end && xa >= 0 && xb >= 0;
+        ra[t] = live ? xa : -1;
+        rb[t] = live ? xb : -1;
+      } else {
+        ra[t] = rb[t] = i < end ? i : -1;
+      }
+    }
+    float va[MOM_STEPS], vb[MOM_STEPS];
+#pragma unroll
+    for (int t = 0; t < MOM_STEPS; t++) {
+      va[t] = (ra[t] >= 0 && p0 + lane < da) ? a[(size_t)ra[t] * da + p0 + lane] : 0.0f;
+      vb[t] = (rb[t] >= 0 && q0 + lane < db) ? b[(size_t)rb[t] * db + q0 + lane] : 0.0f;
+    }
+#pragma unroll
+    for (int t = 0; t < MOM_STEPS; t++) {
+      const int e = (wave + t * (MOM_THREADS / 64)) * MOM_TILE + lane;
+      s_a[e] = va[t];
+      s_b[e] = vb[t];
     }
     __syncthreads();
 #pragma unroll 4
@@ -167,7 +203,19 @@ __global__ void moment_sum_kernel(const double *__restrict__ partial, int chunks
 void moment(const gulon_dataset *a, const gulon_dataset *b, double *out) {
   GULON_REQUIRE(a != nullptr && b != nullptr && out != nullptr, "null argument");
   GULON_REQUIRE(a->n == b->n, "the moment of %d rows with %d rows", a->n, b->n);
-  const int n = a->n, da = a->d, db = b->d;
+  moment_rows(a->x.p, a->d, b->x.p, b->d, nullptr, nullptr, a->n, out);
+}
+
+void check_rotate(long long n, int d) {
+  GULON_REQUIRE(d >= 1, "bad dimension d=%d", d);
+  GULON_REQUIRE(n >= 0 && n <= ROT_MAX_ROWS, "bad row count n=%lld", n);
+}
+
+}  // namespace
+
+void moment_rows(const float *d_a, int da, const float *d_b, int db, const int *d_rows_a, const int *d_rows_b,
+                 long long n, double *out) {
+  GULON_REQUIRE(n >= 0 && n <= MOMENT_MAX_ROWS, "the number of rows must lie in [0, %lld], got %lld", MOMENT_MAX_ROWS, n);
   const size_t entries = (size_t)da * db;
   if (n == 0) {
     std::fill(out, out + entries, 0.0);
@@ -176,10 +224,16 @@ void moment(const gulon_dataset *a, const gulon_dataset *b, double *out) {
   const int chunks = ceil_div(n, MOMENT_ROWS);
   const int batch = (int)std::min<size_t>((size_t)chunks, std::max<size_t>(MOM_SCRATCH_BYTES / (entries * sizeof(double)), 1));
   DevBuf<double> partial((size_t)batch * entries), sum(entries);
+  const bool mapped = d_rows_a != nullptr;
   for (int c0 = 0; c0 < chunks; c0 += batch) {
     const int nc = std::min(batch, chunks - c0);
-    hipLaunchKernelGGL(moment_partial_kernel, dim3(nc, ceil_div(da, MOM_TILE), ceil_div(db, MOM_TILE)),
-                       dim3(MOM_THREADS), 0, 0, a->x.p, da, b->x.p, db, n, c0, partial.p);
+    const dim3 grid(nc, ceil_div(da, MOM_TILE), ceil_div(db, MOM_TILE));
+    if (mapped)
+      hipLaunchKernelGGL(moment_partial_kernel<true>, grid, dim3(MOM_THREADS), 0, 0, d_a, da, d_b, db, d_rows_a, d_rows_b,
+                         n, c0, partial.p);
+    else
+      hipLaunchKernelGGL(moment_partial_kernel<false>, grid, dim3(MOM_THREADS), 0, 0, d_a, da, d_b, db, d_rows_a, d_rows_b,
+                         n, c0, partial.p);
     HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(moment_sum_kernel, dim3(ceil_div((long long)entries, 256)), dim3(256), 0, 0, partial.p, nc,
                        entries, c0 == 0 ? 1 : 0, sum.p);
@@ -189,12 +243,6 @@ void moment(const gulon_dataset *a, const gulon_dataset *b, double *out) {
   HIP_CHECK(hipDeviceSynchronize());
 }
 
-void check_rotate(long long n, int d) {
-  GULON_REQUIRE(d >= 1, "bad dimension d=%d", d);
-  GULON_REQUIRE(n >= 0 && n <= ROT_MAX_ROWS, "bad row count n=%lld", n);
-}
-
-}  // namespace
 }  // namespace gulon
 
 using namespace gulon;

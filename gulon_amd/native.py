@@ -221,6 +221,10 @@ SIGNATURES = {
     "gulon_index_query_offset_dev": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gulon_mean_similarity": (_i32, [_f32p, _vp, _i32, _i32, _i32, _f32p]),
     "gulon_mean_similarity_dev": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "gulon_dataset_pair_moment": (_i32, [_vp, _vp, _vp, _vp, C.c_int64, _f64p, C.POINTER(C.c_int64)]),
+    "gulon_dataset_pair_moment_dev": (_i32, [_vp, _vp, _vp, _vp, C.c_int64, _f64p, C.POINTER(C.c_int64)]),
+    "gulon_mutual_rows": (_i32, [_vp, _i32, _vp, _i32, _vp]),
+    "gulon_mutual_rows_dev": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp]),
 }
 
 _lib = None

@@ -967,6 +967,37 @@ int32_t gulon_mean_similarity(const float *dist_lists, const int32_t *counts, in
                               float *out);
 int32_t gulon_mean_similarity_dev(const float *d_dist_lists, const int32_t *d_counts, int32_t b, int32_t kin, int32_t K,
                                   float *d_out, void *stream);
+
+/* ---- Alignment (alignment.hip) ---------------------------------------------------------------------------
+ * Not Scala methods: the reference aligns nothing.  The two device steps of learning an orthogonal map between two
+ * embedding spaces (MUSE's Procrustes refinement) that the entry points above do not cover.
+ *
+ * pair moment: out[p * b->d + q] = sum_i a[rows_a[i]][p] * b[rows_b[i]][q] over i in [0, n), accumulated in binary64
+ * (host memory, a->d * b->d doubles) -- gulon_dataset_moment over a list of row pairs of two datasets that may differ in
+ * rows and in dimension.  A pair with a negative row on either side adds nothing and is not counted; *out_used (host)
+ * is the number of pairs that were.  Duplicates and any order are allowed.  The products are exact in binary64, only the
+ * additions round, and their order is fixed by the source as for gulon_dataset_moment: the list is cut BY POSITION into
+ * chunks of 4096 pairs (a skipped pair keeps its position and adds +0), each chunk summed i ascending from 0.0, the chunk
+ * sums added in ascending chunk order, no atomics on floating-point values: the same bits on every call and every
+ * device, and with rows_a = rows_b = 0 .. n - 1 over two datasets of n rows the bits of gulon_dataset_moment.
+ * n = 0 gives zeros and *out_used = 0.  Null pointers (the lists may be null when n = 0), n < 0: GULON_ERR_INVALID_ARGUMENT.
+ *   gulon_dataset_pair_moment       the lists in host memory; a row >= its dataset's row count is
+ *                                   GULON_ERR_INVALID_ARGUMENT, before anything is launched
+ *   gulon_dataset_pair_moment_dev   the lists in device memory, trusted: a row beyond its dataset is read out of bounds.
+ *                                   Runs on the null stream and returns when out and *out_used have arrived
+ *
+ * mutual rows: out[s] = fwd[s] if 0 <= fwd[s] < nt and bwd[fwd[s]] == s, else -1, for s in [0, ns): fwd [ns] each
+ * source row's best target row, bwd [nt] each target row's best source row, out [ns] the pairs that chose each other.
+ * Elementwise, nothing is compacted: the pair moment skips the -1.  ns, nt >= 0; entries of fwd outside [0, nt) (-1: a
+ * query without an answer) give -1.  The _dev form takes device pointers, is enqueued on `stream` (hipStream_t),
+ * allocates nothing and does not synchronise. */
+int32_t gulon_dataset_pair_moment(const gulon_dataset *a, const gulon_dataset *b, const int32_t *rows_a,
+                                  const int32_t *rows_b, int64_t n, double *out, int64_t *out_used);
+int32_t gulon_dataset_pair_moment_dev(const gulon_dataset *a, const gulon_dataset *b, const int32_t *d_rows_a,
+                                      const int32_t *d_rows_b, int64_t n, double *out, int64_t *out_used);
+int32_t gulon_mutual_rows(const int32_t *fwd, int32_t ns, const int32_t *bwd, int32_t nt, int32_t *out);
+int32_t gulon_mutual_rows_dev(const int32_t *d_fwd, int32_t ns, const int32_t *d_bwd, int32_t nt, int32_t *d_out,
+                              void *stream);
 #ifdef GULON_TEST_HOOKS   /* libgulon_hip_testhooks.so only */
 /* The launch geometry of the 3CosMul scans (cosmul.hip), by the arithmetic their launchers run; host code, nothing is
  * launched.  b >= 1 questions.  Flat index, rows [from, until): out = {questions per pass, row chunks of the first
