@@ -170,9 +170,11 @@ void query_terms_flat(gulon_index *idx, const int *d_off, const int *d_rows, con
 void compose_grouped(const GroupedParts &g, const int *d_off, const int *d_rows, const float *d_w, int b, bool nt,
                      bool nq, float *d_out, bool dev_rows, hipStream_t st) {
   std::lock_guard<std::mutex> lock(*g.mu);
+  StreamOrder so(g.pq, st);
   if (dev_rows) ensure_row_err(g.pq);
   launch_compose(g.pq, d_off, d_rows, d_w, b, g.gcent, g.offsets, g.n_offsets, nt, nq, d_out,
                  dev_rows ? g.pq->row_err.p : nullptr, st);
+  so.done();
 }
 
 void query_terms_grouped(gulon_grouped_index *idx, const GroupedParts &g, const int *d_off, const int *d_rows,
@@ -186,7 +188,10 @@ void query_terms_grouped(gulon_grouped_index *idx, const GroupedParts &g, const 
   x.oc.ensure((size_t)b + 1);
   compose_grouped(g, d_off, d_rows, d_w, b, nt, nq, x.q.p, dev_rows, st);
   rethrow(gulon_grouped_index_batch_query_dev(idx, x.q.p, b, kin, strategy, limit, x.oi.p, x.od.p, x.oc.p, st));
+  std::lock_guard<std::mutex> lock(*g.mu);
+  StreamOrder so(g.pq, st);
   launch_drop(x.oi.p, x.od.p, x.oc.p, b, kin, k_nn, d_off, d_rows, 0, d_oi, d_od, d_oc, st);
+  so.done();   // the next call on another stream waits for the drop, which reads this workspace
 }
 
 }  // namespace

@@ -89,6 +89,9 @@ void ensure_row_err(gulon_index *ix) {
   if (ix->row_err.n) return;
   ix->row_err.alloc(1);
   HIP_CHECK(hipMemset(ix->row_err.p, 0, sizeof(int)));
+  // the memset runs on the null stream, which the caller's (non-blocking) stream does not wait for: it must have landed
+  // before a kernel on that stream can set the word.  Once per handle; the null stream is idle or nearly so
+  HIP_CHECK(hipStreamSynchronize(nullptr));
 }
 
 int take_row_err(gulon_index *ix) {
@@ -97,6 +100,7 @@ int take_row_err(gulon_index *ix) {
   HIP_CHECK(hipDeviceSynchronize());
   HIP_CHECK(hipMemcpy(&v, ix->row_err.p, sizeof(int), hipMemcpyDeviceToHost));
   HIP_CHECK(hipMemset(ix->row_err.p, 0, sizeof(int)));
+  HIP_CHECK(hipStreamSynchronize(nullptr));   // cleared before the next call's kernels, whatever their stream
   return v;
 }
 

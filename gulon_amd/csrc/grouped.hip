@@ -1068,10 +1068,12 @@ void query_from_host(gulon_grouped_index *idx, int b, int k_nn, int strategy, in
   idx->q_dev.ensure((size_t)b * idx->d + 1);
   idx->oi.ensure(bk + 1); idx->od.ensure(bk + 1); idx->oc.ensure((size_t)b + 1);
   hipStream_t st = nullptr;
+  StreamOrder so(idx->pq, st);
   if (b > 0) fill(st);
   run_grouped_query(idx, idx->q_dev.p, b, k_nn, strategy, limit, idx->oi.p, idx->od.p, idx->oc.p, st);
   if (bk) { idx->oi.download(out_idx, bk, st); idx->od.download(out_dist, bk, st); }
   if (b > 0 && out_count) idx->oc.download(out_count, b, st);
+  so.done();
   HIP_CHECK(hipStreamSynchronize(st));
 }
 
@@ -1169,8 +1171,10 @@ GULON_API int32_t gulon_grouped_index_batch_query_dev(gulon_grouped_index *idx, 
   return guarded([&] {
     GULON_REQUIRE(idx != nullptr, "index is null");
     std::lock_guard<std::mutex> lock(idx->mu);
+    StreamOrder so(idx->pq, (hipStream_t)stream);   // the scratch is the handle's: behind the last call's device work
     run_grouped_query(idx, d_queries, b, k_nn, strategy, limit, d_out_idx, d_out_dist, d_out_count,
                       (hipStream_t)stream);
+    so.done();
   });
 }
 
@@ -1206,9 +1210,11 @@ GULON_API int32_t gulon_grouped_index_lookup_rows_dev(gulon_grouped_index *idx, 
   return guarded([&] {
     GULON_REQUIRE(idx != nullptr, "index is null");
     std::lock_guard<std::mutex> lock(idx->mu);
+    StreamOrder so(idx->pq, (hipStream_t)stream);
     ensure_row_err(idx->pq);
     launch_decode_rows(idx->pq, d_rows, b, idx->gcent.p, idx->bounds.p + 1, idx->g - 1, normalize != 0, d_out,
                        idx->pq->row_err.p, (hipStream_t)stream);
+    so.done();
   });
 }
 
@@ -1223,11 +1229,13 @@ GULON_API int32_t gulon_grouped_index_query_rows_dev(gulon_grouped_index *idx, c
     GULON_REQUIRE(b >= 0 && k_nn >= 0, "k and batch size must be non-negative");
     std::lock_guard<std::mutex> lock(idx->mu);
     const hipStream_t st = (hipStream_t)stream;
+    StreamOrder so(idx->pq, st);
     ensure_row_err(idx->pq);
     idx->lq.ensure((size_t)b * idx->d + 1);
     launch_decode_rows(idx->pq, d_rows, b, idx->gcent.p, idx->bounds.p + 1, idx->g - 1, normalize != 0, idx->lq.p,
                        idx->pq->row_err.p, st);
     run_grouped_query(idx, idx->lq.p, b, k_nn, strategy, limit, d_out_idx, d_out_dist, d_out_count, st);
+    so.done();
   });
 }
 

@@ -197,11 +197,23 @@ struct StreamOrder {
     if (!ix->order_ev) HIP_CHECK(hipEventCreateWithFlags(&ix->order_ev, hipEventDisableTiming));
     if (ix->order_set && ix->order_st != st) HIP_CHECK(hipStreamWaitEvent(st, ix->order_ev, 0));
   }
+  bool recorded = false;
   void done() {
     HIP_CHECK(hipEventRecord(ix->order_ev, st));
+    mark();
+  }
+  void mark() {
     ix->order_st = st;
     ix->order_set = true;
+    recorded = true;
   }
+  // a call that throws after it enqueued part of its work on the handle's scratch never reaches done(): the next call
+  // on another stream still has to wait for what was launched
+  ~StreamOrder() {
+    if (!recorded && hipEventRecord(ix->order_ev, st) == hipSuccess) mark();
+  }
+  StreamOrder(const StreamOrder &) = delete;
+  StreamOrder &operator=(const StreamOrder &) = delete;
 };
 }  // namespace gulon
 

@@ -280,7 +280,11 @@ int32_t gulon_index_destroy(gulon_index *idx);
  *  - the host-pointer gulon_index_batch_query takes such a context internally (up to GULON_HOST_CONTEXTS,
  *    default 4, created on first use, each with a stream of its own), so concurrent callers overlap.
  *  - the two-call sequence scan_bounds -> scan_partial_bounded must not be interleaved with other calls on the
- *    same handle (any other query call drops the pending first half: GULON_ERR_INVALID_ARGUMENT). */
+ *    same handle (any other query call drops the pending first half: GULON_ERR_INVALID_ARGUMENT).
+ *  - a gulon_grouped_index handle follows the first rule as well: it is one workspace (coarse distances, group lists,
+ *    per-group heaps, the pre-selection's tables), its calls are serialised by a mutex, and the device work of a call
+ *    on another stream than the previous call's -- queries, lookups, expressions, pair distances, diagnostics -- is
+ *    ordered behind it with the same event.  It has no contexts: batches that should overlap need a handle each. */
 int32_t gulon_index_context_create(gulon_index *parent, gulon_index **out);
 /* PQIndex.batchQuery(k, vectors, from, until) (Index.scala:417-440) followed by
  * Index.Result.fromHeap (Index.scala:83-94): per query the K nearest rows of
@@ -383,7 +387,9 @@ int32_t gulon_sharded_index_info(const gulon_sharded_index *idx, int32_t *n_shar
  * group repeats a centroid, WordVectors.scala:38-39): queries whose searched groups hang on such a tie
  * (or on a NaN distance) select their groups through the literal exactNearestNeighbours heap.
  * Groups may be empty (offsets may repeat).  k_nn <= GULON_MAX_K on the fast paths; up to 2048 (every code width)
- * through the literal heaps alone, kept in LDS (Tests.scala asks for up to 1000 neighbours). */
+ * through the literal heaps alone, kept in LDS (Tests.scala asks for up to 1000 neighbours).
+ * The _dev form enqueues on `stream` and does not synchronise, with one exception: LimitVectors over more than 64
+ * groups waits for `stream` once, to size the per-group heaps by a counter it reads back. */
 typedef struct gulon_grouped_index gulon_grouped_index;
 int32_t gulon_dataset_group_residuals(const gulon_dataset *ds, const int32_t *perm, const int32_t *group_of,
                                       const float *group_centroids, int32_t g, gulon_dataset **out);
@@ -454,12 +460,15 @@ int32_t gulon_grouped_index_row_error(gulon_grouped_index *idx, int32_t *out);
  * [0, n), else GULON_ERR_INVALID_ARGUMENT naming the first offending position. */
 int32_t gulon_index_select_rows(gulon_index *idx, const int32_t *rows, int32_t s, gulon_index **out);
 /* The rows as a bit mask of ceil(n / 64) 64-bit words in device memory: bit (r & 63) of word (r >> 6) selects row r,
- * bits at or above n are ignored.  Synchronises once to learn s. */
+ * bits at or above n are ignored.  Synchronises once to learn s.  gulon_index_select_mask_dev takes no stream: it works
+ * on the null stream, so the mask must be complete before the call (a caller that wrote it on a stream of its own
+ * synchronises that stream first). */
 int32_t gulon_index_select_mask_dev(gulon_index *idx, const uint64_t *d_mask, gulon_index **out);
 /* The same with the mask in host memory. */
 int32_t gulon_index_select_mask(gulon_index *idx, const uint64_t *mask, gulon_index **out);
 /* s, the rows (s entries, local rows of the root index) to the host, and the device array they live in (valid until
- * the view is destroyed).  On a handle that is not a view: GULON_ERR_INVALID_ARGUMENT. */
+ * the view is destroyed).  On a handle that is not a view: GULON_ERR_INVALID_ARGUMENT.  gulon_index_view_rows_dev takes
+ * no stream: it launches nothing, and the array it returns was completed on the null stream when the view was created. */
 int32_t gulon_index_view_size(gulon_index *view, int32_t *s);
 int32_t gulon_index_view_rows(gulon_index *view, int32_t *rows_out);
 int32_t gulon_index_view_rows_dev(gulon_index *view, const int32_t **d_rows);
