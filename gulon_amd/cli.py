@@ -81,7 +81,8 @@
                                        into the target's space (read normalised for a cosine index).  Every line of
                                        WORDS is a source word, printed as `word: t1,t2,...` with its -k (default 10)
                                        nearest target words, or `word: not found`.  --method nn ranks by the index's
-                                       distance; csls (a flat cosine index, or -v --exact) by CSLS: the distance plus the
+                                       distance; csls (a cosine index, flat or built with -p, or -v --exact; a -p index
+                                       answers from the groups its strategy searches) by CSLS: the distance plus the
                                        mean similarity of the target word to its -n (default 10) nearest source words,
                                        which demotes the hubs that are near everything.  -e DICTIONARY replaces WORDS:
                                        lines of `source target` (MUSE's format, a source word may have several lines),

@@ -192,6 +192,18 @@ def offset_query_raw(host_fn, dev_fn, handle, span, dimension, rows, k, q, offse
     return oi[:, :k], od[:, :k], oc[:b]
 
 
+def host_offsets_for(index, offsets):
+    """`offsets` as `index` will read them in every batch: the grouped index's entry point takes host pointers, so for a
+    GroupedIndex (or a WordIndex over one) a DeviceOffsets is downloaded here, once; anything else is passed on."""
+    from .grouped import GroupedIndex
+    index = getattr(index, "index", index) if getattr(index, "_grouped", False) else index
+    if isinstance(index, GroupedIndex) and isinstance(offsets, DeviceOffsets):
+        if offsets.rows != index.size:
+            raise ValueError(f"requirement failed: {offsets.rows} offsets for {index.size} rows")
+        return offsets.numpy()
+    return offsets
+
+
 def batched_offset_query(index, dimension, k, vectors, offsets, exclude):
     """index.batch_query_offset_raw in batches of up to BATCH queries, as the word indexes ask it."""
     q = np.ascontiguousarray(vectors, np.float32).reshape(-1, dimension)
@@ -200,6 +212,7 @@ def batched_offset_query(index, dimension, k, vectors, offsets, exclude):
         raise ValueError(f"requirement failed: {len(ex)} excluded rows for {len(q)} queries")
     oi, od = np.full((len(q), k), -1, np.int32), np.full((len(q), k), np.inf, np.float32)
     oc = np.zeros(len(q), np.int32)
+    offsets = host_offsets_for(index, offsets)
     for s in range(0, len(q), BATCH):
         oi[s:s + BATCH], od[s:s + BATCH], oc[s:s + BATCH] = index.batch_query_offset_raw(
             k, q[s:s + BATCH], offsets, None if ex is None else ex[s:s + BATCH])
@@ -213,16 +226,18 @@ def as_results(oi, od, oc) -> List[Result]:
 
 
 def _vector_side(index):
-    """A target or source in any of its wrappings -> ("exact", ExactIndex) or ("flat", SortedIndex | PQIndex)."""
+    """A target or source in any of its wrappings -> ("exact", ExactIndex), ("flat", SortedIndex | PQIndex) or
+    ("grouped", GroupedIndex)."""
     from .exact import ExactIndex, ExactWordIndex
+    from .grouped import GroupedIndex
     from .index import PQIndex, PQIndexView, SortedIndex
     from .word_index import WordIndex
     if isinstance(index, (ExactWordIndex, WordIndex)):
-        if getattr(index, "_grouped", False):
-            raise NotImplementedError("offset queries are not supported by the grouped index")
         index = index.index
     if isinstance(index, ExactIndex):
         return "exact", index
+    if isinstance(index, GroupedIndex):
+        return "grouped", index
     if isinstance(index, SortedIndex) or (isinstance(index, PQIndex) and not isinstance(index, PQIndexView)):
         return "flat", index
     raise NotImplementedError(f"{type(index).__name__} has no offset queries")
@@ -231,9 +246,10 @@ def _vector_side(index):
 def csls_offsets(target, source, neighbours=10) -> DeviceOffsets:
     """r_S of CSLS for every row of `target`: the mean cosine similarity of the row to its `neighbours` nearest rows of
     `source`, an ExactIndex (or ExactWordIndex) over the source vectors.  target: an ExactIndex, a SortedIndex / PQIndex
-    over byte codes, or a WordIndex / ExactWordIndex over one.  In batches of target rows, all on the null stream: the
-    rows composed where they live as one-term expressions (the dataset's rows of an exact target, the decoded rows of a
-    flat one; normalised for a cosine index), the source's batch_query_dev at `neighbours`, gulon_mean_similarity_dev
+    over byte codes, a GroupedIndex, or a WordIndex / ExactWordIndex over one.  In batches of target rows, all on the
+    null stream: the rows composed where they live as one-term expressions (the dataset's rows of an exact target, the
+    decoded rows of a flat one, GroupedIndex.lookup of a grouped one by grouped row position; normalised for a cosine
+    index), the source's batch_query_dev at `neighbours`, gulon_mean_similarity_dev
     straight into the result.  -> DeviceOffsets with one value per target row (an exact target: per row of its matrix,
     +inf outside its range).  ValueError: a target whose metric is known and not cosine, a source of another
     dimension."""
@@ -258,6 +274,11 @@ def csls_offsets(target, source, neighbours=10) -> DeviceOffsets:
 
         def compose(off, r, w, b, out):
             N.check(L.gulon_dataset_compose_rows_dev(tgt.matrix._h, off, r, w, b, cosine, cosine, out, None, None))
+    elif kind == "grouped":                              # one offset per grouped row position
+        rows, first, last = tgt.size, 0, tgt.size
+
+        def compose(off, r, w, b, out):
+            N.check(L.gulon_grouped_index_compose_rows_dev(tgt._h, off, r, w, b, cosine, cosine, out, None))
     else:
         pq = tgt.vector_index if isinstance(tgt, SortedIndex) else tgt
         rows, first, last = pq.length, 0, pq.length
@@ -360,6 +381,8 @@ def translation_lists(target, source, source_rows, k, method="nn", offsets=None)
     rows = N.i32(source_rows).reshape(-1)
     oi, od = np.full((len(rows), k), -1, np.int32), np.full((len(rows), k), np.inf, np.float32)
     oc = np.zeros(len(rows), np.int32)
+    if method == "csls":
+        offsets = host_offsets_for(target, offsets)              # a grouped target: one download for every batch
     for s in range(0, len(rows), BATCH):
         vectors = source.index.lookup_rows(rows[s:s + BATCH])
         if method == "csls":

@@ -24,9 +24,13 @@
 //                       Result.fromHeap.  Ids and order therefore equal the reference's also under ties.
 //                       Every query takes this way for k_nn > 63, on an index without rows and with
 //                       GULON_GROUPED_LITERAL=1; gq_group_scan_wide does the same over 16-bit codes.
+// Offset queries: gulon_grouped_index_query_offset runs coarse_stage per pass and hands its groups and the
+// handle's GroupedOffsetWork to grouped_offset.hip.
 #include "scan.hpp"
 
 #include "grouped_filter.hpp"
+#include "grouped_offset.hpp"
+#include "offset.hpp"
 #include "select.hpp"
 #include "topk_heap.hpp"
 using gulon::DevBuf;
@@ -45,6 +49,7 @@ struct gulon_grouped_index {
   // approximate pre-selection (gq_approx_scan): |g + decode(codes_i)|^2 per row, its maximum, per-query tables, lists
   DevBuf<float> xnorm, ptab, apv, amv;
   DevBuf<int> api, ami, anan;
+  gulon::GroupedOffsetWork offset;   // offset queries (grouped_offset.hip)
   gulon::GroupFilter gfilter;     // the same pre-selection batched by group with 8-bit bound tables (grouped_filter.hip)
   float xnmax = 0.f;
   int n_empty = 0;                 // groups without rows (the reference's leading empty group, WordVectors.scala:38-39)
@@ -1255,6 +1260,56 @@ GULON_API int32_t gulon_grouped_index_query_rows(gulon_grouped_index *idx, const
       launch_decode_rows(idx->pq, idx->rows_dev.p, b, idx->gcent.p, idx->bounds.p + 1, idx->g - 1, normalize != 0,
                          idx->q_dev.p, nullptr, st);
     });
+  });
+}
+
+// Offset queries: grouped_offset.hip ranks the rows of every query's searched groups -- coarse_stage's, as
+// the ordinary query at the same (strategy, limit) searches them -- by distance + row_offsets[row]; the offsets and the
+// excluded rows are indexed by grouped row position, as the returned ids are.
+GULON_API int32_t gulon_grouped_index_query_offset(gulon_grouped_index *idx, const float *queries, int32_t b, int32_t k_nn,
+                                                   int32_t strategy, int32_t limit, const float *row_offsets,
+                                                   const int32_t *exclude, int32_t *out_idx, float *out_key,
+                                                   int32_t *out_count) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr, "index is null");
+    check_offset_host(row_offsets, idx->n, exclude, b, k_nn, 0);
+    GULON_REQUIRE(strategy == 0 || strategy == 1, "strategy must be 0 (LimitGroups) or 1 (LimitVectors)");
+    GULON_REQUIRE(limit >= 0, "limit must be non-negative");
+    GULON_UNSUPPORTED(idx->pq->wide, "offset queries take byte codes: k = %d > 256 is not supported", idx->pq->k);
+    const GroupScanLds l = group_scan_lds(GroupedCall{idx, nullptr, b, k_nn, strategy, limit, nullptr, nullptr, nullptr, nullptr});
+    if (b == 0) return;
+    GULON_REQUIRE(queries != nullptr && out_idx != nullptr && out_key != nullptr, "null argument");
+    const size_t bk = (size_t)b * (size_t)k_nn;
+    if (idx->n == 0) {   // no rows, no candidates: nothing is launched
+      std::fill(out_idx, out_idx + bk, -1);
+      std::fill(out_key, out_key + bk, INFINITY);
+      if (out_count) std::fill(out_count, out_count + b, 0);
+      return;
+    }
+    std::lock_guard<std::mutex> lock(idx->mu);
+    const hipStream_t st = nullptr;
+    StreamOrder so(idx->pq, st);
+    GroupedOffsetWork &x = idx->offset;
+    idx->q_dev.upload(queries, (size_t)b * idx->d, st);
+    x.off.upload(row_offsets, (size_t)idx->n, st);
+    if (exclude) x.ex.upload(exclude, (size_t)b, st);
+    idx->oi.ensure(bk); idx->od.ensure(bk); idx->oc.ensure((size_t)b);
+    // (coarse_stage's bound on the groups a query searches)
+    const int slots = (int)std::min<long long>((long long)limit + (strategy == 1 ? idx->n_empty : 0), idx->g);
+    const int per_pass = grouped_offset_pass(slots, k_nn + 1);
+    for (int q0 = 0; q0 < b; q0 += per_pass) {
+      const int nb = std::min(per_pass, b - q0);
+      const GroupedCall c{idx, idx->q_dev.p + (size_t)q0 * idx->d, nb, k_nn, strategy, limit, nullptr, nullptr, nullptr, st};
+      const CoarseResult co = coarse_stage(c, /*all_literal=*/true);
+      const GroupedOffsetPass pass{idx->pq, idx->gcent.p, idx->bounds.p, c.dQ, nb, idx->nn.p, idx->nn_cnt.p, co.nn_stride,
+                                   co.stride, l.bytes};
+      launch_grouped_offset(pass, x, k_nn, x.off.p, exclude ? x.ex.p + q0 : nullptr, idx->oi.p + (size_t)q0 * k_nn,
+                            idx->od.p + (size_t)q0 * k_nn, idx->oc.p + q0, st);
+    }
+    idx->oi.download(out_idx, bk, st); idx->od.download(out_key, bk, st);
+    if (out_count) idx->oc.download(out_count, (size_t)b, st);
+    so.done();
+    HIP_CHECK(hipStreamSynchronize(st));
   });
 }
 

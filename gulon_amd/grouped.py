@@ -242,6 +242,32 @@ class GroupedIndex:
         oi, od, oc, _ = self.batch_query_expressions_raw(k, expressions)
         return [Result(oi[i, :oc[i]].copy(), od[i, :oc[i]].copy(), 0) for i in range(len(oc))]
 
+    # ---- offset queries (csls.py): the offsets are indexed by grouped row position
+    def batch_query_offset_raw(self, k, vectors, offsets, exclude=None):
+        """gulon_grouped_index_query_offset: per query (normalised for a cosine index, as batch_query_raw does) the k
+        rows of its searched groups with the smallest t = distance + offsets[row] among those whose t is finite and
+        that are not exclude[q] (None, or one grouped row position or -1 per query), by (t, row).  offsets: one float32
+        per row, an array or a csls.DeviceOffsets -- the entry point takes host pointers, so a DeviceOffsets is
+        downloaded.  -> (rows [b][k] with -1 after a query's last entry, keys [b][k] with +inf there, counts [b])."""
+        from .csls import DeviceOffsets, offset_query_raw
+        from .index import normalize
+        q = N.f32(vectors.data if hasattr(vectors, "data") and not isinstance(vectors, np.ndarray) else vectors)
+        q = q.reshape(-1, self.dimension)
+        if self.metric == "cosine" and len(q):
+            q = np.stack([normalize(r) for r in q])
+        if isinstance(offsets, DeviceOffsets):
+            if offsets.rows != self.size:
+                raise ValueError(f"requirement failed: {offsets.rows} offsets for {self.size} rows")
+            offsets = offsets.numpy()
+        return offset_query_raw(N.lib().gulon_grouped_index_query_offset, None, self._h, self._strategy(),
+                                self.dimension, self.size, k, q, offsets, exclude)
+
+    def batch_query_offset(self, k, vectors, offsets, exclude=None):
+        """batch_query_offset_raw as Results: `distances` holds the keys t, ascending; flags is 0 (the order (t, row) is
+        total)."""
+        from .csls import as_results
+        return as_results(*self.batch_query_offset_raw(k, vectors, offsets, exclude))
+
     def close(self):
         if self._h is not None and self._h.value:
             N.lib().gulon_grouped_index_destroy(self._h)

@@ -200,10 +200,9 @@ class WordIndex:
 
     def batch_query_offset_raw(self, k, vectors, offsets, exclude=None):
         """SortedIndex.batch_query_offset_raw (csls.py), up to BATCH queries per device batch: (rows
-        [b][k] with -1 after a query's last entry, keys [b][k] with +inf there, counts [b]).  NotImplementedError for a
-        grouped index (and, from the library, for codes wider than a byte)."""
-        if self._grouped:
-            raise NotImplementedError("offset queries are not supported by the grouped index")
+        [b][k] with -1 after a query's last entry, keys [b][k] with +inf there, counts [b]).  A grouped index answers
+        from the groups its strategy searches (GroupedIndex.batch_query_offset_raw).  NotImplementedError,
+        from the library, for codes wider than a byte."""
         from .csls import batched_offset_query
         return batched_offset_query(self.index, self.dimension, k, vectors, offsets, exclude)
 

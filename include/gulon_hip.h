@@ -967,6 +967,21 @@ int32_t gulon_index_query_offset(gulon_index *idx, const float *queries, int32_t
 int32_t gulon_index_query_offset_dev(gulon_index *idx, const float *d_queries, int32_t b, int32_t k_nn, int32_t from,
                                      int32_t until, const float *d_row_offsets, const int32_t *d_exclude,
                                      int32_t *d_out_idx, float *d_out_key, int32_t *d_out_count, void *stream);
+/* The same on a GroupedIndex (grouped_offset.hip), over the handle's own distances.  The rows a query sees
+ * are the rows of the groups gulon_grouped_index_batch_query searches for it at the same (strategy, limit) -- as a set;
+ * rows of other groups are never candidates.  For such a row r, d = the bits that query returns for it: the residual
+ * q - centroid(group) by MathUtils.subtract, Index.prepareQuery on the residual, the row's table entries summed quantizer
+ * 0 first, from 0, unfused.  t = d + row_offsets[r], one binary32 addition; row_offsets has one entry per grouped row
+ * position, exclude (nullable) one row position or -1 per query.  Candidates, order, padding and out_count as above;
+ * queries are taken as given.  Everything is checked before anything is launched: b, NaN or -inf in row_offsets,
+ * exclude outside -1 or [0, n), strategy and limit as the ordinary query checks them (GULON_ERR_INVALID_ARGUMENT);
+ * 1 <= k_nn <= GULON_MAX_K, byte codes only, and the LDS bound of the ordinary query's group scan (160 KiB), else
+ * GULON_ERR_UNSUPPORTED.  b = 0 and an index without rows succeed (no candidates: counts 0).  Host pointers only; the
+ * work runs on the null stream and the call returns when the answers have arrived.  (A device-pointer form with a
+ * stream is left to a later change.) */
+int32_t gulon_grouped_index_query_offset(gulon_grouped_index *idx, const float *queries, int32_t b, int32_t k_nn,
+                                         int32_t strategy, int32_t limit, const float *row_offsets,
+                                         const int32_t *exclude, int32_t *out_idx, float *out_key, int32_t *out_count);
 /* gulon_mean_similarity: the mean cosine similarity of each of b lists of squared distances between unit vectors,
  * dist_lists [b][kin] as a query returns them.  c = min(counts[q], K), or min(kin, K) when counts is NULL; out[q] = 0
  * when c == 0; else s_j = 1 - 0.5 * d_j, sum = s_0, sum = sum + s_j for j = 1 .. c - 1, out[q] = sum / (float)c, every
