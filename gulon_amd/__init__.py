@@ -28,6 +28,7 @@ from .similarity import (SimilarityReport, evaluate_pairs, pair_distance_referen
 from .csls import (DeviceOffsets, TranslationReport, csls_offsets, evaluate_dictionary, mean_similarity,
                    mean_similarity_reference, offset_query_reference, read_dictionary, translate_words,
                    translation_scores)
+from .ranks import RankReport, evaluate_dictionary_ranks, rank_query_reference
 from .alignment import (induce_matches, mutual_rows, mutual_rows_reference, pair_moment, pair_moment_reference,
                         seed_alignment, train_alignment)
 
@@ -45,4 +46,4 @@ __all__ = ["native", "GroupedIndex", "GroupedVectors", "LimitGroups", "LimitVect
            "TranslationReport", "csls_offsets", "evaluate_dictionary", "mean_similarity", "mean_similarity_reference",
            "offset_query_reference", "read_dictionary", "translate_words", "translation_scores",
            "induce_matches", "mutual_rows", "mutual_rows_reference", "pair_moment", "pair_moment_reference",
-           "seed_alignment", "train_alignment"]
+           "seed_alignment", "train_alignment", "RankReport", "evaluate_dictionary_ranks", "rank_query_reference"]

@@ -74,7 +74,7 @@
                                        rows need no rotation
 
   translate -i TARGET -s SOURCE [--method nn|csls] [-n 10] [-k 10] [-v VECTORS --exact] [-R ROTATION] [-a MAP]
-            [--lowercase] (WORDS | -e DICTIONARY)
+            [--lowercase] (WORDS | -e DICTIONARY [--ranks])
                                        (not in the reference) word translation between two aligned embedding spaces
                                        (csls.py, csrc/offset.hip).  TARGET is an index file over the target language's
                                        vectors, SOURCE a word2vec text file of the source language's, already mapped
@@ -88,7 +88,16 @@
                                        lines of `source target` (MUSE's format, a source word may have several lines),
                                        and one line is printed, `csls: @1 0.6120 @5 0.8010 @10 0.8522 (n = 1500,
                                        skipped 12)` -- the precision at -k 1,5,10, n the source words asked, skipped the
-                                       pairs with a word either side lacks.  -v VECTORS --exact: the target is the true
+                                       pairs with a word either side lacks.  --ranks (with -e) adds a second line,
+                                       `csls ranks: mrr 0.7012 median 1 mean 37.42 @1 0.6120 @5 0.8010 @100 0.9312
+                                       (n = 1500, unranked 3, skipped 12)`: the rank of a word is the number of target
+                                       words ahead of its best gold translation, counted on the device over ALL the
+                                       target's words (ranks.py, csrc/rank.hip) -- mrr the mean of 1 / (rank + 1),
+                                       median and mean over the ranked words (1-based), unranked the words none of
+                                       whose translations can be ranked.  The depths of -k may then exceed 63.  With
+                                       --method nn equal distances are ordered by row, which is not the tie order of
+                                       the query behind the first line.  Not on a -p index (`error: ...`, status 1).
+                                       -v VECTORS --exact: the target is the true
                                        vectors of the index's words.  -R ROTATION: the index was built with build-index
                                        -R, and the source vectors are rotated after they are read (not with --exact).
                                        -a MAP: SOURCE is NOT mapped yet; the map `align` wrote is applied to its vectors
@@ -286,6 +295,7 @@ class TranslateConfig:
     exact: bool = False                   # --exact: the true vectors of the index's words are the target
     rotation: Optional[str] = None        # -R: the index was built over vectors rotated by this file
     alignment: Optional[str] = None       # -a: the map of the source vectors into the target's space (align)
+    ranks: bool = False                   # --ranks with -e: the line of rank statistics after the precision line
 
 
 @dataclass(frozen=True)
@@ -508,6 +518,10 @@ def _parser():
                          "separated by commas (default 1,5,10)")
     tr.add_argument("-e", "--evaluate", default=None, metavar="file",
                     help="a dictionary, lines of `source target`: print its precision instead of translations")
+    tr.add_argument("--ranks", action="store_true",
+                    help="with --evaluate: a second line with the mean reciprocal rank, the median and mean rank of the "
+                         "best gold translation and the precision at the depths of -k, which may then exceed 63 (not "
+                         "on an index built with -p)")
     tr.add_argument("-v", "--vectors", default=None, metavar="file",
                     help="word2vec word vectors the index was built from (needs --exact)")
     tr.add_argument("--exact", action="store_true",
@@ -803,6 +817,23 @@ class TranslateError(Exception):
     index that cannot answer it."""
 
 
+def _ranked_evaluation(index, source, pairs, config):
+    """translate -e --ranks -> ranks.RankReport whose lines are the precision line and the line of rank statistics.  The
+    ranks come first, so an index that has no rank queries is refused before anything is evaluated.  csls: the rank IS
+    the position in the offset query's answer, so the precision line is counted from the ranks -- the numbers
+    evaluate_dictionary gives, at any depth and without selecting a list.  nn: the precision line is
+    evaluate_dictionary's, in the tie order of the ordinary query; the ranks order equal distances by row."""
+    from .csls import TranslationReport, evaluate_dictionary
+    from .ranks import evaluate_dictionary_ranks
+    report = evaluate_dictionary_ranks(index, source, pairs, config.ks, config.method, config.neighbours)
+    if config.method == "csls":
+        report.precision_report = TranslationReport(report.ks, config.method, report.asked, report.skipped,
+                                                    {k: report.hits(k) for k in report.ks})
+    else:
+        report.precision_report = evaluate_dictionary(index, source, pairs, config.ks, config.method, config.neighbours)
+    return report
+
+
 def run_translate(config: TranslateConfig, write, load, vectors):
     """translate between its argument handling and the end of its output: the translations are written as they come;
     with a dictionary -> csls.TranslationReport, else None.  The source vectors are read as the index's own were: in
@@ -829,6 +860,8 @@ def run_translate(config: TranslateConfig, write, load, vectors):
             raise TranslateError(f"{config.alignment}: {e.strerror or e}")
         originals = _rotated(config.rotation, originals)
         source = ExactWordIndex(originals.words, ExactIndex(originals.matrix, index.metric), originals.key_index)
+        if pairs is not None and config.ranks:
+            return _ranked_evaluation(index, source, pairs, config)
         if pairs is not None:
             return evaluate_dictionary(index, source, pairs, config.ks, config.method, config.neighbours)
         words = [w.lower() for w in lines] if config.lowercase else lines
@@ -970,6 +1003,8 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
             parser.error("--exact needs -v/--vectors")
         if args.vectors is not None and not args.exact:
             parser.error("--vectors is only applicable with --exact")
+        if args.ranks and args.evaluate is None:
+            parser.error("--ranks is only applicable with -e/--evaluate")
         if args.exact and args.rotation is not None:
             parser.error("--exact is not applicable with -R/--rotation")
         try:
@@ -1079,7 +1114,8 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
     elif args.command == "translate":
         k, ks = (10, depth) if args.evaluate is not None else (depth, (1, 5, 10))      # -k means depths with -e
         config = TranslateConfig(args.index, args.source, args.file, args.evaluate, args.method, args.csls_neighbours,
-                                 k, ks, args.lowercase, args.vectors, args.exact, args.rotation, args.alignment)
+                                 k, ks, args.lowercase, args.vectors, args.exact, args.rotation, args.alignment,
+                                 args.ranks)
         try:
             report = (translate if translate is not None else run_translate)(config, write, load, vectors)
         except TranslateError as e:

@@ -90,7 +90,10 @@ void ensure_row_err(gulon_index *ix) {
   ix->row_err.alloc(1);
   HIP_CHECK(hipMemset(ix->row_err.p, 0, sizeof(int)));
   // the memset runs on the null stream, which the caller's (non-blocking) stream does not wait for: it must have landed
-  // before a kernel on that stream can set the word.  Once per handle; the null stream is idle or nearly so
+  // before a kernel on that stream can set the word.  Once per handle, and every handle has its word from the moment it
+  // is made (gulon_index_create, make_context, build_view, the roots of update.hip): the wait below can last as long as
+  // the work of ANOTHER stream that shares a hardware queue with the null stream, which a *_dev call documented not to
+  // synchronise must not pay for.  The calls in the *_dev paths are the guard for a handle made any other way
   HIP_CHECK(hipStreamSynchronize(nullptr));
 }
 

@@ -26,6 +26,7 @@
 #include "cosmul.hpp"
 #include "exact.hpp"
 #include "offset.hpp"
+#include "rank.hpp"
 #include "select.hpp"
 
 #include <cstdlib>
@@ -293,6 +294,7 @@ struct gulon_exact_index {
   ExprWork expr;                       // the expression queries' term lists, composed vectors and answers at k_nn + extra
   CosmulWork cosmul;                   // the multiplicative analogy queries (cosmul.hip)
   OffsetWork offset;                   // the offset queries (offset.hip)
+  RankWork rank;                       // the rank queries (rank.hip)
   std::vector<int> h_cnt, h_ovf, h_nf, h_ids;
   hipEvent_t order_ev = nullptr;
   hipStream_t order_st = nullptr;
@@ -722,6 +724,40 @@ GULON_API int32_t gulon_exact_index_query_offset(gulon_exact_index *idx, const f
     order_record(idx, st);
     x.fi.download(out_idx, bk, st); x.fd.download(out_key, bk, st);
     if (out_count) x.fc.download(out_count, (size_t)b, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+  });
+}
+
+// Rank queries: rank.hip counts the rows of [from, until) that the offset query above would put before the
+// best row of each query's gold list; offsets, excluded rows and gold rows are dataset rows.  Host pointers, the null
+// stream.
+GULON_API int32_t gulon_exact_index_query_rank(gulon_exact_index *idx, const float *queries, int32_t b,
+                                               const float *row_offsets, const int32_t *exclude,
+                                               const int32_t *gold_offsets, const int32_t *gold_rows, int32_t *out_rank,
+                                               int32_t *out_row, float *out_key, int32_t *out_total) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr, "index is null");
+    GULON_REQUIRE(b >= 0, "batch size must be non-negative");
+    if (b == 0) return;
+    const int gold = check_rank_host(row_offsets, idx->ds->n, exclude, gold_offsets, gold_rows, b, 0);
+    GULON_REQUIRE(queries != nullptr && out_rank != nullptr && out_row != nullptr && out_key != nullptr, "null argument");
+    std::lock_guard<std::mutex> g(idx->mu);
+    RankWork &x = idx->rank;
+    const hipStream_t st = nullptr;
+    order_wait(idx, st);   // the workspace may still be read by the last batch, on another stream
+    x.q.upload(queries, (size_t)b * idx->ds->d, st);
+    if (row_offsets) x.off.upload(row_offsets, (size_t)idx->ds->n, st);
+    if (exclude) x.ex.upload(exclude, (size_t)b, st);
+    x.goff.upload(gold_offsets, (size_t)b + 1, st);
+    x.grows.upload(gold_rows, (size_t)gold, st);
+    x.grows.ensure(1);
+    x.frank.ensure((size_t)b); x.frow.ensure((size_t)b); x.fk.ensure((size_t)b); x.ftotal.ensure((size_t)b);
+    launch_rank_exact(idx->ds, idx->from, idx->until, x, x.q.p, b, row_offsets ? x.off.p : nullptr,
+                      exclude ? x.ex.p : nullptr, x.goff.p, x.grows.p, gold, x.frank.p, x.frow.p, x.fk.p, x.ftotal.p, st);
+    order_record(idx, st);
+    x.frank.download(out_rank, (size_t)b, st); x.frow.download(out_row, (size_t)b, st);
+    x.fk.download(out_key, (size_t)b, st);
+    if (out_total) x.ftotal.download(out_total, (size_t)b, st);
     HIP_CHECK(hipStreamSynchronize(st));
   });
 }

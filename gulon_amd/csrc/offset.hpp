@@ -1,8 +1,56 @@
-// Offset queries: what offset.hip offers the handles that answer them.
+// Offset queries: what offset.hip offers the handles that answer them, and the slot and shape rules of its
+// flat scan, which the rank queries (rank.hip) launch by as well.
 #pragma once
 #include "scan.hpp"
+#include "cosmul.hpp"   // COSMUL_LDS_BUDGET: the LDS the tables of a flat workgroup may take
 
 namespace gulon {
+
+constexpr int OF_THREADS = 1024;            // the flat scans' workgroup: 16 waves, one row block each per step
+constexpr int EXACT_SUB_BATCH = 4096;       // queries per pass: bounds the chunk lists
+constexpr size_t FLAT_TABLE_BYTES = size_t(256) << 20;   // tables of one pass of the flat form
+
+#ifdef __HIPCC__
+__device__ __forceinline__ bool finite_key(float t) { return fabsf(t) < INFINITY; }   // false for NaN
+#endif
+
+// LDS of one query slot: its table while the rows are scanned, then the NW wave lists of the slot for the merge
+constexpr size_t flat_slot_bytes(int m_pad) {
+  const size_t table = (size_t)m_pad * 256 * sizeof(float), lists = (size_t)(OF_THREADS / 64) * 64 * 8;
+  return table > lists ? table : lists;
+}
+
+// the queries of one pass, the row chunks and the 64-row code blocks of one chunk, for b queries E to a workgroup
+struct FlatShape { int per_pass, nchunks, rb_per_chunk; };
+inline FlatShape offset_flat_shape(const gulon_index *ix, int from, int until, int b, int E) {
+  constexpr int NW = OF_THREADS / 64;
+  const size_t tab = (size_t)ix->m_pad * 256;
+  int sub = (int)std::max<size_t>(1, FLAT_TABLE_BYTES / (tab * sizeof(float)));
+  sub = std::max(sub / E * E, E);
+  const int groups = ceil_div(std::min(sub, b), E);
+  const int rb_total = ceil_div(until, 64) - from / 64;
+  const int want = std::max(1, ceil_div(2048, groups));
+  const int nchunks_max = std::max(1, rb_total / (2 * NW));
+  const int rb_per_chunk = std::max(1, ceil_div(rb_total, std::min(want, nchunks_max)));
+  return {sub, std::max(1, ceil_div(rb_total, rb_per_chunk)), rb_per_chunk};
+}
+
+// the query slots of a workgroup: the largest of 8, 4, 2, 1 that fit the LDS budget, 0 if not even one does
+inline int offset_flat_max_e(const gulon_index *ix) {
+  const size_t fit = COSMUL_LDS_BUDGET / flat_slot_bytes(ix->m_pad);
+  return fit >= 8 ? 8 : fit >= 4 ? 4 : fit >= 2 ? 2 : (int)fit;
+}
+
+inline void check_flat(const gulon_index *ix, int b, int k_nn, int from, int until) {
+  GULON_REQUIRE(b >= 0, "batch size must be non-negative");
+  GULON_UNSUPPORTED(k_nn < 1 || k_nn > GULON_MAX_K, "k_nn = %d outside [1, %d]", k_nn, GULON_MAX_K);
+  GULON_UNSUPPORTED(ix->wide, "offset queries take byte codes: k = %d > 256 is not supported", ix->k);
+  GULON_UNSUPPORTED(ix->is_view, "offset queries are not supported on an index view");
+  GULON_REQUIRE(from <= until, "expected: from <= until");
+  GULON_REQUIRE(from >= 0 && until <= ix->n, "expected: from >= 0 && until <= length");
+  GULON_UNSUPPORTED(offset_flat_max_e(ix) < 1, "m = %d: the tables of one query need %d KiB of LDS, %d KiB are there",
+                    ix->m, ix->m_pad, (int)(COSMUL_LDS_BUDGET / 1024));
+}
 
 // The host-pointer forms check everything before anything is launched: b >= 0 (GULON_ERR_INVALID_ARGUMENT),
 // 1 <= k_nn <= GULON_MAX_K (GULON_ERR_UNSUPPORTED), no NaN or -inf among the `rows` offsets, and every exclude[q]

@@ -937,6 +937,7 @@ GULON_API int32_t gulon_index_create(const uint8_t *codes, int32_t n, int32_t d,
         HIP_CHECK(hipDeviceSynchronize());
       }
       wide_store_codes(ix.get(), wide16.p);
+      ensure_row_err(ix.get());
       *out = ix.release();
       return;
     }
@@ -995,6 +996,7 @@ GULON_API int32_t gulon_index_create(const uint8_t *codes, int32_t n, int32_t d,
       build_filter_copy(ix.get());
     }
     HIP_CHECK(hipDeviceSynchronize());
+    ensure_row_err(ix.get());
     *out = ix.release();
   });
 }
@@ -1042,6 +1044,7 @@ gulon_index *make_context(gulon_index *parent) {
   c->is_view = parent->is_view;
   c->view_base = parent->view_base;
   c->vmap.borrow(parent->vmap);
+  ensure_row_err(c.get());
   return c.release();
 }
 }  // namespace gulon

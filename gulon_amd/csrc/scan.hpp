@@ -64,6 +64,17 @@ struct OffsetWork {
   DevBuf<int> ex, fi, fc;       // ... the excluded rows, final rows and counts
   std::mutex mu;
 };
+// Workspace of the rank queries of one handle (rank.hip), under the same two rules.
+struct RankWork {
+  DevBuf<float> qt;             // exact: the queries transposed per workgroup [tile][d][16]
+  DevBuf<float> tables;         // flat: Index.prepareQuery of every query [b][m_pad][256]
+  DevBuf<float> gk, bk;         // exact: the key of every (query, gold row) pair [G]; the best gold key per query [b]
+  DevBuf<int> br, part;         // the best gold row per query [b]; (ahead, total) per (query, row chunk)
+  DevBuf<float> q, off, fk;     // the host-pointer forms: queries, row offsets, final keys
+  DevBuf<int> ex, goff, grows;  // ... the excluded rows, the gold lists (CSR)
+  DevBuf<int> frank, frow, ftotal;   // ... final ranks, rows and totals
+  std::mutex mu;
+};
 }
 // PQIndex on the device (opaque to C callers)
 using gulon::DevBuf;
@@ -108,6 +119,7 @@ struct gulon_index {
   gulon::ExprWork expr;    // expression queries (compose.hip)
   gulon::CosmulWork cosmul;   // multiplicative analogy queries (cosmul.hip)
   gulon::OffsetWork offset;   // offset queries (offset.hip)
+  gulon::RankWork rank;       // rank queries (rank.hip)
   DevBuf<unsigned long long> dbg;   // GULON_REPLAY_STATS stamps (replay.hip)
   // large-K peeling rounds
   DevBuf<float> peel_v, peel_tv, peel_lbv;
@@ -412,7 +424,7 @@ void launch_decode_range(const gulon_index *ix, int from, int until, float *d_ou
 // host rows (checked: GULON_ERR_INVALID_ARGUMENT before any launch) -> host out, through the given scratch; synchronises
 void decode_rows_host(const gulon_index *ix, DevBuf<int> &rows_buf, DevBuf<float> &out_buf, const int32_t *rows, int b,
                       const float *gcent, const int *offsets, int n_offsets, bool normalize, float *out, hipStream_t st);
-void ensure_row_err(gulon_index *ix);   // the handle's row_err word, allocated and zeroed on first use
+void ensure_row_err(gulon_index *ix);   // the handle's row_err word, allocated and zeroed: when the handle is made
 int take_row_err(gulon_index *ix);      // synchronises; returns and clears it
 // grouped.hip: what compose.hip needs of a GroupedIndex handle (the struct is private to grouped.hip) -- the residual
 // index, the group centroids, the raw offsets GroupedIndex.lookup searches, and the handle's mutex; for inspect.hip the

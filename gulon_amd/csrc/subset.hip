@@ -206,6 +206,7 @@ gulon_index *build_view(const gulon_index *P, DevBuf<int> &&rows, int s) {
     HIP_CHECK(hipDeviceSynchronize());
     v->vmap = std::move(rows);
   }
+  ensure_row_err(v.get());
   return v.release();
 }
 

@@ -208,6 +208,7 @@ GULON_API int32_t gulon_index_encode_dataset(gulon_index *idx, const gulon_datas
       }
     }
     finish_root(r.get());
+    ensure_row_err(r.get());
     *out = r.release();
   });
 }
@@ -254,6 +255,7 @@ GULON_API int32_t gulon_index_merge(gulon_index *a, gulon_index *b, const int32_
       HIP_CHECK(hipDeviceSynchronize());         // the take list goes out of scope
     }
     finish_root(r.get());
+    ensure_row_err(r.get());
     *out = r.release();
   });
 }

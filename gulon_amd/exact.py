@@ -182,6 +182,18 @@ class ExactIndex:
         from .csls import as_results
         return as_results(*self.batch_query_offset_raw(k, vectors, offsets, exclude))
 
+    # ---- rank queries (ranks.py): offsets, excluded rows and gold rows are rows of the MATRIX
+    def batch_query_rank_raw(self, vectors, gold, offsets=None, exclude=None):
+        """gulon_exact_index_query_rank: per query the best row of its gold list (an iterable of rows of the matrix) in
+        the order of batch_query_offset_raw -- t = distance + offsets[row] finite, not exclude[q], by (t, row) -- and how
+        many candidates come before it (ranks.rank_query_reference).  No k: nothing is listed.  The queries are
+        normalised for a cosine index.  offsets: None (+0), an array or a csls.DeviceOffsets (downloaded: the entry
+        point takes host pointers).
+        -> (rank [b], -1 without a gold candidate; row [b], -1; key t [b], +inf; total [b] candidates)."""
+        from .ranks import rank_query_raw
+        return rank_query_raw(N.lib().gulon_exact_index_query_rank, self._h, (), self.dimension, self.matrix.rows,
+                              self._prepare(vectors), gold, offsets, exclude)
+
     def stats(self):
         """Of the last batch: queries answered in one pass, by the peeled fallback and one at a time as non-finite; the
         sample rows S (0: no sample pass), the queue capacity, the largest number of rows at or below a bound."""
@@ -322,6 +334,11 @@ class ExactWordIndex:
         holds those keys."""
         from .csls import as_results
         return [self._result(r) for r in as_results(*self.batch_query_offset_raw(k, vectors, offsets, exclude))]
+
+    def batch_query_rank_raw(self, vectors, gold, offsets=None, exclude=None):
+        """ExactIndex.batch_query_rank_raw, up to BATCH queries per device batch."""
+        from .ranks import batched_rank_query
+        return batched_rank_query(self.index, self.dimension, vectors, gold, offsets, exclude)
 
     def close(self):
         """Frees the handle and the gathered matrix this index was built over, when it owns one."""

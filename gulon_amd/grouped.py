@@ -268,6 +268,9 @@ class GroupedIndex:
         from .csls import as_results
         return as_results(*self.batch_query_offset_raw(k, vectors, offsets, exclude))
 
+    def batch_query_rank_raw(self, vectors, gold, offsets=None, exclude=None):
+        raise NotImplementedError("rank queries are not supported by a grouped index")
+
     def close(self):
         if self._h is not None and self._h.value:
             N.lib().gulon_grouped_index_destroy(self._h)

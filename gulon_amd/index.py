@@ -286,6 +286,18 @@ class PQIndex:
         from .csls import as_results
         return as_results(*self.batch_query_offset_raw(k, vectors, offsets, exclude, frm, until))
 
+    def batch_query_rank_raw(self, vectors, gold, offsets=None, exclude=None, frm=0, until=None):
+        """gulon_index_query_rank: per query (taken as given) the best row of its gold list (an iterable of row ids as
+        returned) in the order of batch_query_offset_raw over [frm, until) -- t = distance + offsets[row] finite, not
+        exclude[q], by (t, row) -- and how many candidates come before it (ranks.rank_query_reference).
+        No k: nothing is listed.  offsets: None (+0), an array or a csls.DeviceOffsets (downloaded: the entry point
+        takes host pointers).  Byte codes, no view.
+        -> (rank [b], -1 without a gold candidate; row [b], -1; key t [b], +inf; total [b] candidates)."""
+        from .ranks import rank_query_raw
+        until = self.length if until is None else until
+        return rank_query_raw(N.lib().gulon_index_query_rank, self._h, (frm, until), self.dimension, self.length,
+                              vectors, gold, offsets, exclude)
+
     def select(self, rows=None, mask=None):
         """The view of this index over a subset of its rows (gulon_index_select_*): an index of its own, gathered on
         the device, that answers in THIS index's row ids.  Exactly one of `rows` (strictly ascending row numbers) and
@@ -607,6 +619,12 @@ class SortedIndex:
         """Per query the k rows with the smallest distance + offsets[row] among the rows whose sum is finite and that
         are not exclude[q]; `distances` of a Result holds those keys."""
         return self.vector_index.batch_query_offset(k, self._prepare(vectors), offsets, exclude)
+
+    def batch_query_rank_raw(self, vectors, gold, offsets=None, exclude=None):
+        """PQIndex.batch_query_rank_raw over all rows, the queries normalised for a cosine index (prepared as
+        batch_query_offset_raw prepares them): (rank, row, key, total)."""
+        return self.vector_index.batch_query_rank_raw(self._prepare(vectors), gold, offsets, exclude)
+
 
 
 class Index:

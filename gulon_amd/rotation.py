@@ -278,6 +278,9 @@ class RotatedWordIndex:
     def query_cosmul(self, k, expression):
         raise NotImplementedError("cosmul queries are not supported by a rotated index")
 
+    def batch_query_rank_raw(self, vectors, gold, offsets=None, exclude=None):
+        raise NotImplementedError("rank queries are not supported by a rotated index")
+
     # ---- forms of the index that take word vectors or give an index back
     def refined(self, vectors, candidates):
         return RotatedWordIndex(self.inner.refined(self._vectors(vectors), candidates), self.rotation)

@@ -213,6 +213,15 @@ class WordIndex:
         from .csls import as_results
         return [self._result(r) for r in as_results(*self.batch_query_offset_raw(k, vectors, offsets, exclude))]
 
+    def batch_query_rank_raw(self, vectors, gold, offsets=None, exclude=None):
+        """SortedIndex.batch_query_rank_raw (ranks.py), up to BATCH queries per device batch: (rank [b],
+        row [b], key [b], total [b]) of every query's best gold row.  NotImplementedError for a grouped index, and from
+        the library for codes wider than a byte."""
+        if self._grouped:
+            raise NotImplementedError("rank queries are not supported by a grouped index")
+        from .ranks import batched_rank_query
+        return batched_rank_query(self.index, self.dimension, vectors, gold, offsets, exclude)
+
     def batch_query(self, k, vectors) -> List[WordResult]:
         """Index.batchQuery (Index.scala:25-32) with the results' words."""
         q = np.ascontiguousarray(vectors, np.float32).reshape(-1, self.dimension)
@@ -313,6 +322,9 @@ class RestrictedWordIndex(WordIndex):
 
     def batch_query_offset_raw(self, k, vectors, offsets, exclude=None):
         raise NotImplementedError("offset queries are not supported by a restricted index")
+
+    def batch_query_rank_raw(self, vectors, gold, offsets=None, exclude=None):
+        raise NotImplementedError("rank queries are not supported by a restricted index")
 
     def close(self):
         self.index.vector_index.close()

@@ -992,6 +992,38 @@ int32_t gulon_mean_similarity(const float *dist_lists, const int32_t *counts, in
 int32_t gulon_mean_similarity_dev(const float *d_dist_lists, const int32_t *d_counts, int32_t b, int32_t kin, int32_t K,
                                   float *d_out, void *stream);
 
+/* ---- Rank queries (rank.hip) ------------------------------------------------------------------------------
+ * The counting twin of the offset query: not the first k_nn candidates, but how many candidates come before a given
+ * one -- at any depth, without a list.  Candidates, keys and order are exactly those of "Offset queries and CSLS" above:
+ * d the handle's own distance bits, t = d + row_offsets[r] in one binary32 addition, a row a candidate if and only if t is
+ * finite and its id is not exclude[q] (nullable), the order (t ascending, row id ascending; -0 equals +0).  row_offsets
+ * is indexed as there; NULL stands for +0.0 at every row.
+ * Every query q has a gold list of zero or more row ids, as the handle returns them, in CSR form: gold_offsets[b + 1]
+ * (gold_offsets[0] = 0, non-decreasing) and gold_rows[gold_offsets[b]].  Per query:
+ *   out_row, out_key [b]   the best gold row -- the gold row that is a candidate and comes first in the order -- and its
+ *                          t; -1 and +inf when no gold row is a candidate: the list is empty, or every row of it is
+ *                          masked by +inf, is the excluded row or lies outside the range, or the query's distances are
+ *                          not finite (a NaN query)
+ *   out_rank [b]           the number of candidates strictly before the best gold row, -1 without one: the (0-based)
+ *                          position of that row in the offset query's answer at any k_nn larger than it
+ *   out_total [b]          (nullable) the number of candidates
+ * All integers are exact; out_key carries the bits the offset query returns for that row.
+ * Everything is checked before anything is launched: b, NaN or -inf in row_offsets, exclude outside -1 or the handle's
+ * row ids, gold_offsets, and every gold row, which must be an id the handle returns -- the exact index: a row of its
+ * dataset; the index: in [row_base, row_base + length) -- else GULON_ERR_INVALID_ARGUMENT naming the first bad entry.
+ * The index: from / until and the limits of the offset query (byte codes only, no views, the tables of one query within
+ * 144 KiB of LDS), else GULON_ERR_UNSUPPORTED.  b = 0 succeeds at once.
+ * gulon_exact_index_query_rank and gulon_index_query_rank take host pointers only: the work runs on the null stream
+ * and the call returns when the answers have arrived.  (Device-pointer forms with a stream, and their stream-contract
+ * cases, are left to a later change.) */
+int32_t gulon_exact_index_query_rank(gulon_exact_index *idx, const float *queries, int32_t b, const float *row_offsets,
+                                     const int32_t *exclude, const int32_t *gold_offsets, const int32_t *gold_rows,
+                                     int32_t *out_rank, int32_t *out_row, float *out_key, int32_t *out_total);
+int32_t gulon_index_query_rank(gulon_index *idx, const float *queries, int32_t b, int32_t from, int32_t until,
+                               const float *row_offsets, const int32_t *exclude, const int32_t *gold_offsets,
+                               const int32_t *gold_rows, int32_t *out_rank, int32_t *out_row, float *out_key,
+                               int32_t *out_total);
+
 /* ---- Alignment (alignment.hip) ---------------------------------------------------------------------------
  * Not Scala methods: the reference aligns nothing.  The two device steps of learning an orthogonal map between two
  * embedding spaces (MUSE's Procrustes refinement) that the entry points above do not cover.
