@@ -15,8 +15,7 @@
 //   exact index        cosmul_transpose: q_t of the 16 / E' questions of a workgroup -> Qt; cosmul_exact_scan: the d_t by
 //                      exact_tile (exact.hpp), its 16 accumulators = the term slots of 16 / E' questions
 //   flat index         launch_build_tables: Index.prepareQuery of every q_t; cosmul_flat_scan: a workgroup is (question,
-//                      row chunk), the question's E tables in LDS, lanes the rows of the 64-row code blocks, one running
-//                      sum per term in the order of scan.hip's exact scan
+//                      row chunk), the flat table scan (table_scan.hpp) over the question's E tables, one sum per term
 //   both               after the sums the score, and the key -score into the question's WaveList (wave_offer), which
 //                      orders by (key ascending, row ascending); the workgroup's lists merged (merge_wave_lists) into
 //                      the chunk's; launch_merge: the row chunks' lists -> one list of depth
@@ -31,9 +30,6 @@ namespace gulon {
 namespace {
 
 constexpr int PLAN_THREADS = 256;
-constexpr int CF_THREADS = 1024;            // cosmul_flat_scan's workgroup: 16 waves, one row block each per step
-constexpr int EXACT_SUB_BATCH = 4096;       // questions per pass: bounds the term vectors kept at 8 slots per question
-constexpr size_t FLAT_TABLE_BYTES = size_t(256) << 20;   // tables of one pass of the flat form
 
 // plan[0] = E', plan[1] = T, the term slots in use, plan[2] = off[0]: slot s is term off[0] + s of the caller's lists.
 // Every slot is a usable one-term expression for the compose launchers: a slot that is not in use, or whose row is
@@ -226,52 +222,15 @@ void check_dev_shape(int b, int k_nn, const int *d_off, const int *d_rows, const
 
 // ---- flat index -------------------------------------------------------------------------------------------------------
 
-// The row blocks of one chunk against one question with E terms: tables [E][m_pad][256] in LDS, the wave's lanes the rows
-// of a block, acc[t] += T_t[j][code_j] with j ascending from 0.f, as scan.hip's exact scan adds them.
-template <int E, int VEC>
-__device__ __forceinline__ void flat_rows(const uint8_t *__restrict__ codes, int ng, int tab, const float *lds,
-                                          unsigned pos, int rb0, int rb1, int row_from, int row_until, int row_base,
-                                          int keff, int lane, int wave, WaveList &wl, int &cnt) {
-  using Word = typename CodeWord<VEC>::type;
-  constexpr int NW = CF_THREADS / 64;
-  const Word *cw = reinterpret_cast<const Word *>(codes);
-  for (int rb = rb0 + wave; rb < rb1; rb += NW) {
-    float acc[E];
-#pragma unroll
-    for (int t = 0; t < E; t++) acc[t] = 0.f;
-    const Word *p = cw + ((size_t)rb * ng) * 64 + lane;
-    for (int g = 0; g < ng; g++) {
-      const Word w = p[(size_t)g * 64];
-      const float *tj = lds + g * VEC * 256;
-#pragma unroll 1
-      for (int seg = 0; seg < VEC / 4; seg++) {   // four codes per step: 4 * E look-ups in flight, no spill at E = 8
-        const uint32_t x = code_word32<VEC>(w, seg);
-#pragma unroll
-        for (int bb = 0; bb < 4; bb++) {
-          const float *te = tj + (seg * 4 + bb) * 256 + ((x >> (8 * bb)) & 0xFFu);
-#pragma unroll
-          for (int t = 0; t < E; t++) acc[t] += te[t * tab];
-        }
-      }
-    }
-    const int row = rb * 64 + lane;
-    const bool valid = row >= row_from && row < row_until;
-    const float key = cosmul_key<E>([&](int t) { return acc[t]; }, E, pos);
-    wave_offer(wl, cnt, key, valid, __ballot(valid), rb * 64 + row_base, keff, lane);
-  }
-}
-
+// A workgroup is (question, row chunk): the tables of the question's ne terms in LDS and the flat table scan over them
+// (table_scan.hpp), instantiated for every ne; after the sums the key -score into the question's WaveList.
 template <int VEC>
-__global__ __launch_bounds__(CF_THREADS) void cosmul_flat_scan(const uint8_t *__restrict__ codes, int ng, int m_pad,
-                                                               const float *__restrict__ tables,
-                                                               const int *__restrict__ plan,
-                                                               const int *__restrict__ bad,
-                                                               const int *__restrict__ off,
-                                                               const float *__restrict__ tw, int b, int lds_terms,
-                                                               int row_from, int row_until, int row_base, int rb_begin,
-                                                               int rb_end, int rb_per_chunk, int nchunks, int keff,
-                                                               float *__restrict__ part_v, int *__restrict__ part_i) {
-  constexpr int NW = CF_THREADS / 64;
+__global__ __launch_bounds__(TABLE_SCAN_THREADS) void cosmul_flat_scan(
+    const uint8_t *__restrict__ codes, int ng, int m_pad, const float *__restrict__ tables, const int *__restrict__ plan,
+    const int *__restrict__ bad, const int *__restrict__ off, const float *__restrict__ tw, int b, int lds_terms,
+    int row_from, int row_until, int row_base, int rb_begin, int rb_end, int rb_per_chunk, int nchunks, int keff,
+    float *__restrict__ part_v, int *__restrict__ part_i) {
+  constexpr int NW = TABLE_SCAN_THREADS / 64;
   extern __shared__ float4 lds4[];
   __shared__ float sv[NW * 64];
   __shared__ int si[NW * 64];
@@ -285,14 +244,19 @@ __global__ __launch_bounds__(CF_THREADS) void cosmul_flat_scan(const uint8_t *__
   wl.init();
   int cnt = 0;
   if (ne > 0) {   // (uniform over the workgroup)
-    const float4 *src = reinterpret_cast<const float4 *>(tables + (size_t)(t0 - plan[2]) * tab);
-    const int n4 = ne * (tab / 4);
-    for (int e = tid; e < n4; e += CF_THREADS) lds4[e] = src[e];
-    __syncthreads();
-    const float *lds = reinterpret_cast<const float *>(lds4);
+    stage_tables(lds4, tables + (size_t)(t0 - plan[2]) * tab, tab, ne, ne, tid);
     const int rb0 = rb_begin + chunk * rb_per_chunk, rb1 = min(rb_end, rb0 + rb_per_chunk);
-#define CF_ROWS(EE) flat_rows<EE, VEC>(codes, ng, tab, lds, pos, rb0, rb1, row_from, row_until, row_base, keff, lane, \
-                                       wave, wl, cnt)
+    auto rows = [&](auto e) {
+      constexpr int E = decltype(e)::value;
+      table_scan_rows<E, VEC>(codes, ng, tab, reinterpret_cast<const float *>(lds4), rb0, rb1, lane, wave,
+                              [&](int rb, const float (&acc)[E]) {
+        const int row = rb * 64 + lane;
+        const bool valid = row >= row_from && row < row_until;
+        const float key = cosmul_key<E>([&](int t) { return acc[t]; }, E, pos);
+        wave_offer(wl, cnt, key, valid, __ballot(valid), rb * 64 + row_base, keff, lane);
+      });
+    };
+#define CF_ROWS(EE) rows(std::integral_constant<int, EE>{})
     switch (ne) {
       case 1: CF_ROWS(1); break;
       case 2: CF_ROWS(2); break;
@@ -349,7 +313,7 @@ CosmulShape cosmul_exact_shape(int from, int until, int b) {
 }
 
 CosmulShape cosmul_flat_shape(const gulon_index *ix, int from, int until, int b) {
-  constexpr int NW = CF_THREADS / 64;
+  constexpr int NW = TABLE_SCAN_THREADS / 64;
   const size_t tab = (size_t)ix->m_pad * 256;
   const int sub = (int)std::max<size_t>(1, FLAT_TABLE_BYTES / ((size_t)COSMUL_MAX_TERMS * tab * sizeof(float)));
   const int nb = std::min(sub, b);
@@ -398,7 +362,7 @@ void launch_cosmul_exact(const gulon_dataset *ds, int from, int until, CosmulWor
 
 int cosmul_flat_max_terms(const gulon_index *ix) {
   const size_t per_term = (size_t)ix->m_pad * 256 * sizeof(float);
-  return (int)std::min<size_t>(COSMUL_MAX_TERMS, COSMUL_LDS_BUDGET / per_term);
+  return (int)std::min<size_t>(COSMUL_MAX_TERMS, TABLE_LDS_BUDGET / per_term);
 }
 
 void launch_cosmul_flat(gulon_index *ix, CosmulWork &x, const int *d_off, const int *d_rows, const float *d_w, int b,
@@ -411,7 +375,7 @@ void launch_cosmul_flat(gulon_index *ix, CosmulWork &x, const int *d_off, const 
   GULON_REQUIRE(from >= 0 && until <= ix->n, "expected: from >= 0 && until <= length");
   const int max_terms = cosmul_flat_max_terms(ix);
   GULON_UNSUPPORTED(max_terms < 1, "m = %d: the tables of one term need %d KiB of LDS, %d KiB are there", ix->m,
-                    ix->m_pad, (int)(COSMUL_LDS_BUDGET / 1024));
+                    ix->m_pad, (int)(TABLE_LDS_BUDGET / 1024));
   if (b == 0) return;
   lds_terms = std::min(std::max(lds_terms, 1), max_terms);
   const int kin = std::min(k_nn + COSMUL_MAX_TERMS, GULON_MAX_K), keff = kin + 1;
@@ -451,7 +415,7 @@ void launch_cosmul_flat(gulon_index *ix, CosmulWork &x, const int *d_off, const 
   do {                                                                                                                \
     HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(cosmul_flat_scan<VEC>),                              \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));                       \
-    hipLaunchKernelGGL(cosmul_flat_scan<VEC>, dim3(nb, nchunks), dim3(CF_THREADS), lds_bytes, st, ix->codes.p, ix->ng, \
+    hipLaunchKernelGGL(cosmul_flat_scan<VEC>, dim3(nb, nchunks), dim3(TABLE_SCAN_THREADS), lds_bytes, st, ix->codes.p, ix->ng, \
                        ix->m_pad, x.tables.p, x.plan.p, x.bad.p, off, d_w, nb, lds_terms, from, until, ix->row_base,   \
                        rb_begin, rb_end, rb_per_chunk, nchunks, keff, x.pv.p, x.pi.p);                                \
   } while (0)
@@ -494,7 +458,7 @@ GULON_API int32_t gulon_index_query_cosmul(gulon_index *idx, const int32_t *term
     GULON_UNSUPPORTED(idx->is_view, "cosmul queries are not supported on an index view");
     GULON_UNSUPPORTED(emax > cosmul_flat_max_terms(idx),
                       "m = %d, E = %d: the tables of one question need %d KiB of LDS, %d KiB are there", idx->m, emax,
-                      emax * idx->m_pad, (int)(COSMUL_LDS_BUDGET / 1024));
+                      emax * idx->m_pad, (int)(TABLE_LDS_BUDGET / 1024));
     CosmulWork &x = idx->cosmul;
     std::lock_guard<std::mutex> work(x.mu);
     const hipStream_t st = nullptr;

@@ -1,12 +1,11 @@
 // Multiplicative analogy queries, 3CosMul: what cosmul.hip offers the handles that answer them.
 #pragma once
 #include "compose.hpp"
-#include "scan.hpp"
+#include "table_scan.hpp"   // TABLE_LDS_BUDGET, the tables of one question of the flat form
 
 namespace gulon {
 
 constexpr int COSMUL_MAX_TERMS = 8;                  // terms of one expression
-constexpr size_t COSMUL_LDS_BUDGET = 144 * 1024;     // the tables of one question of the flat form
 
 // The host-pointer forms check everything before anything is launched (GULON_ERR_INVALID_ARGUMENT, or
 // GULON_ERR_UNSUPPORTED for a limit); returns the number of terms and, in *emax, the largest E of the batch.
@@ -26,7 +25,7 @@ void launch_cosmul_exact(const gulon_dataset *ds, int from, int until, CosmulWor
 void launch_cosmul_flat(gulon_index *ix, CosmulWork &x, const int *d_off, const int *d_rows, const float *d_w, int b,
                         int k_nn, bool normalize, int from, int until, int lds_terms, int *out_idx, float *out_score,
                         int *out_count, bool dev_rows, hipStream_t st);
-int cosmul_flat_max_terms(const gulon_index *ix);   // the E whose tables fit COSMUL_LDS_BUDGET, at most COSMUL_MAX_TERMS
+int cosmul_flat_max_terms(const gulon_index *ix);   // the E whose tables fit TABLE_LDS_BUDGET, at most COSMUL_MAX_TERMS
 
 // The launch geometry of the two launchers, which take it from here: the questions of one pass, and for a pass whose
 // first question has b questions from it on (a pass takes the first per_pass of them) the row chunks and what one chunk

@@ -1,8 +1,9 @@
 // The exact distance tile and what is built on it: the brute-force kNN (knn.hip), the exact index (exact.hip) and the
 // exact 3CosMul scan (cosmul.hip) all compute their distances by exact_tile(); the exact index answers small k_nn and
-// its fallbacks by knn.hip's single-pass / peeled driver, exact_knn_dev().
+// its fallbacks by knn.hip's single-pass / peeled driver, exact_knn_dev(); the offset and rank scans (offset.hip,
+// rank.hip) walk their queries by exact_passes().
 #pragma once
-#include "scan.hpp"
+#include "table_scan.hpp"   // EXACT_SUB_BATCH
 
 namespace gulon {
 
@@ -67,6 +68,23 @@ inline RowChunks split_groups(int groups, int want) {
 // knn_kernel's and cosmul_exact_scan's grids: about 2048 workgroups over `tiles` query tiles
 inline RowChunks knn_row_chunks(int from, int until, int tiles) {
   return split_groups(row_groups(from, until), ceil_div(2048, tiles));
+}
+
+// The passes of a scan in knn_kernel's geometry over the b >= 1 queries at d_q [b][d], rows [from, until):
+// EXACT_SUB_BATCH queries each, their Qt into `qt` (transpose_queries) on `st`, then pass(p) -- the caller's buffers,
+// kernels and tail for queries [q0, q0 + nb), `tiles` query tiles by `nchunks` row chunks of `rows_per_chunk` rows.
+struct ExactPass { int q0, nb, tiles, nchunks, rows_per_chunk; };
+template <class Pass>
+void exact_passes(const float *d_q, int b, int d, int from, int until, DevBuf<float> &qt, hipStream_t st, Pass pass) {
+  for (int q0 = 0; q0 < b; q0 += EXACT_SUB_BATCH) {
+    const int nb = std::min(EXACT_SUB_BATCH, b - q0), tiles = ceil_div(nb, KNN_QT);
+    const RowChunks ch = knn_row_chunks(from, until, tiles);
+    const long long tq = (long long)tiles * d * KNN_QT;
+    qt.ensure((size_t)tq);
+    hipLaunchKernelGGL(transpose_queries, dim3(ceil_div(tq, 256)), dim3(256), 0, st, d_q + (size_t)q0 * d, nb, d, tiles,
+                       qt.p);
+    pass(ExactPass{q0, nb, tiles, ch.nchunks, ch.groups_per_chunk * KNN_THREADS});
+  }
 }
 
 // gulon_exact_knn's device work, all on `st`: b >= 1 queries at d_q against rows [from, until) of ds, from < until,

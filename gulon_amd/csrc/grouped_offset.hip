@@ -15,11 +15,10 @@
 //   launch_merge          the `stride` lists of a query -> the first k_nn, -1 / +inf after the last.  A candidate's key
 //                         is finite, so it is never confused with the padding.
 #include "grouped_offset.hpp"
+#include "table_scan.hpp"   // finite_key
 
 namespace gulon {
 namespace {
-
-__device__ __forceinline__ bool finite_key(float t) { return fabsf(t) < INFINITY; }   // false for NaN
 
 // gq_group_scan's constants (grouped.hip), which the launch's LDS (group_scan_lds) is sized by
 constexpr int GO_WAVES = 4;    // (query, group) pairs per workgroup: they share the staged codebook slices

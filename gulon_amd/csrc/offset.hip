@@ -9,10 +9,9 @@
 //   exact index   offset_exact_scan: knn.hip's knn_kernel with the offset -- 16 queries per workgroup, lane = row, the d
 //                 by exact_tile (exact.hpp), the row's offset loaded once per 256-row step and added to each of the 16
 //                 sums
-//   flat index    launch_build_tables: Index.prepareQuery of every query; offset_flat_scan: a workgroup is (E queries,
-//                 row chunk), their E tables in LDS, lanes the rows of the 64-row code blocks, one running sum per
-//                 query in the order of scan.hip's exact scan (as cosmul.hip's cosmul_flat_scan forms its terms' sums),
-//                 one offset load per row shared by the E queries, each with its own WaveList and excluded row
+//   flat index    launch_build_tables(): Index.prepareQuery of every query; offset_flat_scan: the flat table scan
+//                 (table_scan.hpp) of a workgroup's E queries, one offset load per row shared by the E queries, each
+//                 with its own WaveList and excluded row
 //   both          t into the query's WaveList (wave_offer), which orders by (key ascending, row ascending); the
 //                 workgroup's lists merged (merge_wave_lists) into the chunk's; launch_merge: the row chunks' lists ->
 //                 the first k_nn, -1 / +inf after the last.  The lists' own padding is (+inf, INT_MAX); a candidate's
@@ -78,30 +77,21 @@ __global__ __launch_bounds__(KNN_THREADS) void offset_exact_scan(const float *__
 
 // ---- flat index -------------------------------------------------------------------------------------------------------
 
-// A workgroup is (E query slots, row chunk): slot t is query blockIdx.x * E + t, tables [E][m_pad][256] in LDS; per row
-// acc[t] += T_t[j][code_j] with j ascending from 0.f, as scan.hip's exact scan adds them.
+// A workgroup is (E query slots, row chunk): slot t is query blockIdx.x * E + t, its table in LDS (table_scan.hpp); the
+// slots past the batch hold zero tables and offer nothing.
 template <int E, int VEC>
-__global__ __launch_bounds__(OF_THREADS) void offset_flat_scan(const uint8_t *__restrict__ codes, int ng, int m_pad,
-                                                               const float *__restrict__ tables,
-                                                               const float *__restrict__ offsets,
-                                                               const int *__restrict__ exclude, int b, int row_from,
-                                                               int row_until, int row_base, int rb_begin, int rb_end,
-                                                               int rb_per_chunk, int nchunks, int keff,
-                                                               float *__restrict__ part_v, int *__restrict__ part_i) {
-  using Word = typename CodeWord<VEC>::type;
-  constexpr int NW = OF_THREADS / 64;
+__global__ __launch_bounds__(TABLE_SCAN_THREADS) void offset_flat_scan(
+    const uint8_t *__restrict__ codes, int ng, int m_pad, const float *__restrict__ tables,
+    const float *__restrict__ offsets, const int *__restrict__ exclude, int b, int row_from, int row_until, int row_base,
+    int rb_begin, int rb_end, int rb_per_chunk, int nchunks, int keff, float *__restrict__ part_v,
+    int *__restrict__ part_i) {
+  constexpr int NW = TABLE_SCAN_THREADS / 64;
   extern __shared__ float4 lds4[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int q0 = blockIdx.x * E, chunk = blockIdx.y;
   const int tab = m_pad * 256;
-  const int nq = min(E, b - q0);   // live slots (uniform over the workgroup); the others hold zero tables
-  {
-    const float4 *src = reinterpret_cast<const float4 *>(tables + (size_t)q0 * tab);
-    const int n4 = nq * (tab / 4), all4 = E * (tab / 4);
-    for (int e = tid; e < all4; e += OF_THREADS) lds4[e] = e < n4 ? src[e] : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  __syncthreads();
-  const float *lds = reinterpret_cast<const float *>(lds4);
+  const int nq = min(E, b - q0);   // live slots (uniform over the workgroup)
+  stage_tables(lds4, tables + (size_t)q0 * tab, tab, nq, E, tid);
 
   WaveList wl[E];
   int cnt[E], ex[E];
@@ -111,27 +101,9 @@ __global__ __launch_bounds__(OF_THREADS) void offset_flat_scan(const uint8_t *__
     ex[t] = __builtin_amdgcn_readfirstlane((exclude != nullptr && t < nq) ? exclude[q0 + t] : -1);
   }
 
-  const Word *cw = reinterpret_cast<const Word *>(codes);
   const int rb0 = rb_begin + chunk * rb_per_chunk, rb1 = min(rb_end, rb0 + rb_per_chunk);
-  for (int rb = rb0 + wave; rb < rb1; rb += NW) {
-    float acc[E];
-#pragma unroll
-    for (int t = 0; t < E; t++) acc[t] = 0.f;
-    const Word *p = cw + ((size_t)rb * ng) * 64 + lane;
-    for (int g = 0; g < ng; g++) {
-      const Word w = p[(size_t)g * 64];
-      const float *tj = lds + g * VEC * 256;
-#pragma unroll 1
-      for (int seg = 0; seg < VEC / 4; seg++) {   // four codes per step: 4 * E look-ups in flight
-        const uint32_t x = code_word32<VEC>(w, seg);
-#pragma unroll
-        for (int bb = 0; bb < 4; bb++) {
-          const float *te = tj + (seg * 4 + bb) * 256 + ((x >> (8 * bb)) & 0xFFu);
-#pragma unroll
-          for (int t = 0; t < E; t++) acc[t] += te[t * tab];
-        }
-      }
-    }
+  table_scan_rows<E, VEC>(codes, ng, tab, reinterpret_cast<const float *>(lds4), rb0, rb1, lane, wave,
+                          [&](int rb, const float (&acc)[E]) {
     const int row = rb * 64 + lane;
     const bool in = row >= row_from && row < row_until;
     const float off = in ? offsets[row] : 0.f;
@@ -144,7 +116,7 @@ __global__ __launch_bounds__(OF_THREADS) void offset_flat_scan(const uint8_t *__
         wave_offer(wl[t], cnt[t], key, valid, __ballot(valid), rb * 64 + row_base, keff, lane);
       }
     }
-  }
+  });
   __syncthreads();   // every wave is done with the tables: their LDS takes the lists
   float *sv = reinterpret_cast<float *>(lds4);
   int *si = reinterpret_cast<int *>(sv + E * NW * 64);
@@ -157,58 +129,30 @@ __global__ __launch_bounds__(OF_THREADS) void offset_flat_scan(const uint8_t *__
   });
 }
 
-// (the slots, the shape and the refusals: flat_slot_bytes, offset_flat_shape, offset_flat_max_e, check_flat in offset.hpp)
-template <int E, int VEC>
-void launch_flat_ev(const gulon_index *ix, OffsetWork &x, const float *d_off, const int *d_ex, int nb, int from,
-                    int until, const FlatShape &s, int keff, hipStream_t st) {
-  const size_t lds_bytes = (size_t)E * flat_slot_bytes(ix->m_pad);
-  HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(offset_flat_scan<E, VEC>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  hipLaunchKernelGGL((offset_flat_scan<E, VEC>), dim3(ceil_div(nb, E), s.nchunks), dim3(OF_THREADS), lds_bytes, st,
-                     ix->codes.p, ix->ng, ix->m_pad, x.tables.p, d_off, d_ex, nb, from, until, ix->row_base, from / 64,
-                     ceil_div(until, 64), s.rb_per_chunk, s.nchunks, keff, x.pv.p, x.pi.p);
-  HIP_CHECK(hipGetLastError());
-}
-
-template <int E>
-void launch_flat_e(const gulon_index *ix, OffsetWork &x, const float *d_off, const int *d_ex, int nb, int from,
-                   int until, const FlatShape &s, int keff, hipStream_t st) {
-  if (ix->vec == 4) launch_flat_ev<E, 4>(ix, x, d_off, d_ex, nb, from, until, s, keff, st);
-  else launch_flat_ev<E, 16>(ix, x, d_off, d_ex, nb, from, until, s, keff, st);
-}
-
 // Rows [from, until) of a flat byte-code index against the b queries at d_q; called with x.mu held and the handle's
-// mutex free.  The arguments are checked (check_flat) by the caller.
+// mutex free.  The arguments are checked (check_flat) by the caller; the passes by flat_passes (offset.hpp).
 void launch_offset_flat(gulon_index *ix, OffsetWork &x, const float *d_q, int b, int k_nn, int from, int until,
                         const float *d_off, const int *d_ex, int *out_idx, float *out_key, int *out_count,
                         hipStream_t st) {
   if (b == 0) return;
   GULON_REQUIRE(d_q != nullptr && d_off != nullptr && out_idx != nullptr && out_key != nullptr, "null argument");
-  const int keff = k_nn + 1, tab = ix->m_pad * 256;
-  int E = offset_flat_max_e(ix);
-  while (E > 1 && E / 2 >= b) E /= 2;   // no more slots than a small batch fills
-  const int sub = offset_flat_shape(ix, from, until, b, E).per_pass;
-  std::lock_guard<std::mutex> lock(ix->mu);
-  ix->pend_b = -1;
-  StreamOrder so(ix, st);
-  for (int q0 = 0; q0 < b; q0 += sub) {
-    const int nb = std::min(sub, b - q0);
-    const FlatShape s = offset_flat_shape(ix, from, until, nb, E);
-    x.tables.ensure((size_t)nb * tab);
+  const int keff = k_nn + 1;
+  flat_passes(ix, x.tables, d_q, b, from, until, st, [&](int q0, int nb, int E, const FlatShape &s) {
     x.pv.ensure((size_t)nb * s.nchunks * keff); x.pi.ensure((size_t)nb * s.nchunks * keff);
-    launch_build_tables(1, ix, d_q + (size_t)q0 * ix->d, nb, nb, x.tables.p, st);
-    const int *ex = d_ex ? d_ex + q0 : nullptr;
-    switch (E) {
-      case 8: launch_flat_e<8>(ix, x, d_off, ex, nb, from, until, s, keff, st); break;
-      case 4: launch_flat_e<4>(ix, x, d_off, ex, nb, from, until, s, keff, st); break;
-      case 2: launch_flat_e<2>(ix, x, d_off, ex, nb, from, until, s, keff, st); break;
-      default: launch_flat_e<1>(ix, x, d_off, ex, nb, from, until, s, keff, st); break;
-    }
+    dispatch_e_vec(E, ix->vec, [&](auto e, auto vec) {
+      const auto scan = offset_flat_scan<decltype(e)::value, decltype(vec)::value>;
+      const size_t lds_bytes = (size_t)e * flat_slot_bytes(ix->m_pad);
+      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(scan), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)lds_bytes));
+      hipLaunchKernelGGL(scan, dim3(ceil_div(nb, e), s.nchunks), dim3(TABLE_SCAN_THREADS), lds_bytes, st, ix->codes.p,
+                         ix->ng, ix->m_pad, x.tables.p, d_off, d_ex ? d_ex + q0 : nullptr, nb, from, until, ix->row_base,
+                         from / 64, ceil_div(until, 64), s.rb_per_chunk, s.nchunks, keff, x.pv.p, x.pi.p);
+      HIP_CHECK(hipGetLastError());
+    });
     launch_merge(true, x.pv.p, x.pi.p, s.nchunks, (long long)keff, (long long)s.nchunks * keff, nb, k_nn,
                  out_idx + (size_t)q0 * k_nn, out_key + (size_t)q0 * k_nn, out_count ? out_count + q0 : nullptr, nullptr,
                  nullptr, nullptr, st);
-  }
-  so.done();
+  });
 }
 
 // ---- mean similarity ----------------------------------------------------------------------------------------------------
@@ -239,19 +183,25 @@ void launch_mean_similarity(const float *d_dist, const int *d_counts, int b, int
 
 }  // namespace
 
-void check_offset_host(const float *offsets, int rows, const int *exclude, int b, int k_nn, int id_base) {
-  GULON_REQUIRE(b >= 0, "batch size must be non-negative");
-  GULON_UNSUPPORTED(k_nn < 1 || k_nn > GULON_MAX_K, "k_nn = %d outside [1, %d]", k_nn, GULON_MAX_K);
-  GULON_REQUIRE(rows == 0 || offsets != nullptr, "row_offsets is null");
-  for (int r = 0; r < rows; r++)
-    GULON_REQUIRE(offsets[r] == offsets[r] && offsets[r] != -INFINITY, "row_offsets[%d] = %g: NaN and -inf are not offsets",
-                  r, (double)offsets[r]);
+void check_rows_host(const float *offsets, bool nullable, int rows, const int *exclude, int b, int id_base) {
+  GULON_REQUIRE(nullable || rows == 0 || offsets != nullptr, "row_offsets is null");
+  if (offsets)
+    for (int r = 0; r < rows; r++)
+      GULON_REQUIRE(offsets[r] == offsets[r] && offsets[r] != -INFINITY,
+                    "row_offsets[%d] = %g: NaN and -inf are not offsets", r, (double)offsets[r]);
   if (exclude)
     for (int q = 0; q < b; q++)
       GULON_REQUIRE(exclude[q] == -1 || (exclude[q] >= id_base && exclude[q] - id_base < rows),
                     "exclude[%d] = %d: expected -1 or a row in [%d, %d)", q, exclude[q], id_base, id_base + rows);
 }
 
+void check_offset_host(const float *offsets, int rows, const int *exclude, int b, int k_nn, int id_base) {
+  GULON_REQUIRE(b >= 0, "batch size must be non-negative");
+  GULON_UNSUPPORTED(k_nn < 1 || k_nn > GULON_MAX_K, "k_nn = %d outside [1, %d]", k_nn, GULON_MAX_K);
+  check_rows_host(offsets, false, rows, exclude, b, id_base);
+}
+
+// (the passes, their query tiles and row chunks: exact_passes in exact.hpp, by knn_row_chunks())
 void launch_offset_exact(const gulon_dataset *ds, int from, int until, OffsetWork &x, const float *d_q, int b, int k_nn,
                          const float *d_offsets, const int *d_exclude, int *out_idx, float *out_key, int *out_count,
                          hipStream_t st) {
@@ -259,24 +209,18 @@ void launch_offset_exact(const gulon_dataset *ds, int from, int until, OffsetWor
   GULON_UNSUPPORTED(k_nn < 1 || k_nn > GULON_MAX_K, "k_nn = %d outside [1, %d]", k_nn, GULON_MAX_K);
   if (b == 0) return;
   GULON_REQUIRE(d_q != nullptr && d_offsets != nullptr && out_idx != nullptr && out_key != nullptr, "null argument");
-  const int d = ds->d, keff = k_nn + 1;
-  for (int q0 = 0; q0 < b; q0 += EXACT_SUB_BATCH) {
-    const int nb = std::min(EXACT_SUB_BATCH, b - q0), ntiles = ceil_div(nb, KNN_QT), bp = ntiles * KNN_QT;
-    const RowChunks ch = knn_row_chunks(from, until, ntiles);
-    const int nchunks = ch.nchunks, rows_per_chunk = ch.groups_per_chunk * KNN_THREADS;
-    x.qt.ensure((size_t)ntiles * d * KNN_QT);
-    x.pv.ensure((size_t)bp * nchunks * keff); x.pi.ensure((size_t)bp * nchunks * keff);
-    const long long tq = (long long)ntiles * d * KNN_QT;
-    hipLaunchKernelGGL(transpose_queries, dim3(ceil_div(tq, 256)), dim3(256), 0, st, d_q + (size_t)q0 * d, nb, d, ntiles,
-                       x.qt.p);
-    hipLaunchKernelGGL(offset_exact_scan, dim3(ntiles, nchunks), dim3(KNN_THREADS), 0, st, ds->x.p, ds->n, d, x.qt.p,
-                       d_offsets, d_exclude ? d_exclude + q0 : nullptr, nb, from, until, rows_per_chunk, nchunks, keff,
-                       x.pv.p, x.pi.p);
+  const int keff = k_nn + 1;
+  exact_passes(d_q, b, ds->d, from, until, x.qt, st, [&](const ExactPass &p) {
+    const size_t lists = (size_t)p.tiles * KNN_QT * p.nchunks * keff;
+    x.pv.ensure(lists); x.pi.ensure(lists);
+    hipLaunchKernelGGL(offset_exact_scan, dim3(p.tiles, p.nchunks), dim3(KNN_THREADS), 0, st, ds->x.p, ds->n, ds->d,
+                       x.qt.p, d_offsets, d_exclude ? d_exclude + p.q0 : nullptr, p.nb, from, until, p.rows_per_chunk,
+                       p.nchunks, keff, x.pv.p, x.pi.p);
     HIP_CHECK(hipGetLastError());
-    launch_merge(true, x.pv.p, x.pi.p, nchunks, (long long)keff, (long long)nchunks * keff, nb, k_nn,
-                 out_idx + (size_t)q0 * k_nn, out_key + (size_t)q0 * k_nn, out_count ? out_count + q0 : nullptr, nullptr,
-                 nullptr, nullptr, st);
-  }
+    launch_merge(true, x.pv.p, x.pi.p, p.nchunks, (long long)keff, (long long)p.nchunks * keff, p.nb, k_nn,
+                 out_idx + (size_t)p.q0 * k_nn, out_key + (size_t)p.q0 * k_nn, out_count ? out_count + p.q0 : nullptr,
+                 nullptr, nullptr, nullptr, st);
+  });
 }
 
 }  // namespace gulon

@@ -11,9 +11,9 @@
 //                 a lane per gold row, the row's code words gathered and its entries of the query's Index.prepareQuery
 //                 table summed quantizer 0 first from 0.f, as the scan sums them
 //   counting      rank_exact_scan: knn.hip's knn_kernel geometry (16 queries per workgroup, lane = row, exact_tile, one
-//                 offset load per 256-row step, knn_row_chunks).  rank_flat_scan<E, VEC>: the flat offset scan's
-//                 geometry (E tables in LDS, 1024 threads, one code read and one offset load per row for the E
-//                 queries; the slots and the grid by offset.hpp).  Per query (key*, row*) and the excluded id are
+//                 offset load per 256-row step, knn_row_chunks).  rank_flat_scan<E, VEC>: the flat table scan
+//                 (table_scan.hpp) in the flat offset scan's geometry, one offset load per row for the E queries; the
+//                 slots, the grid and the passes by offset.hpp.  Per query (key*, row*) and the excluded id are
 //                 wave-uniform; per row  valid = in range && finite(t) && id != ex,
 //                 ahead = valid && (t < key* || (t == key* && id < row*)), and two scalar counters advance by the
 //                 population of the two ballots.  No list, no merge, no atomics; one LDS reduction over the waves
@@ -188,31 +188,21 @@ __global__ __launch_bounds__(256) void rank_flat_gold(const uint8_t *__restrict_
   }
 }
 
-// A workgroup is (E query slots, row chunk), as in the flat offset scan: slot t is query blockIdx.x * E + t, tables
-// [E][m_pad][256] in LDS; per row acc[t] += T_t[j][code_j] with j ascending from 0.f, as scan.hip's exact scan adds them.
+// A workgroup is (E query slots, row chunk), as in the flat offset scan: slot t is query blockIdx.x * E + t, its table in
+// LDS (table_scan.hpp); the slots past the batch hold zero tables and their counters are not written.
 template <int E, int VEC>
-__global__ __launch_bounds__(OF_THREADS) void rank_flat_scan(const uint8_t *__restrict__ codes, int ng, int m_pad,
-                                                             const float *__restrict__ tables,
-                                                             const float *__restrict__ offsets,
-                                                             const int *__restrict__ exclude,
-                                                             const float *__restrict__ best_key,
-                                                             const int *__restrict__ best_row, int b, int row_from,
-                                                             int row_until, int row_base, int rb_begin, int rb_end,
-                                                             int rb_per_chunk, int nchunks, int *__restrict__ part) {
-  using Word = typename CodeWord<VEC>::type;
-  constexpr int NW = OF_THREADS / 64;
+__global__ __launch_bounds__(TABLE_SCAN_THREADS) void rank_flat_scan(
+    const uint8_t *__restrict__ codes, int ng, int m_pad, const float *__restrict__ tables,
+    const float *__restrict__ offsets, const int *__restrict__ exclude, const float *__restrict__ best_key,
+    const int *__restrict__ best_row, int b, int row_from, int row_until, int row_base, int rb_begin, int rb_end,
+    int rb_per_chunk, int nchunks, int *__restrict__ part) {
+  constexpr int NW = TABLE_SCAN_THREADS / 64;
   extern __shared__ float4 lds4[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int q0 = blockIdx.x * E, chunk = blockIdx.y;
   const int tab = m_pad * 256;
-  const int nq = min(E, b - q0);   // live slots (uniform over the workgroup); the others hold zero tables
-  {
-    const float4 *src = reinterpret_cast<const float4 *>(tables + (size_t)q0 * tab);
-    const int n4 = nq * (tab / 4), all4 = E * (tab / 4);
-    for (int e = tid; e < all4; e += OF_THREADS) lds4[e] = e < n4 ? src[e] : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  __syncthreads();
-  const float *lds = reinterpret_cast<const float *>(lds4);
+  const int nq = min(E, b - q0);   // live slots (uniform over the workgroup)
+  stage_tables(lds4, tables + (size_t)q0 * tab, tab, nq, E, tid);
 
   float key[E];
   int gold[E], ex[E], ahead[E], total[E];
@@ -224,27 +214,9 @@ __global__ __launch_bounds__(OF_THREADS) void rank_flat_scan(const uint8_t *__re
     ahead[t] = 0; total[t] = 0;
   }
 
-  const Word *cw = reinterpret_cast<const Word *>(codes);
   const int rb0 = rb_begin + chunk * rb_per_chunk, rb1 = min(rb_end, rb0 + rb_per_chunk);
-  for (int rb = rb0 + wave; rb < rb1; rb += NW) {
-    float acc[E];
-#pragma unroll
-    for (int t = 0; t < E; t++) acc[t] = 0.f;
-    const Word *p = cw + ((size_t)rb * ng) * 64 + lane;
-    for (int g = 0; g < ng; g++) {
-      const Word w = p[(size_t)g * 64];
-      const float *tj = lds + g * VEC * 256;
-#pragma unroll 1
-      for (int seg = 0; seg < VEC / 4; seg++) {   // four codes per step: 4 * E look-ups in flight
-        const uint32_t x = code_word32<VEC>(w, seg);
-#pragma unroll
-        for (int bb = 0; bb < 4; bb++) {
-          const float *te = tj + (seg * 4 + bb) * 256 + ((x >> (8 * bb)) & 0xFFu);
-#pragma unroll
-          for (int t = 0; t < E; t++) acc[t] += te[t * tab];
-        }
-      }
-    }
+  table_scan_rows<E, VEC>(codes, ng, tab, reinterpret_cast<const float *>(lds4), rb0, rb1, lane, wave,
+                          [&](int rb, const float (&acc)[E]) {
     const int row = rb * 64 + lane;
     const bool in = row >= row_from && row < row_until;
     const float off = (in && offsets != nullptr) ? offsets[row] : 0.f;
@@ -257,7 +229,7 @@ __global__ __launch_bounds__(OF_THREADS) void rank_flat_scan(const uint8_t *__re
       ahead[t] += __popcll(valid & ahead_mask(k, id, key[t], gold[t]));
       total[t] += __popcll(valid);
     }
-  }
+  });
   __syncthreads();   // every wave is done with the tables: their LDS takes the waves' counters [NW][E][2]
   int *sc = reinterpret_cast<int *>(lds4);
   if (lane == 0) {
@@ -299,45 +271,12 @@ void launch_finish(const RankWork &x, int nchunks, int nb, int *out_rank, int *o
   HIP_CHECK(hipGetLastError());
 }
 
-template <int E, int VEC>
-void launch_flat_ev(const gulon_index *ix, RankWork &x, const float *d_off, const int *d_ex, int nb, int from, int until,
-                    const FlatShape &s, hipStream_t st) {
-  const size_t lds_bytes = (size_t)E * flat_slot_bytes(ix->m_pad);
-  HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(rank_flat_scan<E, VEC>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  hipLaunchKernelGGL((rank_flat_scan<E, VEC>), dim3(ceil_div(nb, E), s.nchunks), dim3(OF_THREADS), lds_bytes, st,
-                     ix->codes.p, ix->ng, ix->m_pad, x.tables.p, d_off, d_ex, x.bk.p, x.br.p, nb, from, until,
-                     ix->row_base, from / 64, ceil_div(until, 64), s.rb_per_chunk, s.nchunks, x.part.p);
-  HIP_CHECK(hipGetLastError());
-}
-
-template <int VEC>
-void launch_flat_v(const gulon_index *ix, RankWork &x, const float *d_off, const int *d_ex, const int *d_goff,
-                   const int *d_grows, int nb, int from, int until, int E, const FlatShape &s, hipStream_t st) {
-  hipLaunchKernelGGL(rank_flat_gold<VEC>, dim3(ceil_div(nb, 4)), dim3(256), 0, st, ix->codes.p, ix->ng, ix->m_pad,
-                     x.tables.p, d_off, d_ex, nb, from, until, ix->row_base, d_goff, d_grows, x.bk.p, x.br.p);
-  HIP_CHECK(hipGetLastError());
-  switch (E) {
-    case 8: launch_flat_ev<8, VEC>(ix, x, d_off, d_ex, nb, from, until, s, st); break;
-    case 4: launch_flat_ev<4, VEC>(ix, x, d_off, d_ex, nb, from, until, s, st); break;
-    case 2: launch_flat_ev<2, VEC>(ix, x, d_off, d_ex, nb, from, until, s, st); break;
-    default: launch_flat_ev<1, VEC>(ix, x, d_off, d_ex, nb, from, until, s, st); break;
-  }
-}
-
 }  // namespace
 
 int check_rank_host(const float *offsets, int rows, const int *exclude, const int *gold_offsets, const int *gold_rows,
                     int b, int id_base) {
   GULON_REQUIRE(b >= 0, "batch size must be non-negative");
-  if (offsets)
-    for (int r = 0; r < rows; r++)
-      GULON_REQUIRE(offsets[r] == offsets[r] && offsets[r] != -INFINITY,
-                    "row_offsets[%d] = %g: NaN and -inf are not offsets", r, (double)offsets[r]);
-  if (exclude)
-    for (int q = 0; q < b; q++)
-      GULON_REQUIRE(exclude[q] == -1 || (exclude[q] >= id_base && exclude[q] - id_base < rows),
-                    "exclude[%d] = %d: expected -1 or a row in [%d, %d)", q, exclude[q], id_base, id_base + rows);
+  check_rows_host(offsets, true, rows, exclude, b, id_base);
   GULON_REQUIRE(gold_offsets != nullptr, "gold_offsets is null");
   GULON_REQUIRE(gold_offsets[0] == 0, "gold_offsets[0] = %d: expected 0", gold_offsets[0]);
   for (int q = 0; q < b; q++)
@@ -351,6 +290,7 @@ int check_rank_host(const float *offsets, int rows, const int *exclude, const in
   return gold;
 }
 
+// (the passes, their query tiles and row chunks: exact_passes in exact.hpp, by knn_row_chunks())
 void launch_rank_exact(const gulon_dataset *ds, int from, int until, RankWork &x, const float *d_q, int b,
                        const float *d_offsets, const int *d_exclude, const int *d_gold_off, const int *d_gold_rows,
                        int gold, int *out_rank, int *out_row, float *out_key, int *out_total, hipStream_t st) {
@@ -358,54 +298,50 @@ void launch_rank_exact(const gulon_dataset *ds, int from, int until, RankWork &x
   if (b == 0) return;
   GULON_REQUIRE(d_q != nullptr && d_gold_off != nullptr && out_rank != nullptr && out_row != nullptr &&
                 out_key != nullptr, "null argument");
-  const int d = ds->d;
   x.gk.ensure((size_t)std::max(gold, 1));
-  for (int q0 = 0; q0 < b; q0 += EXACT_SUB_BATCH) {
-    const int nb = std::min(EXACT_SUB_BATCH, b - q0), ntiles = ceil_div(nb, KNN_QT), bp = ntiles * KNN_QT;
-    const RowChunks ch = knn_row_chunks(from, until, ntiles);
-    const int nchunks = ch.nchunks, rows_per_chunk = ch.groups_per_chunk * KNN_THREADS;
-    x.qt.ensure((size_t)ntiles * d * KNN_QT);
-    x.bk.ensure((size_t)bp); x.br.ensure((size_t)bp);
-    x.part.ensure((size_t)bp * nchunks * 2);
-    const int *ex = d_exclude ? d_exclude + q0 : nullptr;
-    const long long tq = (long long)ntiles * d * KNN_QT;
-    hipLaunchKernelGGL(transpose_queries, dim3(ceil_div(tq, 256)), dim3(256), 0, st, d_q + (size_t)q0 * d, nb, d, ntiles,
-                       x.qt.p);
-    hipLaunchKernelGGL(rank_exact_gold, dim3(ntiles), dim3(KNN_THREADS), 0, st, ds->x.p, ds->n, d, x.qt.p, d_offsets, ex,
-                       nb, from, until, d_gold_off + q0, d_gold_rows, x.gk.p, x.bk.p, x.br.p);
-    hipLaunchKernelGGL(rank_exact_scan, dim3(ntiles, nchunks), dim3(KNN_THREADS), 0, st, ds->x.p, ds->n, d, x.qt.p,
-                       d_offsets, ex, x.bk.p, x.br.p, nb, from, until, rows_per_chunk, nchunks, x.part.p);
+  exact_passes(d_q, b, ds->d, from, until, x.qt, st, [&](const ExactPass &p) {
+    const size_t bp = (size_t)p.tiles * KNN_QT;
+    x.bk.ensure(bp); x.br.ensure(bp);
+    x.part.ensure(bp * p.nchunks * 2);
+    const int *ex = d_exclude ? d_exclude + p.q0 : nullptr;
+    hipLaunchKernelGGL(rank_exact_gold, dim3(p.tiles), dim3(KNN_THREADS), 0, st, ds->x.p, ds->n, ds->d, x.qt.p,
+                       d_offsets, ex, p.nb, from, until, d_gold_off + p.q0, d_gold_rows, x.gk.p, x.bk.p, x.br.p);
+    hipLaunchKernelGGL(rank_exact_scan, dim3(p.tiles, p.nchunks), dim3(KNN_THREADS), 0, st, ds->x.p, ds->n, ds->d,
+                       x.qt.p, d_offsets, ex, x.bk.p, x.br.p, p.nb, from, until, p.rows_per_chunk, p.nchunks, x.part.p);
     HIP_CHECK(hipGetLastError());
-    launch_finish(x, nchunks, nb, out_rank + q0, out_row + q0, out_key + q0, out_total ? out_total + q0 : nullptr, st);
-  }
+    launch_finish(x, p.nchunks, p.nb, out_rank + p.q0, out_row + p.q0, out_key + p.q0,
+                  out_total ? out_total + p.q0 : nullptr, st);
+  });
 }
 
+// The passes by flat_passes (offset.hpp): the slots by offset_flat_max_e(), the grid by offset_flat_shape(), the tables by
+// launch_build_tables(), under the handle's mutex and one StreamOrder.
 void launch_rank_flat(gulon_index *ix, RankWork &x, const float *d_q, int b, int from, int until, const float *d_off,
                       const int *d_ex, const int *d_goff, const int *d_grows, int *out_rank, int *out_row,
                       float *out_key, int *out_total, hipStream_t st) {
   if (b == 0) return;
   GULON_REQUIRE(d_q != nullptr && d_goff != nullptr && out_rank != nullptr && out_row != nullptr && out_key != nullptr,
                 "null argument");
-  const int tab = ix->m_pad * 256;
-  int E = offset_flat_max_e(ix);
-  while (E > 1 && E / 2 >= b) E /= 2;   // no more slots than a small batch fills
-  const int sub = offset_flat_shape(ix, from, until, b, E).per_pass;
-  std::lock_guard<std::mutex> lock(ix->mu);
-  ix->pend_b = -1;
-  StreamOrder so(ix, st);
-  for (int q0 = 0; q0 < b; q0 += sub) {
-    const int nb = std::min(sub, b - q0);
-    const FlatShape s = offset_flat_shape(ix, from, until, nb, E);
-    x.tables.ensure((size_t)nb * tab);
+  flat_passes(ix, x.tables, d_q, b, from, until, st, [&](int q0, int nb, int E, const FlatShape &s) {
     x.bk.ensure((size_t)nb); x.br.ensure((size_t)nb);
     x.part.ensure((size_t)nb * s.nchunks * 2);
-    launch_build_tables(1, ix, d_q + (size_t)q0 * ix->d, nb, nb, x.tables.p, st);
     const int *ex = d_ex ? d_ex + q0 : nullptr;
-    if (ix->vec == 4) launch_flat_v<4>(ix, x, d_off, ex, d_goff + q0, d_grows, nb, from, until, E, s, st);
-    else launch_flat_v<16>(ix, x, d_off, ex, d_goff + q0, d_grows, nb, from, until, E, s, st);
+    dispatch_e_vec(E, ix->vec, [&](auto e, auto vec) {
+      hipLaunchKernelGGL(rank_flat_gold<decltype(vec)::value>, dim3(ceil_div(nb, 4)), dim3(256), 0, st, ix->codes.p,
+                         ix->ng, ix->m_pad, x.tables.p, d_off, ex, nb, from, until, ix->row_base, d_goff + q0, d_grows,
+                         x.bk.p, x.br.p);
+      HIP_CHECK(hipGetLastError());
+      const auto scan = rank_flat_scan<decltype(e)::value, decltype(vec)::value>;
+      const size_t lds_bytes = (size_t)e * flat_slot_bytes(ix->m_pad);
+      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(scan), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)lds_bytes));
+      hipLaunchKernelGGL(scan, dim3(ceil_div(nb, e), s.nchunks), dim3(TABLE_SCAN_THREADS), lds_bytes, st, ix->codes.p,
+                         ix->ng, ix->m_pad, x.tables.p, d_off, ex, x.bk.p, x.br.p, nb, from, until, ix->row_base, from / 64,
+                         ceil_div(until, 64), s.rb_per_chunk, s.nchunks, x.part.p);
+      HIP_CHECK(hipGetLastError());
+    });
     launch_finish(x, s.nchunks, nb, out_rank + q0, out_row + q0, out_key + q0, out_total ? out_total + q0 : nullptr, st);
-  }
-  so.done();
+  });
 }
 
 }  // namespace gulon

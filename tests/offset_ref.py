@@ -39,8 +39,8 @@ def draw_offsets(seed, n, twins=(), inf_share=0.1, keep=None, levels=LEVELS):
 SIGNED_LEVELS = np.concatenate([np.array([-1.5, -0.75, -0.125, -0.0], np.float32), LEVELS])
 HUGE = np.float32(3e38)                      # a finite offset that a finite distance of 1e38 or more overflows
 
-LDS_BUDGET = 144 * 1024                      # COSMUL_LDS_BUDGET (cosmul.hpp)
-FLAT_TABLE_BYTES = 256 << 20                 # the tables of one pass (offset.hip)
+LDS_BUDGET = 144 * 1024                      # TABLE_LDS_BUDGET (table_scan.hpp)
+FLAT_TABLE_BYTES = 256 << 20                 # the tables of one pass (table_scan.hpp)
 
 
 def ceil_div(a, b):

@@ -7,7 +7,7 @@ Shapes: 4 300 rows, the range [70, n - 33) -- neither end on a 64-row code block
 centroids at (m, d) = (16, 32), (25, 50) and (64, 64): one 16-byte code word, seven 4-byte words and four 16-byte words,
 with eight, four and two query slots to a workgroup; batches of 19 (a last workgroup with idle slots) and 1 (one slot).
 Twenty rows are copies of others with the same offset; a tenth of the offsets are +inf; every other query excludes the row
-it was made from."""
+it was made from.  The launcher's second pass has a case of its own: 4 100 queries at m = 64 on 327 rows."""
 import numpy as np
 import pytest
 
@@ -121,6 +121,51 @@ def test_a_used_handle_answers_the_same(g):
     w["vi"].batch_query_offset_raw(10, w["Q"][:3], w["offsets"])
     rank_ref.same(ask(w, gold), first)
     rank_ref.same(first, rank_ref.reference(g, w, w["offsets"], gold))
+
+
+def test_more_queries_than_one_pass_holds(g):
+    """The rank twin of test_gpu_offset_paths.test_flat_more_queries_than_one_pass_holds, on its index: 327 rows, the
+    range [5, n - 3), m = 64 -- 256 MiB of tables are 4 096 queries, so 4 100 take two passes and the second reads its
+    gold lists, excluded rows and outputs from query 4 096 on.  The queries are 41 noisy copies of rows, repeated: the
+    second pass holds copies 37 .. 40 where the first begins with 0 .. 3.  Every one of those four has a planted rank of 1
+    or more, two of them exclude a row, and the reference itself answers each of them differently once it is given the
+    gold lists, or the excluded rows, of queries 0 .. 3 instead."""
+    n, base = 64 * 5 + 7, 41
+    frm, until = 5, n - 3
+    assert flat_chunks(frm, until, 4100, 64)[0] == 4096
+    X = unit_rows(7 * 64 + n, n, 64)
+    dm = g.DeviceMatrix.from_host(X)
+    try:
+        pq = g.ProductQuantizer.apply(dm, g.ProductQuantizerConfig(K, 64, ITERS))
+        enc = pq.encode(dm)
+    finally:
+        dm.close()
+    vi = g.PQIndex(pq, enc)
+    try:
+        Q, exclude = noisy_queries(64 + base, X, base, frm, until)
+        ids = np.arange(frm, until)
+        w = {"dist": distances_by_row(vi.batch_query_raw(len(ids), Q, frm, until), ids), "ids": ids, "exclude": exclude}
+        offsets = draw_offsets(301, n)
+        offsets[exclude[exclude >= 0]] = 0.0                     # an excluded row would be a candidate otherwise
+        order = rank_ref.full_order(g, w, offsets)
+        kinds = ("three", "at1", "at64", "at-1")
+        planted = {kind: rank_ref.plant(kind, order, w, offsets, None, None) for kind in kinds}
+        gold = [planted[kinds[q % 4]][q] for q in range(base)]
+        want = rank_ref.reference(g, w, offsets, gold)
+        rank_ref.same(vi.batch_query_rank_raw(Q, gold, offsets, exclude, frm, until), want)      # one pass
+
+        pick = np.arange(4100) % base
+        head, tail = pick[:4], pick[4096:]
+        assert (want[0][tail] >= 1).all() and (exclude[tail] >= 0).sum() == 2
+        there = dict(w, dist=w["dist"][tail], exclude=exclude[tail])
+        other_gold = rank_ref.reference(g, there, offsets, [gold[q] for q in head])
+        other_rows = rank_ref.reference(g, dict(there, exclude=exclude[head]), offsets, [gold[q] for q in tail])
+        assert (other_gold[1] != want[1][tail]).all() and (other_rows[3] != want[3][tail]).all()
+
+        got = vi.batch_query_rank_raw(Q[pick], [gold[q] for q in pick], offsets, exclude[pick], frm, until)
+        rank_ref.same(got, tuple(a[pick] for a in want))
+    finally:
+        vi.close()
 
 
 def test_wide_index_view_and_tables_past_the_lds_budget_are_refused(g):
