@@ -80,6 +80,91 @@ def same(got, want):
         assert np.array_equal(a, c), (name, np.flatnonzero(a != c)[:8], a[a != c][:8], c[a != c][:8])
 
 
+def unranked(want, q):
+    """Does the reference give query q no best gold row?"""
+    rank, row, key, _ = want
+    return bool(rank[q] == -1 and row[q] == -1 and np.isposinf(key[q]))
+
+
+# ---- what test_gpu_rank_paths.py adds: gold lists of up to 300 rows, and the exact launcher's row chunks --------------
+
+LONG_LENGTHS = (0, 1, 2, 63, 64, 65, 129, 300)   # per query in turn: a wave's 64 lanes from both sides, 3 and 5 trips
+SLOTS = ("last", 64, 130, 63, "first")           # where the best row sits in its list, clipped to the list's last index
+
+
+def slot_index(slot, length):
+    return min({"first": 0, "last": length - 1}.get(slot, slot), length - 1)
+
+
+def plant_long(order, w, offsets, outside, positions, lengths=LONG_LENGTHS, turn=0, twin=None, seed=0):
+    """Per query a gold list of lengths[q % len(lengths)] rows whose best row is the one at a chosen position p of the
+    query's full order: p = positions[(q + turn) % len(positions)] (negative: from the end), or with `twin` = (row, copy)
+    the position of `row`.  The best row sits at SLOTS[...] of its list -- the lists of 65 rows and more and the shorter
+    ones take the SLOTS in turn, each kind from `turn` on -- and the other entries are the query's excluded row,
+    `outside`, three rows masked by +inf and rows drawn from those strictly behind position p (masked rows again where
+    there are too few), shuffled, with one repeat of the best row somewhere behind it where the list has room.  With
+    `twin` the copy -- an equal key, the higher id -- is the list's first entry and the best row comes after it.
+    -> (gold: b lists, at [b]: the index of the best row in its list, -1 for an empty list, expect: per query
+    (p, row), None for an empty list)."""
+    ids = w["ids"]
+    masked = ids[np.isposinf(offsets[ids])]
+    rng = np.random.default_rng(seed)
+    gold, at, expect = [], [], []
+    seen = {True: 0, False: 0}
+    for q, o in enumerate(order):
+        length = lengths[q % len(lengths)]
+        if twin is None:
+            p = positions[(q + turn) % len(positions)]
+            p = p if p >= 0 else len(o) + p
+        else:
+            p = o.tolist().index(twin[0])
+        assert 0 <= p < len(o), (p, len(o))
+        if length == 0:
+            gold.append([]), at.append(-1), expect.append(None)
+            continue
+        i = slot_index(SLOTS[(seen[length >= 65] + turn) % len(SLOTS)], length)
+        seen[length >= 65] += 1
+        best = int(o[p])
+        others = [int(twin[1])] if twin is not None and length >= 2 else []
+        i = max(i, len(others))
+        rest = ([int(w["exclude"][q])] if w["exclude"][q] >= 0 else []) + ([] if outside is None else [int(outside)])
+        rest += [int(masked[(q + j) % len(masked)]) for j in range(3)]
+        behind = o[p + 1:]
+        want = max(0, length - 1 - len(others) - len(rest))
+        rest += rng.choice(behind, min(want, len(behind)), replace=False).tolist()
+        rest += [int(masked[(q + j) % len(masked)]) for j in range(length)]      # where too few rows are behind
+        rest = rest[:length - 1 - len(others)]
+        others += [rest[j] for j in rng.permutation(len(rest))]
+        mine = others[:i] + [best] + others[i:]
+        if length >= 3 and i < length - 1:
+            mine[int(rng.integers(i + 1, length))] = best                        # a repeat of the best row, behind it
+        assert len(mine) == length and mine[i] == best and best not in mine[:i]
+        gold.append(mine), at.append(i), expect.append((p, best))
+    return gold, np.array(at), expect
+
+
+def shows_long(want, order, expect):
+    """The reference ranks every query's best row at its chosen position, and no query with an empty list."""
+    rank, row, key, total = want
+    for q, e in enumerate(expect):
+        if total[q] != len(order[q]):
+            return False
+        if e is None:
+            if not unranked(want, q):
+                return False
+        elif not (rank[q] == e[0] and row[q] == e[1] == order[q][e[0]] and np.isfinite(key[q])):
+            return False
+    return True
+
+
+def knn_row_chunks(frm, until, tiles):
+    """exact.hpp's knn_row_chunks restated: the 256-row groups that cover [frm, until), frm rounded down to a group, in
+    chunks for about 2048 workgroups over `tiles` query tiles of 16.  -> (row chunks, groups per chunk)."""
+    groups = max(1, -(-(until - frm // 256 * 256) // 256))
+    per = -(-groups // min(max(-(-2048 // tiles), 1), groups))
+    return -(-groups // per), per
+
+
 def agrees_with_the_offset_query(got, lists):
     """Every rank below 63 is the position of the row in the offset query's answer at 63; -> how many were checked."""
     rank, row = got[0], got[1]
