@@ -202,8 +202,8 @@ void launch_exact_ep(const gulon_dataset *ds, CosmulWork &x, const int *d_off, c
 // merge -> drop -> negate: the tail of both forms, for the b questions whose chunk lists are in x.pv / x.pi
 void finish_lists(CosmulWork &x, int nchunks, int keff, int b, int kin, int k_nn, const int *d_off, const int *d_rows,
                   int row_base, int *out_idx, float *out_score, int *out_count, hipStream_t st) {
-  launch_merge(true, x.pv.p, x.pi.p, nchunks, (long long)keff, (long long)nchunks * keff, b, kin, x.oi.p, x.od.p, x.oc.p,
-               nullptr, nullptr, nullptr, st);
+  launch_merge(x.pv.p, x.pi.p, nchunks, (long long)keff, (long long)nchunks * keff, b, kin,
+               QueryOut::final_lists(x.oi.p, x.od.p, x.oc.p, nullptr), st);
   launch_drop(x.oi.p, x.od.p, x.oc.p, b, kin, k_nn, d_off, d_rows, row_base, out_idx, out_score, out_count, st);
   const long long bk = (long long)b * k_nn;
   if (bk > 0) {

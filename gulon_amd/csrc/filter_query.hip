@@ -146,8 +146,8 @@ struct FilterBatch {
   int NW, srows;
   int fb_tiles, pfb, cfb_n;         // the fallback scan: tiles, row blocks per chunk, chunks
 
-  FilterBatch(gulon_index *ix_, const float *dQ_, int B_, int keff_, int from_, int until_, hipStream_t st_)
-      : ix(ix_), t(tuning_of(ix_)), dQ(dQ_), B(B_), keff(keff_), from(from_), until(until_), st(st_) {}
+  explicit FilterBatch(const FlatCall &c)
+      : ix(c.ix), t(tuning_of(c.ix)), dQ(c.dQ), B(c.B), keff(c.K + 1), from(c.from), until(c.until), st(c.st) {}
   void plan(const SharedBounds *sb);
   void filter_workspace(bool fallback_too);
   void sample_bounds(float *bounds_out);
@@ -342,24 +342,22 @@ void FilterBatch::print_fallback_stats() const {
 
 }  // namespace
 
-void run_filter_query(gulon_index *ix, const float *dQ, int B, int K, int from, int until, bool final_out, int *d_oi,
-                      float *d_od, int *d_oc, int *d_of, float *d_pv, int *d_pi, hipStream_t st,
-                      const SharedBounds *sb) {
+void run_filter_query(const FlatCall &c) {
+  gulon_index *ix = c.ix;
+  const SharedBounds *sb = c.sb;
   const int phase = sb ? sb->phase : 0;
-  const int keff = K + 1;
-  FilterBatch fb(ix, dQ, B, keff, from, until, st);
+  FilterBatch fb(c);
   fb.plan(sb);
   fb.filter_workspace(true);
   ix->last_filter_tiles = fb.ntiles;
   if (phase != 2) fb.sample_bounds(phase == 1 ? sb->bounds_out : nullptr);
   if (phase == 1) return;     // the caller exchanges the bounds and comes back with phase 2
-  if (phase == 2) launch_shared_tau(ix, sb->all_bounds, sb->lists, B, keff, st);
+  if (phase == 2) launch_shared_tau(ix, sb->all_bounds, sb->lists, c.B, fb.keff, c.st);
   const bool stats = getenv("GULON_FILTER_STATS") != nullptr;
   for (int sidx = 0; sidx < 3; sidx++) fb.stage(sidx, stats);
   fb.fallback_scan();
   if (stats) fb.print_fallback_stats();
-  finish_flat_query(ix, dQ, B, K, from, until, final_out, ix->fin_v.p, ix->fin_i.p, 1, 0LL, (long long)keff, d_oi, d_od,
-                    d_oc, d_of, d_pv, d_pi, st);
+  finish_query(c, ix->fin_v.p, ix->fin_i.p, 1, 0LL, (long long)fb.keff, true);
 }
 
 bool replay_level2_filtered(gulon_index *ix, int F, int K, int rb_lo, int rb_hi, int from, int until,
@@ -450,7 +448,7 @@ GULON_API int32_t gulon_selftest_filter_stage(const uint8_t *codes, int32_t n, i
       build_filter_copy(ix);
     }
     hipStream_t st = nullptr;
-    FilterBatch fb(ix, nullptr, b, 11, from, until, st);
+    FilterBatch fb(FlatCall{ix, nullptr, b, 10, from, until, QueryOut{}, st, nullptr});   // lists of keff = 11
     fb.plan(nullptr);
     GULON_REQUIRE(fb.fs.nadd == nadd, "internal: nadd");
     GULON_REQUIRE(fb.sorted == (copy == 2), "internal: copy");

@@ -988,8 +988,8 @@ void preselect(const GroupedCall &c, const CoarseResult &co, bool by_group) {
     hipLaunchKernelGGL(kern, dim3(B), dim3(64 * GA_WAVES), lds_ga, st, ix->codes.p, ix->ng, ix->m_pad, ix->d, gx->ptab.p,
                        gx->xnorm.p, gx->gcent.p, gx->bounds.p, c.dQ, gx->nn.p, nn_stride, gx->nn_cnt.p, gx->apv.p, gx->api.p,
                        gx->anan.p);
-    launch_merge(false, gx->apv.p, gx->api.p, GA_WAVES, (long long)GA_C, (long long)GA_WAVES * GA_C, B, GA_C - 1, nullptr,
-                 nullptr, nullptr, nullptr, gx->amv.p, gx->ami.p, st);
+    launch_merge(gx->apv.p, gx->api.p, GA_WAVES, (long long)GA_C, (long long)GA_WAVES * GA_C, B, GA_C - 1,
+                 QueryOut::partial_lists(gx->amv.p, gx->ami.p), st);
   }
 }
 

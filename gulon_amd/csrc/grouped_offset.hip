@@ -165,8 +165,8 @@ void launch_grouped_offset(const GroupedOffsetPass &p, GroupedOffsetWork &x, int
                      ix->ng, ix->m, ix->m_pad, ix->k, ix->d, ix->cents.p, ix->from.p, ix->sdim.p, p.gcent, p.bounds, p.d_q,
                      p.nn, p.nn_stride, p.nn_cnt, p.stride, d_offsets, d_exclude, keff, x.pv.p, x.pi.p);
   HIP_CHECK(hipGetLastError());
-  launch_merge(true, x.pv.p, x.pi.p, p.stride, (long long)keff, (long long)p.stride * keff, p.nb, k_nn, out_idx, out_key,
-               out_count, nullptr, nullptr, nullptr, st);
+  launch_merge(x.pv.p, x.pi.p, p.stride, (long long)keff, (long long)p.stride * keff, p.nb, k_nn,
+               QueryOut::final_lists(out_idx, out_key, out_count, nullptr), st);
 }
 
 }  // namespace gulon

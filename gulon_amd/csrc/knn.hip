@@ -94,8 +94,8 @@ void exact_knn_dev(const gulon_dataset *ds, int from, int until, const float *d_
       hipLaunchKernelGGL(knn_kernel, dim3(ntiles, nchunks), dim3(KNN_THREADS), 0, st, ds->x.p, ds->n, d, s.qt.p, from,
                          until, rows_per_chunk, nchunks, 64, s.pv.p, s.pi.p, s.lbv.p, s.lbi.p);
       HIP_CHECK(hipGetLastError());
-      launch_merge(false, s.pv.p, s.pi.p, nchunks, 64LL, (long long)nchunks * 64, b, 63, nullptr, nullptr, nullptr,
-                   nullptr, s.tv.p, s.ti.p, st);
+      launch_merge(s.pv.p, s.pi.p, nchunks, 64LL, (long long)nchunks * 64, b, 63,
+                   QueryOut::partial_lists(s.tv.p, s.ti.p), st);
       launch_peel_update(s.tv.p, s.ti.p, b, r, cap, s.accv.p, s.acci.p, s.lbv.p, s.lbi.p, st);
     }
     launch_peel_finalize(s.accv.p, s.acci.p, b, cap, K, oi, od, oc, of, st);
@@ -104,8 +104,8 @@ void exact_knn_dev(const gulon_dataset *ds, int from, int until, const float *d_
                        until, rows_per_chunk, nchunks, keff, s.pv.p, s.pi.p, (const float *)nullptr,
                        (const int *)nullptr);
     HIP_CHECK(hipGetLastError());
-    launch_merge(true, s.pv.p, s.pi.p, nchunks, (long long)keff, (long long)nchunks * keff, b, K, oi, od, oc, of,
-                 nullptr, nullptr, st);
+    launch_merge(s.pv.p, s.pi.p, nchunks, (long long)keff, (long long)nchunks * keff, b, K,
+                 QueryOut::final_lists(oi, od, oc, of), st);
   }
 }
 

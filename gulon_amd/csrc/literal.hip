@@ -178,8 +178,13 @@ float centroid_absmax(const float *d_cents, long long count) {
   return f;
 }
 
-void run_nonfinite_literal(gulon_index *ix, const float *dQ, int B, int K, int from, int until, int *d_oi, float *d_od,
-                           int *d_oc, int *d_of, hipStream_t st) {
+void run_nonfinite_literal(const FlatCall &c, int *flags) {
+  gulon_index *ix = c.ix;
+  const float *dQ = c.dQ;
+  const int B = c.B, K = c.K, from = c.from, until = c.until;
+  int *d_oi = c.out.idx, *d_oc = c.out.count, *d_of = flags;
+  float *d_od = c.out.dist;
+  const hipStream_t st = c.st;
   if (B <= 0 || K <= 0 || K > GULON_MAX_K || ix->wide) return;
   const int grid = std::min(B, 1024);
   ix->nf_tables.ensure((size_t)grid * ix->m_pad * 256);

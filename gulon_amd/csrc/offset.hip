@@ -149,9 +149,8 @@ void launch_offset_flat(gulon_index *ix, OffsetWork &x, const float *d_q, int b,
                          from / 64, ceil_div(until, 64), s.rb_per_chunk, s.nchunks, keff, x.pv.p, x.pi.p);
       HIP_CHECK(hipGetLastError());
     });
-    launch_merge(true, x.pv.p, x.pi.p, s.nchunks, (long long)keff, (long long)s.nchunks * keff, nb, k_nn,
-                 out_idx + (size_t)q0 * k_nn, out_key + (size_t)q0 * k_nn, out_count ? out_count + q0 : nullptr, nullptr,
-                 nullptr, nullptr, st);
+    launch_merge(x.pv.p, x.pi.p, s.nchunks, (long long)keff, (long long)s.nchunks * keff, nb, k_nn,
+                 QueryOut::final_lists(out_idx, out_key, out_count, nullptr).from_query(q0, k_nn), st);
   });
 }
 
@@ -217,9 +216,8 @@ void launch_offset_exact(const gulon_dataset *ds, int from, int until, OffsetWor
                        x.qt.p, d_offsets, d_exclude ? d_exclude + p.q0 : nullptr, p.nb, from, until, p.rows_per_chunk,
                        p.nchunks, keff, x.pv.p, x.pi.p);
     HIP_CHECK(hipGetLastError());
-    launch_merge(true, x.pv.p, x.pi.p, p.nchunks, (long long)keff, (long long)p.nchunks * keff, p.nb, k_nn,
-                 out_idx + (size_t)p.q0 * k_nn, out_key + (size_t)p.q0 * k_nn, out_count ? out_count + p.q0 : nullptr,
-                 nullptr, nullptr, nullptr, st);
+    launch_merge(x.pv.p, x.pi.p, p.nchunks, (long long)keff, (long long)p.nchunks * keff, p.nb, k_nn,
+                 QueryOut::final_lists(out_idx, out_key, out_count, nullptr).from_query(p.q0, k_nn), st);
   });
 }
 

@@ -711,8 +711,13 @@ void replay_apply(const int *packs, int lists, long long stride_words, int F, in
   }
 }
 
-void run_tie_replay(gulon_index *ix, const float *dQ, int B, int K, int from, int until, int *d_oi, float *d_od,
-                    int *d_oc, int *d_of, hipStream_t st) {
+void run_tie_replay(const FlatCall &c, int *flags) {
+  gulon_index *ix = c.ix;
+  const float *dQ = c.dQ;
+  const int B = c.B, K = c.K, from = c.from, until = c.until;
+  int *d_oi = c.out.idx, *d_oc = c.out.count, *d_of = flags;
+  float *d_od = c.out.dist;
+  hipStream_t st = c.st;
   if (B <= 0 || K <= 0 || until <= from) return;
   // wide codes: a flagged query's table is m * k floats in HBM -- at most 256 MiB of them per round, and as many
   // rounds as the batch could need (the flagged-query count stays on the device: later rounds find nothing to do)

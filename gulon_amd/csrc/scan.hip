@@ -1,63 +1,16 @@
 // ADC scan path: Index.prepareQuery -> PQIndex.distances -> TopKHeap -> Result.fromHeap
 // (Index.scala:352-440, TopKHeap.scala, Index.scala:83-94), re-designed for gfx950.
 //
+// The table build, the scan kernels, the driver of a flat query (run_query) and the query entry points; the handle
+// itself is index_handle.hip, the merge of the scan's partial lists merge.hip.
+//
 // Kernels
-//   relayout_codes   [m][n] u8 (EncodedMatrix SoA) -> [n/64][ng][64][VEC] row-blocked
 //   build_tables     per-query m x 256 distance tables, 4 queries interleaved (float4)
 //   scan_kernel      tables in LDS (ds_read_b128 = 4 queries per lookup), codes streamed
 //                    coalesced, j-ordered fp32 sums, wavefront-register top-k
-//   merge_lists      per-query merge of partial lists (chunks, or GPUs)
 #include "scan.hpp"
 
 namespace gulon {
-
-// ---------------------------------------------------------------------------
-// code re-layout
-// ---------------------------------------------------------------------------
-template <int VEC>
-__global__ void relayout_codes(const uint8_t *__restrict__ src /*[m][n]*/, int n, int m, int ng,
-                               uint8_t *__restrict__ dst, long long total /* nblk*ng*64 */) {
-  long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  int lane = (int)(t & 63);
-  long long bg = t >> 6;
-  int g = (int)(bg % ng);
-  long long rb = bg / ng;
-  long long row = rb * 64 + lane;
-  uint8_t out[VEC];
-#pragma unroll
-  for (int b = 0; b < VEC; b++) {
-    int j = g * VEC + b;
-    out[b] = (row < n && j < m) ? src[(size_t)j * n + row] : (uint8_t)0;
-  }
-  uint8_t *o = dst + (size_t)t * VEC;
-#pragma unroll
-  for (int b = 0; b < VEC; b++) o[b] = out[b];
-}
-
-// unpack 2/4-bit and 10/12/16-bit Coder layouts to one index per row
-// (Coder.scala:110-111,125-126,138-139,163-167)
-__global__ void unpack_codes(const uint8_t *__restrict__ packed, int width, int n, int bytes_per_code,
-                             int m, uint16_t *__restrict__ out /*[m][n]*/) {
-  long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (long long)m * n) return;
-  int j = (int)(t / n);
-  int i = (int)(t % n);
-  const uint8_t *code = packed + (size_t)j * bytes_per_code;
-  int lw = width > 8 ? width - 8 : width;
-  int off = width > 8 ? n : 0;
-  int lo;
-  if (lw == 2) lo = (code[off + (i >> 2)] >> ((i & 3) * 2)) & 0x3;
-  else if (lw == 4) lo = (code[off + (i >> 1)] >> ((i & 1) * 4)) & 0xF;
-  else lo = code[off + i];
-  int v = width > 8 ? ((code[i] << lw) | lo) : lo;
-  out[t] = (uint16_t)v;
-}
-
-__global__ void narrow_codes(const uint16_t *__restrict__ in, long long total, uint8_t *__restrict__ out) {
-  long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < total) out[t] = (uint8_t)in[t];
-}
 
 // ---------------------------------------------------------------------------
 // Index.prepareQuery (Index.scala:352-383): T[q][j][c] = sum_t (q[from_j+t]-c[t])^2,
@@ -372,238 +325,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(7))) vo
 #undef GULON_SCAN_PARAMS
 #undef GULON_SCAN_ARGS
 
-// ---------------------------------------------------------------------------
-// merge `lists` sorted partial lists per query; one wave per query.
-// in: element (l, q, e) at  l*stride_l + q*stride_q + e.
-// FINAL: write idx/dist/count/flags [B][K]; else write a (K+1)-list [B][keff].
-// ---------------------------------------------------------------------------
-template <bool FINAL>
-__global__ __launch_bounds__(64) void merge_lists(const float *__restrict__ in_v, const int *__restrict__ in_i,
-                                                  int lists, long long stride_l, long long stride_q,
-                                                  int B, int K, int keff, int *__restrict__ out_idx,
-                                                  float *__restrict__ out_dist, int *__restrict__ out_count,
-                                                  int *__restrict__ out_flags, float *__restrict__ out_pv,
-                                                  int *__restrict__ out_pi, const int *__restrict__ tile_enable,
-                                                  int qt) {
-  const int q = blockIdx.x;
-  const int lane = threadIdx.x;
-  if (q >= B) return;
-  if (tile_enable && tile_enable[q / qt] == 0) return;
-  WaveList wl;
-  wl.init();
-  const int total = lists * keff;
-  for (int base = 0; base < total; base += 64) {
-    int e = base + lane;
-    float cv = INFINITY;
-    int cr = INT_MAX;
-    if (e < total) {
-      int l = e / keff, x = e - l * keff;
-      size_t o = (size_t)l * stride_l + (size_t)q * stride_q + x;
-      cv = in_v[o];
-      cr = in_i[o];
-    }
-    unsigned long long mk = __ballot(cr != INT_MAX && wl.accepts(cv, cr));
-    while (mk) {
-      int l = __ffsll((long long)mk) - 1;
-      mk &= mk - 1;
-      float v = readlane_f(cv, l);
-      int r = readlane_i(cr, l);
-      if (wl.accepts(v, r)) wl.insert(v, r, keff, lane);
-    }
-  }
-  if (FINAL) {
-    int live = __popcll(__ballot(lane < K && wl.i != INT_MAX));
-    if (lane < K) {
-      bool ok = wl.i != INT_MAX;
-      out_idx[(size_t)q * K + lane] = ok ? wl.i : -1;
-      out_dist[(size_t)q * K + lane] = ok ? wl.v : INFINITY;
-    }
-    float nv = __shfl_down(wl.v, 1);
-    int ni = __shfl_down(wl.i, 1);
-    bool tie = wl.i != INT_MAX && ni != INT_MAX && wl.v == nv && lane + 1 < keff;
-    unsigned long long tm = __ballot(tie);
-    if (lane == 0) {
-      if (out_count) out_count[q] = live;
-      if (out_flags) {
-        int f = 0;
-        if (K >= 1 && ((tm >> (K - 1)) & 1ull)) f |= GULON_FLAG_BOUNDARY_TIE;
-        if (K >= 2 && (tm & ((1ull << (K - 1)) - 1ull))) f |= GULON_FLAG_INTERIOR_TIE;
-        out_flags[q] = f;
-      }
-    }
-  } else {
-    if (lane < keff) {
-      out_pv[(size_t)q * keff + lane] = wl.v;
-      out_pi[(size_t)q * keff + lane] = wl.i;
-    }
-  }
-}
-
-
-void launch_merge(bool final_out, const float *in_v, const int *in_i, int lists, long long stride_l,
-                  long long stride_q, int B, int K, int *out_idx, float *out_dist, int *out_count,
-                  int *out_flags, float *out_pv, int *out_pi, hipStream_t st) {
-  if (B <= 0) return;
-  int keff = K + 1;
-  if (final_out)
-    hipLaunchKernelGGL(merge_lists<true>, dim3(B), dim3(64), 0, st, in_v, in_i, lists, stride_l, stride_q, B, K,
-                       keff, out_idx, out_dist, out_count, out_flags, out_pv, out_pi, (const int *)nullptr, 1);
-  else
-    hipLaunchKernelGGL(merge_lists<false>, dim3(B), dim3(64), 0, st, in_v, in_i, lists, stride_l, stride_q, B, K,
-                       keff, out_idx, out_dist, out_count, out_flags, out_pv, out_pi, (const int *)nullptr, 1);
-  HIP_CHECK(hipGetLastError());
-}
-
-void launch_merge_enabled(const float *in_v, const int *in_i, int lists, long long stride_l, long long stride_q, int B,
-                          int K, float *out_pv, int *out_pi, const int *tile_enable, int qt, hipStream_t st) {
-  if (B <= 0) return;
-  hipLaunchKernelGGL(merge_lists<false>, dim3(B), dim3(64), 0, st, in_v, in_i, lists, stride_l, stride_q, B, K, K + 1,
-                     (int *)nullptr, (float *)nullptr, (int *)nullptr, (int *)nullptr, out_pv, out_pi, tile_enable, qt);
-  HIP_CHECK(hipGetLastError());
-}
-
-// ---- large K: peel the result 64 entries at a time (each round = one scan restricted to the
-// ---- entries after the previous round's last one) -------------------------------------
-__global__ __launch_bounds__(64) void peel_update(const float *__restrict__ tv, const int *__restrict__ ti, int round,
-                                                  int cap, float *__restrict__ pv, int *__restrict__ pi,
-                                                  float *__restrict__ lbv, int *__restrict__ lbi) {
-  const int q = blockIdx.x, lane = threadIdx.x;
-  const float v = tv[(size_t)q * 64 + lane];
-  const int i = ti[(size_t)q * 64 + lane];
-  pv[(size_t)q * cap + round * 64 + lane] = v;
-  pi[(size_t)q * cap + round * 64 + lane] = i;
-  if (lane == 63) {
-    if (i != INT_MAX) { lbv[q] = v; lbi[q] = i; }
-    else { lbv[q] = INFINITY; lbi[q] = INT_MAX; }   // list exhausted: nothing is eligible any more
-  }
-}
-
-__global__ void peel_finalize(const float *__restrict__ pv, const int *__restrict__ pi, int B, int cap, int K,
-                              int *__restrict__ out_idx, float *__restrict__ out_dist, int *__restrict__ out_count,
-                              int *__restrict__ out_flags) {
-  const int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= B) return;
-  const float *v = pv + (size_t)q * cap;
-  const int *id = pi + (size_t)q * cap;
-  int live = 0, flags = 0;
-  for (int e = 0; e < K; e++) {
-    const bool ok = id[e] != INT_MAX;
-    out_idx[(size_t)q * K + e] = ok ? id[e] : -1;
-    out_dist[(size_t)q * K + e] = ok ? v[e] : INFINITY;
-    live += ok ? 1 : 0;
-    if (ok && e + 1 < cap && id[e + 1] != INT_MAX && v[e] == v[e + 1])
-      flags |= (e == K - 1) ? GULON_FLAG_BOUNDARY_TIE : GULON_FLAG_INTERIOR_TIE;
-  }
-  if (out_count) out_count[q] = live;
-  if (out_flags) out_flags[q] = flags;
-}
-
-// the peeled list as a partial (K+1)-list for the multi-GPU merge: [B][cap] -> [B][K+1]
-__global__ void peel_export(const float *__restrict__ pv, const int *__restrict__ pi, int B, int cap, int keff,
-                            float *__restrict__ out_v, int *__restrict__ out_i) {
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (long long)B * keff) return;
-  const int q = (int)(t / keff), e = (int)(t - (long long)q * keff);
-  out_v[t] = pv[(size_t)q * cap + e];
-  out_i[t] = pi[(size_t)q * cap + e];
-}
-
-// Merge of two ascending (distance, row id) lists of `len` entries per query (padded with (+inf, INT_MAX)) into
-// the `len` smallest, ascending: every entry's position = its own index + its rank in the other list (row ids
-// are distinct across lists, so the order is strict).  b == nullptr: a copies through.
-__global__ __launch_bounds__(256) void merge2_long(const float *__restrict__ av, const int *__restrict__ ai,
-                                                   const float *__restrict__ bv, const int *__restrict__ bi, int len,
-                                                   float *__restrict__ ov, int *__restrict__ oi) {
-  const int q = blockIdx.x;
-  const float *A = av + (size_t)q * len, *Bv = bv ? bv + (size_t)q * len : nullptr;
-  const int *Ai = ai + (size_t)q * len, *Bi = bi ? bi + (size_t)q * len : nullptr;
-  float *O = ov + (size_t)q * len;
-  int *Oi = oi + (size_t)q * len;
-  auto less = [](float v0, int i0, float v1, int i1) { return v0 < v1 || (v0 == v1 && i0 < i1); };
-  for (int e = threadIdx.x; e < len; e += blockDim.x) {
-    if (!Bv) { O[e] = A[e]; Oi[e] = Ai[e]; continue; }
-    {   // A[e]: entries of B before it
-      const float v = A[e]; const int id = Ai[e];
-      int lo = 0, hi = len;
-      while (lo < hi) { const int mid = (lo + hi) >> 1; if (less(Bv[mid], Bi[mid], v, id)) lo = mid + 1; else hi = mid; }
-      const int pos = e + lo;
-      if (pos < len && id != INT_MAX) { O[pos] = v; Oi[pos] = id; }
-    }
-    {   // B[e]: entries of A before it
-      const float v = Bv[e]; const int id = Bi[e];
-      int lo = 0, hi = len;
-      while (lo < hi) { const int mid = (lo + hi) >> 1; if (less(A[mid], Ai[mid], v, id)) lo = mid + 1; else hi = mid; }
-      const int pos = e + lo;
-      if (pos < len && id != INT_MAX) { O[pos] = v; Oi[pos] = id; }
-    }
-  }
-}
-__global__ void fill_list(float *__restrict__ v, int *__restrict__ i, long long n) {
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < n) { v[t] = INFINITY; i[t] = INT_MAX; }
-}
-
-// `lists` partial (K+1)-lists per query (element (l, q, e) at l*stride_l + q*keff + e) -> final [B][K] + count + flags,
-// for K beyond the 63 a wavefront list holds: a tree of pairwise merges through device scratch
-void launch_merge_long(const float *in_v, const int *in_i, int lists, long long stride_l, int B, int K, int *out_idx,
-                       float *out_dist, int *out_count, int *out_flags, hipStream_t st) {
-  const int keff = K + 1;
-  const size_t per = (size_t)B * keff;
-  int width = lists;                       // lists alive in the current round
-  DevBuf<float> va, vb;
-  DevBuf<int> ia, ib;
-  const size_t half = (size_t)((lists + 1) / 2);
-  va.alloc(std::max<size_t>(half * per, 1)); ia.alloc(std::max<size_t>(half * per, 1));
-  vb.alloc(std::max<size_t>(((half + 1) / 2) * per, 1)); ib.alloc(std::max<size_t>(((half + 1) / 2) * per, 1));
-  const float *cv = in_v;
-  const int *ci = in_i;
-  long long cs = stride_l;
-  bool to_a = true;
-  if (width == 1) {   // a single list: straight to the finaliser
-    launch_peel_finalize(cv, ci, B, keff, K, out_idx, out_dist, out_count, out_flags, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-    return;
-  }
-  while (width > 1) {
-    const int next = (width + 1) / 2;
-    float *ov = to_a ? va.p : vb.p;
-    int *oi = to_a ? ia.p : ib.p;
-    hipLaunchKernelGGL(fill_list, dim3((unsigned)ceil_div((long long)next * per, 256LL)), dim3(256), 0, st, ov, oi,
-                       (long long)next * per);
-    for (int p = 0; p < next; p++) {
-      const bool pair = 2 * p + 1 < width;
-      hipLaunchKernelGGL(merge2_long, dim3(B), dim3(256), 0, st, cv + (size_t)(2 * p) * cs, ci + (size_t)(2 * p) * cs,
-                         pair ? cv + (size_t)(2 * p + 1) * cs : nullptr, pair ? ci + (size_t)(2 * p + 1) * cs : nullptr, keff,
-                         ov + (size_t)p * per, oi + (size_t)p * per);
-    }
-    HIP_CHECK(hipGetLastError());
-    cv = ov; ci = oi; cs = (long long)per;
-    width = next;
-    to_a = !to_a;
-  }
-  launch_peel_finalize(cv, ci, B, keff, K, out_idx, out_dist, out_count, out_flags, st);
-  HIP_CHECK(hipStreamSynchronize(st));   // the scratch lists above go out of scope
-}
-
-void launch_peel_update(const float *tv, const int *ti, int B, int round, int cap, float *pv, int *pi, float *lbv,
-                        int *lbi, hipStream_t st) {
-  hipLaunchKernelGGL(peel_update, dim3(B), dim3(64), 0, st, tv, ti, round, cap, pv, pi, lbv, lbi);
-  HIP_CHECK(hipGetLastError());
-}
-void launch_peel_finalize(const float *pv, const int *pi, int B, int cap, int K, int *out_idx, float *out_dist,
-                          int *out_count, int *out_flags, hipStream_t st) {
-  hipLaunchKernelGGL(peel_finalize, dim3(ceil_div(B, 64)), dim3(64), 0, st, pv, pi, B, cap, K, out_idx, out_dist,
-                     out_count, out_flags);
-  HIP_CHECK(hipGetLastError());
-}
-
-void launch_peel_export(const float *pv, const int *pi, int B, int cap, int keff, float *out_v, int *out_i,
-                        hipStream_t st) {
-  hipLaunchKernelGGL(peel_export, dim3((unsigned)ceil_div((long long)B * keff, 256LL)), dim3(256), 0, st, pv, pi, B, cap,
-                     keff, out_v, out_i);
-  HIP_CHECK(hipGetLastError());
-}
-
 void launch_build_tables(int W, gulon_index *ix, const float *dQ, int B, int Bpad, float *tables, hipStream_t st,
                          const int *live_queries, float *mins) {
   long long total = (long long)(Bpad / W) * ix->m_pad * 256;
@@ -616,74 +337,40 @@ void launch_build_tables(int W, gulon_index *ix, const float *dQ, int B, int Bpa
   HIP_CHECK(hipGetLastError());
 }
 
-ScanTuning::ScanTuning() {
-  static const char *keys[] = {"GULON_SCAN_BLOCKS", "GULON_SCAN_PRUNE", "GULON_SCAN_PRUNE_FROM", "GULON_SCAN_FILTER",
-                               "GULON_FILTER_MIN_RB", "GULON_FILTER_PERIOD", "GULON_FILTER_STAGE1", "GULON_FILTER_CAP",
-                               "GULON_FILTER_NADD", "GULON_FILTER_SAMPLE", "GULON_FILTER_STAGE0", "GULON_FILTER_BLOCKS",
-                               "GULON_FILTER_SHARED_STAGE1", "GULON_FILTER_ORDER", "GULON_FILTER_SORT",
-                               "GULON_FILTER_PREFIX"};
-  for (const char *k : keys)
-    if (const char *e = getenv(k)) set(k, atoi(e));
-}
-
-bool ScanTuning::set(const char *key, int v) {
-  std::string k(key);
-  if (k == "GULON_SCAN_BLOCKS") { if (v >= 1) target_blocks = v; }
-  else if (k == "GULON_SCAN_PRUNE") prune = v != 0;
-  else if (k == "GULON_SCAN_PRUNE_FROM") prune_from = v;
-  else if (k == "GULON_SCAN_FILTER") filter = v != 0;
-  else if (k == "GULON_FILTER_MIN_RB") filter_min_rb = v < 4 ? 4 : v;
-  else if (k == "GULON_FILTER_PERIOD") { if (v >= 3) filter_period = v; }
-  else if (k == "GULON_FILTER_STAGE1") { if (v >= 1) filter_stage1 = v; }
-  else if (k == "GULON_FILTER_CAP") { if (v >= 64) filter_cap = v; }
-  else if (k == "GULON_FILTER_NADD") { if (v == 0 || v == 2 || v == 4) filter_nadd = v; }
-  else if (k == "GULON_FILTER_SAMPLE") { if (v >= 1) filter_sample = v; }
-  else if (k == "GULON_FILTER_STAGE0") { if (v >= 0) filter_stage0 = v; }
-  else if (k == "GULON_FILTER_BLOCKS") { if (v >= 1) filter_blocks = v; }
-  else if (k == "GULON_FILTER_SHARED_STAGE1") { if (v >= -1 && v <= 1) filter_shared_stage1 = v; }
-  else if (k == "GULON_FILTER_ORDER") { if (v >= 0 && v <= 8) filter_order = v; }
-  else if (k == "GULON_FILTER_SORT") filter_sort = v != 0;
-  else if (k == "GULON_FILTER_PREFIX") { if (v == 0 || v == FILTER_PREFIX_P) filter_prefix = v; }
-  else return false;
-  return true;
-}
-
-// The knobs have no process-wide mutable state: a handle takes its settings from the ENVIRONMENT when it is created
-// (ScanTuning's constructor) and keeps them; gulon_index_tuning changes one handle.  (A null handle: the compiled-in defaults.)
-const ScanTuning &tuning_defaults() { static const ScanTuning t; return t; }
-
 bool replay_enabled() {
   static const bool on = [] { const char *e = getenv("GULON_TIE_REPLAY"); return !(e && atoi(e) == 0); }();
   return on;
 }
 
-int *tie_flags(gulon_index *ix, bool final_out, int *d_of, int B) {
-  if (!(final_out && replay_enabled() && d_of == nullptr)) return d_of;
-  ix->flags_scratch.ensure((size_t)B);
-  return ix->flags_scratch.p;
+QueryOut merge_outputs(const FlatCall &c) {
+  QueryOut out = c.out;
+  if (out.final_out() && replay_enabled() && out.flags == nullptr) {
+    c.ix->flags_scratch.ensure((size_t)c.B);
+    out.flags = c.ix->flags_scratch.p;
+  }
+  return out;
 }
 
-void finish_flat_query(gulon_index *ix, const float *dQ, int B, int K, int from, int until, bool final_out,
-                       const float *in_v, const int *in_i, int lists, long long stride_l, long long stride_q, int *d_oi,
-                       float *d_od, int *d_oc, int *d_of, float *d_pv, int *d_pi, hipStream_t st) {
-  int *flags = tie_flags(ix, final_out, d_of, B);
-  launch_merge(final_out, in_v, in_i, lists, stride_l, stride_q, B, K, d_oi, d_od, d_oc, flags, d_pv, d_pi, st);
+void finish_replay(const FlatCall &c, int *flags, bool literal_pass) {
+  if (!(c.out.final_out() && replay_enabled())) return;
   // queries with exact distance ties: replay the reference heap's insertion history
-  if (final_out && replay_enabled()) run_tie_replay(ix, dQ, B, K, from, until, d_oi, d_od, d_oc, flags, st);
+  run_tie_replay(c, flags);
   // queries whose distances can be NaN / +inf: the literal heap over all rows (TopKHeap.scala:69-79)
-  if (final_out && replay_enabled()) run_nonfinite_literal(ix, dQ, B, K, from, until, d_oi, d_od, d_oc, d_of, st);
+  if (literal_pass) run_nonfinite_literal(c, c.out.flags);
+}
+
+void finish_query(const FlatCall &c, const float *in_v, const int *in_i, int lists, long long stride_l,
+                  long long stride_q, bool literal_pass) {
+  const QueryOut out = merge_outputs(c);
+  launch_merge(in_v, in_i, lists, stride_l, stride_q, c.B, c.K, out, c.st);
+  finish_replay(c, out.flags, literal_pass);
 }
 
 }  // namespace gulon
 
 using namespace gulon;
 
-// ---------------------------------------------------------------------------
-// index handle
-// ---------------------------------------------------------------------------
 namespace {
-
-constexpr size_t LDS_BUDGET = 144 * 1024;
 
 template <int W, int NSUB, int VEC, int SCAN_THREADS, bool PRUNE>
 void launch_scan_p(gulon_index *ix, int ntiles, int nchunks, int rb_begin, int e_count, int e_per_chunk, RbMap mp,
@@ -772,335 +459,125 @@ void launch_scan(gulon_index *ix, int ntiles, int nchunks, int rb_begin, int e_c
 
 namespace {
 
-// Enqueue table build + scan + merge.  Exactly one of (final outputs) / (partial outputs) is used.
 __global__ void fill_f32(float *__restrict__ p, long long n, float v) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = v;
 }
+void launch_fill_f32(float *p, long long n, float v, hipStream_t st) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(fill_f32, dim3((unsigned)ceil_div(n, 256LL)), dim3(256), 0, st, p, n, v);
+  HIP_CHECK(hipGetLastError());
+}
 
-void run_query(gulon_index *ix, const float *dQ, int B, int K, int from, int until, bool final_out, int *d_oi,
-               float *d_od, int *d_oc, int *d_of, float *d_pv, int *d_pi, hipStream_t st,
-               const SharedBounds *sb = nullptr) {
-  GULON_REQUIRE(from <= until, "expected: from <= until");                               // Index.scala:418
-  GULON_REQUIRE(from >= 0 && until <= ix->n, "expected: from >= 0 && until <= length");  // Index.scala:419
-  GULON_REQUIRE(K >= 0 && B >= 0, "k and batch size must be non-negative");
-  GULON_UNSUPPORTED(K > GULON_MAX_K_PEELED, "k_nn = %d > %d is not supported", K, GULON_MAX_K_PEELED);
-  GULON_UNSUPPORTED(K + 1 > GULON_MAX_K_PEELED && !final_out, "k_nn = %d: a shard returns k_nn + 1 <= %d entries", K,
-                    GULON_MAX_K_PEELED);
-  if (B == 0) return;
-  if (!sb || sb->phase != 2) ix->last_filter_tiles = 0;
-  if (sb && sb->phase == 1) {
-    // first half of a query with shared bounds: ranges the filter does not take have no bounds to offer
-    const int rbt = ceil_div(until, 64) - from / 64;
-    if (!(K >= 1 && rbt > 0 && filter_eligible(ix, K, rbt))) {
-      const long long nb = (long long)B * (K + 1);
-      hipLaunchKernelGGL(fill_f32, dim3((unsigned)ceil_div(nb, 256LL)), dim3(256), 0, st, sb->bounds_out, nb, INFINITY);
-      HIP_CHECK(hipGetLastError());
-      return;
-    }
-  }
-  const bool peeled = K > GULON_MAX_K;            // results come 64 at a time
-  const int keff = peeled ? 64 : K + 1;
-  const int W = ix->w;
-  const int QT = W * ix->nsub;
-  const int ntiles = ceil_div(B, QT);
-  const int rb_begin = from / 64;
-  const int rb_end = ceil_div(until, 64);
-  const int rb_total = rb_end - rb_begin;
-  if (K == 0 || rb_total <= 0) {
-    // empty heaps: nothing to scan
-    if (final_out) {
-      if (K > 0) {
-        HIP_CHECK(hipMemsetAsync(d_oi, 0xFF, sizeof(int) * (size_t)B * K, st));
-        std::vector<float> inf((size_t)B * K, INFINITY);
-        HIP_CHECK(hipMemcpyAsync(d_od, inf.data(), sizeof(float) * inf.size(), hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-      }
-      if (d_oc) HIP_CHECK(hipMemsetAsync(d_oc, 0, sizeof(int) * (size_t)B, st));
-      if (d_of) HIP_CHECK(hipMemsetAsync(d_of, 0, sizeof(int) * (size_t)B, st));
-    } else {
-      const int kout = K + 1;   // (peeled queries: keff is the 64-entry round, the partial list K+1 long)
-      std::vector<float> inf((size_t)B * kout, INFINITY);
-      std::vector<int> mx((size_t)B * kout, INT_MAX);
-      HIP_CHECK(hipMemcpyAsync(d_pv, inf.data(), sizeof(float) * inf.size(), hipMemcpyHostToDevice, st));
-      HIP_CHECK(hipMemcpyAsync(d_pi, mx.data(), sizeof(int) * mx.size(), hipMemcpyHostToDevice, st));
-      HIP_CHECK(hipStreamSynchronize(st));
-    }
-    return;
-  }
-  // chunking: ~4096 workgroups, at least 2 row blocks per wave
-  const int NW = tuning_of(ix).threads / 64;
-  int want = ceil_div(tuning_of(ix).target_blocks, ntiles);
-  int max_chunks = rb_total / (2 * NW);
-  if (max_chunks < 1) max_chunks = 1;
-  int nchunks = want < max_chunks ? want : max_chunks;
-  if (nchunks < 1) nchunks = 1;
-  int rb_per_chunk = ceil_div(rb_total, nchunks);
-  nchunks = ceil_div(rb_total, rb_per_chunk);
+// ---- run_query: table build + scan + merge of one batch, in the order of its checks ----
 
-  if (ix->wide) {
-    run_wide_query(ix, dQ, B, K, from, until, final_out, d_oi, d_od, d_oc, d_of, d_pv, d_pi, st);
-    return;
-  }
-  // the empty-range partial list of a large-K query is [B][K+1], not [B][64]
-  const int Bp = ntiles * QT;
-  const RbMap all{1, 0, 1};
-  if (!peeled && filter_eligible(ix, K, rb_total)) {
-    run_filter_query(ix, dQ, B, K, from, until, final_out, d_oi, d_od, d_oc, d_of, d_pv, d_pi, st, sb);
-    return;
-  }
-  if (peeled) {
-    launch_build_tables(W, ix, dQ, B, Bp, (ix->tables.ensure((size_t)Bp * ix->m_pad * 256), ix->tables.p), st);
-    const int rounds = ceil_div(K + 1, 64), cap = rounds * 64;
-    ix->part_v.ensure((size_t)Bp * nchunks * 64);
-    ix->part_i.ensure((size_t)Bp * nchunks * 64);
-    ix->gtau.ensure((size_t)Bp);
-    ix->peel_v.ensure((size_t)B * cap); ix->peel_i.ensure((size_t)B * cap);
-    ix->peel_tv.ensure((size_t)B * 64); ix->peel_ti.ensure((size_t)B * 64);
-    ix->peel_lbv.ensure((size_t)Bp); ix->peel_lbi.ensure((size_t)Bp);
-    HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)ix->peel_lbv.p, 0xBF800000 /* -1.0f */, (size_t)Bp, st));
-    HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)ix->peel_lbi.p, 0xFFFFFFFF /* -1 */, (size_t)Bp, st));
-    for (int r = 0; r < rounds; r++) {
-      HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)ix->gtau.p, 0x7F800000 /* +inf */, (size_t)Bp, st));
-      launch_scan(ix, ntiles, nchunks, rb_begin, rb_total, rb_per_chunk, all, from, until, 64, st, ix->peel_lbv.p,
-                  ix->peel_lbi.p);
-      launch_merge(false, ix->part_v.p, ix->part_i.p, nchunks, 64LL, (long long)nchunks * 64, B, 63, nullptr, nullptr,
-                   nullptr, nullptr, ix->peel_tv.p, ix->peel_ti.p, st);
-      hipLaunchKernelGGL(peel_update, dim3(B), dim3(64), 0, st, ix->peel_tv.p, ix->peel_ti.p, r, cap, ix->peel_v.p,
-                         ix->peel_i.p, ix->peel_lbv.p, ix->peel_lbi.p);
-    }
-    if (final_out)
-      hipLaunchKernelGGL(peel_finalize, dim3(ceil_div(B, 64)), dim3(64), 0, st, ix->peel_v.p, ix->peel_i.p, B, cap, K,
-                         d_oi, d_od, d_oc, d_of);
-    else   // a shard of a large-K query: its K+1 smallest as a partial list (merged by gulon_topk_merge_dev)
-      hipLaunchKernelGGL(peel_export, dim3((unsigned)ceil_div((long long)B * (K + 1), 256LL)), dim3(256), 0, st,
-                         ix->peel_v.p, ix->peel_i.p, B, cap, K + 1, d_pv, d_pi);
-    HIP_CHECK(hipGetLastError());
-    return;
-  }
-  ix->tables.ensure((size_t)Bp * ix->m_pad * 256);
-  ix->part_v.ensure((size_t)Bp * nchunks * keff);
-  ix->part_i.ensure((size_t)Bp * nchunks * keff);
-  ix->gtau.ensure((size_t)Bp);
-  HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)ix->gtau.p, 0x7F800000 /* +inf */, (size_t)Bp, st));
+void validate(const FlatCall &c) {
+  GULON_REQUIRE(c.from <= c.until, "expected: from <= until");                                  // Index.scala:418
+  GULON_REQUIRE(c.from >= 0 && c.until <= c.ix->n, "expected: from >= 0 && until <= length");   // Index.scala:419
+  GULON_REQUIRE(c.K >= 0 && c.B >= 0, "k and batch size must be non-negative");
+  GULON_UNSUPPORTED(c.K > GULON_MAX_K_PEELED, "k_nn = %d > %d is not supported", c.K, GULON_MAX_K_PEELED);
+  GULON_UNSUPPORTED(c.K + 1 > GULON_MAX_K_PEELED && !c.out.final_out(), "k_nn = %d: a shard returns k_nn + 1 <= %d entries",
+                    c.K, GULON_MAX_K_PEELED);
+}
 
-  launch_build_tables(W, ix, dQ, B, Bp, ix->tables.p, st);
+int row_blocks(const FlatCall &c) { return ceil_div(c.until, 64) - c.from / 64; }
+
+// first half of a query with shared bounds: ranges the filter does not take have no bounds to offer (+inf).  Returns
+// whether that was the whole call.
+bool bounds_only_unfiltered(const FlatCall &c) {
+  if (!(c.sb && c.sb->phase == 1)) return false;
+  const int rbt = row_blocks(c);
+  if (c.K >= 1 && rbt > 0 && filter_eligible(c.ix, c.K, rbt)) return false;
+  launch_fill_f32(c.sb->bounds_out, (long long)c.B * (c.K + 1), INFINITY, c.st);
+  return true;
+}
+
+// empty heaps (no neighbours asked for, or no row block in the range): nothing to scan.  Final lists of (-1, +inf) with
+// zero counts and flags; partial lists of K + 1 entries of (+inf, INT_MAX), also where a peeled round would be 64 long.
+// Every output is written where the caller gave one, on the call's stream.
+bool empty_result(const FlatCall &c) {
+  if (!(c.K == 0 || row_blocks(c) <= 0)) return false;
+  const QueryOut &o = c.out;
+  if (o.idx && c.K > 0) {
+    HIP_CHECK(hipMemsetAsync(o.idx, 0xFF, sizeof(int) * (size_t)c.B * c.K, c.st));
+    launch_fill_f32(o.dist, (long long)c.B * c.K, INFINITY, c.st);
+  }
+  if (o.count) HIP_CHECK(hipMemsetAsync(o.count, 0, sizeof(int) * (size_t)c.B, c.st));
+  if (o.flags) HIP_CHECK(hipMemsetAsync(o.flags, 0, sizeof(int) * (size_t)c.B, c.st));
+  if (o.part_v) launch_fill_list(o.part_v, o.part_i, (long long)c.B * (c.K + 1), c.st);
+  return true;
+}
+
+// what the byte-coded scans share: the padded batch, and the chunks of a launch of ~target_blocks workgroups
+struct ScanShape {
+  int W, QT, ntiles, Bp, rb_begin, rb_total, nchunks, rb_per_chunk;
+  explicit ScanShape(const FlatCall &c)
+      : W(c.ix->w), QT(W * c.ix->nsub), ntiles(ceil_div(c.B, QT)), Bp(ntiles * QT), rb_begin(c.from / 64),
+        rb_total(row_blocks(c)) {
+    const ScanTuning &t = tuning_of(c.ix);
+    scan_chunks(rb_total, ceil_div(t.target_blocks, ntiles), t.threads / 64, nchunks, rb_per_chunk);
+  }
+};
+const RbMap ALL_BLOCKS{1, 0, 1};
+
+// K > GULON_MAX_K: the result comes 64 entries per scan round (PeelRounds, merge.hip); no tie replay
+void run_peeled_query(const FlatCall &c) {
+  gulon_index *ix = c.ix;
+  const ScanShape s(c);
+  launch_build_tables(s.W, ix, c.dQ, c.B, s.Bp, (ix->tables.ensure((size_t)s.Bp * ix->m_pad * 256), ix->tables.p), c.st);
+  ix->part_v.ensure((size_t)s.Bp * s.nchunks * 64);
+  ix->part_i.ensure((size_t)s.Bp * s.nchunks * 64);
+  ix->gtau.ensure((size_t)s.Bp);
+  PeelRounds peel(ix, c.B, s.Bp, c.B, c.K, c.st);
+  for (int r = 0; r < peel.rounds; r++) {
+    HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)ix->gtau.p, 0x7F800000 /* +inf */, (size_t)s.Bp, c.st));
+    launch_scan(ix, s.ntiles, s.nchunks, s.rb_begin, s.rb_total, s.rb_per_chunk, ALL_BLOCKS, c.from, c.until, 64, c.st,
+                peel.bounds(0).v, peel.bounds(0).i);
+    peel.append(r, 0, c.B, s.nchunks);
+  }
+  peel.finish(c.out);
+}
+
+void run_plain_query(const FlatCall &c) {
+  gulon_index *ix = c.ix;
+  const ScanShape s(c);
+  const int keff = c.K + 1;
+  ix->tables.ensure((size_t)s.Bp * ix->m_pad * 256);
+  ix->part_v.ensure((size_t)s.Bp * s.nchunks * keff);
+  ix->part_i.ensure((size_t)s.Bp * s.nchunks * keff);
+  ix->gtau.ensure((size_t)s.Bp);
+  HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)ix->gtau.p, 0x7F800000 /* +inf */, (size_t)s.Bp, c.st));
+
+  launch_build_tables(s.W, ix, c.dQ, c.B, s.Bp, ix->tables.p, c.st);
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (ix->profile) {
     e0 = ix->take_event();
     e1 = ix->take_event();
-    HIP_CHECK(hipEventRecord(e0, st));
+    HIP_CHECK(hipEventRecord(e0, c.st));
   }
-  launch_scan(ix, ntiles, nchunks, rb_begin, rb_total, rb_per_chunk, all, from, until, keff, st);
+  launch_scan(ix, s.ntiles, s.nchunks, s.rb_begin, s.rb_total, s.rb_per_chunk, ALL_BLOCKS, c.from, c.until, keff, c.st);
   if (ix->profile) {
-    HIP_CHECK(hipEventRecord(e1, st));
+    HIP_CHECK(hipEventRecord(e1, c.st));
     ix->events.emplace_back(e0, e1);
-    ix->prof_rows += until - from;
+    ix->prof_rows += c.until - c.from;
   }
-  finish_flat_query(ix, dQ, B, K, from, until, final_out, ix->part_v.p, ix->part_i.p, nchunks, (long long)keff,
-                    (long long)nchunks * keff, d_oi, d_od, d_oc, d_of, d_pv, d_pi, st);
+  finish_query(c, ix->part_v.p, ix->part_i.p, s.nchunks, (long long)keff, (long long)s.nchunks * keff, true);
+}
+
+void run_query(const FlatCall &c) {
+  validate(c);
+  if (c.B == 0) return;
+  if (!c.sb || c.sb->phase != 2) c.ix->last_filter_tiles = 0;
+  if (bounds_only_unfiltered(c)) return;
+  if (empty_result(c)) return;
+  const bool peeled = c.K > GULON_MAX_K;
+  if (c.ix->wide) run_wide_query(c);
+  else if (!peeled && filter_eligible(c.ix, c.K, row_blocks(c))) run_filter_query(c);
+  else if (peeled) run_peeled_query(c);
+  else run_plain_query(c);
 }
 
 }  // namespace
-
-GULON_API int32_t gulon_index_create(const uint8_t *codes, int32_t n, int32_t d, int32_t m, int32_t k,
-                                     const float *cents, int32_t row_base, gulon_index **out) {
-  return guarded([&] {
-    GULON_REQUIRE(out != nullptr, "out is null");
-    *out = nullptr;
-    GULON_REQUIRE(n >= 0 && d >= 1 && m >= 1 && m <= d && k >= 1, "bad index shape n=%d d=%d m=%d k=%d", n, d, m, k);
-    GULON_REQUIRE(cents != nullptr && (codes != nullptr || n == 0), "null input");
-    int width = -1;
-    GULON_REQUIRE(gulon_coder_width(k, &width) == GULON_OK && width >= 0, "too many clusters: %d", k);  // PQ.scala:12-15
-    std::unique_ptr<gulon_index> ix(new gulon_index());
-    ix->tune = std::make_shared<ScanTuning>();   // the environment as it is now
-    ix->n = n; ix->d = d; ix->m = m; ix->k = k; ix->row_base = row_base;
-    if (k > 256) {
-      // Coder.BytePlus widths 10/12/16 (Coder.scala:99-127): 16-bit codes, tables in HBM (wide.hip)
-      ix->wide = true;
-      std::vector<int> from, until, sdim(m);
-      subvectors(d, m, from, until);
-      for (int j = 0; j < m; j++) sdim[j] = until[j] - from[j];
-      ix->from.upload(from.data(), m);
-      ix->sdim.upload(sdim.data(), m);
-      ix->cents.upload(cents, (size_t)k * d);
-      int bytes_per_code = 0;
-      gulon_coder_bytes(width, n, &bytes_per_code);
-      DevBuf<uint16_t> wide16(std::max<size_t>((size_t)m * n, 1));
-      if (n > 0) {
-        DevBuf<uint8_t> packed;
-        packed.upload(codes, (size_t)m * bytes_per_code);
-        const long long tot = (long long)m * n;
-        hipLaunchKernelGGL(unpack_codes, dim3(ceil_div(tot, 256)), dim3(256), 0, 0, packed.p, width, n, bytes_per_code, m,
-                           wide16.p);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipDeviceSynchronize());
-      }
-      wide_store_codes(ix.get(), wide16.p);
-      ensure_row_err(ix.get());
-      *out = ix.release();
-      return;
-    }
-    ix->vec = (m % 16 == 0) ? 16 : 4;
-    ix->ng = ceil_div(m, ix->vec);
-    ix->m_pad = ix->ng * ix->vec;
-    // queries interleaved per table entry: as many as LDS holds (m = 64 -> 2, m > 72 -> 1)
-    ix->w = 4;
-    while (ix->w > 1 && (size_t)ix->m_pad * 256 * ix->w * 4 > LDS_BUDGET) ix->w /= 2;
-    size_t per_sub = (size_t)ix->m_pad * 256 * ix->w * 4;
-    GULON_UNSUPPORTED(per_sub > LDS_BUDGET, "m = %d quantizers need %zu B of LDS for one query's table (> %zu)", m,
-                      per_sub, LDS_BUDGET);
-    ix->nsub = ix->w < 4 ? 1 : (4 * per_sub <= LDS_BUDGET) ? 4 : (2 * per_sub <= LDS_BUDGET) ? 2 : 1;
-
-    std::vector<int> from, until, sdim(m);
-    subvectors(d, m, from, until);
-    for (int j = 0; j < m; j++) sdim[j] = until[j] - from[j];
-    ix->from.upload(from.data(), m);
-    ix->sdim.upload(sdim.data(), m);
-    ix->cents.upload(cents, (size_t)k * d);
-    ix->cents_absmax = centroid_absmax(ix->cents.p, (long long)k * d);
-
-    int bytes_per_code = 0;
-    gulon_coder_bytes(width, n, &bytes_per_code);
-    size_t nblk = (size_t)ceil_div(n, 64);
-    ix->codes.alloc(std::max<size_t>(nblk * ix->ng * 64 * ix->vec, 16));
-    if (n > 0) {
-      DevBuf<uint8_t> raw;  // [m][n] one byte per (quantizer,row)
-      if (width == 8) {
-        raw.upload(codes, (size_t)m * n);
-      } else {
-        raw.alloc((size_t)m * n);
-        if (width == 0) {
-          HIP_CHECK(hipMemset(raw.p, 0, (size_t)m * n));
-        } else {
-          DevBuf<uint8_t> packed;
-          packed.upload(codes, (size_t)m * bytes_per_code);
-          DevBuf<uint16_t> wide((size_t)m * n);
-          long long tot = (long long)m * n;
-          hipLaunchKernelGGL(unpack_codes, dim3(ceil_div(tot, 256)), dim3(256), 0, 0, packed.p, width, n,
-                             bytes_per_code, m, wide.p);
-          hipLaunchKernelGGL(narrow_codes, dim3(ceil_div(tot, 256)), dim3(256), 0, 0, wide.p, tot, raw.p);
-          HIP_CHECK(hipGetLastError());
-          HIP_CHECK(hipDeviceSynchronize());
-        }
-      }
-      long long total = (long long)nblk * ix->ng * 64;
-      if (ix->vec == 16)
-        hipLaunchKernelGGL(relayout_codes<16>, dim3(ceil_div(total, 256)), dim3(256), 0, 0, raw.p, n, m, ix->ng,
-                           ix->codes.p, total);
-      else
-        hipLaunchKernelGGL(relayout_codes<4>, dim3(ceil_div(total, 256)), dim3(256), 0, 0, raw.p, n, m, ix->ng,
-                           ix->codes.p, total);
-      HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipDeviceSynchronize());
-      build_filter_copy(ix.get());
-    }
-    HIP_CHECK(hipDeviceSynchronize());
-    ensure_row_err(ix.get());
-    *out = ix.release();
-  });
-}
-
-namespace gulon {
-// the filter's conflict-ordered copy (one 16-byte code word per row; ranges the filter is never used for
-// do not need one).  GULON_FILTER_ORDER = rounds of the ordering (0: no copy)
-void build_filter_copy(gulon_index *ix) {
-  const size_t nblk = (size_t)ceil_div(ix->n, 64);
-  const int rounds = ix->tune->filter_order;
-  if (rounds > 0 && ix->vec == 16 && ix->ng == 1 && (long long)nblk >= ix->tune->filter_min_rb) {
-    ix->fcodes.alloc(nblk * 1024);
-    ix->fperm.alloc(nblk * 64);
-    launch_conflict_order(ix->codes.p, ix->fcodes.p, ix->fperm.p, (long long)nblk, FILTER_LDS_QUANTIZERS, rounds, 0);
-    ix->fwindow = conflict_order_windowed() ? 4 : 1;
-    HIP_CHECK(hipDeviceSynchronize());
-  }
-  // the key-sorted copy (GULON_FILTER_SORT): 16 bytes of codes + a 32-bit row id per row
-  if (ix->tune->filter_sort > 0 && ix->vec == 16 && ix->ng == 1 && (long long)nblk >= ix->tune->filter_min_rb) {
-    const size_t nwin = (size_t)ceil_div(ix->n, 256);
-    ix->scodes.alloc(nwin * 4096);
-    ix->sids.alloc(nwin * 256);
-    launch_sorted_copy(ix->codes.p, ix->n, ix->scodes.p, ix->sids.p, std::max(1, rounds), 0);
-    HIP_CHECK(hipDeviceSynchronize());
-  }
-}
-
-gulon_index *make_context(gulon_index *parent) {
-  std::unique_ptr<gulon_index> c(new gulon_index());
-  c->n = parent->n; c->d = parent->d; c->m = parent->m; c->k = parent->k; c->row_base = parent->row_base;
-  c->vec = parent->vec; c->ng = parent->ng; c->m_pad = parent->m_pad; c->nsub = parent->nsub; c->w = parent->w;
-  c->wide = parent->wide;
-  c->cents_absmax = parent->cents_absmax;
-  c->tune = parent->tune;
-  c->codes.borrow(parent->codes);
-  c->fcodes.borrow(parent->fcodes);
-  c->fperm.borrow(parent->fperm);
-  c->fwindow = parent->fwindow;
-  c->scodes.borrow(parent->scodes);
-  c->sids.borrow(parent->sids);
-  c->wcodes.borrow(parent->wcodes);
-  c->cents.borrow(parent->cents);
-  c->from.borrow(parent->from);
-  c->sdim.borrow(parent->sdim);
-  c->is_view = parent->is_view;
-  c->view_base = parent->view_base;
-  c->vmap.borrow(parent->vmap);
-  ensure_row_err(c.get());
-  return c.release();
-}
-}  // namespace gulon
-
-namespace {
-void release_index(gulon_index *ix) {
-  if (!ix) return;
-  if (ix->refs.fetch_sub(1) != 1) return;       // contexts of this index are still alive
-  gulon_index *parent = ix->parent;
-  delete ix;
-  release_index(parent);
-}
-
-// host-pointer calls: take a free workspace of this handle (the handle itself first), creating up to
-// GULON_HOST_CONTEXTS (default 4) internal contexts; blocks while all are busy
-int host_context_limit() {
-  static const int lim = [] { const char *e = getenv("GULON_HOST_CONTEXTS"); int v = e ? atoi(e) : 4; return v < 1 ? 1 : v > 64 ? 64 : v; }();
-  return lim;
-}
-gulon_index *acquire_host_context(gulon_index *idx) {
-  std::unique_lock<std::mutex> lk(idx->host_mu);
-  for (;;) {
-    if (!idx->host_self_busy) { idx->host_self_busy = true; return idx; }
-    if (!idx->host_free.empty()) { gulon_index *c = idx->host_free.back(); idx->host_free.pop_back(); return c; }
-    if ((int)idx->host_all.size() + 1 < host_context_limit()) {
-      gulon_index *c = make_context(idx);
-      idx->host_all.push_back(c);
-      return c;
-    }
-    idx->host_cv.wait(lk);
-  }
-}
-void release_host_context(gulon_index *idx, gulon_index *c) {
-  {
-    std::lock_guard<std::mutex> lk(idx->host_mu);
-    if (c == idx) idx->host_self_busy = false; else idx->host_free.push_back(c);
-  }
-  idx->host_cv.notify_one();
-}
-}  // namespace
-
-GULON_API int32_t gulon_index_destroy(gulon_index *idx) {
-  return guarded([&] { release_index(idx); });
-}
-
-GULON_API int32_t gulon_index_context_create(gulon_index *parent, gulon_index **out) {
-  return guarded([&] {
-    GULON_REQUIRE(parent != nullptr && out != nullptr, "null argument");
-    *out = nullptr;
-    gulon_index *root = parent->parent ? parent->parent : parent;   // contexts of contexts hang off the owner
-    gulon_index *c = make_context(root);
-    c->parent = root;
-    root->refs.fetch_add(1);
-    *out = c;
-  });
-}
 
 namespace gulon {
 void batch_query_dev_on(gulon_index *idx, const float *d_queries, int32_t b, int32_t k_nn, int32_t from, int32_t until,
@@ -1109,8 +586,8 @@ void batch_query_dev_on(gulon_index *idx, const float *d_queries, int32_t b, int
   std::lock_guard<std::mutex> lock(idx->mu);
   idx->pend_b = -1;
   StreamOrder so(idx, st);
-  run_query(idx, d_queries, b, k_nn, from, until, true, d_out_idx, d_out_dist, d_out_count, d_out_flags, nullptr,
-            nullptr, st);
+  run_query({idx, d_queries, b, k_nn, from, until,
+             QueryOut::final_lists(d_out_idx, d_out_dist, d_out_count, d_out_flags), st, nullptr});
   if (map_view) launch_map_rows(idx, d_out_idx, (long long)b * k_nn, st);
   so.done();
 }
@@ -1134,8 +611,8 @@ GULON_API int32_t gulon_index_scan_partial_dev(gulon_index *idx, const float *d_
     std::lock_guard<std::mutex> lock(idx->mu);
     idx->pend_b = -1;
     StreamOrder so(idx, (hipStream_t)stream);
-    run_query(idx, d_queries, b, k_nn, from, until, false, nullptr, nullptr, nullptr, nullptr, d_part_dist,
-              d_part_idx, (hipStream_t)stream);
+    run_query({idx, d_queries, b, k_nn, from, until, QueryOut::partial_lists(d_part_dist, d_part_idx),
+               (hipStream_t)stream, nullptr});
     so.done();
   });
 }
@@ -1150,8 +627,7 @@ GULON_API int32_t gulon_index_scan_bounds_dev(gulon_index *idx, const float *d_q
     const SharedBounds sb{1, d_bounds, nullptr, 0};
     idx->pend_b = -1;
     StreamOrder so(idx, (hipStream_t)stream);
-    run_query(idx, d_queries, b, k_nn, from, until, false, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-              (hipStream_t)stream, &sb);
+    run_query({idx, d_queries, b, k_nn, from, until, QueryOut{}, (hipStream_t)stream, &sb});   // no outputs but sb's
     so.done();
     idx->pend_b = b; idx->pend_k = k_nn; idx->pend_from = from; idx->pend_until = until;
   });
@@ -1169,15 +645,17 @@ GULON_API int32_t gulon_index_scan_partial_bounded_dev(gulon_index *idx, const f
     idx->pend_b = -1;
     const SharedBounds sb{2, nullptr, d_all_bounds, lists};
     StreamOrder so(idx, (hipStream_t)stream);
-    run_query(idx, d_queries, b, k_nn, from, until, false, nullptr, nullptr, nullptr, nullptr, d_part_dist,
-              d_part_idx, (hipStream_t)stream, &sb);
+    run_query({idx, d_queries, b, k_nn, from, until, QueryOut::partial_lists(d_part_dist, d_part_idx),
+               (hipStream_t)stream, &sb});
     so.done();
   });
 }
 
-namespace gulon {
-void batch_query_host_on(gulon_index *idx, const float *queries, int32_t b, int32_t k_nn, int32_t from, int32_t until,
-                         int32_t *out_idx, float *out_dist, int32_t *out_count, int32_t *out_flags, bool map_view) {
+namespace {
+// A host-pointer query.  stage(c, st) puts the b queries into c->stage_q on the workspace's stream.
+template <class Stage>
+void host_query(gulon_index *idx, int32_t b, int32_t k_nn, int32_t from, int32_t until, int32_t *out_idx,
+                float *out_dist, int32_t *out_count, int32_t *out_flags, bool map_view, Stage stage) {
   GULON_REQUIRE(b >= 0 && k_nn >= 0, "k and batch size must be non-negative");
   // concurrent callers (Tests.scala:109-122 queries from a thread pool) each get a workspace of their own
   gulon_index *c = acquire_host_context(idx);
@@ -1193,9 +671,9 @@ void batch_query_host_on(gulon_index *idx, const float *queries, int32_t b, int3
   if (!c->host_stream) HIP_CHECK(hipStreamCreateWithFlags(&c->host_stream, hipStreamNonBlocking));
   hipStream_t st = c->host_stream;
   StreamOrder so(c, st);
-  if (b > 0) HIP_CHECK(hipMemcpyAsync(c->stage_q.p, queries, sizeof(float) * (size_t)b * c->d, hipMemcpyHostToDevice, st));
-  run_query(c, c->stage_q.p, b, k_nn, from, until, true, c->stage_oi.p, c->stage_od.p, c->stage_oc.p,
-            c->stage_of.p, nullptr, nullptr, st);
+  stage(c, st);
+  run_query({c, c->stage_q.p, b, k_nn, from, until,
+             QueryOut::final_lists(c->stage_oi.p, c->stage_od.p, c->stage_oc.p, c->stage_of.p), st, nullptr});
   if (map_view) launch_map_rows(c, c->stage_oi.p, (long long)bk, st);   // the context borrows the view's map
   if (bk) {
     c->stage_oi.download(out_idx, bk, st);
@@ -1206,6 +684,16 @@ void batch_query_host_on(gulon_index *idx, const float *queries, int32_t b, int3
   so.done();
   HIP_CHECK(hipStreamSynchronize(st));
 }
+}  // namespace
+
+namespace gulon {
+void batch_query_host_on(gulon_index *idx, const float *queries, int32_t b, int32_t k_nn, int32_t from, int32_t until,
+                         int32_t *out_idx, float *out_dist, int32_t *out_count, int32_t *out_flags, bool map_view) {
+  host_query(idx, b, k_nn, from, until, out_idx, out_dist, out_count, out_flags, map_view,
+             [&](gulon_index *c, hipStream_t st) {
+    if (b > 0) HIP_CHECK(hipMemcpyAsync(c->stage_q.p, queries, sizeof(float) * (size_t)b * c->d, hipMemcpyHostToDevice, st));
+  });
+}
 }  // namespace gulon
 
 GULON_API int32_t gulon_index_batch_query(gulon_index *idx, const float *queries, int32_t b, int32_t k_nn,
@@ -1214,114 +702,6 @@ GULON_API int32_t gulon_index_batch_query(gulon_index *idx, const float *queries
   return guarded([&] {
     GULON_REQUIRE(idx != nullptr, "index is null");
     batch_query_host_on(idx, queries, b, k_nn, from, until, out_idx, out_dist, out_count, out_flags, false);
-  });
-}
-
-GULON_API int32_t gulon_index_profile(gulon_index *idx, int32_t enable) {
-  return guarded([&] {
-    GULON_REQUIRE(idx != nullptr, "index is null");
-    std::lock_guard<std::mutex> lock(idx->mu);
-    idx->events.clear();
-    idx->ev_next = 0;
-    idx->prof_rows = 0;
-    idx->profile = enable != 0;
-    if (idx->profile)
-      while (idx->ev_pool.size() < 512) {
-        hipEvent_t e = nullptr;
-        HIP_CHECK(hipEventCreate(&e));
-        idx->ev_pool.push_back(e);
-      }
-  });
-}
-
-GULON_API int32_t gulon_index_profile_read(gulon_index *idx, double *scan_ms_total, int32_t *launches) {
-  return guarded([&] {
-    GULON_REQUIRE(idx != nullptr, "index is null");
-    std::lock_guard<std::mutex> lock(idx->mu);
-    double tot = 0;
-    for (auto &e : idx->events) {
-      HIP_CHECK(hipEventSynchronize(e.second));
-      float ms = 0;
-      HIP_CHECK(hipEventElapsedTime(&ms, e.first, e.second));
-      tot += ms;
-    }
-    if (scan_ms_total) *scan_ms_total = tot;
-    if (launches) *launches = (int32_t)idx->events.size();
-  });
-}
-
-GULON_API int32_t gulon_index_profile_read_ex(gulon_index *idx, double *ms_total, int32_t *launches,
-                                              int64_t *rows_total) {
-  int32_t rc = gulon_index_profile_read(idx, ms_total, launches);
-  if (rc == GULON_OK && rows_total) *rows_total = idx->prof_rows;
-  return rc;
-}
-
-GULON_API int32_t gulon_index_filter_stats(gulon_index *idx, int32_t *query_tiles, int32_t *tiles_redone) {
-  return guarded([&] {
-    GULON_REQUIRE(idx != nullptr, "index is null");
-    std::lock_guard<std::mutex> lock(idx->mu);
-    HIP_CHECK(hipDeviceSynchronize());
-    const int nt = idx->last_filter_tiles;
-    int redone = 0;
-    if (nt > 0) {
-      std::vector<int> h((size_t)nt);
-      HIP_CHECK(hipMemcpy(h.data(), idx->fb_tile.p, sizeof(int) * h.size(), hipMemcpyDeviceToHost));
-      for (int v : h) redone += v != 0;
-    }
-    if (query_tiles) *query_tiles = nt;
-    if (tiles_redone) *tiles_redone = redone;
-  });
-}
-
-GULON_API int32_t gulon_index_tuning(gulon_index *idx, const char *key, int32_t value) {
-  return guarded([&] {
-    GULON_REQUIRE(idx != nullptr && key != nullptr, "null argument");
-    std::lock_guard<std::mutex> lock(idx->mu);
-    // copy-on-write: contexts created earlier keep the settings they were created with
-    auto t = std::make_shared<ScanTuning>(tuning_of(idx));
-    GULON_REQUIRE(t->set(key, value), "unknown tuning key");
-    idx->tune = t;
-  });
-}
-
-GULON_API int32_t gulon_topk_merge_dev(const float *d_part_dist, const int32_t *d_part_idx, int32_t lists,
-                                       int64_t list_stride, int32_t b, int32_t k_nn, int32_t *d_out_idx,
-                                       float *d_out_dist, int32_t *d_out_count, int32_t *d_out_flags, void *stream) {
-  return guarded([&] {
-    GULON_REQUIRE(lists >= 1 && b >= 0 && k_nn >= 1, "bad merge shape");
-    GULON_UNSUPPORTED(k_nn + 1 > GULON_MAX_K_PEELED, "k_nn = %d > %d", k_nn, GULON_MAX_K_PEELED - 1);
-    int keff = k_nn + 1;
-    GULON_REQUIRE(list_stride == 0 || list_stride >= (long long)b * keff, "list_stride too small");
-    if (b == 0) return;
-    if (k_nn > GULON_MAX_K) {   // beyond a wavefront list: pairwise merges through scratch (synchronises the stream)
-      launch_merge_long(d_part_dist, d_part_idx, lists, list_stride ? (long long)list_stride : (long long)b * keff, b, k_nn,
-                        d_out_idx, d_out_dist, d_out_count, d_out_flags, (hipStream_t)stream);
-      return;
-    }
-    launch_merge(true, d_part_dist, d_part_idx, lists, list_stride ? (long long)list_stride : (long long)b * keff,
-                 (long long)keff, b, k_nn, d_out_idx,
-                 d_out_dist, d_out_count, d_out_flags, nullptr, nullptr, (hipStream_t)stream);
-  });
-}
-
-GULON_API int32_t gulon_topk_merge(const float *part_dist, const int32_t *part_idx, int32_t lists, int32_t b,
-                                   int32_t k_nn, int32_t *out_idx, float *out_dist, int32_t *out_count,
-                                   int32_t *out_flags) {
-  return guarded([&] {
-    GULON_REQUIRE(lists >= 1 && b >= 0 && k_nn >= 1, "bad merge shape");
-    GULON_UNSUPPORTED(k_nn > GULON_MAX_K, "k_nn = %d > GULON_MAX_K = %d", k_nn, GULON_MAX_K);
-    if (b == 0) return;
-    size_t np = (size_t)lists * b * (k_nn + 1), bk = (size_t)b * k_nn;
-    DevBuf<float> pv; DevBuf<int> pi; DevBuf<int> oi(bk), oc(b), of(b); DevBuf<float> od(bk);
-    pv.upload(part_dist, np); pi.upload(part_idx, np);
-    int keff = k_nn + 1;
-    launch_merge(true, pv.p, pi.p, lists, (long long)b * keff, (long long)keff, b, k_nn, oi.p, od.p, oc.p, of.p,
-                 nullptr, nullptr, nullptr);
-    oi.download(out_idx, bk); od.download(out_dist, bk);
-    if (out_count) oc.download(out_count, b);
-    if (out_flags) of.download(out_flags, b);
-    HIP_CHECK(hipDeviceSynchronize());
   });
 }
 
@@ -1369,8 +749,8 @@ GULON_API int32_t gulon_index_query_rows_dev(gulon_index *idx, const int32_t *d_
     ensure_row_err(idx);
     idx->stage_q.ensure((size_t)b * idx->d + 1);
     launch_decode_rows(idx, d_rows, b, nullptr, nullptr, 0, normalize != 0, idx->stage_q.p, idx->row_err.p, st);
-    run_query(idx, idx->stage_q.p, b, k_nn, from, until, true, d_out_idx, d_out_dist, d_out_count, d_out_flags, nullptr,
-              nullptr, st);
+    run_query({idx, idx->stage_q.p, b, k_nn, from, until,
+               QueryOut::final_lists(d_out_idx, d_out_dist, d_out_count, d_out_flags), st, nullptr});
     so.done();
   });
 }
@@ -1384,33 +764,12 @@ GULON_API int32_t gulon_index_query_rows(gulon_index *idx, const int32_t *rows, 
     GULON_REQUIRE(b == 0 || rows != nullptr, "rows is null");
     for (int r = 0; r < b; r++)   // checked before anything is launched
       GULON_REQUIRE(rows[r] >= 0 && rows[r] < idx->n, "row %d = %d outside [0, %d)", r, rows[r], idx->n);
-    gulon_index *c = acquire_host_context(idx);
-    struct Release { gulon_index *i, *c; ~Release() { release_host_context(i, c); } } rel{idx, c};
-    std::lock_guard<std::mutex> lock(c->mu);
-    c->pend_b = -1;
-    const size_t bk = (size_t)b * (size_t)k_nn;
-    c->stage_q.ensure((size_t)b * c->d + 1);
-    c->stage_rows.ensure((size_t)b + 1);
-    c->stage_oi.ensure(bk + 1);
-    c->stage_od.ensure(bk + 1);
-    c->stage_oc.ensure((size_t)b + 1);
-    c->stage_of.ensure((size_t)b + 1);
-    if (!c->host_stream) HIP_CHECK(hipStreamCreateWithFlags(&c->host_stream, hipStreamNonBlocking));
-    hipStream_t st = c->host_stream;
-    StreamOrder so(c, st);
-    if (b > 0) {
+    host_query(idx, b, k_nn, from, until, out_idx, out_dist, out_count, out_flags, false,
+               [&](gulon_index *c, hipStream_t st) {
+      c->stage_rows.ensure((size_t)b + 1);
+      if (b == 0) return;
       HIP_CHECK(hipMemcpyAsync(c->stage_rows.p, rows, sizeof(int32_t) * (size_t)b, hipMemcpyHostToDevice, st));
       launch_decode_rows(c, c->stage_rows.p, b, nullptr, nullptr, 0, normalize != 0, c->stage_q.p, nullptr, st);
-    }
-    run_query(c, c->stage_q.p, b, k_nn, from, until, true, c->stage_oi.p, c->stage_od.p, c->stage_oc.p,
-              c->stage_of.p, nullptr, nullptr, st);
-    if (bk) {
-      c->stage_oi.download(out_idx, bk, st);
-      c->stage_od.download(out_dist, bk, st);
-    }
-    if (b > 0 && out_count) c->stage_oc.download(out_count, b, st);
-    if (b > 0 && out_flags) c->stage_of.download(out_flags, b, st);
-    so.done();
-    HIP_CHECK(hipStreamSynchronize(st));
+    });
   });
 }

@@ -1,4 +1,7 @@
-// Internal declarations shared by the top-k users (scan, exact kNN).
+// The library's internal header: the index handle (gulon_index) with its workspaces and stream ordering, the call and
+// output structs of the flat query path (QueryOut, FlatCall), the merge and peel launchers every top-k user shares
+// (merge.hip), the tuning knobs, and the launchers the query drivers of scan.hip, wide*.hip, filter*.hip, replay.hip,
+// literal.hip and decode.hip call across files.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -7,26 +10,49 @@
 
 #include "common.hpp"
 
+struct gulon_index;
 namespace gulon {
+// Where a query writes: final [B][K] idx / dist (+ count, flags, both nullable), or one partial (K+1)-list per query.
+// All members null: a call with no outputs (the phase-1 bounds call, whose bounds go to its SharedBounds).
+struct QueryOut {
+  int *idx; float *dist; int *count; int *flags; float *part_v; int *part_i;
+  static QueryOut final_lists(int *idx, float *dist, int *count, int *flags) {
+    return {idx, dist, count, flags, nullptr, nullptr};
+  }
+  static QueryOut partial_lists(float *v, int *i) { return {nullptr, nullptr, nullptr, nullptr, v, i}; }
+  bool final_out() const { return idx != nullptr; }
+  // the same outputs, starting at query q0 (null members stay null)
+  QueryOut from_query(int q0, int K) const {
+    auto at = [](auto *p, size_t o) { return p ? p + o : p; };
+    return {at(idx, (size_t)q0 * K), at(dist, (size_t)q0 * K), at(count, (size_t)q0), at(flags, (size_t)q0),
+            at(part_v, (size_t)q0 * (K + 1)), at(part_i, (size_t)q0 * (K + 1))};
+  }
+};
 // Merge `lists` sorted partial lists per query (element (l,q,e) at l*stride_l + q*stride_q + e,
-// each list K+1 long, padded with (+inf, INT_MAX)).  final_out: write [B][K] idx/dist/count/flags,
-// else write one (K+1)-list per query to out_pv/out_pi.
-void launch_merge(bool final_out, const float *in_v, const int *in_i, int lists, long long stride_l,
-                  long long stride_q, int B, int K, int *out_idx, float *out_dist, int *out_count,
-                  int *out_flags, float *out_pv, int *out_pi, hipStream_t st);
-bool replay_enabled();
-// large-K peeling helpers (scan.hip): append a 64-entry round to [B][cap] and set the next lower bound;
-// then cut the concatenated list to [B][K] + count + tie flags, or (a shard) copy its first keff = K + 1 entries
-// out as a partial list [B][keff]
+// each list K+1 long, padded with (+inf, INT_MAX)) into out: its final lists, else its partial ones.
+void launch_merge(const float *in_v, const int *in_i, int lists, long long stride_l, long long stride_q, int B, int K,
+                  const QueryOut &out, hipStream_t st);
+// large-K peeling (merge.hip): append a 64-entry round to [B][cap] and set the next lower bound; then cut the
+// concatenated list to [B][K] + count + tie flags
 void launch_peel_update(const float *tv, const int *ti, int B, int round, int cap, float *pv, int *pi, float *lbv,
                         int *lbi, hipStream_t st);
 void launch_peel_finalize(const float *pv, const int *pi, int B, int cap, int K, int *out_idx, float *out_dist,
                           int *out_count, int *out_flags, hipStream_t st);
-void launch_peel_export(const float *pv, const int *pi, int B, int cap, int keff, float *out_v, int *out_i,
-                        hipStream_t st);
-}  // namespace gulon
-
-namespace gulon {
+void launch_fill_list(float *v, int *i, long long n, hipStream_t st);   // n entries of (+inf, INT_MAX)
+// The rounds of a query for K > GULON_MAX_K neighbours on an index handle: 64 entries per scan round, every round
+// restricted to the entries after the previous one's last.  The constructor sizes the handle's peel buffers -- the lists
+// [B][cap], one round [tv_slots][64], the bounds [bound_slots] -- and writes the first bounds (nothing returned yet).
+struct PeelRounds {
+  gulon_index *ix;
+  int B, K, rounds, cap;
+  hipStream_t st;
+  struct Bounds { const float *v; const int *i; };
+  PeelRounds(gulon_index *ix, int B, int bound_slots, int tv_slots, int K, hipStream_t st);
+  Bounds bounds(int q0) const;   // of queries q0, q0 + 1, ...: what the scan launch of a round reads
+  // round r of queries [q0, q0 + nq): their `lists` 64-lists each in ix->part_v / part_i merged, appended, bounds moved
+  void append(int r, int q0, int nq, int lists);
+  void finish(const QueryOut &out);   // cut to final lists with count and tie flags, or (a shard) to K + 1 partial entries
+};
 struct ScanTuning;
 // Workspace of the expression calls (compose.hip): the term lists, the composed vectors and the index's answer at
 // k_nn + extra before the operands are dropped.  `mu` is held for a whole call, so the three steps of a query -- compose,
@@ -190,6 +216,10 @@ struct gulon_index {
 namespace gulon {
 // a new workspace over `parent`'s read-only data (no reference counting: the caller keeps `parent` alive)
 gulon_index *make_context(gulon_index *parent);
+// index_handle.hip, host-pointer calls: take a free workspace of this handle (the handle itself first), creating up to
+// GULON_HOST_CONTEXTS (default 4) internal contexts; blocks while all are busy
+gulon_index *acquire_host_context(gulon_index *idx);
+void release_host_context(gulon_index *idx, gulon_index *c);
 // scan.hip: the bodies of gulon_index_batch_query_dev / gulon_index_batch_query; map_view (a view only): the returned
 // positions are translated to the root's row ids on the same stream, inside the handle's StreamOrder
 void batch_query_dev_on(gulon_index *idx, const float *d_queries, int32_t b, int32_t k_nn, int32_t from, int32_t until,
@@ -197,7 +227,7 @@ void batch_query_dev_on(gulon_index *idx, const float *d_queries, int32_t b, int
                         hipStream_t st, bool map_view);
 void batch_query_host_on(gulon_index *idx, const float *queries, int32_t b, int32_t k_nn, int32_t from, int32_t until,
                          int32_t *out_idx, float *out_dist, int32_t *out_count, int32_t *out_flags, bool map_view);
-// scan.hip: the filter's conflict-ordered copy of ix->codes, where this handle's tuning and shape call for one
+// index_handle.hip: the filter's conflict-ordered copy of ix->codes, where this handle's tuning and shape call for one
 void build_filter_copy(gulon_index *ix);
 // subset.hip: d_idx[0..count) positions of `view` -> row ids of its root, in place; negative entries stay
 void launch_map_rows(const gulon_index *view, int *d_idx, long long count, hipStream_t st);
@@ -227,10 +257,7 @@ struct StreamOrder {
   StreamOrder(const StreamOrder &) = delete;
   StreamOrder &operator=(const StreamOrder &) = delete;
 };
-}  // namespace gulon
 
-
-namespace gulon {
 // Strided selection of row blocks: the e-th eligible block (relative to the first block of the
 // scanned range) is (e / width) * period + lo + e % width.  {1, 0, 1} = every block.
 struct RbMap { int period, lo, width; };
@@ -284,18 +311,32 @@ struct ScanTuning {
 const ScanTuning &tuning_defaults();
 inline const ScanTuning &tuning_of(const gulon_index *ix) { return ix && ix->tune ? *ix->tune : tuning_defaults(); }
 
+// One batch query over rows [from, until) of a flat (byte-coded or wide) index: what run_query and every driver under
+// it take.  sb: the shared-bounds half this call is (nullptr: an ordinary query).
+struct SharedBounds;
+struct FlatCall {
+  gulon_index *ix; const float *dQ; int B, K, from, until; QueryOut out; hipStream_t st; const SharedBounds *sb;
+};
+// The chunks of a scan launch over row_blocks 64-row blocks: about `want` of them, but at least two row blocks for each
+// of a workgroup's `waves` waves
+inline void scan_chunks(int row_blocks, int want, int waves, int &nchunks, int &per_chunk) {
+  nchunks = std::max(1, std::min(want, row_blocks / (2 * waves)));
+  per_chunk = ceil_div(row_blocks, nchunks);
+  nchunks = ceil_div(row_blocks, per_chunk);
+}
+
 // wide.hip: indexes with more than 256 centroids per quantizer (code widths 10/12/16)
+constexpr int WIDE_THREADS = 512;              // scan_wide's workgroup: one partial list per wave
+constexpr int WIDE_NW = WIDE_THREADS / 64;
 void wide_store_codes(gulon_index *ix, const uint16_t *wide16 /* device, [m][n] */);
 void launch_build_tables_wide(const float *cents, const int *from, const int *sdim, int d, int m, int k, const float *dQ,
                               int q0, int nq, float *tables /*[nq][m][k]*/, hipStream_t st);
 // wide_filter.hip: the quantized lower-bound filter for 16-bit code words (k <= 1024 at m = 16)
 bool wide_filter_eligible(const gulon_index *ix, int B, int K, int rb_total);
-void run_wide_filter_query(gulon_index *ix, const float *dQ, int B, int K, int from, int until, bool final_out,
-                           int *d_oi, float *d_od, int *d_oc, int *d_of, float *d_pv, int *d_pi, hipStream_t st);
+void run_wide_filter_query(const FlatCall &c);
 void launch_scan_wide_range(gulon_index *ix, int B, int K, int from, int until, int rb_begin, int rb_total,
                             int rb_per_chunk, int nchunks, const int *enable, hipStream_t st);
-void run_wide_query(gulon_index *ix, const float *dQ, int B, int K, int from, int until, bool final_out, int *d_oi,
-                    float *d_od, int *d_oc, int *d_of, float *d_pv, int *d_pi, hipStream_t st);
+void run_wide_query(const FlatCall &c);
 
 // scan.hip: exact scan of the selected row blocks of [from, until) into ix->part_v/part_i
 // ([query][nchunks][keff]); tile_enable (device, per query tile) skips disabled tiles.
@@ -362,9 +403,7 @@ bool filter_eligible(const gulon_index *ix, int K, int rb_total);
 // (K+1)-th distance of the WHOLE index, so every shard filters against the global bound.
 struct SharedBounds { int phase; float *bounds_out; const float *all_bounds; int lists; };
 // filter_query.hip: sample scan -> quantized filter stages -> exact re-evaluation of the survivors.
-void run_filter_query(gulon_index *ix, const float *dQ, int B, int K, int from, int until, bool final_out, int *d_oi,
-                      float *d_od, int *d_oc, int *d_of, float *d_pv, int *d_pi, hipStream_t st,
-                      const SharedBounds *sb = nullptr);
+void run_filter_query(const FlatCall &c);
 
 #ifdef __HIPCC__
 template <int VEC> struct CodeWord;
@@ -395,20 +434,22 @@ void launch_build_tables(int W, gulon_index *ix, const float *dQ, int B, int Bpa
                          const int *live_queries = nullptr, float *mins = nullptr);
 // literal.hip: queries whose distances can be NaN / +inf are redone through the literal TopKHeap over all rows
 float centroid_absmax(const float *d_cents, long long count);
-void run_nonfinite_literal(gulon_index *ix, const float *dQ, int B, int K, int from, int until, int *d_oi, float *d_od,
-                           int *d_oc, int *d_of, hipStream_t st);
+// (over the call's final outputs; `flags`: the flags array the pass reads and updates, nullable)
+void run_nonfinite_literal(const FlatCall &c, int *flags);
 // For every query flagged with an exact distance tie, recompute the result with the
 // reference's TopKHeap semantics (insertion history in row order) -- replay.hip
-void run_tie_replay(gulon_index *ix, const float *dQ, int B, int K, int from, int until, int *d_oi, float *d_od,
-                    int *d_oc, int *d_of, hipStream_t st);
-// scan.hip: where a query path's merge writes its tie flags -- the caller's d_of, or (final outputs with the replay on: it
-// needs the flags even if the caller does not) the handle's scratch
-int *tie_flags(gulon_index *ix, bool final_out, int *d_of, int B);
-// scan.hip: the tail of the flat paths (run_query, run_filter_query) -- `lists` sorted lists per query merged into the
-// outputs, then the tie replay and the non-finite literal pass over the final ones
-void finish_flat_query(gulon_index *ix, const float *dQ, int B, int K, int from, int until, bool final_out,
-                       const float *in_v, const int *in_i, int lists, long long stride_l, long long stride_q, int *d_oi,
-                       float *d_od, int *d_oc, int *d_of, float *d_pv, int *d_pi, hipStream_t st);
+void run_tie_replay(const FlatCall &c, int *flags);
+// scan.hip: the tail of every query path that is not peeled -- `lists` sorted lists per query merged into the call's
+// outputs, then, over final ones, the tie replay and (literal_pass) the non-finite literal pass.  The byte-coded paths
+// pass literal_pass = true; the wide paths pass false: they have never run that pass, and unifying the tail did not
+// change that.  A driver that merges in sub-batches (run_wide_query) calls the two halves itself: its merges write to
+// merge_outputs(c).from_query(q0, K), and finish_replay gets merge_outputs(c).flags.
+void finish_query(const FlatCall &c, const float *in_v, const int *in_i, int lists, long long stride_l,
+                  long long stride_q, bool literal_pass);
+// c.out as the merge writes it: final outputs with the replay on need the tie flags even if the caller does not, and
+// take the handle's scratch for them
+QueryOut merge_outputs(const FlatCall &c);
+void finish_replay(const FlatCall &c, int *flags, bool literal_pass);
 void launch_conflict_order(const uint8_t *src, uint8_t *dst, uint8_t *perm, long long nblk, int nq, int rounds,
                            hipStream_t st);
 bool conflict_order_windowed();   // the ordering spans windows of four blocks (default) or single blocks

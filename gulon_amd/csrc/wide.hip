@@ -15,7 +15,7 @@
 //            slice with the running sums parked in HBM in between; k > 32 768 (one quantizer = 256 KiB)
 //            gathered from L2/HBM; lane = row; every wave keeps its own sorted top-(K+1) list in
 //            registers (WaveList), written out as one partial list per wave;
-//   merge    the common merge_lists of scan.hip; queries flagged with exact distance ties are then replayed with
+//   merge    the common merge_lists of merge.hip; queries flagged with exact distance ties are then replayed with
 //            the literal TopKHeap like those of a byte-coded index (replay.hip: rp_scan_wide gathers the flagged
 //            query's table from global memory).
 //   K > 63   the result is peeled 64 entries per round like a byte-coded index's (scan.hip): scan_wide<.., PEEL> admits
@@ -30,8 +30,6 @@ namespace gulon {
 
 namespace {
 
-constexpr int WIDE_THREADS = 512;
-constexpr int WIDE_NW = WIDE_THREADS / 64;
 constexpr size_t WIDE_LDS_TABLE = 128 * 1024;
 constexpr size_t WIDE_TABLE_BYTES = 1ull << 30;   // tables of one sub-batch of queries
 
@@ -226,13 +224,16 @@ void launch_scan_wide_range(gulon_index *ix, int B, int K, int from, int until, 
 // appended by peel_update; peel_finalize cuts the concatenation to [B][K] with its tie flags (no exact tie replay),
 // peel_export to the (K+1)-list of a shard.  With sliced tables the slices before the last do not depend on the bound:
 // they run once per sub-batch, and a round repeats only the last-slice launch over the parked sums.
-void run_wide_query(gulon_index *ix, const float *dQ, int B, int K, int from, int until, bool final_out, int *d_oi,
-                    float *d_od, int *d_oc, int *d_of, float *d_pv, int *d_pi, hipStream_t st) {
+void run_wide_query(const FlatCall &c) {
+  gulon_index *ix = c.ix;
+  const float *dQ = c.dQ;
+  const int B = c.B, K = c.K, from = c.from, until = c.until;
+  const hipStream_t st = c.st;
   const bool peeled = K > GULON_MAX_K;            // results come 64 at a time
   const int keff = peeled ? 64 : K + 1, m = ix->m, k = ix->k;
   const int rb_begin = from / 64, rb_total = ceil_div(until, 64) - rb_begin;
   if (!peeled && wide_filter_eligible(ix, B, K, rb_total)) {   // 8-bit lower bounds in front of the exact arithmetic (wide_filter.hip)
-    run_wide_filter_query(ix, dQ, B, K, from, until, final_out, d_oi, d_od, d_oc, d_of, d_pv, d_pi, st);
+    run_wide_filter_query(c);
     return;
   }
   const size_t table_bytes = (size_t)m * k * sizeof(float);
@@ -246,10 +247,8 @@ void run_wide_query(gulon_index *ix, const float *dQ, int B, int K, int from, in
   size_t qb_cap = WIDE_TABLE_BYTES / table_bytes;
   if (passes > 1) qb_cap = std::min(qb_cap, WIDE_TABLE_BYTES / (rows_pad * sizeof(float)));
   const int qb = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, qb_cap));
-  // chunks: ~2048 workgroups per launch, at least 2 row blocks per wave
-  int nchunks = std::max(1, std::min(ceil_div(2048, std::min(qb, B)), rb_total / (2 * WIDE_NW)));
-  const int rb_per_chunk = ceil_div(rb_total, nchunks);
-  nchunks = ceil_div(rb_total, rb_per_chunk);
+  int nchunks, rb_per_chunk;   // ~2048 workgroups per launch
+  scan_chunks(rb_total, ceil_div(2048, std::min(qb, B)), WIDE_NW, nchunks, rb_per_chunk);
   const int lists = nchunks * WIDE_NW;
   ix->tables.ensure((size_t)qb * m * k);
   ix->part_v.ensure((size_t)qb * lists * keff);
@@ -281,41 +280,30 @@ void run_wide_query(gulon_index *ix, const float *dQ, int B, int K, int from, in
     HIP_CHECK(hipGetLastError());
   };
   if (peeled) {
-    const int rounds = ceil_div(K + 1, 64), cap = rounds * 64;
     const int j_last = (passes - 1) * jp;           // first quantizer of the selecting launch
-    ix->peel_v.ensure((size_t)B * cap); ix->peel_i.ensure((size_t)B * cap);
-    ix->peel_tv.ensure((size_t)qb * 64); ix->peel_ti.ensure((size_t)qb * 64);
-    ix->peel_lbv.ensure((size_t)B); ix->peel_lbi.ensure((size_t)B);
-    HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)ix->peel_lbv.p, 0xBF800000 /* -1.0f */, (size_t)B, st));
-    HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)ix->peel_lbi.p, 0xFFFFFFFF /* -1 */, (size_t)B, st));
+    PeelRounds peel(ix, B, B, qb, K, st);
     for (int q0 = 0; q0 < B; q0 += qb) {
       const int nq = std::min(qb, B - q0);
       launch_build_tables_wide(ix->cents.p, ix->from.p, ix->sdim.p, ix->d, m, k, dQ, q0, nq, ix->tables.p, st);
       for (int j0 = 0; j0 < j_last; j0 += jp) launch_slice(nq, j0, nullptr, nullptr);   // parked sums: once per sub-batch
-      for (int r = 0; r < rounds; r++) {
-        launch_slice(nq, j_last, ix->peel_lbv.p + q0, ix->peel_lbi.p + q0);
-        launch_merge(false, ix->part_v.p, ix->part_i.p, lists, 64LL, (long long)lists * 64, nq, 63, nullptr, nullptr,
-                     nullptr, nullptr, ix->peel_tv.p, ix->peel_ti.p, st);
-        launch_peel_update(ix->peel_tv.p, ix->peel_ti.p, nq, r, cap, ix->peel_v.p + (size_t)q0 * cap,
-                           ix->peel_i.p + (size_t)q0 * cap, ix->peel_lbv.p + q0, ix->peel_lbi.p + q0, st);
+      for (int r = 0; r < peel.rounds; r++) {
+        launch_slice(nq, j_last, peel.bounds(q0).v, peel.bounds(q0).i);
+        peel.append(r, q0, nq, lists);
       }
     }
-    if (final_out) launch_peel_finalize(ix->peel_v.p, ix->peel_i.p, B, cap, K, d_oi, d_od, d_oc, d_of, st);
-    else launch_peel_export(ix->peel_v.p, ix->peel_i.p, B, cap, K + 1, d_pv, d_pi, st);   // a shard's K+1 smallest
+    peel.finish(c.out);
     return;
   }
-  int *flags = tie_flags(ix, final_out, d_of, B);
+  const QueryOut out = merge_outputs(c);
   for (int q0 = 0; q0 < B; q0 += qb) {
     const int nq = std::min(qb, B - q0);
     launch_build_tables_wide(ix->cents.p, ix->from.p, ix->sdim.p, ix->d, m, k, dQ, q0, nq, ix->tables.p, st);
     for (int j0 = 0; j0 < m; j0 += jp) launch_slice(nq, j0, nullptr, nullptr);
-    launch_merge(final_out, ix->part_v.p, ix->part_i.p, lists, (long long)keff, (long long)lists * keff, nq, K,
-                 final_out ? d_oi + (size_t)q0 * K : nullptr, final_out ? d_od + (size_t)q0 * K : nullptr,
-                 final_out && d_oc ? d_oc + q0 : nullptr, final_out && flags ? flags + q0 : nullptr,
-                 final_out ? nullptr : d_pv + (size_t)q0 * keff, final_out ? nullptr : d_pi + (size_t)q0 * keff, st);
+    launch_merge(ix->part_v.p, ix->part_i.p, lists, (long long)keff, (long long)lists * keff, nq, K,
+                 out.from_query(q0, K), st);
   }
-  // queries with exact distance ties: the reference heap's insertion history (replay.hip, rp_scan_wide)
-  if (final_out && replay_enabled()) run_tie_replay(ix, dQ, B, K, from, until, d_oi, d_od, d_oc, flags, st);
+  // queries with exact distance ties: the reference heap's insertion history (replay.hip, rp_scan_wide); no literal pass
+  finish_replay(c, out.flags, false);
 }
 
 }  // namespace gulon

@@ -404,7 +404,9 @@ struct WideFilterBatch {
   void sample_lists();
   void filter_stages();
   void fallback_scan();
-  void finish(bool final_out, int *d_oi, float *d_od, int *d_oc, int *d_of, float *d_pv, int *d_pi);
+
+  explicit WideFilterBatch(const FlatCall &c)
+      : ix(c.ix), dQ(c.dQ), B(c.B), K(c.K), keff(c.K + 1), from(c.from), until(c.until), st(c.st) {}
 };
 
 void WideFilterBatch::plan() {
@@ -425,14 +427,9 @@ void WideFilterBatch::plan() {
   const int f_first = f_count >= 64 * WF_NW ? std::max(WF_NW, f_count / 20) : 0;      // blocks of the short stage
   stage_begin[0] = f_begin, stage_begin[1] = f_begin + f_first;
   stage_count[0] = f_first, stage_count[1] = f_count - f_first;
-  // scan_wide's launch shape (wide.hip): ~2048 workgroups, at least 2 row blocks per wave
-  auto chunks_of = [&](int blocks, int &nchunks, int &per) {
-    nchunks = std::max(1, std::min(ceil_div(2048, B), blocks / (2 * 8)));
-    per = ceil_div(blocks, nchunks);
-    nchunks = ceil_div(blocks, per);
-  };
-  chunks_of(sblocks, nc_s, per_s);
-  chunks_of(rb_total, nc_all, per_all);
+  // scan_wide's launch shape (wide.hip): ~2048 workgroups
+  scan_chunks(sblocks, ceil_div(2048, B), WIDE_NW, nc_s, per_s);
+  scan_chunks(rb_total, ceil_div(2048, B), WIDE_NW, nc_all, per_all);
 }
 
 void WideFilterBatch::workspace() {
@@ -454,8 +451,8 @@ void WideFilterBatch::workspace() {
 void WideFilterBatch::sample_lists() {
   wf_reset_and_tables(ix, dQ, B, Bq, st);
   launch_scan_wide_range(ix, B, K, from, s_end, rb_begin, sblocks, per_s, nc_s, nullptr, st);
-  launch_merge(false, ix->part_v.p, ix->part_i.p, nc_s * 8, (long long)keff, (long long)nc_s * 8 * keff, B, K, nullptr,
-               nullptr, nullptr, nullptr, ix->fin_v.p, ix->fin_i.p, st);
+  launch_merge(ix->part_v.p, ix->part_i.p, nc_s * 8, (long long)keff, (long long)nc_s * 8 * keff, B, K,
+               QueryOut::partial_lists(ix->fin_v.p, ix->fin_i.p), st);
 }
 
 // 2.-4. the table minima, then per stage: quantize -> filter -> the survivors, exactly
@@ -478,12 +475,6 @@ void WideFilterBatch::fallback_scan() {
                        ix->fin_v.p, ix->fin_i.p, ix->fb_tile.p, 1, st);
 }
 
-void WideFilterBatch::finish(bool final_out, int *d_oi, float *d_od, int *d_oc, int *d_of, float *d_pv, int *d_pi) {
-  int *flags = tie_flags(ix, final_out, d_of, B);
-  launch_merge(final_out, ix->fin_v.p, ix->fin_i.p, 1, 0LL, (long long)keff, B, K, d_oi, d_od, d_oc, flags, d_pv, d_pi, st);
-  if (final_out && replay_enabled()) run_tie_replay(ix, dQ, B, K, from, until, d_oi, d_od, d_oc, flags, st);
-}
-
 }  // namespace
 
 // (K <= 63, one sub-batch of fp32 tables, the query's fp32 table in LDS for the sample scan, enough rows to pay)
@@ -496,16 +487,15 @@ bool wide_filter_eligible(const gulon_index *ix, int B, int K, int rb_total) {
          (!sliced || (size_t)B * rb_total * 64 <= (2ull << 30) /* the parked byte sums */);
 }
 
-void run_wide_filter_query(gulon_index *ix, const float *dQ, int B, int K, int from, int until, bool final_out,
-                           int *d_oi, float *d_od, int *d_oc, int *d_of, float *d_pv, int *d_pi, hipStream_t st) {
-  WideFilterBatch wb{ix, dQ, B, K, K + 1, from, until, st};
+void run_wide_filter_query(const FlatCall &c) {
+  WideFilterBatch wb(c);
   wb.plan();
   wb.workspace();
-  ix->last_filter_tiles = B;
+  c.ix->last_filter_tiles = c.B;
   wb.sample_lists();
   wb.filter_stages();
   wb.fallback_scan();
-  wb.finish(final_out, d_oi, d_od, d_oc, d_of, d_pv, d_pi);
+  finish_query(c, c.ix->fin_v.p, c.ix->fin_i.p, 1, 0LL, (long long)wb.keff, false);   // (wide: no literal pass)
 }
 
 }  // namespace gulon

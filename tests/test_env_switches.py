@@ -30,7 +30,7 @@ def _table():
 
 
 def _scan_tuning_keys():
-    src = _read(os.path.join(CSRC, "scan.hip"))
+    src = _read(os.path.join(CSRC, "index_handle.hip"))
     body = re.search(r"ScanTuning::ScanTuning\(\) \{\s*static const char \*keys\[\] = \{(.*?)\};", src, re.S).group(1)
     return set(re.findall(r'"(GULON_[A-Z0-9_]+)"', body))
 
@@ -42,7 +42,7 @@ def test_native_switches_and_tuning_keys_are_the_documented_ones():
         native |= set(re.findall(r'getenv\("(GULON_[A-Z0-9_]+)"\)', src))
         # every other getenv is ScanTuning's loop over its key list
         other = re.findall(r'getenv\((?!"GULON_)[^)]*\)', src)
-        assert other == (["getenv(k)"] if name == "scan.hip" else []), (name, other)
+        assert other == (["getenv(k)"] if name == "index_handle.hip" else []), (name, other)
     keys = _scan_tuning_keys()
     table = _table()
     assert len(keys) >= 10 and not keys & native
