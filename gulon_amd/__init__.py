@@ -31,6 +31,8 @@ from .csls import (DeviceOffsets, TranslationReport, csls_offsets, evaluate_dict
 from .ranks import RankReport, evaluate_dictionary_ranks, rank_query_reference
 from .alignment import (induce_matches, mutual_rows, mutual_rows_reference, pair_moment, pair_moment_reference,
                         seed_alignment, train_alignment)
+from .csls import isf_offsets
+from .softmax import isf_offsets_from, isf_probabilities, logsumexp_reference
 
 __all__ = ["native", "GroupedIndex", "GroupedVectors", "LimitGroups", "LimitVectors", "group", "Coder", "width_for_clusters", "Index", "PQIndex", "PQIndexView", "DevicePQIndex", "Result", "SortedIndex",
            "exact_nearest_neighbours", "prepare_query", "tune_live", "KMeans", "KMeansConfig", "DeviceMatrix", "Matrix",
@@ -46,4 +48,5 @@ __all__ = ["native", "GroupedIndex", "GroupedVectors", "LimitGroups", "LimitVect
            "TranslationReport", "csls_offsets", "evaluate_dictionary", "mean_similarity", "mean_similarity_reference",
            "offset_query_reference", "read_dictionary", "translate_words", "translation_scores",
            "induce_matches", "mutual_rows", "mutual_rows_reference", "pair_moment", "pair_moment_reference",
-           "seed_alignment", "train_alignment", "RankReport", "evaluate_dictionary_ranks", "rank_query_reference"]
+           "seed_alignment", "train_alignment", "RankReport", "evaluate_dictionary_ranks", "rank_query_reference",
+           "isf_offsets", "isf_offsets_from", "isf_probabilities", "logsumexp_reference"]

@@ -73,8 +73,8 @@
                                        and ranks are computed on the device.  -R is not offered: distances between stored
                                        rows need no rotation
 
-  translate -i TARGET -s SOURCE [--method nn|csls] [-n 10] [-k 10] [-v VECTORS --exact] [-R ROTATION] [-a MAP]
-            [--lowercase] (WORDS | -e DICTIONARY [--ranks])
+  translate -i TARGET -s SOURCE [--method nn|csls|isf] [-n 10] [--beta 30] [--isf-sources N] [-k 10]
+            [-v VECTORS --exact] [-R ROTATION] [-a MAP] [--lowercase] (WORDS | -e DICTIONARY [--ranks])
                                        (not in the reference) word translation between two aligned embedding spaces
                                        (csls.py, csrc/offset.hip).  TARGET is an index file over the target language's
                                        vectors, SOURCE a word2vec text file of the source language's, already mapped
@@ -84,7 +84,13 @@
                                        distance; csls (a cosine index, flat or built with -p, or -v --exact; a -p index
                                        answers from the groups its strategy searches) by CSLS: the distance plus the
                                        mean similarity of the target word to its -n (default 10) nearest source words,
-                                       which demotes the hubs that are near everything.  -e DICTIONARY replaces WORDS:
+                                       which demotes the hubs that are near everything.  isf (the same indexes) ranks
+                                       by the inverted softmax of Smith et al. 2017 (softmax.py, csrc/logsumexp.hip):
+                                       the distance plus (2 / beta) * log sum exp(-(beta / 2) * distance) over ALL the
+                                       source words, --beta (default 30) the inverse temperature, --isf-sources N the
+                                       sum over the N most frequent source words only (the first N lines of SOURCE); its lines are those of csls with `isf`
+                                       as the method name.  --beta and --isf-sources without --method isf are usage
+                                       errors.  -e DICTIONARY replaces WORDS:
                                        lines of `source target` (MUSE's format, a source word may have several lines),
                                        and one line is printed, `csls: @1 0.6120 @5 0.8010 @10 0.8522 (n = 1500,
                                        skipped 12)` -- the precision at -k 1,5,10, n the source words asked, skipped the
@@ -152,6 +158,7 @@ update, -R FILE rotates the vectors file (-a for update) after reading it; the i
 Input is UTF-8; lines end as java.io.BufferedReader.readLine ends them (\\n, \\r or \\r\\n).  Words are queried in
 batches; the output is the same as querying them one at a time."""
 import argparse
+import math
 import re
 import sys
 from dataclasses import dataclass
@@ -179,6 +186,16 @@ def _positive(s):
         raise argparse.ArgumentTypeError(f"invalid integer: {s!r}")
     if v <= 0:
         raise argparse.ArgumentTypeError("must be at least 1")
+    return v
+
+
+def _positive_float(s):
+    try:
+        v = float(s)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"invalid number: {s!r}")
+    if not (math.isfinite(v) and v > 0):
+        raise argparse.ArgumentTypeError("must be a finite number above 0")
     return v
 
 
@@ -296,6 +313,16 @@ class TranslateConfig:
     rotation: Optional[str] = None        # -R: the index was built over vectors rotated by this file
     alignment: Optional[str] = None       # -a: the map of the source vectors into the target's space (align)
     ranks: bool = False                   # --ranks with -e: the line of rank statistics after the precision line
+    # (`ranks` stays the last field: the options of --method isf are IsfTranslateConfig's, these are what nn and csls see)
+    beta = 30.0
+    isf_sources = None
+
+
+@dataclass(frozen=True)
+class IsfTranslateConfig(TranslateConfig):
+    """TranslateConfig of --method isf: the same fields, then the inverted softmax's own."""
+    beta: float = 30.0                    # --beta: the inverse temperature of the inverted softmax
+    isf_sources: Optional[int] = None     # --isf-sources: normalise over the first N words of the FILE (None: all)
 
 
 @dataclass(frozen=True)
@@ -508,9 +535,15 @@ def _parser():
     tr.add_argument("-i", "--index", required=True, metavar="file", help="path to the ANN index of the target language")
     tr.add_argument("-s", "--source", required=True, metavar="file",
                     help="word2vec word vectors of the source language, mapped into the target's space")
-    tr.add_argument("--method", choices=("nn", "csls"), default="nn",
+    tr.add_argument("--method", choices=("nn", "csls", "isf"), default="nn",
                     help="nn ranks by the index's distance; csls adds the mean similarity of every target word to its "
-                         "nearest source words (a cosine index)")
+                         "nearest source words (a cosine index); isf, the inverted softmax, adds (2 / beta) times the "
+                         "log of the sum of exp(-(beta / 2) * distance) over all source words (a cosine index)")
+    tr.add_argument("--beta", type=_positive_float, default=None, metavar="num",
+                    help="with --method isf: the inverse temperature of the inverted softmax (default 30)")
+    tr.add_argument("--isf-sources", type=_positive, default=None, metavar="num",
+                    help="with --method isf: normalise over the num most frequent source words only, the first num lines of "
+                         "the source file (default: all)")
     tr.add_argument("-n", "--csls-neighbours", type=_positive, default=10, metavar="num",
                     help="neighbours behind the mean similarities of csls (default 10)")
     tr.add_argument("-k", "--neighbours", default=None, metavar="num",
@@ -817,7 +850,22 @@ class TranslateError(Exception):
     index that cannot answer it."""
 
 
-def _ranked_evaluation(index, source, pairs, config):
+def _frequent_rows(count, read):
+    """--isf-sources N -> the rows of the source that hold the N most frequent words.  A word2vec file lists its words
+    by falling frequency and `read`, the source as its reader returned it, is in word order: sorted() left behind the
+    line every row came from (file_rows), and the rows of the first N lines are returned, ascending.  A reader that
+    kept the file's order leaves no file_rows, and then the first N rows are the answer: N itself.  None stays None.
+    ValueError: N beyond the source's words."""
+    if count is None:
+        return None
+    if not 1 <= count <= read.size:
+        raise ValueError(f"requirement failed: --isf-sources {count} outside [1, {read.size}], the source's words")
+    import numpy as np
+    file_rows = getattr(read, "file_rows", None)
+    return count if file_rows is None else np.flatnonzero(np.asarray(file_rows) < count).astype(np.int32)
+
+
+def _ranked_evaluation(index, source, pairs, config, sources=None):
     """translate -e --ranks -> ranks.RankReport whose lines are the precision line and the line of rank statistics.  The
     ranks come first, so an index that has no rank queries is refused before anything is evaluated.  csls: the rank IS
     the position in the offset query's answer, so the precision line is counted from the ranks -- the numbers
@@ -825,8 +873,9 @@ def _ranked_evaluation(index, source, pairs, config):
     evaluate_dictionary's, in the tie order of the ordinary query; the ranks order equal distances by row."""
     from .csls import TranslationReport, evaluate_dictionary
     from .ranks import evaluate_dictionary_ranks
-    report = evaluate_dictionary_ranks(index, source, pairs, config.ks, config.method, config.neighbours)
-    if config.method == "csls":
+    report = evaluate_dictionary_ranks(index, source, pairs, config.ks, config.method, config.neighbours, config.beta,
+                                       sources)
+    if config.method in ("csls", "isf"):
         report.precision_report = TranslationReport(report.ks, config.method, report.asked, report.skipped,
                                                     {k: report.hits(k) for k in report.ks})
     else:
@@ -837,7 +886,9 @@ def _ranked_evaluation(index, source, pairs, config):
 def run_translate(config: TranslateConfig, write, load, vectors):
     """translate between its argument handling and the end of its output: the translations are written as they come;
     with a dictionary -> csls.TranslationReport, else None.  The source vectors are read as the index's own were: in
-    word order, normalised for a cosine index."""
+    word order, normalised for a cosine index.  config.beta and config.isf_sources are read for --method isf only (nn
+    and csls never use them; a plain TranslateConfig carries their defaults), and --isf-sources counts in FILE order:
+    _frequent_rows turns it into the rows of the most frequent words."""
     from .csls import evaluate_dictionary, read_dictionary, translate_words
     from .exact import ExactIndex, ExactWordIndex
     path = config.dictionary if config.dictionary is not None else config.words
@@ -855,20 +906,23 @@ def run_translate(config: TranslateConfig, write, load, vectors):
         if config.exact:
             index = index.exact(vectors(config.vectors, cosine))
         try:
-            originals = _aligned(config.alignment, vectors(config.source, cosine))
+            read = vectors(config.source, cosine)
+            sources = _frequent_rows(config.isf_sources, read)       # before -a and -R wrap the vectors: rows stay rows
+            originals = _aligned(config.alignment, read)
         except OSError as e:
             raise TranslateError(f"{config.alignment}: {e.strerror or e}")
         originals = _rotated(config.rotation, originals)
         source = ExactWordIndex(originals.words, ExactIndex(originals.matrix, index.metric), originals.key_index)
         if pairs is not None and config.ranks:
-            return _ranked_evaluation(index, source, pairs, config)
+            return _ranked_evaluation(index, source, pairs, config, sources)
         if pairs is not None:
-            return evaluate_dictionary(index, source, pairs, config.ks, config.method, config.neighbours)
+            return evaluate_dictionary(index, source, pairs, config.ks, config.method, config.neighbours, config.beta,
+                                       sources)
         words = [w.lower() for w in lines] if config.lowercase else lines
         offsets = None
-        if config.method == "csls" and words:                    # r_S once, for every chunk of words
-            from .csls import csls_offsets
-            offsets = csls_offsets(index, source, config.neighbours)
+        if words:                                                # the offsets once, for every chunk of words
+            from .csls import method_offsets
+            offsets = method_offsets(index, source, config.method, config.neighbours, config.beta, sources)
         try:
             for s in range(0, len(words), CHUNK):
                 part = words[s:s + CHUNK]
@@ -1005,6 +1059,10 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
             parser.error("--vectors is only applicable with --exact")
         if args.ranks and args.evaluate is None:
             parser.error("--ranks is only applicable with -e/--evaluate")
+        if args.beta is not None and args.method != "isf":
+            parser.error("--beta is only applicable with --method isf")
+        if args.isf_sources is not None and args.method != "isf":
+            parser.error("--isf-sources is only applicable with --method isf")
         if args.exact and args.rotation is not None:
             parser.error("--exact is not applicable with -R/--rotation")
         try:
@@ -1113,9 +1171,10 @@ def main(argv=None, stdin=None, stdout=None, load=None, build=None, recall=None,
             write(line + "\n")
     elif args.command == "translate":
         k, ks = (10, depth) if args.evaluate is not None else (depth, (1, 5, 10))      # -k means depths with -e
-        config = TranslateConfig(args.index, args.source, args.file, args.evaluate, args.method, args.csls_neighbours,
-                                 k, ks, args.lowercase, args.vectors, args.exact, args.rotation, args.alignment,
-                                 args.ranks)
+        fields = (args.index, args.source, args.file, args.evaluate, args.method, args.csls_neighbours, k, ks,
+                  args.lowercase, args.vectors, args.exact, args.rotation, args.alignment, args.ranks)
+        config = TranslateConfig(*fields) if args.method != "isf" else \
+            IsfTranslateConfig(*fields, 30.0 if args.beta is None else args.beta, args.isf_sources)
         try:
             report = (translate if translate is not None else run_translate)(config, write, load, vectors)
         except TranslateError as e:

@@ -16,7 +16,10 @@ offsets = r_S (csls_offsets).  r_T(x) shifts every score of one query alike; tra
 
   csls_offsets         r_S for every target row, on the device: the target's rows composed where they live, the source
                        ExactIndex asked for their K nearest, gulon_mean_similarity_dev straight into the offsets array
-  evaluate_dictionary  precision@k of a bilingual dictionary (MUSE's format, read_dictionary), plain ("nn") or "csls"
+  isf_offsets          the offsets of the inverted softmax (softmax.py) over the same passes: the composed
+                       rows asked of the source's batch_query_logsumexp
+  evaluate_dictionary  precision@k of a bilingual dictionary (MUSE's format, read_dictionary), plain ("nn"), "csls" or
+                       "isf"
   translate_words      the k translations of a list of source words
 
 The two *_reference functions restate the arithmetic in numpy, as cosmul_reference does for its kernel."""
@@ -31,7 +34,8 @@ from .index import Result
 from .word_index import BATCH, WordResult
 
 ROWS_PER_PASS = 4096          # target rows per batch of csls_offsets
-METHODS = ("nn", "csls")
+METHODS = ("nn", "csls", "isf")
+OFFSET_METHODS = ("csls", "isf")  # the methods that rank by an offset query
 
 
 # ---- references (numpy) ----------------------------------------------------------------------------------------------------
@@ -243,28 +247,27 @@ def _vector_side(index):
     raise NotImplementedError(f"{type(index).__name__} has no offset queries")
 
 
-def csls_offsets(target, source, neighbours=10) -> DeviceOffsets:
-    """r_S of CSLS for every row of `target`: the mean cosine similarity of the row to its `neighbours` nearest rows of
-    `source`, an ExactIndex (or ExactWordIndex) over the source vectors.  target: an ExactIndex, a SortedIndex / PQIndex
-    over byte codes, a GroupedIndex, or a WordIndex / ExactWordIndex over one.  In batches of target rows, all on the
-    null stream: the rows composed where they live as one-term expressions (the dataset's rows of an exact target, the
-    decoded rows of a flat one, GroupedIndex.lookup of a grouped one by grouped row position; normalised for a cosine
-    index), the source's batch_query_dev at `neighbours`, gulon_mean_similarity_dev
-    straight into the result.  -> DeviceOffsets with one value per target row (an exact target: per row of its matrix,
-    +inf outside its range).  ValueError: a target whose metric is known and not cosine, a source of another
-    dimension."""
-    from .exact import ExactIndex
-    from .index import SortedIndex
-    from .refine import _DeviceArray
+def _offset_sides(target, source, name):
+    """(kind, target side, source ExactIndex) of `name` = csls_offsets / isf_offsets; ValueError for a source that is
+    no exact index."""
     kind, tgt = _vector_side(target)
     skind, src = _vector_side(source)
     if skind != "exact":
-        raise ValueError("requirement failed: the source of csls_offsets is an exact index")
-    if neighbours < 1:
-        raise ValueError(f"requirement failed: neighbours = {neighbours} < 1")
+        raise ValueError(f"requirement failed: the source of {name} is an exact index")
+    return kind, tgt, src
+
+
+def _target_span(kind, tgt, src, rule):
+    """What csls_offsets and isf_offsets need of their target before the first pass.  ValueError for a target whose
+    metric is known and not cosine (`rule` names who asks) and for a source of another dimension.
+    -> (the number of offsets the target takes, the first and the row after the last to compute, compose): compose(off,
+    rows, w, b, out) composes b one-term expressions where the target's rows live -- the dataset's rows of an exact
+    target, the decoded rows of a flat one, GroupedIndex.lookup of a grouped one by grouped row position; normalised for a
+    cosine index -- into the device array `out` [b][d], on the null stream."""
+    from .index import SortedIndex
     metric = getattr(tgt, "metric", None)
     if metric is not None and metric != "cosine":
-        raise ValueError("requirement failed: CSLS needs a cosine index")
+        raise ValueError(f"requirement failed: {rule} needs a cosine index")
     if src.dimension != tgt.dimension:
         raise ValueError(f"requirement failed: the source has {src.dimension} dimensions, the target {tgt.dimension}")
     L = N.lib()
@@ -285,25 +288,123 @@ def csls_offsets(target, source, neighbours=10) -> DeviceOffsets:
 
         def compose(off, r, w, b, out):
             N.check(L.gulon_index_compose_rows_dev(pq._h, off, r, w, b, cosine, cosine, out, None))
-    out = DeviceOffsets.from_host(np.full(rows, np.inf, np.float32))
-    K, d = int(neighbours), tgt.dimension
-    dev = {name: _DeviceArray() for name in ("off", "rows", "w", "q", "oi", "od", "oc")}
+    return rows, first, last, compose
+
+
+def _composed_passes(span, d):
+    """The batch loop of csls_offsets and isf_offsets over a _target_span: rows [first, last) in passes of
+    ROWS_PER_PASS, each composed into one device array [b][d] that is yielded as (r0, b, array) -- both callers start
+    from the same composed bits.  The device is synchronised after the last pass, before the arrays are freed."""
+    from .refine import _DeviceArray
+    _, first, last, compose = span
+    dev = {name: _DeviceArray() for name in ("off", "rows", "w", "q")}
     try:
         for r0 in range(first, last, ROWS_PER_PASS):
             b = min(ROWS_PER_PASS, last - r0)
             dev["off"].upload(np.arange(b + 1, dtype=np.int32))
             dev["rows"].upload(np.arange(r0, r0 + b, dtype=np.int32))
             dev["w"].upload(np.ones(b, np.float32))
-            dev["q"].ensure(4 * b * d), dev["oi"].ensure(4 * b * K), dev["od"].ensure(4 * b * K), dev["oc"].ensure(4 * b)
+            dev["q"].ensure(4 * b * d)
             compose(dev["off"].ptr, dev["rows"].ptr, dev["w"].ptr, b, dev["q"].ptr)
-            src.batch_query_dev(K, dev["q"].ptr, b, dev["oi"].ptr, dev["od"].ptr, dev["oc"].ptr)
-            N.check(L.gulon_mean_similarity_dev(dev["od"].ptr, dev["oc"].ptr, b, K, K,
-                                                C.c_void_p(out.ptr.value + 4 * r0), None))
-        N.check(L.gulon_device_synchronize())
+            yield r0, b, dev["q"]
+        N.check(N.lib().gulon_device_synchronize())
     finally:
         for a in dev.values():
             a.free()
+
+
+def csls_offsets(target, source, neighbours=10) -> DeviceOffsets:
+    """r_S of CSLS for every row of `target`: the mean cosine similarity of the row to its `neighbours` nearest rows of
+    `source`, an ExactIndex (or ExactWordIndex) over the source vectors.  target: an ExactIndex, a SortedIndex / PQIndex
+    over byte codes, a GroupedIndex, or a WordIndex / ExactWordIndex over one.  In batches of target rows, all on the
+    null stream (_composed_passes): the rows composed where they live, the source's batch_query_dev at `neighbours` --
+    the composed vectors taken as they are -- and gulon_mean_similarity_dev straight into the result.  -> DeviceOffsets
+    with one value per target row (an exact target: per row of its matrix, +inf outside its range).  ValueError: a
+    target whose metric is known and not cosine, a source of another dimension."""
+    from .refine import _DeviceArray
+    kind, tgt, src = _offset_sides(target, source, "csls_offsets")
+    if neighbours < 1:
+        raise ValueError(f"requirement failed: neighbours = {neighbours} < 1")
+    span = _target_span(kind, tgt, src, "CSLS")
+    out = DeviceOffsets.from_host(np.full(span[0], np.inf, np.float32))
+    K, L = int(neighbours), N.lib()
+    oi, od, oc = _DeviceArray(), _DeviceArray(), _DeviceArray()
+    try:
+        for r0, b, q in _composed_passes(span, tgt.dimension):
+            oi.ensure(4 * b * K), od.ensure(4 * b * K), oc.ensure(4 * b)
+            src.batch_query_dev(K, q.ptr, b, oi.ptr, od.ptr, oc.ptr)
+            N.check(L.gulon_mean_similarity_dev(od.ptr, oc.ptr, b, K, K, C.c_void_p(out.ptr.value + 4 * r0), None))
+    finally:
+        for a in (oi, od, oc):
+            a.free()
     return out
+
+
+def _checked_sources(src, sources):
+    """isf_offsets' `sources` before anything is made: None, an int N in [1, the source's rows], or distinct rows of the
+    source's matrix inside its range as an int32 array; else ValueError."""
+    if sources is None:
+        return None
+    if np.ndim(sources) == 0:
+        if not 1 <= int(sources) <= src.size:
+            raise ValueError(f"requirement failed: sources = {sources} outside [1, {src.size}]")
+        return int(sources)
+    rows = np.asarray(sources, np.int64).reshape(-1)
+    if not len(rows) or rows.min() < src.frm or rows.max() >= src.until or len(np.unique(rows)) != len(rows):
+        raise ValueError(f"requirement failed: sources: expected distinct rows in [{src.frm}, {src.until})")
+    return N.i32(rows)
+
+
+def _normaliser_scan(src, sources):
+    """The handle isf_offsets sums over and what to close after it, for checked `sources`.  None: the source itself.
+    An int N: a temporary ExactIndex over the first N rows of the source's range.  An array: a temporary ExactIndex over
+    a device gather of those rows of the source's matrix, in the order given."""
+    from .exact import ExactIndex
+    from .matrix import DeviceMatrix
+    if sources is None:
+        return src, ()
+    if isinstance(sources, int):
+        scan = ExactIndex(src.matrix, src.metric, src.frm, src.frm + sources)
+        return scan, (scan,)
+    h = C.c_void_p()
+    N.check(N.lib().gulon_dataset_gather(src.matrix._h, sources, len(sources), C.byref(h)))
+    matrix = DeviceMatrix(h, len(sources), src.matrix.cols)
+    scan = ExactIndex(matrix, src.metric)
+    return scan, (scan, matrix)
+
+
+def isf_offsets(target, source, beta=30.0, sources=None) -> DeviceOffsets:
+    """The offsets of the inverted softmax (softmax.py) for every row of `target`: (2 / beta) * L(y),
+    L(y) the log of the sum of exp(-(beta / 2) * d(x', y)) over the rows x' of `source`, an ExactIndex (or
+    ExactWordIndex) over the source vectors.  target: as csls_offsets takes it.  Per pass of ROWS_PER_PASS target rows
+    (_composed_passes, the loop csls_offsets runs) the composed batch is downloaded, asked of the source's
+    batch_query_logsumexp, and softmax.isf_offsets_from fills the pass's slice.  A cosine source normalises what it is
+    asked, as its batch_query_raw does: the composed rows, unit vectors already, are normalised once more on the way
+    in, where csls_offsets hands them on as they are -- the two routes start from the same composed bits and may differ
+    in the last bit of a component after that.
+    sources restricts the normaliser, as Smith et al. sample it: an int N sums over the first N rows of the source,
+    which are its N most frequent words ONLY where the rows are in the order of a word2vec file; an array sums over
+    those rows of the source's matrix, in the order given (_normaliser_scan), which is how `translate --isf-sources` names the most frequent
+    words of a source it holds in word order.
+    -> DeviceOffsets with one value per target row (an exact target: per row of its matrix, +inf outside its range).
+    ValueError: as csls_offsets; beta not finite or <= 0; sources outside [1, the source's rows] or not distinct rows of
+    its range; a row all of whose terms underflow (beta too large for these distances)."""
+    from .softmax import _beta, isf_offsets_from
+    kind, tgt, src = _offset_sides(target, source, "isf_offsets")
+    beta = _beta(beta)
+    sources = _checked_sources(src, sources)
+    span = _target_span(kind, tgt, src, "the inverted softmax")
+    d = tgt.dimension
+    host = np.full(span[0], np.inf, np.float32)
+    scan, owned = _normaliser_scan(src, sources)
+    try:
+        for r0, b, q in _composed_passes(span, d):
+            vectors = q.download(np.zeros((b, d), np.float32))
+            host[r0:r0 + b] = isf_offsets_from(*scan.batch_query_logsumexp(vectors, beta), beta)
+    finally:
+        for x in owned:
+            x.close()
+    return DeviceOffsets.from_host(host)
 
 
 # ---- dictionaries ------------------------------------------------------------------------------------------------------------
@@ -374,18 +475,19 @@ def score_lists(lists, counts, gold, ks) -> Dict[int, int]:
 
 def translation_lists(target, source, source_rows, k, method="nn", offsets=None):
     """The k translations of the source words at `source_rows` (rows of the source ExactWordIndex): per batch of up to
-    BATCH words their vectors are looked up and asked of `target` -- "nn": its ordinary batch_query; "csls": its
-    batch_query_offset_raw with `offsets` (csls_offsets).  -> (rows [b][k] padded with -1, keys [b][k], counts [b])."""
+    BATCH words their vectors are looked up and asked of `target` -- "nn": its ordinary batch_query; "csls" and "isf":
+    its batch_query_offset_raw with `offsets` (csls_offsets, isf_offsets).
+    -> (rows [b][k] padded with -1, keys [b][k], counts [b])."""
     if method not in METHODS:
         raise ValueError(f"unknown method {method!r}")
     rows = N.i32(source_rows).reshape(-1)
     oi, od = np.full((len(rows), k), -1, np.int32), np.full((len(rows), k), np.inf, np.float32)
     oc = np.zeros(len(rows), np.int32)
-    if method == "csls":
+    if method in OFFSET_METHODS:
         offsets = host_offsets_for(target, offsets)              # a grouped target: one download for every batch
     for s in range(0, len(rows), BATCH):
         vectors = source.index.lookup_rows(rows[s:s + BATCH])
-        if method == "csls":
+        if method in OFFSET_METHODS:
             oi[s:s + BATCH], od[s:s + BATCH], oc[s:s + BATCH] = target.batch_query_offset_raw(k, vectors, offsets)
         else:
             for i, r in enumerate(target.batch_query(k, vectors)):
@@ -402,19 +504,33 @@ def _check_pair(target, source, method):
                          f"{target.dimension}")
     if method == "csls" and target.metric != "cosine":
         raise ValueError("requirement failed: CSLS needs a cosine index")
+    if method == "isf" and target.metric != "cosine":
+        raise ValueError("requirement failed: the inverted softmax needs a cosine index")
 
 
-def translate_words(target, source, words, k, method="nn", neighbours=10, offsets=None) -> List[Optional[WordResult]]:
+def method_offsets(target, source, method, neighbours=10, beta=30.0, sources=None) -> Optional[DeviceOffsets]:
+    """The offsets `method` ranks by: csls_offsets at `neighbours`, isf_offsets at `beta` over `sources`, None for "nn"."""
+    if method == "csls":
+        return csls_offsets(target, source, neighbours)
+    if method == "isf":
+        return isf_offsets(target, source, beta, sources)
+    return None
+
+
+def translate_words(target, source, words, k, method="nn", neighbours=10, offsets=None, beta=30.0,
+                    sources=None) -> List[Optional[WordResult]]:
     """Per source word its k translations among the target's words, None for a word the source lacks.  method "csls":
-    `distances` of a result holds the keys d + r_S; offsets: r_S from an earlier csls_offsets (None: computed here)."""
+    `distances` of a result holds the keys d + r_S; "isf": the keys d + (2 / beta) * L, the normaliser over `sources`
+    as isf_offsets takes it (None: every source row).  offsets: from an earlier csls_offsets / isf_offsets (None: computed
+    here)."""
     _check_pair(target, source, method)
     words = list(words)
     rows = [source.row_of(w) for w in words]
     present = [i for i, r in enumerate(rows) if r is not None]
     out: List[Optional[WordResult]] = [None] * len(words)
-    own = method == "csls" and offsets is None
+    own = method in OFFSET_METHODS and offsets is None
     if own:
-        offsets = csls_offsets(target, source, neighbours)
+        offsets = method_offsets(target, source, method, neighbours, beta, sources)
     try:
         oi, od, oc = translation_lists(target, source, [rows[i] for i in present], k, method, offsets)
     finally:
@@ -427,13 +543,14 @@ def translate_words(target, source, words, k, method="nn", neighbours=10, offset
 
 
 def evaluate_dictionary(target, source, pairs: Sequence[Tuple[str, str]], ks=(1, 5, 10), method="nn",
-                        neighbours=10) -> TranslationReport:
+                        neighbours=10, beta=30.0, sources=None) -> TranslationReport:
     """Precision@k of translating the dictionary's source words into the target's words.  target: a WordIndex over byte
     codes or an ExactWordIndex; source: an ExactWordIndex over the source vectors; pairs: read_dictionary.  A source word
     counts at k if any of its gold translations is among its first k answers; a pair with a word missing on either side
     is skipped and counted.  method "nn": the target's ordinary neighbours; "csls": its offset query with
-    csls_offsets(target, source, neighbours), at most 63 answers per word.  ValueError: an unknown method, a source and
-    target of different dimension, "csls" on a target that is not cosine."""
+    csls_offsets(target, source, neighbours), at most 63 answers per word; "isf": the same with
+    isf_offsets(target, source, beta, sources).  ValueError: an unknown method, a source and target of different
+    dimension, "csls" or "isf" on a target that is not cosine."""
     from .analogies import _check_ks
     ks = _check_ks(ks)
     _check_pair(target, source, method)
@@ -441,7 +558,7 @@ def evaluate_dictionary(target, source, pairs: Sequence[Tuple[str, str]], ks=(1,
     report = TranslationReport(ks, method, len(rows), skipped, {k: 0 for k in ks})
     if not rows:
         return report
-    offsets = csls_offsets(target, source, neighbours) if method == "csls" else None
+    offsets = method_offsets(target, source, method, neighbours, beta, sources)
     try:
         oi, _, oc = translation_lists(target, source, rows, ks[-1], method, offsets)
     finally:

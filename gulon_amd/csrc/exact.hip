@@ -25,6 +25,7 @@
 #include "compose.hpp"
 #include "cosmul.hpp"
 #include "exact.hpp"
+#include "logsumexp.hpp"
 #include "offset.hpp"
 #include "rank.hpp"
 #include "select.hpp"
@@ -295,6 +296,7 @@ struct gulon_exact_index {
   CosmulWork cosmul;                   // the multiplicative analogy queries (cosmul.hip)
   OffsetWork offset;                   // the offset queries (offset.hip)
   RankWork rank;                       // the rank queries (rank.hip)
+  LseWork lse;                         // the log-sum-exp queries (logsumexp.hip)
   std::vector<int> h_cnt, h_ovf, h_nf, h_ids;
   hipEvent_t order_ev = nullptr;
   hipStream_t order_st = nullptr;
@@ -758,6 +760,34 @@ GULON_API int32_t gulon_exact_index_query_rank(gulon_exact_index *idx, const flo
     x.frank.download(out_rank, (size_t)b, st); x.frow.download(out_row, (size_t)b, st);
     x.fk.download(out_key, (size_t)b, st);
     if (out_total) x.ftotal.download(out_total, (size_t)b, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+  });
+}
+
+// Log-sum-exp queries: logsumexp.hip sums exp(-(beta / 2) * distance) over the rows of [from, until) per
+// query, in binary64 and in a fixed order, and takes the log; the excluded rows are dataset rows.  Host pointers, the
+// null stream.
+GULON_API int32_t gulon_exact_index_query_logsumexp(gulon_exact_index *idx, const float *queries, int32_t b, float beta,
+                                                    const int32_t *exclude, double *out_lse, int32_t *out_terms) {
+  return guarded([&] {
+    GULON_REQUIRE(idx != nullptr, "index is null");
+    GULON_REQUIRE(b >= 0, "batch size must be non-negative");
+    GULON_REQUIRE(std::isfinite(beta) && beta > 0.f, "beta = %g: expected a finite value > 0", (double)beta);
+    check_rows_host(nullptr, true, idx->ds->n, exclude, b, 0);
+    if (b == 0) return;
+    GULON_REQUIRE(queries != nullptr && out_lse != nullptr, "null argument");
+    std::lock_guard<std::mutex> g(idx->mu);
+    LseWork &x = idx->lse;
+    const hipStream_t st = nullptr;
+    order_wait(idx, st);   // the workspace may still be read by the last batch, on another stream
+    x.q.upload(queries, (size_t)b * idx->ds->d, st);
+    if (exclude) x.ex.upload(exclude, (size_t)b, st);
+    x.fl.ensure((size_t)b); x.ft.ensure((size_t)b);
+    launch_logsumexp_exact(idx->ds, idx->from, idx->until, x, x.q.p, b, -0.5 * (double)beta, exclude ? x.ex.p : nullptr,
+                           x.fl.p, x.ft.p, st);
+    order_record(idx, st);
+    x.fl.download(out_lse, (size_t)b, st);
+    if (out_terms) x.ft.download(out_terms, (size_t)b, st);
     HIP_CHECK(hipStreamSynchronize(st));
   });
 }

@@ -20,6 +20,18 @@ KNOBS = ("GULON_EXACT_SAMPLE", "GULON_EXACT_QUEUE_CAP")
 STATS = ("one_pass", "fallback", "nonfinite", "sample", "capacity", "max_fill")
 
 
+def normalize_rows(q):
+    """index.normalize of every row of q [b][d] float32, the bits of the row-by-row call: the float32 sum of squares
+    advances one dimension at a time for all the rows at once, the square root is taken in float64."""
+    q = N.f32(q)
+    s = np.zeros(len(q), np.float32)
+    with np.errstate(all="ignore"):
+        for e in range(q.shape[1]):
+            s = s + q[:, e] * q[:, e]
+        dist = np.sqrt(s.astype(np.float64)).astype(np.float32)
+        return (q / dist[:, None]).astype(np.float32)
+
+
 class ExactIndex:
     """Exact neighbours of rows [frm, until) of `matrix` (a DeviceMatrix, a Matrix or an array; the index does not own a
     DeviceMatrix it is given, which must outlive it).  metric "cosine": the queries are normalised as
@@ -194,6 +206,29 @@ class ExactIndex:
         return rank_query_raw(N.lib().gulon_exact_index_query_rank, self._h, (), self.dimension, self.matrix.rows,
                               self._prepare(vectors), gold, offsets, exclude)
 
+    # ---- log-sum-exp queries (softmax.py): the excluded rows are rows of the MATRIX
+    def batch_query_logsumexp(self, vectors, beta, exclude=None):
+        """gulon_exact_index_query_logsumexp: per query L = log of the sum of exp(-(beta / 2) * distance) over the rows
+        of [frm, until) whose distance is finite and that are not exclude[q] (a row of the matrix, or -1), summed in
+        float64 in a fixed order (softmax.logsumexp_reference), and the number of those rows.  The queries are
+        normalised for a cosine index.  beta: finite and > 0, taken as a float32.  The last bits of L may differ
+        between batches of different sizes.
+        -> (L [b] float64, -inf without a term or where every term underflows; terms [b] int32)."""
+        from .softmax import _beta
+        beta = _beta(beta)
+        q = N.f32(vectors).reshape(-1, self.dimension)
+        if self.metric == "cosine" and len(q):
+            q = normalize_rows(q)
+        b = len(q)
+        ex = None if exclude is None else N.i32(exclude).reshape(-1)
+        if ex is not None and len(ex) != b:
+            raise ValueError(f"requirement failed: {len(ex)} excluded rows for {b} queries")
+        out, terms = np.full(max(b, 1), -np.inf, np.float64), np.zeros(max(b, 1), np.int32)
+        N.check(N.lib().gulon_exact_index_query_logsumexp(
+            self._h, q.reshape(-1) if q.size else np.zeros(1, np.float32), b, beta,
+            None if ex is None or not b else ex.ctypes.data, out, terms.ctypes.data))
+        return out[:b], terms[:b]
+
     def stats(self):
         """Of the last batch: queries answered in one pass, by the peeled fallback and one at a time as non-finite; the
         sample rows S (0: no sample pass), the queue capacity, the largest number of rows at or below a bound."""
@@ -339,6 +374,11 @@ class ExactWordIndex:
         """ExactIndex.batch_query_rank_raw, up to BATCH queries per device batch."""
         from .ranks import batched_rank_query
         return batched_rank_query(self.index, self.dimension, vectors, gold, offsets, exclude)
+
+    def batch_query_logsumexp(self, vectors, beta, exclude=None):
+        """ExactIndex.batch_query_logsumexp, as it is: one device batch, so that a vector's answer does not depend on
+        how a caller's batch would have been cut."""
+        return self.index.batch_query_logsumexp(vectors, beta, exclude)
 
     def close(self):
         """Frees the handle and the gathered matrix this index was built over, when it owns one."""

@@ -222,6 +222,7 @@ SIGNATURES = {
     "gulon_grouped_index_query_offset": (_i32, [_vp, _f32p, _i32, _i32, _i32, _i32, _f32p, _vp, _i32p, _f32p, _i32p]),
     "gulon_exact_index_query_rank": (_i32, [_vp, _f32p, _i32, _vp, _vp, _i32p, _i32p, _i32p, _i32p, _f32p, _vp]),
     "gulon_index_query_rank": (_i32, [_vp, _f32p, _i32, _i32, _i32, _vp, _vp, _i32p, _i32p, _i32p, _i32p, _f32p, _vp]),
+    "gulon_exact_index_query_logsumexp": (_i32, [_vp, _f32p, _i32, C.c_float, _vp, _f64p, _vp]),
     "gulon_mean_similarity": (_i32, [_f32p, _vp, _i32, _i32, _i32, _f32p]),
     "gulon_mean_similarity_dev": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "gulon_dataset_pair_moment": (_i32, [_vp, _vp, _vp, _vp, C.c_int64, _f64p, C.POINTER(C.c_int64)]),

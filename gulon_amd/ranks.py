@@ -11,7 +11,7 @@ precision at any depth, and a gold translation far down the order still counts.
   rank_query_reference        the numpy restatement over a distance matrix, as csls.offset_query_reference is
   rank_query_raw              the ctypes call behind every batch_query_rank_raw
   RankReport                  mrr, median and mean rank, hits at any depths
-  evaluate_dictionary_ranks   csls.evaluate_dictionary by ranks: "nn" or "csls"
+  evaluate_dictionary_ranks   csls.evaluate_dictionary by ranks: "nn", "csls" or "isf"
 """
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
@@ -190,19 +190,20 @@ class RankReport:
 
 
 def evaluate_dictionary_ranks(target, source, pairs: Sequence[Tuple[str, str]], ks=(1, 5, 10), method="nn",
-                              neighbours=10) -> RankReport:
+                              neighbours=10, beta=30.0, sources=None) -> RankReport:
     """csls.evaluate_dictionary by rank queries: per source word the rank of its best gold translation among ALL the
     target's words, so the depths `ks` are not bound by the 63 entries of an offset query's list, a translation far down
     still counts (mrr, median and mean rank), and no list is selected.  target: a WordIndex over byte codes or an
     ExactWordIndex; source: an ExactWordIndex over the source vectors; pairs: csls.read_dictionary.
 
     method "csls": the order is the offset query's with csls_offsets(target, source, neighbours), so hits(k) equals
-    evaluate_dictionary's at every k <= 63.  method "nn": the order is (distance ascending, row ascending) with no
+    evaluate_dictionary's at every k <= 63; method "isf": the same with isf_offsets(target, source, beta, sources).
+    method "nn": the order is (distance ascending, row ascending) with no
     offsets -- total, but NOT the tie order of the ordinary query's heap, so among equal distances a position can differ
     from batch_query's.  The offsets are downloaded once for the whole evaluation.  NotImplementedError: a grouped, a
     rotated or a restricted target; ValueError as evaluate_dictionary."""
     from .analogies import _check_ks
-    from .csls import _check_pair, _vector_side, csls_offsets, resolve_dictionary
+    from .csls import _check_pair, _vector_side, method_offsets, resolve_dictionary
     ks = _check_ks(ks)
     _check_pair(target, source, method)
     if _vector_side(target)[0] == "grouped":
@@ -212,8 +213,8 @@ def evaluate_dictionary_ranks(target, source, pairs: Sequence[Tuple[str, str]], 
     if not rows:
         return report
     offsets = None
-    if method == "csls":
-        device = csls_offsets(target, source, neighbours)
+    device = method_offsets(target, source, method, neighbours, beta, sources)
+    if device is not None:
         try:
             offsets = device.numpy()
         finally:

@@ -231,10 +231,13 @@ class DeviceWordVectors:
 
     def sorted(self):
         """WordVectors.sorted (WordVectors.scala:60-71): the order on the host (String.compareTo), the rows gathered
-        on the device."""
+        on the device.  file_rows[i] of the result is the row that sorted row i had here: for vectors as read, its
+        line in the file, which in a word2vec file is its frequency rank."""
         order = self._word_order()
         words = [self.words[i] for i in order]
-        return DeviceWordVectors(words, self._gather(order), KeyIndexSorted(words), self.stats)
+        out = DeviceWordVectors(words, self._gather(order), KeyIndexSorted(words), self.stats)
+        out.file_rows = np.asarray(order, np.int64)
+        return out
 
     def grouped(self, clustering, gather=True):
         """WordVectors.grouped (WordVectors.scala:24-58) over grouped.group: (the word vectors in grouped order,

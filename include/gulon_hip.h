@@ -1024,6 +1024,35 @@ int32_t gulon_index_query_rank(gulon_index *idx, const float *queries, int32_t b
                                const int32_t *gold_rows, int32_t *out_rank, int32_t *out_row, float *out_key,
                                int32_t *out_total);
 
+/* ---- Log-sum-exp queries and the inverted softmax (logsumexp.hip) ----------------------------------------
+ * Not a Scala method.  Per query q and per row r of the handle's range [from, until):
+ *   d        the handle's own distance bits (MathUtils.distanceSq order, binary32), as the ordinary query returns them
+ *   term     r is a term if and only if d is finite and r != exclude[q] (exclude nullable; -1 excludes nothing)
+ *   z, e     z = (double)d * (-0.5 * (double)beta), one binary64 product; e = exp(z) in binary64
+ *   S_q      the sum of e over the terms, in binary64, in a fixed order: per lane the 256-row steps of its row chunk
+ *            ascending, the lanes of a wave by an xor butterfly (32 down to 1), the waves in wave order, the chunks
+ *            ascending.  No atomics
+ *   out_lse [b]     L_q = log(S_q) in binary64; -inf for a query without a term, and for one whose terms all underflow
+ *                   to 0 (beta too large for these distances)
+ *   out_terms [b]   (nullable) the number of terms, exact
+ * The bits of out_lse are a function of (range, queries, b, beta) alone: a used handle answers like a fresh one.  They
+ * are NOT pinned across batch shapes: the number of row chunks follows the number of 16-query tiles of a pass (4096
+ * queries at most), so the same query asked in a batch of another size may differ in its last bits.  Against the exactly
+ * rounded sum of the same terms, |L - L_ref| <= 2^-40 + 4 ulp(L_ref) for ranges of up to 2^20 rows.
+ * The offsets of the inverted softmax (Smith et al. 2017) follow from it.  On unit vectors cos = 1 - d / 2, and the rule
+ * ranks target row y for source word x by beta * cos(x, y) - log sum_x' exp(beta * cos(x', y)), which is the ascending
+ * order of t = d(x, y) + (2 / beta) * L(y) with L(y) = log sum_x' exp(-(beta / 2) * d(x', y)): an offset query
+ * ("Offset queries and CSLS" above) with row_offsets[y] = (float)((2 / beta) * L(y)), L(y) this entry point's answer on
+ * a handle over the SOURCE vectors with the target row y as the query.
+ * Queries are taken as given (nothing is normalised).  Everything is checked before anything is launched: idx, b >= 0,
+ * beta finite and > 0, every exclude[q] either -1 or a row of the dataset, queries and out_lse non-null when b > 0, else
+ * GULON_ERR_INVALID_ARGUMENT naming the first bad entry.  b = 0 launches nothing.
+ * gulon_exact_index_query_logsumexp takes host pointers only: the work runs on the null stream and the call returns when
+ * the answers have arrived.  (A device-pointer form with a stream, and its stream-contract case, is left to a later
+ * change.) */
+int32_t gulon_exact_index_query_logsumexp(gulon_exact_index *idx, const float *queries, int32_t b, float beta,
+                                          const int32_t *exclude, double *out_lse, int32_t *out_terms);
+
 /* ---- Alignment (alignment.hip) ---------------------------------------------------------------------------
  * Not Scala methods: the reference aligns nothing.  The two device steps of learning an orthogonal map between two
  * embedding spaces (MUSE's Procrustes refinement) that the entry points above do not cover.
