@@ -50,6 +50,26 @@ def test_native_switches_and_tuning_keys_are_the_documented_ones():
     assert {n for n, kind in table.items() if kind == "`ScanTuning`"} == keys
 
 
+def test_every_switch_that_changes_a_path_is_named_by_a_gpu_test():
+    """A ScanTuning key, a switch that turns a fast path off, a knob of the exact index, a testing or a debugging switch
+    that no GPU test names is a path nobody runs: section 7 promises that results do not depend on the former and that
+    the latter can be used to bisect.  GULON_HOST_CONTEXTS changes how concurrent host calls share workspaces, so it
+    counts as well."""
+    kinds = {"`ScanTuning`", "fast path off", "exact index", "testing", "debugging"}
+    # GULON_RCCL_LIB only names the file dlopen tries first; the sharded index either loads RCCL or reports that it
+    # cannot, and no result depends on which name worked
+    exempt = {"GULON_RCCL_LIB"}
+    table = _table()
+    assert set(table.values()) - kinds == {"configuration"}, set(table.values())
+    must = {n for n, kind in table.items() if kind in kinds} | {"GULON_HOST_CONTEXTS"}
+    assert not must & exempt and exempt < set(table)
+    tests_dir = os.path.join(ROOT, "tests")
+    text = "\n".join(_read(os.path.join(tests_dir, f)) for f in sorted(os.listdir(tests_dir))
+                     if f.startswith("test_gpu_") and f.endswith(".py"))
+    named = set(re.findall(r"\bGULON_[A-Z0-9_]+\b", text))
+    assert not must - named, sorted(must - named)
+
+
 def test_scripts_set_only_existing_variables():
     known = set(_table()) | PYTHON_SIDE
     bad = []
