@@ -283,8 +283,8 @@ __global__ __launch_bounds__(256) void sort_place(const UpdDesc *__restrict__ de
 // dependent operations:   q0 = RN(a y);  r = RN(a - n q0) (exact, one fma);  q = RN(q0 + r y)  ==  RN(a / n)
 // whenever y is the correctly rounded reciprocal and nothing under- or overflows (a faithful q0 plus one
 // fma-corrected step; Markstein 1990, Cornea-Harrison-Tang 2002).  mean_step_fast is only trusted for
-// 2^-60 < |a| < 2^60 (n <= 2^24: every intermediate stays normal); a batch in which any step falls outside is
-// recomputed with __fdiv_rn.  gulon_selftest_mean_division checks the identity against __fdiv_rn for EVERY
+// 2^-60 < |a| < 2^60 and n < 2^24 (every intermediate stays normal, every step number is a float); a batch in which
+// any step falls outside is recomputed with __fdiv_rn.  gulon_selftest_mean_division checks the identity against __fdiv_rn for EVERY
 // n in [1, 2^24) over random and near-halfway numerators (tests/test_gpu_kmeans.py).
 __device__ __forceinline__ float mean_quotient_fast(float a, float nf, float y) {
   const float q0 = a * y;
@@ -397,12 +397,14 @@ __global__ __launch_bounds__(64) void update_chains(const UpdDesc *__restrict__ 
         lo = fminf(lo, fabsf(a));
         hi = fmaxf(hi, fabsf(a));
         p = p + mean_quotient_fast(a, nf, rcp[i + u]);
-        nf += 1.0f;                                   // exact below 2^24
+        nf += 1.0f;                                   // exact up to 2^24; a batch that reaches it is redone below
       }
-      // a zero, tiny, huge or NaN numerator somewhere in the batch, or a divisor whose significand is all ones
-      // (2^j - 1: see mean_quotient_fast) among its 32: the plain division, from the batch's start
+      // a zero, tiny, huge or NaN numerator somewhere in the batch, a divisor whose significand is all ones
+      // (2^j - 1: see mean_quotient_fast) among its 32, or a last step at or beyond 2^24 (the divisor is RN(count) there,
+      // which `nf` above does not follow, and the corrected quotient is only checked below it; stream_chains has the same
+      // rule): the plain division, from the batch's start
       if (!__all(lo > 8.673617379884035e-19f /* 2^-60 */ && hi < 1.152921504606847e18f /* 2^60 */) ||
-          batch_has_all_ones_divisor(i / U)) {
+          batch_has_all_ones_divisor(i / U) || i + U >= (1u << 24)) {
         p = p0;
 #pragma unroll
         for (int u = 0; u < U; u++) p = p + __fdiv_rn(xa[u] - p, (float)(int)(i + u + 1));
@@ -494,10 +496,11 @@ __global__ __launch_bounds__(64) void update_chains_pk(const UpdDesc *__restrict
         const f32x2 r = __builtin_elementwise_fma(nn, q0, a);
         p = p + __builtin_elementwise_fma(r, y2, q0);
       }
-      // a zero, tiny, huge or NaN numerator somewhere in a live lane's batch, or a divisor whose significand is all ones
-      // (2^j - 1: see mean_quotient_fast) among its 32: the plain division, from the batch's start
+      // a zero, tiny, huge or NaN numerator somewhere in a live lane's batch, a divisor whose significand is all ones
+      // (2^j - 1: see mean_quotient_fast) among its 32, or a last step at or beyond 2^24 (where the corrected quotient
+      // is not checked): the plain division, from the batch's start
       if (!__all(!live || (lo > 8.673617379884035e-19f /* 2^-60 */ && hi < 1.152921504606847e18f /* 2^60 */)) ||
-          batch_has_all_ones_divisor(b)) {
+          batch_has_all_ones_divisor(b) || i + U >= (1u << 24)) {
         p = p0;
 #pragma unroll
         for (int u = 0; u < U; u++) p = slow(p, cur[u], i + u + 1);

@@ -352,3 +352,58 @@ def test_pq_train_with_stream_update_off(oracle, g, tmp_path, n, d, m, k, iters)
                        env={**os.environ, "GULON_UPDATE_STREAM": "0"}, timeout=120, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     _check_pq_against_oracle(oracle, X, m, k, np.load(cf), np.load(kf), iters)
+
+
+# ---- a cluster of 2^24 rows or more: the step number no longer fits a float's 24 bits ------------------------------------------
+
+LONG = (1 << 24) + (1 << 20)          # rows of the long cluster
+_LONG_BLOCK = {}
+
+
+def _long_cluster(s, k):
+    """LONG rows of cluster 0 with 1000 rows of clusters 1 .. 5 scattered among them; the rows tile one random block of
+    2^16 rows, so that making them costs little host time."""
+    if "block" not in _LONG_BLOCK:
+        _LONG_BLOCK["block"] = np.random.default_rng(2024).standard_normal((1 << 16, 18)).astype(np.float32)
+    n = LONG + 1000
+    X = np.tile(np.ascontiguousarray(_LONG_BLOCK["block"][:, :s]), (n // (1 << 16) + 1, 1))[:n]
+    a = np.zeros(n, np.int32)
+    short = np.arange(1000) * (n // 1000) + 17
+    a[short] = 1 + np.arange(1000) % 5
+    assert (a == 0).sum() == LONG and k > 5
+    return np.ascontiguousarray(X), a
+
+
+def _same_centroids(got, want, chains):
+    assert np.array_equal(bits(got)[1:], bits(want)[1:])                       # the short clusters and the empty ones
+    differ = np.flatnonzero(bits(got)[0] != bits(want)[0])
+    assert len(differ) == 0, f"{len(differ)} of {chains} chains of the long cluster end on other bits: dims {differ.tolist()}"
+
+
+def test_streamed_update_redoes_the_chunks_past_2_24_rows(oracle, g):
+    """stream_chains takes the plain division for every chunk at whose end the cluster's count has reached 2^24: the
+    last 129 chunks of the long cluster here."""
+    from batch_seams_ref import STREAM_CH, stream_redo_chunks
+    s, k = 2, 6
+    X, a = _long_cluster(s, k)
+    per_chunk = np.bincount(np.flatnonzero(a == 0) // STREAM_CH, minlength=-(-len(a) // STREAM_CH))
+    redo = stream_redo_chunks(per_chunk.tolist())
+    assert len(redo) >= 128 and redo[-1] == len(per_chunk) - 1 and redo[0] > 2000
+    _same_centroids(_stream_update(g, X, 0, s, k, a), oracle.kmeans_from_assignment(X, 0, s, k, a), s)
+
+
+@pytest.mark.parametrize("s,k", [(2, 1100), (18, 1100), (1, 12000)])
+def test_from_assignment_with_a_cluster_past_2_24_rows(oracle, g, s, k):
+    """KMeans.fromAssignment (KMeans.scala:211-224) divides by the Int count converted to float: beyond 2^24 that is
+    RN(count), not the count.  s = 2: update_chains_pk; s = 18 (stride above 16): update_chains, 18 chains of the long
+    cluster; k = 12000: update_chains_indirect.  Before update_chains redid the batches that reach 2^24 with the plain
+    division, all 18 chains of its case ended on other bits than the oracle's.  (Bound by the host: the s = 18 case
+    copies 1.2 GB to the device.)"""
+    X, a = _long_cluster(s, k)
+    chains = s                                              # of the long cluster: one per dimension
+    if s == 18:
+        assert chains >= 12                                 # one lucky chain cannot hide a wrong divisor
+    v = g.Vectors(g.DeviceMatrix.from_host(X), 0, s)
+    got = g.KMeans.from_assignment(k, s, v, a).centroids
+    del v
+    _same_centroids(got, oracle.kmeans_from_assignment(X, 0, s, k, a), chains)

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import merge_ref as mr
+from batch_seams_ref import wide_sub_batch
 from conftest import bits
 from test_gpu_merge import Dev, merge_dev
 
@@ -62,17 +63,6 @@ def byte_query_tile(m):
     return w * nsub
 
 
-def wide_sub_batch(B, m, k, rows_pad):
-    """run_wide_query: the queries whose tables (and, with a sliced table, parked sums) fit in 1 GiB."""
-    table_bytes = m * k * 4
-    jp_fit = (128 * 1024) // (k * 4)
-    passes = ceil_div(m, min(jp_fit, m)) if jp_fit >= 1 else 1
-    cap = (1 << 30) // table_bytes
-    if passes > 1:
-        cap = min(cap, (1 << 30) // (rows_pad * 4))
-    return max(1, min(B, cap))
-
-
 def nchunks_of(form, B, frm, until):
     f = FORMS[form]
     rb = ceil_div(until, 64) - frm // 64
@@ -88,7 +78,8 @@ def test_launch_shapes_restated():
         assert nchunks_of(form, 5, 0, 500) == 1
         assert form == "wide" or B_TILE > 2 * byte_query_tile(FORMS[form]["m"])
     # the wide sub-batch: a table is m * k * 4 = 64 KiB here, so 1 GiB holds 16 384 queries' -- 37 are ONE sub-batch.  A
-    # sub-batch below 37 needs > 27 MiB of tables per query (m * k > 7 M), which no index of a test's size has.
+    # sub-batch below 37 needs > 27 MiB of tables per query (m * k > 7 M), which no index of this file's size has
+    # (tests/test_gpu_batch_seams.py crosses that seam).
     f = FORMS["wide"]
     assert wide_sub_batch(B_TILE, f["m"], f["k"], ceil_div(N_ROWS, 64) * 64) == B_TILE
     assert wide_sub_batch(B_TILE, 112, 65536, 64) == 36
