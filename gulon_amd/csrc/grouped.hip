@@ -163,11 +163,13 @@ __global__ __launch_bounds__(256) void gq_sorted_groups(const float *__restrict_
   // (distance, id) order is the reference's heap order only while the entries that decide the answer -- the
   // searched ones and the first one left out -- have pairwise different distances; otherwise gq_literal_groups
   // redoes this query (equal centroid distances are common: the reference's leading empty group repeats a centroid)
-  // level 2: the tie sits AT the cut (or a NaN is around): the searched SET hangs on the heap's order -- redone before
-  // the scan; level 1: only the ORDER of searched groups does, which matters solely to queries whose RESULT is later
-  // redone literally (TopKHeap.merge runs in search order) -- those are redone then
+  // level 2: the searched SET hangs on the heap's order -- redone before the scan: the tie sits AT the cut (or a NaN is
+  // around), or, cutting by rows, between the LAST TWO searched groups: the cut is cumulative, so with the larger twin
+  // first the heap reaches `limit` rows one group earlier and never opens the other (a tie class further inside adds
+  // the same rows in either order); level 1: only the ORDER of searched groups does, which matters solely
+  // to queries whose RESULT is later redone literally (TopKHeap.merge runs in search order) -- those are redone then
   for (int e = tid; e + 1 < min(cnt + 1, g); e += 256)
-    if (sv[e] == sv[e + 1]) atomicMax(&s_lit, e + 1 == cnt ? 2 : 1);
+    if (sv[e] == sv[e + 1]) atomicMax(&s_lit, e + 1 == cnt || (by_vectors && e + 2 == cnt) ? 2 : 1);
   __syncthreads();
   if (tid == 0) lit[q] = s_lit;
 }
@@ -1425,5 +1427,60 @@ GULON_API int32_t gulon_selftest_grouped_stage(const uint8_t *codes, int32_t n, 
   });
   if (gx) (void)gulon_grouped_index_destroy(gx);
   return rc != GULON_OK ? rc : refused ? 78 : GULON_OK;
+}
+
+// The group selection on its own (tests/test_gpu_group_select.py, tests/group_select_ref.py).  Builds a
+// grouped index from gulon_grouped_index_create's arguments and calls coarse_stage(c, all_literal) as the drivers do
+// (K = 1).  lit_flag and sel_ok are filled with -1 first, so the caller sees which kernels wrote them.  Where the
+// order-only ties are still to be redone (!all_literal and lit_cap > 0) the level-1 pass then runs as redo_flagged runs
+// it, over a list of every query, and nn / nn_cnt are returned a second time.
+// out[]: 0 nn [b][nn_stride], 1 nn_cnt [b], 2 cdist [b][g], 3 lit_flag [b], 4 sel_ok [b], 5 nn after the level-1 pass,
+//   6 nn_cnt after it (5 and 6 are left alone where the pass does not run).  Room for [b][min(limit + g, g)] = [b][g]
+//   entries in 0 and 5.
+// info: nn_stride, stride, lit_cap.
+// (Declared here and bound by its test, like the hook above.)
+GULON_API int32_t gulon_selftest_group_selection(const uint8_t *codes, int32_t n, int32_t d, int32_t m, int32_t k,
+                                                 const float *pq_cents, const float *group_centroids, const int32_t *offsets,
+                                                 int32_t g, const float *queries, int32_t b, int32_t strategy, int32_t limit,
+                                                 int32_t all_literal, void **out, int32_t *info) {
+  gulon_grouped_index *gx = nullptr;
+  const int32_t rc = guarded([&] {
+    GULON_REQUIRE(pq_cents && group_centroids && queries && out && info, "null argument");
+    GULON_REQUIRE(b >= 1 && b <= 4096 && (strategy == 0 || strategy == 1) && limit >= 1, "bad arguments");
+    for (int i = 0; i < 7; i++) GULON_REQUIRE(out[i] != nullptr, "out[%d] is null", i);
+    GULON_REQUIRE(gulon_grouped_index_create(codes, n, d, m, k, pq_cents, group_centroids, offsets, g, &gx) == GULON_OK && gx, "no index");
+    hipStream_t st = nullptr;
+    const int B = b;
+    gx->q_dev.upload(queries, (size_t)B * d, st);
+    gx->lit_flag.ensure((size_t)B);
+    gx->sel_ok.ensure((size_t)B);
+    HIP_CHECK(hipMemsetAsync(gx->lit_flag.p, 0xFF, sizeof(int) * (size_t)B, st));
+    HIP_CHECK(hipMemsetAsync(gx->sel_ok.p, 0xFF, sizeof(int) * (size_t)B, st));
+    const GroupedCall c{gx, gx->q_dev.p, B, 1, strategy, limit, nullptr, nullptr, nullptr, st};
+    const CoarseResult co = coarse_stage(c, all_literal != 0);
+    HIP_CHECK(hipStreamSynchronize(st));
+    auto get = [&](int slot, const void *dev, size_t bytes) {
+      if (bytes) HIP_CHECK(hipMemcpy(out[slot], dev, bytes, hipMemcpyDeviceToHost));
+    };
+    get(0, gx->nn.p, sizeof(int) * (size_t)B * co.nn_stride);
+    get(1, gx->nn_cnt.p, sizeof(int) * (size_t)B);
+    get(2, gx->cdist.p, sizeof(float) * (size_t)B * g);
+    get(3, gx->lit_flag.p, sizeof(int) * (size_t)B);
+    get(4, gx->sel_ok.p, sizeof(int) * (size_t)B);
+    if (!all_literal && co.lit_cap > 0) {   // redo_flagged's pass over the group order, every query listed
+      std::vector<int> ql((size_t)B);
+      for (int q = 0; q < B; q++) ql[q] = q;
+      gx->qlist.upload(ql.data(), (size_t)B, st);
+      gx->qcount.upload(&B, 1, st);
+      launch_literal_groups(c, co.nn_stride, co.lit_cap, 1, std::min(B, 16), gx->qlist.p, gx->qcount.p);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipStreamSynchronize(st));
+      get(5, gx->nn.p, sizeof(int) * (size_t)B * co.nn_stride);
+      get(6, gx->nn_cnt.p, sizeof(int) * (size_t)B);
+    }
+    info[0] = co.nn_stride; info[1] = co.stride; info[2] = co.lit_cap;
+  });
+  if (gx) (void)gulon_grouped_index_destroy(gx);
+  return rc;
 }
 #endif

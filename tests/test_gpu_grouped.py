@@ -323,3 +323,50 @@ def test_grouping_assigns_in_original_order_then_sorts_by_word(oracle, g):
     assert not np.array_equal(assign_sorted, assign[word_order])
     R = oracle.group_residuals(X, perm, cents, offsets)
     assert np.array_equal(bits(R), bits(gv.residuals.get_rows(np.arange(n, dtype=np.int32))))
+
+
+@pytest.mark.parametrize("literal", [False, True])
+def test_limit_vectors_cut_between_twin_groups(oracle, g, monkeypatch, literal):
+    """Two non-empty groups share a centroid and are the last two the (distance, id) order searches: groups 2 (4 rows) and
+    3 (100 rows) at distance 3 from the query, behind groups 0 (1 row) and 1 (3 rows), LimitVectors(24).  The reference's
+    deleteAll has group 3 first, reaches 24 rows with it and never opens group 2 (Index.scala:289-298) -- whose rows are
+    the nearest of the two groups'.  Nothing ties at the cut of the (distance, id) order, which searches all four, and no
+    two of the eleven nearest rows are equally far (asserted): the approximate path certifies the query, nothing redoes it,
+    and the groups it answers from are the ones the group selection chose at once."""
+    import ctypes as C
+    from gulon_amd import native as N
+    if literal:
+        monkeypatch.setenv("GULON_GROUPED_LITERAL", "1")
+    d, m, k, K, limit = 6, 2, 16, 10, 24
+    rng = np.random.default_rng(17)
+    gc = np.array([[0, 0, 0, 0, 0, 0], [1, 0, 0, 0, 0, 0], [1, 1, 1, 0, 0, 0], [0, 0, 0, 1, 1, 1]], np.float32)
+    sizes = np.array([1, 3, 4, 100])
+    offsets, n = np.cumsum(sizes)[:-1].astype(np.int32), int(sizes.sum())
+    cents = (0.1 * rng.standard_normal((m, k, d // m))).astype(np.float32)     # [quantizer][centroid][3]
+    cents[0, 0] = -0.5                                                          # code 0 of the first quantizer: towards the query
+    idx = rng.integers(1, k, (m, n)).astype(np.int32)
+    idx[0, 4:8] = 0                                                             # the rows of group 2: (0.5, 0.5, 0.5, ...)
+    flat = np.ascontiguousarray(cents.reshape(-1))
+    pq = g.ProductQuantizer.from_flat(k, d, m, flat)
+    coder = pq.coder_factory(n)
+    packed = np.ascontiguousarray(g.EncodedMatrix(coder, [coder.build_code(idx[j]) for j in range(m)]).packed())
+    Q = np.zeros((2, d), np.float32)
+    Q[1] = [0.2, -0.1, 0.3, 0.1, 0.0, -0.2]                                     # (no ties for this one)
+    ei, ed, ec = oracle.grouped_query(idx, d, k, flat, gc, offsets, Q, K, 1, limit)
+    ai, ad, ac = oracle.grouped_query(idx, d, k, flat, gc, offsets, Q, K, 0, 4)    # every group: a superset of the (distance, id) set
+    assert ec[0] == ac[0] == K and set(ei[0].tolist()) != set(ai[0].tolist())
+    assert set(range(4, 8)) <= set(ai[0].tolist()) and not set(range(4, 8)) & set(ei[0].tolist())
+    for strategy, lim in ((1, limit), (0, 4)):                                  # no equal distances among the K + 1 nearest
+        di = oracle.grouped_query(idx, d, k, flat, gc, offsets, Q, K + 1, strategy, lim)[1]
+        assert all(len(set(di[q].tolist())) == K + 1 for q in range(2))
+    h = C.c_void_p()
+    assert N.lib().gulon_grouped_index_create(packed, n, d, m, k, flat, np.ascontiguousarray(gc.reshape(-1)), offsets, 4,
+                                              C.byref(h)) == 0
+    oi, od, oc = np.zeros(2 * K, np.int32), np.zeros(2 * K, np.float32), np.full(2, -1, np.int32)
+    assert N.lib().gulon_grouped_index_batch_query(h, np.ascontiguousarray(Q.reshape(-1)), 2, K, 1, limit, oi, od, oc) == 0
+    assert N.lib().gulon_grouped_index_destroy(h) == 0
+    oi, od = oi.reshape(2, K), od.reshape(2, K)
+    assert np.array_equal(oc, ec)
+    for q in range(2):
+        assert oi[q, :oc[q]].tolist() == ei[q, :ec[q]].tolist(), q
+        assert np.array_equal(bits(od[q, :oc[q]]), bits(ed[q, :ec[q]])), q
